@@ -16,13 +16,22 @@ touched a GPU -- and exits with their status.  The frame is sharded by interleav
 xGMI (torch.distributed backend "nccl"), rank 0 de-interleaves them into the full frame.  The gather of launch b
 overlaps the trace of launch b+1.  Total work per step is fixed -> "scaling": "strong".
 
-Every run checks one TIMED frame against the CPU oracle on a fixed pixel grid (every 4th pixel in x and y, all samples,
+A plain run does only what the headline needs: set up, warm up, time exactly K steps once, write the last timed frame if
+--dump-outputs DIR is given, print the result line.  Everything below -- the oracle check, the repetitions, the roofline, the
+reference's call shape, the sustained run, C4 and the CPU baselines -- runs with --full only.
+
+--dump-outputs DIR: after the timed steps, the radiance of the last timed frame (what a caller of the timed path receives:
+height x width x 4 float32, rank 0's de-interleaved frame when sharded) is written as DIR/radiance.npy; above DUMP_BUDGET
+bytes a fixed, seeded sample of pixels goes to DIR/radiance_sample.npy with their flat pixel indices in
+DIR/radiance_sample_pixel.npy (float64).  Same arguments, same scene, same frame indices: two builds compare output for output.
+
+--full checks one TIMED frame against the CPU oracle on a fixed pixel grid (every 4th pixel in x and y, all samples,
 bit for bit) and prints "verified": true; a mismatch ends the run with a non-zero status and no result line.
 
-The timed region (exactly K steps between barriers + synchronisations, max over ranks) is repeated --reps times (default 9;
-SURVEY 8d asks for at least 3) after the warm-up; `value` / `ms_per_step` are the MEDIAN repetition, `ms_per_step_min_max` the spread, `ms_per_step_all`
-every repetition in order.  (Nine since round 5: behind a 5-step warm-up the chip is still ramping -- twelve repetitions of the driver's command read 0.777, 0.727, 0.721,
-0.708, 0.717, 0.714, 0.705, 0.707, 0.705, 0.711, 0.703, 0.705 ms per step -- and the median of five sat on the ramp.)
+With --full the timed region (exactly K steps between barriers + synchronisations, max over ranks) is repeated --reps times (default 9
+there, 1 in a plain run; SURVEY 8d asks for at least 3) after the warm-up; `value` / `ms_per_step` are the MEDIAN repetition, `ms_per_step_min_max` the spread,
+`ms_per_step_all` every repetition in order.  (Nine since round 5: behind a 5-step warm-up the chip is still ramping -- twelve repetitions of the driver's command read
+0.777, 0.727, 0.721, 0.708, 0.717, 0.714, 0.705, 0.707, 0.705, 0.711, 0.703, 0.705 ms per step -- and the median of five sat on the ramp.)
 
 The JSON line's `roofline`: `fractions` holds, for every resource a gather-and-compute kernel can be bound by (vector issue, scalar issue, L2 bandwidth, HBM-side
 traffic, the vector L1's request rate), per-frame counter total / kernel busy time / peak; `peaks` says where each peak comes from -- "guide" =
@@ -81,6 +90,8 @@ PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_bench.json")
 KERNEL_SOURCES = ["pt_megakernel.hip", "pt_megakernel_loop.inc", "pt_device.h", "pt_kernels.h"]
 VERIFY_STEP = 4         # the timed frame is checked on every 4th pixel in x and y (1/16 of the frame, ~0.6 s of oracle time)
 SHARD_PIECES = 3        # launches a sharded run is cut into at least (tools/ab/pieces_sweep.sh -> profiles/r05_m3_shard_pieces.txt: [7, 7, 6] beats [5, 5, 5, 5] by 2.5 .. 5.5 % at N = 2 / 4 / 8 once the last gather is added)
+DUMP_BUDGET = 48 << 20  # --dump-outputs: a frame larger than this is sampled (the 1080p frame, 33 MB, is written whole)
+DUMP_SEED = 20260109
 
 
 def _normalised_source(path):
@@ -103,6 +114,22 @@ def source_tag():
 
 def algorithmic_bytes(st):
     return BYTES_NODE * st["nodes_examined"] + BYTES_TRI * st["tris_tested"] + BYTES_SAMPLE * st["samples"]
+
+
+def dump_outputs(out_dir, name, arr, budget=DUMP_BUDGET):
+    """--dump-outputs: `arr` (a frame, [..., channels]) as out_dir/<name>.npy in float32; larger than `budget` bytes, a seeded sample of
+    its pixels (sorted flat indices, the same for every run of this shape) as <name>_sample.npy plus the indices as <name>_sample_pixel.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if arr.nbytes <= budget:
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        return
+    flat = arr.reshape(-1, arr.shape[-1])
+    n = budget // (flat.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.shape[0], n, replace=False))
+    np.save(os.path.join(out_dir, name + "_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, name + "_sample_pixel.npy"), idx.astype(np.float64))
 
 
 def load_oracle():
@@ -313,16 +340,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=32)
-    ap.add_argument("--reps", type=int, default=9, help="repetitions of the timed region (value = the median one)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C4 leg of the `configs` block")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region (value = the median one); default 1, 9 with --full")
+    ap.add_argument("--full", action="store_true", help="also the oracle check, the repetitions, the roofline, the reference's call shape, the sustained run, "
+                                                        "C4 and the CPU baselines (a plain run times the K steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed frame's radiance to DIR (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the C4 leg of the `configs` block")
     ap.add_argument("--width", type=int, default=WIDTH)
     ap.add_argument("--height", type=int, default=HEIGHT)
-    ap.add_argument("--verify", action="store_true", help="kept for compatibility: the check against the oracle always runs")
-    ap.add_argument("--no-reference-shape", action="store_true", help="skip the one-render()-per-frame figures")
-    ap.add_argument("--sustained-seconds", type=float, default=11.0, help="N = 1: after the timed region, render for about this long in 32-frame launches and compare the "
-                                                                          "last frame with the verified one, bit for bit (0 = skip)")
+    ap.add_argument("--verify", action="store_true", help="kept for compatibility: the check against the oracle runs with --full")
+    ap.add_argument("--no-reference-shape", action="store_true", help="--full: skip the one-render()-per-frame figures")
+    ap.add_argument("--sustained-seconds", type=float, default=11.0, help="--full, N = 1: after the timed region, render for about this long in 32-frame launches and "
+                                                                          "compare the last frame with the verified one, bit for bit (0 = skip)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 9 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -409,7 +441,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
         frames_out = torch.zeros(2 * batch, height * width * 4, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
 
-    # exact traversal counters of this rank's share of every timed frame (deterministic per frame index): one instrumented
+    # --full: exact traversal counters of this rank's share of every timed frame (deterministic per frame index): one instrumented
     # launch per frame, before the timed region
     my_stats = None
     frame_bytes = []
@@ -417,16 +449,17 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
     dbg = np.zeros(24, np.uint64)
     rays_entering = 0                # rays that enter the root box at all (camera rays that miss it are most of C2's "rays")
     rcp_short_variant = True
-    with torch.cuda.stream(stream):
-        if sharded:
-            ctx.set_compact_buffer(compact[0][0].data_ptr(), stride)
-        for i in range(args.steps):
-            ctx.render(params(i, stats=True))
-            st = ctx.stats()
-            rt.lib.pt_debug_counters(ctx.h, dbg.ctypes.data_as(C.c_void_p)); rays_entering += (int(dbg[7]) & ((1 << 63) - 1)) >> 1
-            rcp_short_variant = rcp_short_variant and bool(int(dbg[7]) & 1)      # which variant the host picks for this scene / camera (the same decision for the timed launches)
-            frame_bytes.append(algorithmic_bytes(st))
-            my_stats = st if my_stats is None else {k: my_stats[k] + st[k] for k in st}
+    if sharded:
+        ctx.set_compact_buffer(compact[0][0].data_ptr(), stride)
+    if args.full:
+        with torch.cuda.stream(stream):
+            for i in range(args.steps):
+                ctx.render(params(i, stats=True))
+                st = ctx.stats()
+                rt.lib.pt_debug_counters(ctx.h, dbg.ctypes.data_as(C.c_void_p)); rays_entering += (int(dbg[7]) & ((1 << 63) - 1)) >> 1
+                rcp_short_variant = rcp_short_variant and bool(int(dbg[7]) & 1)      # which variant the host picks for this scene / camera (the same decision for the timed launches)
+                frame_bytes.append(algorithmic_bytes(st))
+                my_stats = st if my_stats is None else {k: my_stats[k] + st[k] for k in st}
     my_bytes = float(sum(frame_bytes)) / max(len(frame_bytes), 1)       # mean per frame
     ctx.set_batch(batch)
 
@@ -473,7 +506,8 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
         if sharded:
             dist.barrier()
         torch.cuda.synchronize()
-        ctx.timing_begin(args.steps)
+        if args.full:
+            ctx.timing_begin(args.steps)
         t0 = time.perf_counter()
         with torch.cuda.stream(stream):
             run(args.steps, 0, p, "timed" if rep == 0 else "timed-rep%d" % rep)      # the same K frame indices every repetition: the same work
@@ -481,7 +515,8 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
         if sharded:
             dist.barrier()
         e = time.perf_counter() - t0
-        rep_spans.append(ctx.timing_collect_spans(args.steps))
+        if args.full:
+            rep_spans.append(ctx.timing_collect_spans(args.steps))
         if sharded:
             t = torch.tensor([e], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -490,21 +525,23 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
     order = sorted(range(reps), key=lambda i: rep_elapsed[i])
     med = order[(reps - 1) // 2]                     # the median repetition (the lower one of an even count)
     elapsed = rep_elapsed[med]
-    k_start, k_ms = rep_spans[med]
+    k_start, k_ms = rep_spans[med] if args.full else (None, None)
 
-    # ---- the last timed frame against the CPU oracle (fixed pixel grid, every sample, bit for bit) -----------------------------
+    # ---- the last timed frame as its caller receives it (rank 0): written out for --dump-outputs, checked by --full ----------------
+    got = None
+    if rank == 0 and (args.full or args.dump_outputs):
+        with torch.cuda.stream(stream):
+            ctx.synchronize()
+            got = (frames_full if sharded else frames_out)[last_frame["buf"]].reshape(height, width, 4).cpu().numpy()     # sharded: the last de-interleaved frame
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "radiance", got)
+
+    # ---- --full: the last timed frame against the CPU oracle (fixed pixel grid, every sample, bit for bit) ----------------------
     verified = None
     bvh4 = None
-    if rank == 0:
+    if rank == 0 and args.full:
         orc_mod, orc = load_oracle()
         bvh4 = ctx.read_bvh4()
-        with torch.cuda.stream(stream):
-            if sharded:
-                ctx.synchronize()
-                got = frames_full[last_frame["buf"]].reshape(height, width, 4).cpu().numpy()     # the last de-interleaved frame
-            else:
-                ctx.synchronize()
-                got = frames_out[last_frame["buf"]].reshape(height, width, 4).cpu().numpy()
         want, _, _ = orc.render(orc.make_params(width, height, NUM_TRIS, mode=orc_mod.MODE_PATH, spp=SPP, max_bounces=BOUNCES, seed=SEED,
                                                 frame=args.steps - 1, step=(VERIFY_STEP, VERIFY_STEP)), tris, bvh4)
         a, b = got[::VERIFY_STEP, ::VERIFY_STEP], want[::VERIFY_STEP, ::VERIFY_STEP]
@@ -512,20 +549,20 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
         if not verified:
             print("bench.py: timed frame %d differs from the CPU oracle on the %d-pixel grid (%d of %d pixels)"
                   % (args.steps - 1, VERIFY_STEP, int((a != b).any(axis=2).sum()), a.shape[0] * a.shape[1]), file=sys.stderr, flush=True)
-    if sharded:
+    if args.full and sharded:
         ok = torch.tensor([1 if (verified or rank != 0) else 0], dtype=torch.int32, device="cuda" if backend == "nccl" else "cpu")
         dist.broadcast(ok, src=0)
         if int(ok.item()) == 0:
             ctx.close(); dist.destroy_process_group()
             sys.exit(3)
-    elif not verified:
+    elif args.full and not verified:
         ctx.close()
         sys.exit(3)
 
     # ---- where the lanes are: one more launch of the timed shape on the TIMELINE variant of the kernel (production registers and speed; wave-uniform
     #      counters in scalar registers): wavefront-steps, traversing lanes, lanes at a leaf -- the decomposition of the counter files' lane utilisation
     lanes_by_side = None
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         import ctypes as C2
         ctx.debug_set_tune("TIMELINE", 1)
         with torch.cuda.stream(stream):
@@ -563,7 +600,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
 
     # ---- the reference's own call shape: one render() per frame, no batching (src/main.js:70-74) ------------------------------
     ref_shape = None
-    if world == 1 and not args.no_reference_shape:
+    if args.full and world == 1 and not args.no_reference_shape:
         ctx.set_output_buffer(0, 0)
         ctx.set_batch(1)
         n_ref, n_solo = 64, max(8, min(args.steps, 32))
@@ -597,7 +634,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
     # ---- sustained: a second or two of back-to-back 32-frame launches (the driver's 20 steps are 15 ms of GPU time: too short for any outside
     #      observer -- a utilisation sampler, a power reading -- to see), ending on the frame that was verified above: it must come out bit-identical
     sustained = None
-    if world == 1 and args.sustained_seconds > 0 and rank == 0:
+    if args.full and world == 1 and args.sustained_seconds > 0 and rank == 0:
         ctx.set_output_buffer(0, 0)
         ctx.set_batch(32)
         ps = params(whole=True)
@@ -628,7 +665,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
 
     # ---- the other single-GPU configuration: C4, a sponza-class interior (every camera ray hits, long paths: no empty space to lean on) --------
     configs = None
-    if world == 1 and not args.no_configs and (width, height) == (WIDTH, HEIGHT):
+    if args.full and world == 1 and not args.no_configs and (width, height) == (WIDTH, HEIGHT):
         def rates(st, seconds_per_frame, entering):
             return {"rays_per_s": round((st["rays_closest"] + st["rays_shadow"]) / seconds_per_frame, 1), "rays_entering_root_per_s": round(entering / seconds_per_frame, 1), "node_tests_per_s": round(st["nodes_examined"] / seconds_per_frame, 1),
                     "tri_tests_per_s": round(st["tris_tested"] / seconds_per_frame, 1)}
@@ -670,6 +707,8 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
             json.dump({"launches": launch_log, "steps": args.steps, "warmup": args.warmup, "batch": batch, "source_tag": source_tag()}, open(log_path, "w"))
         samples_per_step = width * height * SPP
         value = samples_per_step * args.steps / elapsed / 1e6
+    roofline = None
+    if rank == 0 and args.full:
         n_launch = max(len(k_ms), 1)
         frames_per_launch = args.steps / n_launch
         busy = busy_ms(k_start, k_ms) if len(k_ms) else float("nan")            # ms the GPU spent in trace_paths_kernel (overlaps counted once)
@@ -765,6 +804,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
                                     "of HBM roofline' is not met by measured HBM-side traffic (hbm_fabric above) and cannot be for a cache-resident scene",
                             "counters_all_timed_frames": {k: my_stats[k] for k in ("rays_closest", "rays_shadow", "nodes_examined", "tris_tested", "samples")}},
         }
+    if rank == 0:
         out = {
             "metric": "Msamples/sec @1920x1080 Stanford-Dragon-class, 4 spp, 8 bounces",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -774,7 +814,8 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
             "ms_per_step_first5": round(sorted(rep_elapsed[:5])[(min(reps, 5) - 1) // 2] / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic", "verified": verified,
-            "verified_how": "timed frame %d, every %dth pixel in x and y (all %d samples each), bit for bit against oracle/pt_oracle.cpp" % (args.steps - 1, VERIFY_STEP, SPP),
+            "verified_how": "timed frame %d, every %dth pixel in x and y (all %d samples each), bit for bit against oracle/pt_oracle.cpp" % (args.steps - 1, VERIFY_STEP, SPP)
+                            if args.full else "not checked (plain run: --full checks the timed frame against the oracle)",
             "config": {"workload": "C2: dragon-class procedural closed mesh (%d tris, seed %d; dragon.glb absent), native LBVH2->BVH4, %dx%d, %d spp, %d bounces, camera (0,0,2.5) identity quat FOV 70, a new frame index (sample set) every step"
                                    % (NUM_TRIS, SCENE_SEED, width, height, SPP, BOUNCES),
                        "triangles": NUM_TRIS, "bvh4_nodes": ctx.scene_info()["numNodes4"], "width": width, "height": height,
@@ -786,7 +827,7 @@ def run_bench(args, rank, world, device, backend, torch, dist, np, rt):
             "sustained": sustained,
             "configs": configs,
         }
-        if world == 1 and not args.no_cpu_baseline and (width, height) == (WIDTH, HEIGHT):
+        if args.full and world == 1 and not args.no_cpu_baseline and (width, height) == (WIDTH, HEIGHT):
             out["cpu_baseline"] = cpu_baseline(tris, bvh4)
             out["cpu_baseline_threads"] = cpu_baseline_threads(tris, bvh4)
             out["cpu_baseline_node"] = cpu_baseline_node(tris, bvh4)

@@ -205,7 +205,7 @@ def test_bench_two_ranks_gloo_rehearsal_verifies_gathered_frame(gpus, steps, fix
     env.update(PT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     if fixed_batch:
         env["PT_BENCH_BATCH"] = fixed_batch
-    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", "3" if gpus == 2 else "5",
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(gpus), "--steps", str(steps), "--warmup", "3" if gpus == 2 else "5",
                                    "--width", "640", "--height", "360"], env=env, cwd=root, text=True, stderr=subprocess.STDOUT, timeout=600)
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -232,12 +232,12 @@ def test_bench_rank_failure_ends_the_run_nonzero_and_fast(fail):
 
 
 def test_bench_single_gpu_contract_line():
-    """bench.py at N = 1 (small frame, few steps): ONE JSON line with the contract's keys, the roofline and CPU-baseline
+    """bench.py --full at N = 1 (small frame, few steps): ONE JSON line with the contract's keys, the roofline and CPU-baseline
     objects, a frame verified against the oracle, kernel busy time consistent with the step time, and the figures for the
     reference's own call shape (one render() per frame)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--width", "480", "--height", "272",
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--width", "480", "--height", "272",
                                    "--no-cpu-baseline"], cwd=root, text=True, stderr=subprocess.DEVNULL, timeout=600)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -268,6 +268,33 @@ def test_bench_single_gpu_contract_line():
     assert abs(r["value"] - 480 * 272 * 4 / (r["ms_per_step"] * 1e-3) / 1e6) / r["value"] < 1e-2
     shape = r["reference_call_shape"]
     assert shape["ms_per_frame_solo"] >= shape["ms_per_frame_pipelined"] * 0.9 > 0
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_frame(rt, orc, gpu_ctx_full, tmp_path):
+    """bench.py without --full: ONE JSON line with the contract's keys, exactly K timed steps in one repetition (bench.py's own launch
+    log), none of --full's extras, and --dump-outputs writes the last timed frame's radiance -- the CPU oracle's frame K-1 on the
+    every-4th-pixel grid, bit for bit (the same C2 scene: gpu_ctx_full holds it)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    w, h, steps = 320, 180, 7
+    env = dict(os.environ, PT_BENCH_LAUNCH_LOG=str(tmp_path / "launches.json"))
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "2", "--width", str(w), "--height", str(h),
+                                   "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, text=True, stderr=subprocess.DEVNULL, timeout=600)
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["unit"] == "Msamples/s" and r["higher_is_better"] is True and r["dtype"] == "f32" and r["metric"].startswith("Msamples/sec")
+    assert r["n_gpus"] == 1 and r["steps"] == steps and r["warmup"] == 2 and r["reps"] == 1 and r["ms_per_step"] > 0
+    assert abs(r["value"] - w * h * 4 / (r["ms_per_step"] * 1e-3) / 1e6) / r["value"] < 1e-2
+    assert r["verified"] is None and all(r[k] is None for k in ("roofline", "reference_call_shape", "sustained", "configs", "cpu_baseline"))
+    log = json.load(open(str(tmp_path / "launches.json")))
+    assert log["launches"] == [["warmup", 2], ["timed", steps]]
+    assert os.listdir(str(tmp_path / "out")) == ["radiance.npy"]
+    img = np.load(str(tmp_path / "out" / "radiance.npy"))
+    assert img.dtype == np.float32 and img.shape == (h, w, 4)
+    want, _, _ = orc.render(orc.make_params(w, h, 871414, mode=orc_mod.MODE_PATH, spp=4, max_bounces=8, seed=1, frame=steps - 1, step=(4, 4)),
+                            gpu_ctx_full._tris, gpu_ctx_full.read_bvh4())
+    assert same_bits(img[::4, ::4], want[::4, ::4])
 
 
 def test_prebuilt_bvh_files_roundtrip(rt, orc, gpu_ctx, tmp_path):
