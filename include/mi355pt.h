@@ -123,6 +123,25 @@ PT_API int pt_compute_bvh4_sizing(uint32_t num_nodes4, uint64_t* bytes);
 PT_API int pt_morton_sort(const float* tris, uint32_t num_tris, uint32_t* morton_sorted, uint32_t* tri_index_sorted);
 /* collapseLBVH2ToBVH4 (PathTracer.js:506-667): out holds up to 1 + 8*(2N-1) words */
 PT_API int pt_collapse_lbvh2_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, uint32_t* out, uint64_t out_words, uint32_t* num_nodes4);
+/* Opt-in tree quality.  The reference builds one tree, LBVH2 + first-internal collapse ("BVH-only, no
+ * SAH"); levels 1 and 2 depart from it in the TREE only, every buffer stays in the reference layout (BVH2 u32[1 + 6(2N-1)], root 0,
+ * internal nodes 0..N-2, leaf N-1+k = Morton-sorted triangle k with the LBVH's leaf words; BVH4 u32[1 + 8M] in DFS pre-order, one
+ * triangle per leaf), so readBVH2 / data/BVH2.bin / pt_bvh2_to_bvh4_wide and the oracle's traversal work on them unchanged.
+ *   PT_ACCEL_REFERENCE      the reference's tree, exactly (pt_build_bvh)
+ *   PT_ACCEL_AREA_COLLAPSE  the same LBVH2; the collapse expands the internal entry of LARGEST SURFACE AREA instead of the first
+ *                           one (PathTracer.js:608-621 departs here)
+ *   PT_ACCEL_PLOC           a PLOC BVH2 (Meister & Bittner, TVCG 2018; radius 16) instead of the LBVH2 of BVHBuilder.wgsl:152-240,
+ *                           same leaves, same refit (:242-306), then the area-guided collapse
+ * A BVH2 installed with pt_set_bvh2 (e.g. a level-2 data/BVH2.bin reloaded) is collapsed the reference's way, first-internal. */
+#define PT_ACCEL_REFERENCE     0
+#define PT_ACCEL_AREA_COLLAPSE 1
+#define PT_ACCEL_PLOC          2
+/* collapseLBVH2ToBVH4 with the collapse rule of `accel` (0: identical to pt_collapse_lbvh2_to_bvh4; 1, 2: area-guided, which
+ * reads the internal BVH2 bounds -- give it a complete BVH2, e.g. pt_read_bvh2's or pt_build_bvh2_ploc's) */
+PT_API int pt_collapse_bvh2_to_bvh4_accel(const uint32_t* bvh2, uint32_t num_tris, uint32_t accel, uint32_t* out, uint64_t out_words, uint32_t* num_nodes4);
+/* PLOC BVH2 of PT_ACCEL_PLOC on the host, refit bounds included (the device build equals it word for word); out holds
+ * 1 + 6*(2N-1) words.  Replaces the reference's LBVH2 kernels (BVHBuilder.wgsl:152-240) by PLOC; leaves and refit as there. */
+PT_API int pt_build_bvh2_ploc(const float* tris, uint32_t num_tris, uint32_t* out, uint64_t out_words);
 /* BVH2 -> BVH4_wide promotion (tests/test.cpp:106-196): out holds 1 + 8*bvh2[0] words */
 PT_API int pt_bvh2_to_bvh4_wide(const uint32_t* bvh2, uint64_t bvh2_words, uint32_t* out, uint64_t out_words);
 /* data/BVH2.bin, data/BVH4_wide.bin: raw little-endian u32 dumps (src/server/api.js:27-31,
@@ -146,6 +165,10 @@ PT_API int pt_set_triangles(PtContext* ctx, const float* tris, uint32_t num_tris
  * (the host entry points below mirror the JS steps one by one).  The bounds of the INTERNAL BVH2 nodes, which only a BVH2
  * read-back looks at, are filled in by the first pt_read_bvh2. */
 PT_API int pt_build_bvh(PtContext* ctx);
+/* pt_build_bvh with a tree-quality level (PT_ACCEL_*; departures from the reference listed there).  accel 0 is pt_build_bvh.
+ * Every level builds on the device; levels 1 and 2 leave a complete BVH2 (internal bounds included) for pt_read_bvh2.  Any other
+ * value returns PT_ERR_INVALID_ARG and leaves the context as it was. */
+PT_API int pt_build_bvh_accel(PtContext* ctx, uint32_t accel);
 /* LBVH2 kernels only, from caller-supplied sorted codes (the two dispatches at
  * PathTracer.js:709-728); result stays on the device for pt_read_bvh2. */
 PT_API int pt_build_lbvh2(PtContext* ctx, const uint32_t* morton_sorted, const uint32_t* tri_index_sorted);
@@ -313,6 +336,8 @@ PT_API int  pt_group_context(PtGroup* group, uint32_t rank, PtContext** ctx);
 /* scene, replicated on every member: pt_set_triangles / pt_build_bvh / pt_set_bvh2 / pt_set_bvh4 */
 PT_API int  pt_group_set_triangles(PtGroup* group, const float* tris, uint32_t num_tris);
 PT_API int  pt_group_build_bvh(PtGroup* group);
+/* pt_build_bvh_accel on every member: the build is deterministic, every member holds the same tree */
+PT_API int  pt_group_build_bvh_accel(PtGroup* group, uint32_t accel);
 PT_API int  pt_group_set_bvh2(PtGroup* group, const uint32_t* bvh2, uint64_t words);
 PT_API int  pt_group_set_bvh4(PtGroup* group, const uint32_t* bvh4, uint64_t words);
 /* pt_set_batch for every member; the gather then moves one batch per collective.  A group delivers ONE image per batch: the batch's LAST frame

@@ -25,6 +25,8 @@ PT_FLAG_SIMPLE_KERNEL = 2
 PT_FLAG_BRUTE_FORCE = 4
 PT_FLAG_COMPACT = 8
 SCENE_DRAGON_CLASS, SCENE_SPONZA_CLASS = 0, 1
+# opt-in tree quality of build_bvh (include/mi355pt.h PT_ACCEL_*): 0 = the reference's tree
+PT_ACCEL_REFERENCE, PT_ACCEL_AREA_COLLAPSE, PT_ACCEL_PLOC = 0, 1, 2
 
 
 class PtError(RuntimeError):
@@ -64,13 +66,14 @@ class PtAccumInfo(C.Structure):
 EXPORTS = [
     "pt_create", "pt_destroy", "pt_last_error", "pt_version", "pt_set_stream", "pt_get_stream", "pt_synchronize",
     "pt_compute_bvh2_sizing", "pt_compute_bvh4_sizing", "pt_morton_sort", "pt_collapse_lbvh2_to_bvh4",
-    "pt_bvh2_to_bvh4_wide", "pt_file_write_u32", "pt_file_read_u32", "pt_scene_procedural",
-    "pt_set_triangles", "pt_build_bvh", "pt_build_lbvh2", "pt_read_bvh2", "pt_set_bvh4", "pt_set_bvh2",
+    "pt_collapse_bvh2_to_bvh4_accel", "pt_build_bvh2_ploc", "pt_bvh2_to_bvh4_wide", "pt_file_write_u32", "pt_file_read_u32", "pt_scene_procedural",
+    "pt_set_triangles", "pt_build_bvh", "pt_build_bvh_accel", "pt_build_lbvh2", "pt_read_bvh2", "pt_set_bvh4", "pt_set_bvh2",
     "pt_read_bvh4", "pt_set_spheres", "pt_scene_info", "pt_render", "pt_last_render_ms", "pt_set_batch", "pt_flush", "pt_timing_begin", "pt_timing_collect", "pt_timing_collect_spans", "pt_set_compact_buffer", "pt_set_output_buffer", "pt_get_stats", "pt_read_radiance",
     "pt_read_rgba8", "pt_read_tonemapped", "pt_tile_layout", "pt_tile_ids", "pt_compact_radiance", "pt_deinterleave", "pt_deinterleave_batch", "pt_buffer_busy",
     "pt_accum_info", "pt_read_accum", "pt_set_accum",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
+    "pt_group_build_bvh_accel",
     "pt_group_set_bvh2", "pt_group_set_bvh4", "pt_group_set_batch", "pt_group_render", "pt_group_flush", "pt_group_synchronize", "pt_group_read_radiance",
     "pt_group_read_rgba8", "pt_group_read_tonemapped",
     "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan",     # diagnostics section of the header
@@ -142,6 +145,26 @@ def collapse_lbvh2_to_bvh4(bvh2, num_tris):
     n4 = C.c_uint32()
     _check(lib.pt_collapse_lbvh2_to_bvh4(_p(bvh2, C.c_uint32), C.c_uint32(num_tris), _p(out, C.c_uint32), C.c_uint64(cap), C.byref(n4)))
     return out[: 1 + 8 * n4.value].copy(), n4.value
+
+
+def collapse_bvh2_to_bvh4_accel(bvh2, num_tris, accel):
+    """The collapse of build level `accel` on the host (1, 2: area-guided, needs a complete BVH2); returns (bvh4, numNodes4)."""
+    bvh2 = np.ascontiguousarray(bvh2, np.uint32)
+    cap = 1 + 8 * max(2 * num_tris - 1, 0)
+    out = np.zeros(cap, np.uint32)
+    n4 = C.c_uint32()
+    _check(lib.pt_collapse_bvh2_to_bvh4_accel(_p(bvh2, C.c_uint32), C.c_uint32(num_tris), C.c_uint32(accel), _p(out, C.c_uint32),
+                                              C.c_uint64(cap), C.byref(n4)))
+    return out[: 1 + 8 * n4.value].copy(), n4.value
+
+
+def build_bvh2_ploc(tris):
+    """The PLOC BVH2 of PT_ACCEL_PLOC on the host, refit bounds included (what Context.read_bvh2 returns after build_bvh(accel=2))."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    n = tris.size // 9
+    out = np.zeros(1 + 6 * max(2 * n - 1, 0), np.uint32)
+    _check(lib.pt_build_bvh2_ploc(_p(tris, C.c_float), C.c_uint32(n), _p(out, C.c_uint32), C.c_uint64(out.size)))
+    return out
 
 
 def bvh2_to_bvh4_wide(bvh2):
@@ -245,8 +268,11 @@ class Context:
         xyzr = np.ascontiguousarray(xyzr, np.float32).reshape(-1)
         self._ck(lib.pt_set_spheres(self.h, _p(xyzr, C.c_float), C.c_uint32(xyzr.size // 4)))
 
-    def build_bvh(self):
-        self._ck(lib.pt_build_bvh(self.h))
+    def build_bvh(self, accel=PT_ACCEL_REFERENCE):
+        if accel == PT_ACCEL_REFERENCE:
+            self._ck(lib.pt_build_bvh(self.h))
+        else:
+            self._ck(lib.pt_build_bvh_accel(self.h, C.c_uint32(accel)))
 
     def build_lbvh2(self, morton, tri_idx):
         morton = np.ascontiguousarray(morton, np.uint32); tri_idx = np.ascontiguousarray(tri_idx, np.uint32)
@@ -456,8 +482,11 @@ class Group:
         self._ck(lib.pt_group_set_triangles(self.h, _p(tris, C.c_float), C.c_uint32(tris.size // 9)))
         self.num_tris = tris.size // 9
 
-    def build_bvh(self):
-        self._ck(lib.pt_group_build_bvh(self.h))
+    def build_bvh(self, accel=PT_ACCEL_REFERENCE):
+        if accel == PT_ACCEL_REFERENCE:
+            self._ck(lib.pt_group_build_bvh(self.h))
+        else:
+            self._ck(lib.pt_group_build_bvh_accel(self.h, C.c_uint32(accel)))
 
     def set_bvh4(self, bvh4):
         bvh4 = np.ascontiguousarray(bvh4, np.uint32)

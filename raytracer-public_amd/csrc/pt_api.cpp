@@ -88,6 +88,7 @@ struct PtContext {
     // device-side scene build (pt_build.hip): scratch kept for rebuilds
     DevBuf<unsigned long long> d_bounds; DevBuf<uint32_t> d_counters, d_code_tmp, d_index_tmp, d_node2, d_subtree, d_ids, d_bnd;
     DevBuf<uint4> d_child_pos; DevBuf<unsigned char> d_build_temp; uint32_t* h_word = nullptr;
+    DevBuf<uint32_t> d_ploc;         // PT_ACCEL_PLOC cluster buffers (ptk::ploc_words), allocated on first use
     DevBuf<float4> d_spheres; uint32_t num_spheres = 0;
 
     // frame
@@ -680,6 +681,25 @@ int pt_collapse_lbvh2_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, uint32_t*
     if (num_nodes4) *num_nodes4 = v[0];
     return PT_OK;
 }
+int pt_collapse_bvh2_to_bvh4_accel(const uint32_t* bvh2, uint32_t num_tris, uint32_t accel, uint32_t* out, uint64_t out_words, uint32_t* num_nodes4) {
+    if (accel > PT_ACCEL_PLOC) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_collapse_bvh2_to_bvh4_accel: accel must be 0, 1 or 2");
+    if (!out || (num_tris && !bvh2)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_collapse_bvh2_to_bvh4_accel: null pointer");
+    std::vector<uint32_t> v; std::string err;
+    if (!pt::collapse_to_bvh4(bvh2, num_tris, accel != PT_ACCEL_REFERENCE, v, err)) return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (v.size() > out_words) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_collapse_bvh2_to_bvh4_accel: output buffer too small");
+    std::memcpy(out, v.data(), v.size() * 4);
+    if (num_nodes4) *num_nodes4 = v[0];
+    return PT_OK;
+}
+int pt_build_bvh2_ploc(const float* tris, uint32_t num_tris, uint32_t* out, uint64_t out_words) {
+    if (!out || (num_tris && !tris)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_build_bvh2_ploc: null pointer");
+    if (num_tris >= 0x7fffffffu) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_build_bvh2_ploc: too many triangles for the 31-bit leaf index");
+    std::vector<uint32_t> v; std::string err;
+    if (!pt::build_bvh2_ploc(tris, num_tris, v, err)) return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (v.size() > out_words) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_build_bvh2_ploc: output buffer too small");
+    std::memcpy(out, v.data(), v.size() * 4);
+    return PT_OK;
+}
 int pt_bvh2_to_bvh4_wide(const uint32_t* bvh2, uint64_t bvh2_words, uint32_t* out, uint64_t out_words) {
     if (!bvh2 || !out) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_bvh2_to_bvh4_wide: null pointer");
     std::vector<uint32_t> v; std::string err;
@@ -813,8 +833,11 @@ int pt_set_bvh2(PtContext* ctx, const uint32_t* bvh2, uint64_t words) {
     return upload_wide(ctx, b4.data(), b4.size());
 }
 
-int pt_build_bvh(PtContext* ctx) {
+int pt_build_bvh(PtContext* ctx) { return pt_build_bvh_accel(ctx, PT_ACCEL_REFERENCE); }
+
+int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     if (int rc = bind(ctx)) return rc;
+    if (accel > PT_ACCEL_PLOC) return fail(ctx, PT_ERR_INVALID_ARG, "pt_build_bvh_accel: accel must be 0 (reference), 1 (area collapse) or 2 (PLOC)");
     if (int rc = flush_pending(ctx)) return rc;
     if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_build_bvh: no triangles uploaded");
     const uint32_t n = ctx->num_tris;
@@ -834,7 +857,11 @@ int pt_build_bvh(PtContext* ctx) {
     PT_HIP(ctx, ctx->d_code_tmp.ensure(n)); PT_HIP(ctx, ctx->d_index_tmp.ensure(n));
     PT_HIP(ctx, ctx->d_node2.ensure(nn2)); PT_HIP(ctx, ctx->d_child_pos.ensure(nn2)); PT_HIP(ctx, ctx->d_subtree.ensure(nn2));
     PT_HIP(ctx, ctx->d_ids.ensure(nn2)); PT_HIP(ctx, ctx->d_bnd.ensure(size_t(nn2) * 3));
-    const size_t temp_bytes = ptk::build_temp_bytes(n);
+    size_t temp_bytes = ptk::build_temp_bytes(n);
+    if (accel == PT_ACCEL_PLOC) {
+        temp_bytes = std::max(temp_bytes, ptk::ploc_temp_bytes(n));
+        PT_HIP(ctx, ctx->d_ploc.ensure(ptk::ploc_words(n)));
+    }
     PT_HIP(ctx, ctx->d_build_temp.ensure(temp_bytes));
     if (!ctx->h_word) PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_word, 64, hipHostMallocDefault));
     PT_HIP(ctx, ctx->d_bvh4.ensure(1 + size_t(nn2) * 8));      // M <= 2N-1 nodes
@@ -846,12 +873,22 @@ int pt_build_bvh(PtContext* ctx) {
     ctx->have_bvh = false; ctx->have_bvh2 = false;
     PT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh2.ptr, &nn2, 4, hipMemcpyHostToDevice, ctx->stream));   // BVH2[0] = numNodes2, PathTracer.js:699
     PT_HIP(ctx, ptk::launch_morton_sort(B, ctx->d_tris9.ptr, n, ctx->stream));
-    PT_HIP(ctx, ptk::launch_lbvh2(ctx->d_bvh2.ptr, ctx->d_tris9.ptr, ctx->d_morton.ptr, ctx->d_triidx.ptr, ctx->d_parent.ptr, ctx->d_flags.ptr, n, false, ctx->stream));
-    ctx->bvh2_refit_pending = true;                 // internal BVH2 bounds: on demand (pt_read_bvh2)
+    if (accel == PT_ACCEL_PLOC) {                   // PLOC topology, LBVH leaves, the reference's refit
+        uint32_t iterations = 0;
+        hipError_t e = ptk::build_ploc_on_device(B, ctx->d_ploc.ptr, ctx->d_tris9.ptr, n, ctx->d_bvh2.ptr, ctx->d_parent.ptr, ctx->d_flags.ptr, &iterations, ctx->stream);
+        if (e == hipErrorInvalidValue) return fail(ctx, PT_ERR_BAD_BVH, "pt_build_bvh_accel: a PLOC iteration merged no pair");
+        PT_HIP(ctx, e);
+        ctx->bvh2_refit_pending = false;
+    } else {
+        // accel 1: the area-guided collapse reads the internal bounds, so the refit runs now (the reference's complete BVH2)
+        PT_HIP(ctx, ptk::launch_lbvh2(ctx->d_bvh2.ptr, ctx->d_tris9.ptr, ctx->d_morton.ptr, ctx->d_triidx.ptr, ctx->d_parent.ptr, ctx->d_flags.ptr, n,
+                                      accel == PT_ACCEL_AREA_COLLAPSE, ctx->stream));
+        ctx->bvh2_refit_pending = accel == PT_ACCEL_REFERENCE;     // internal BVH2 bounds: on demand (pt_read_bvh2)
+    }
     ctx->num_nodes2 = nn2;
     uint32_t m = 0;
     {
-        hipError_t e = ptk::collapse_on_device(B, ctx->d_bvh2.ptr, n, ctx->d_bvh4.ptr, &m, ctx->stream);
+        hipError_t e = ptk::collapse_on_device(B, ctx->d_bvh2.ptr, n, ctx->d_bvh4.ptr, &m, accel != PT_ACCEL_REFERENCE, ctx->stream);
         if (e == hipErrorInvalidValue) return fail(ctx, PT_ERR_BAD_BVH, "pt_build_bvh: the LBVH2 is not a tree of 2N-1 nodes");
         PT_HIP(ctx, e);
     }

@@ -141,8 +141,23 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 __device__ __forceinline__ bool leaf2(const uint32_t* __restrict__ bvh2, uint32_t node) { return (bvh2[1 + (size_t)node * 6 + 5] & kLeaf) != 0u; }
 
+__device__ __forceinline__ float half_exact(uint32_t h);
+// surface area of a BVH2 node from its stored f16 box words, decoded exactly: ((dx*dy) + (dy*dz)) + (dz*dx), f32, no fma
+// (-ffp-contract=off; pt_host.cpp::node_area2 is the same expression)
+__device__ __forceinline__ float node_area2(const uint32_t* __restrict__ bvh2, uint32_t node) {
+    const uint32_t* p = bvh2 + 1 + (size_t)node * 6;
+    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+    const float dx = half_exact(w1 >> 16) - half_exact(w0 & 0xffffu);
+    const float dy = half_exact(w2 & 0xffffu) - half_exact(w0 >> 16);
+    const float dz = half_exact(w2 >> 16) - half_exact(w1 & 0xffffu);
+    return ((dx * dy) + (dy * dz)) + (dz * dx);
+}
+
 // one thread per BVH4 node of this level: greedy expansion of its BVH2 subtree top into <= 4 entries
-// (repeatedly replace the first internal entry by its two children), children appended to the next level
+// (repeatedly replace the first internal entry by its two children), children appended to the next level.
+// AREA (PT_ACCEL_AREA_COLLAPSE / PT_ACCEL_PLOC): replace the internal entry of largest surface area instead -- strict >, so ties and
+// NaN keep the earlier slot; reads the internal BVH2 bounds, which the caller has refitted.
+template <bool AREA>
 __global__ __launch_bounds__(256) void collapse_expand_kernel(const uint32_t* __restrict__ bvh2, uint32_t nn2, uint32_t* __restrict__ node2, uint4* __restrict__ child_pos,
                                                                uint32_t level_begin, uint32_t level_count, uint32_t next_begin, uint32_t capacity, uint32_t* next_count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -156,8 +171,13 @@ __global__ __launch_bounds__(256) void collapse_expand_kernel(const uint32_t* __
             kid[0] = p[3]; kid[1] = p[4]; nk = 2;
             for (int round = 0; round < 2 && nk < 4u; ++round) {
                 uint32_t pos = nk;
-                for (uint32_t s = 0; s < nk; ++s)
-                    if (kid[s] < nn2 && !leaf2(bvh2, kid[s])) { pos = s; break; }
+                float best = 0.0f;
+                for (uint32_t s = 0; s < nk; ++s) {
+                    if (!(kid[s] < nn2 && !leaf2(bvh2, kid[s]))) continue;
+                    if (!AREA) { pos = s; break; }
+                    const float a = node_area2(bvh2, kid[s]);
+                    if (pos == nk || a > best) { pos = s; best = a; }
+                }
                 if (pos == nk) break;
                 const uint32_t* kp = bvh2 + 1 + (size_t)kid[pos] * 6;
                 const uint32_t a = kp[3], b = kp[4];
@@ -303,9 +323,150 @@ __global__ __launch_bounds__(256) void wide_nodes_kernel(const uint32_t* __restr
     o[3] = make_uint4(box[9], box[10], box[11], ref[3]);
 }
 
+// ------------------------------------------------------------------------------------
+// PLOC BVH2 (PT_ACCEL_PLOC; Meister & Bittner, TVCG 2018).  Host twin: pt_host.cpp::build_bvh2_ploc, word for word.
+// Clusters live in SoA ping-pong buffers (six f32 box planes + the BVH2 node id), in Morton order; per iteration:
+// nearest neighbour in [i-R, i+R] (ploc_nn_kernel), mutual pairs and survivors flagged (ploc_flags_kernel), one inclusive
+// scan of (merge << 32 | keep), then merge + stable compaction (ploc_merge_kernel).
+// ------------------------------------------------------------------------------------
+constexpr uint32_t kPlocRadius = 16;      // pt_host.h::kPlocRadius
+constexpr uint32_t kPlocSpan = 256u + 2u * kPlocRadius;
+
+__device__ __forceinline__ float sel_min(float a, float b) { return b < a ? b : a; }    // pt_host.cpp: the same expressions
+__device__ __forceinline__ float sel_max(float a, float b) { return b > a ? b : a; }
+
+__global__ __launch_bounds__(256) void ploc_init_kernel(const float* __restrict__ tris, const uint32_t* __restrict__ tri_index, uint32_t n,
+                                                         float* __restrict__ box, uint32_t* __restrict__ node) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float* t = tris + (size_t)tri_index[k] * 9;
+    for (int a = 0; a < 3; ++a) {
+        box[(size_t)a * n + k] = sel_min(sel_min(t[a], t[3 + a]), t[6 + a]);
+        box[(size_t)(3 + a) * n + k] = sel_max(sel_max(t[a], t[3 + a]), t[6 + a]);
+    }
+    node[k] = (n - 1u) + k;
+}
+
+// one 256-thread block per 256 clusters; the 256 + 2R boxes it reads are staged in LDS as SoA.  Key (d, min(i,j), max(i,j)),
+// d = area of the union box (lower position's box first), NaN as +inf: a total order, so the smallest pair is mutual.
+__global__ __launch_bounds__(256) void ploc_nn_kernel(const float* __restrict__ box, uint32_t stride, uint32_t count, uint32_t* __restrict__ nn) {
+    __shared__ float sb[6][kPlocSpan];
+    const uint32_t base = blockIdx.x * 256u;
+    for (uint32_t t = threadIdx.x; t < kPlocSpan; t += 256u) {
+        const int64_t g = (int64_t)base + t - (int64_t)kPlocRadius;
+        if (g >= 0 && g < (int64_t)count)
+            for (int a = 0; a < 6; ++a) sb[a][t] = box[(size_t)a * stride + (size_t)g];
+    }
+    __syncthreads();
+    const uint32_t i = base + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t lo = i >= kPlocRadius ? i - kPlocRadius : 0u;
+    const uint32_t hi = (count - 1u - i) > kPlocRadius ? i + kPlocRadius : count - 1u;
+    float bd = 0.0f; uint32_t bj = kNone, blo = 0u, bhi = 0u;
+    for (uint32_t j = lo; j <= hi; ++j) {
+        if (j == i) continue;
+        const uint32_t a = i < j ? i : j, b = i < j ? j : i;
+        const uint32_t la = a + kPlocRadius - base, lb = b + kPlocRadius - base;
+        const float dx = sel_max(sb[3][la], sb[3][lb]) - sel_min(sb[0][la], sb[0][lb]);
+        const float dy = sel_max(sb[4][la], sb[4][lb]) - sel_min(sb[1][la], sb[1][lb]);
+        const float dz = sel_max(sb[5][la], sb[5][lb]) - sel_min(sb[2][la], sb[2][lb]);
+        float d = ((dx * dy) + (dy * dz)) + (dz * dx);
+        if (!(d == d)) d = __uint_as_float(0x7f800000u);
+        if (bj == kNone || d < bd || (d == bd && (a < blo || (a == blo && b < bhi)))) { bd = d; bj = j; blo = a; bhi = b; }
+    }
+    nn[i] = bj;
+}
+
+// flags[i] = (merge << 32) | keep: merge = i is the lower end of a mutual pair, keep = i survives (as itself or as the merged cluster)
+__global__ __launch_bounds__(256) void ploc_flags_kernel(const uint32_t* __restrict__ nn, uint32_t count, unsigned long long* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t j = nn[i];
+    const bool mutual = j < count && nn[j] == i;
+    const unsigned long long merge = (mutual && i < j) ? 1ull : 0ull, keep = (mutual && j < i) ? 0ull : 1ull;
+    flags[i] = (merge << 32) | keep;
+}
+
+// merge + stable compaction: a merging cluster becomes internal node internal-1-(created + rank) (ids count down in creation order:
+// iteration, then position), left = its own node, right = its partner's
+__global__ __launch_bounds__(256) void ploc_merge_kernel(const float* __restrict__ box_in, const uint32_t* __restrict__ node_in, const uint32_t* __restrict__ nn,
+                                                          const unsigned long long* __restrict__ flags, const unsigned long long* __restrict__ scan,
+                                                          uint32_t count, uint32_t stride, uint32_t created, uint32_t internal,
+                                                          float* __restrict__ box_out, uint32_t* __restrict__ node_out, uint32_t* __restrict__ bvh2, uint32_t* __restrict__ parent) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const unsigned long long f = flags[i];
+    if (!(f & 1ull)) return;
+    const unsigned long long ex = scan[i] - f;
+    const uint32_t pos = (uint32_t)ex, rank = (uint32_t)(ex >> 32);
+    if (f >> 32) {
+        const uint32_t j = nn[i];
+        const uint32_t id = internal - 1u - (created + rank);
+        const uint32_t l = node_in[i], r = node_in[j];
+        uint32_t* p = bvh2 + 1 + (size_t)id * 6;
+        p[3] = l; p[4] = r; p[5] = 0u;
+        parent[l] = id; parent[r] = id;
+        for (int a = 0; a < 3; ++a) {
+            box_out[(size_t)a * stride + pos] = sel_min(box_in[(size_t)a * stride + i], box_in[(size_t)a * stride + j]);
+            box_out[(size_t)(3 + a) * stride + pos] = sel_max(box_in[(size_t)(3 + a) * stride + i], box_in[(size_t)(3 + a) * stride + j]);
+        }
+        node_out[pos] = id;
+    } else {
+        for (int a = 0; a < 6; ++a) box_out[(size_t)a * stride + pos] = box_in[(size_t)a * stride + i];
+        node_out[pos] = node_in[i];
+    }
+}
+
 inline uint32_t blocks(uint32_t n) { return (n + 255u) / 256u; }
 
 } // namespace
+
+size_t ploc_words(uint32_t n) { return (size_t)n * 19u; }
+
+size_t ploc_temp_bytes(uint32_t n) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n);
+    return bytes;
+}
+
+hipError_t build_ploc_on_device(const BuildBuffers& B, uint32_t* ploc, const float* tris9, uint32_t n, uint32_t* bvh2, uint32_t* parent, uint32_t* flags2,
+                                uint32_t* iterations, hipStream_t stream) {
+    *iterations = 0;
+    if (n == 0) return hipSuccess;
+    // ploc_words(n) words: flags, scan (u64 each) | 2 x (six box planes, node ids) | nearest neighbours
+    unsigned long long* flags = (unsigned long long*)ploc;
+    unsigned long long* scan = flags + n;
+    float* box[2] = {(float*)(ploc + 4 * (size_t)n), (float*)(ploc + 11 * (size_t)n)};
+    uint32_t* node[2] = {ploc + 10 * (size_t)n, ploc + 17 * (size_t)n};
+    uint32_t* nn = ploc + 18 * (size_t)n;
+    const uint32_t internal = n - 1u;
+    hipLaunchKernelGGL(ploc_init_kernel, dim3(blocks(n)), dim3(256), 0, stream, tris9, B.tri_index, n, box[0], node[0]);
+    hipError_t e = hipGetLastError(); if (e != hipSuccess) return e;
+    uint32_t count = n, created = 0, cur = 0, iter = 0;
+    unsigned long long* host = (unsigned long long*)B.host_word;
+    while (count > 1u) {
+        if (iter >= n) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ploc_nn_kernel, dim3(blocks(count)), dim3(256), 0, stream, box[cur], n, count, nn);
+        hipLaunchKernelGGL(ploc_flags_kernel, dim3(blocks(count)), dim3(256), 0, stream, nn, count, flags);
+        e = hipGetLastError(); if (e != hipSuccess) return e;
+        size_t bytes = B.temp_bytes;
+        e = hipcub::DeviceScan::InclusiveSum(B.temp, bytes, (const unsigned long long*)flags, scan, (int)count, stream); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ploc_merge_kernel, dim3(blocks(count)), dim3(256), 0, stream, box[cur], node[cur], nn, flags, scan, count, n, created, internal,
+                           box[cur ^ 1u], node[cur ^ 1u], bvh2, parent);
+        e = hipGetLastError(); if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(host, scan + (count - 1u), sizeof(unsigned long long), hipMemcpyDeviceToHost, stream); if (e != hipSuccess) return e;
+        e = hipStreamSynchronize(stream); if (e != hipSuccess) return e;
+        const uint32_t kept = (uint32_t)*host, merged = (uint32_t)(*host >> 32);
+        ++iter;
+        if (merged == 0u || created + merged > internal || kept >= count) return hipErrorInvalidValue;    // no progress: not a PLOC step
+        created += merged; count = kept; cur ^= 1u;
+    }
+    *iterations = iter;
+    // leaves exactly as launch_lbvh2 writes them, then the reference's refit over the new parent[] (root's parent invalid, arrival flags zero)
+    e = hipMemsetAsync(parent, 0xFF, sizeof(uint32_t), stream); if (e != hipSuccess) return e;
+    if (internal) { e = hipMemsetAsync(flags2, 0, sizeof(uint32_t) * internal, stream); if (e != hipSuccess) return e; }
+    return launch_lbvh2_leaves(bvh2, tris9, B.tri_index, parent, flags2, n, stream);
+}
 
 size_t build_temp_bytes(uint32_t num_tris) {
     if (num_tris == 0) return 0;
@@ -332,7 +493,7 @@ hipError_t launch_morton_sort(const BuildBuffers& B, const float* tris9, uint32_
     return hipcub::DeviceRadixSort::SortPairs(B.temp, bytes, (const uint32_t*)B.code_tmp, B.morton, (const uint32_t*)B.index_tmp, B.tri_index, (int)n, 0, 30, stream);
 }
 
-hipError_t collapse_on_device(const BuildBuffers& B, const uint32_t* bvh2, uint32_t num_tris, uint32_t* bvh4, uint32_t* num_nodes4, hipStream_t stream) {
+hipError_t collapse_on_device(const BuildBuffers& B, const uint32_t* bvh2, uint32_t num_tris, uint32_t* bvh4, uint32_t* num_nodes4, bool by_area, hipStream_t stream) {
     *num_nodes4 = 0;
     if (num_tris == 0) return hipSuccess;
     const uint32_t nn2 = 2u * num_tris - 1u;
@@ -343,7 +504,8 @@ hipError_t collapse_on_device(const BuildBuffers& B, const uint32_t* bvh2, uint3
     level_off[0] = 0; level_off[1] = 1;
     for (;;) {
         const uint32_t begin = level_off[levels], count = level_off[levels + 1] - begin;
-        hipLaunchKernelGGL(collapse_expand_kernel, dim3(blocks(count)), dim3(256), 0, stream, bvh2, nn2, B.node2, B.child_pos, begin, count, level_off[levels + 1], nn2, B.counters + levels);
+        if (by_area) hipLaunchKernelGGL(collapse_expand_kernel<true>, dim3(blocks(count)), dim3(256), 0, stream, bvh2, nn2, B.node2, B.child_pos, begin, count, level_off[levels + 1], nn2, B.counters + levels);
+        else         hipLaunchKernelGGL(collapse_expand_kernel<false>, dim3(blocks(count)), dim3(256), 0, stream, bvh2, nn2, B.node2, B.child_pos, begin, count, level_off[levels + 1], nn2, B.counters + levels);
         e = hipGetLastError(); if (e != hipSuccess) return e;
         e = hipMemcpyAsync(B.host_word, B.counters + levels, sizeof(uint32_t), hipMemcpyDeviceToHost, stream); if (e != hipSuccess) return e;
         e = hipStreamSynchronize(stream); if (e != hipSuccess) return e;

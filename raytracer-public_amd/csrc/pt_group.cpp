@@ -296,6 +296,13 @@ int pt_group_build_bvh(PtGroup* g) {
     for (uint32_t r = 0; r < g->n; ++r) G_PT(g, r, pt_build_bvh(g->ctx[r]));      // deterministic: every member ends up with the same BVH2 / BVH4, bit for bit
     return PT_OK;
 }
+int pt_group_build_bvh_accel(PtGroup* g, uint32_t accel) {
+    if (!g) return gfail(nullptr, PT_ERR_INVALID_ARG, "null group");
+    if (accel > PT_ACCEL_PLOC) return gfail(g, PT_ERR_INVALID_ARG, "pt_group_build_bvh_accel: accel must be 0, 1 or 2");
+    if (int rc = flush_group(g)) return rc;
+    for (uint32_t r = 0; r < g->n; ++r) G_PT(g, r, pt_build_bvh_accel(g->ctx[r], accel));   // deterministic, like pt_group_build_bvh
+    return PT_OK;
+}
 int pt_group_set_bvh2(PtGroup* g, const uint32_t* bvh2, uint64_t words) {
     if (!g) return gfail(nullptr, PT_ERR_INVALID_ARG, "null group");
     if (int rc = flush_group(g)) return rc;

@@ -122,7 +122,21 @@ void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32
 static inline float js_min_f(float a, float b) { if (a < b) return a; if (b < a) return b; return std::signbit(a) ? a : b; }
 static inline float js_max_f(float a, float b) { if (a > b) return a; if (b > a) return b; return std::signbit(a) ? b : a; }
 
+// Surface area of a BVH2 node from its stored f16 box words, decoded exactly: ((dx*dy) + (dy*dz)) + (dz*dx) in f32, no fma
+// (pt_build.hip::node_area2 is the same expression)
+static inline float node_area2(const uint32_t* bvh2, uint32_t node) {
+    const uint32_t* p = bvh2 + 1 + size_t(node) * kNode2Stride;
+    const float dx = half_to_float(p[1] >> 16) - half_to_float(p[0] & 0xffffu);
+    const float dy = half_to_float(p[2] & 0xffffu) - half_to_float(p[0] >> 16);
+    const float dz = half_to_float(p[2] >> 16) - half_to_float(p[1] & 0xffffu);
+    return ((dx * dy) + (dy * dz)) + (dz * dx);
+}
+
 bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint32_t>& out, std::string& err) {
+    return collapse_to_bvh4(bvh2, num_tris, false, out, err);
+}
+
+bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std::vector<uint32_t>& out, std::string& err) {
     out.clear();
     if (num_tris == 0) { out.push_back(0u); return true; }
     const uint32_t nn2 = 2 * num_tris - 1;
@@ -148,15 +162,20 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint3
             out[base + 7] = word(cur.node2, 5);
             continue;
         }
-        // greedy: repeatedly replace the first internal entry by its two children until 4 entries
+        // greedy: repeatedly replace the first internal entry (by_area: the first internal entry of largest area; strict >, so ties
+        // and NaN keep the earlier slot) by its two children until 4 entries
         uint32_t kid[4]; uint32_t nk = 2;
         kid[0] = word(cur.node2, 3); kid[1] = word(cur.node2, 4);
         for (;;) {
             if (nk >= 4) break;
             uint32_t pos = nk;
+            float best = 0.0f;
             for (uint32_t i = 0; i < nk; ++i) {
                 if (kid[i] >= nn2) { err = "BVH2 child index out of range"; return false; }
-                if (!leaf(kid[i])) { pos = i; break; }
+                if (leaf(kid[i])) continue;
+                if (!by_area) { pos = i; break; }
+                const float a = node_area2(bvh2, kid[i]);
+                if (pos == nk || a > best) { pos = i; best = a; }
             }
             if (pos == nk) break;
             const uint32_t k = kid[pos];
@@ -185,6 +204,119 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint3
         out[base + 0] = float_to_half_trunc(mn[0]) | (float_to_half_trunc(mn[1]) << 16);
         out[base + 1] = float_to_half_trunc(mn[2]) | (float_to_half_trunc(mx[0]) << 16);
         out[base + 2] = float_to_half_trunc(mx[1]) | (float_to_half_trunc(mx[2]) << 16);
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// PLOC BVH2 (Meister & Bittner, "Parallel Locally-Ordered Clustering for BVH Construction", TVCG 2018), host twin of
+// pt_build.hip's device build.  Clusters start as the Morton-sorted leaves with an f32 box (per-axis min / max of the three
+// vertices); each iteration every cluster i picks the j in [i-R, i+R] minimising (area(box_i u box_j), min(i,j), max(i,j)),
+// mutual pairs merge into a new internal node (ids counting down from N-2 in creation order: iteration, then position), and
+// the survivors are compacted in order.  Then the LBVH's leaf words and the reference's refit (BVHBuilder.wgsl:242-306).
+// ------------------------------------------------------------------------------------
+namespace {
+struct Box { float mn[3], mx[3]; };
+inline float sel_min(float a, float b) { return b < a ? b : a; }       // the same expression on the device
+inline float sel_max(float a, float b) { return b > a ? b : a; }
+inline Box box_union(const Box& a, const Box& b) {                    // a = the cluster at the lower position
+    Box u;
+    for (int k = 0; k < 3; ++k) { u.mn[k] = sel_min(a.mn[k], b.mn[k]); u.mx[k] = sel_max(a.mx[k], b.mx[k]); }
+    return u;
+}
+inline float box_area(const Box& b) {                                 // NaN counts as +inf
+    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
+    const float a = ((dx * dy) + (dy * dz)) + (dz * dx);
+    return a == a ? a : INFINITY;
+}
+// BVHBuilder.wgsl:63-102 (pt_kernels.hip::step_f16 / store_bounds2): round to f16, then one f16 step outwards
+inline uint32_t step_f16(float v, bool up) {
+    const uint32_t bits = float_to_half_rtne(v);
+    uint32_t ord = (bits & 0x8000u) ? ((~bits) & 0xFFFFu) : (bits ^ 0x8000u);
+    ord = up ? ord + 1u : ord - 1u;
+    return ((ord & 0x8000u) ? (ord ^ 0x8000u) : ((~ord) & 0xFFFFu)) & 0xFFFFu;
+}
+inline void store_bounds2(uint32_t* p, const float mn[3], const float mx[3]) {
+    p[0] = step_f16(mn[0], false) | (step_f16(mn[1], false) << 16);
+    p[1] = step_f16(mn[2], false) | (step_f16(mx[0], true) << 16);
+    p[2] = step_f16(mx[1], true) | (step_f16(mx[2], true) << 16);
+}
+} // namespace
+
+bool build_bvh2_ploc(const float* tris, uint32_t n, std::vector<uint32_t>& out, std::string& err) {
+    out.clear();
+    if (n == 0) { out.push_back(0u); return true; }
+    const uint32_t nn2 = 2 * n - 1, internal = n - 1;
+    out.assign(1 + size_t(nn2) * kNode2Stride, 0u);
+    out[0] = nn2;
+    std::vector<uint32_t> morton(n), tri_index(n);
+    morton_codes_sorted(tris, n, morton.data(), tri_index.data());
+    std::vector<Box> box(n), box2(n);
+    std::vector<uint32_t> node(n), node2(n), nn(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const float* t = tris + size_t(tri_index[k]) * 9;
+        for (int a = 0; a < 3; ++a) {
+            box[k].mn[a] = sel_min(sel_min(t[a], t[3 + a]), t[6 + a]);
+            box[k].mx[a] = sel_max(sel_max(t[a], t[3 + a]), t[6 + a]);
+        }
+        node[k] = internal + k;
+    }
+    uint32_t count = n, created = 0;
+    for (uint32_t iter = 0; count > 1; ++iter) {
+        if (iter >= n) { err = "PLOC did not converge"; return false; }
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t lo = i >= kPlocRadius ? i - kPlocRadius : 0u, hi = std::min(count - 1, i + kPlocRadius);
+            float bd = 0.0f; uint32_t bj = kInvalid, blo = 0, bhi = 0;
+            for (uint32_t j = lo; j <= hi; ++j) {
+                if (j == i) continue;
+                const uint32_t a = std::min(i, j), b = std::max(i, j);
+                const float d = box_area(box_union(box[a], box[b]));
+                if (bj == kInvalid || d < bd || (d == bd && (a < blo || (a == blo && b < bhi)))) { bd = d; bj = j; blo = a; bhi = b; }
+            }
+            nn[i] = bj;
+        }
+        uint32_t kept = 0, merged = 0;
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t j = nn[i];
+            const bool mutual = nn[j] == i;
+            if (mutual && j < i) continue;                            // absorbed by cluster j
+            if (mutual) {
+                const uint32_t id = internal - 1u - (created + merged++);
+                uint32_t* p = out.data() + 1 + size_t(id) * kNode2Stride;
+                p[3] = node[i]; p[4] = node[j]; p[5] = 0u;
+                box2[kept] = box_union(box[i], box[j]);
+                node2[kept++] = id;
+            } else {
+                box2[kept] = box[i];
+                node2[kept++] = node[i];
+            }
+        }
+        if (merged == 0) { err = "PLOC iteration merged no pair"; return false; }
+        created += merged;
+        count = kept;
+        std::swap(box, box2); std::swap(node, node2);
+    }
+    // leaves: writeLeaf2 (BVHBuilder.wgsl:124-132, 278-306), exactly the LBVH's leaf words; WGSL min / max as the device's
+    // v_min_f32 / v_max_f32 compute them, -0 below +0 (js_min_f / js_max_f above)
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t ti = tri_index[k];
+        const float* t = tris + size_t(ti) * 9;
+        float mn[3], mx[3];
+        for (int a = 0; a < 3; ++a) { mn[a] = js_min_f(js_min_f(t[a], t[3 + a]), t[6 + a]); mx[a] = js_max_f(js_max_f(t[a], t[3 + a]), t[6 + a]); }
+        uint32_t* p = out.data() + 1 + size_t(internal + k) * kNode2Stride;
+        store_bounds2(p, mn, mx);
+        p[3] = 0u; p[4] = 0u; p[5] = kLeafFlag | (ti & 0x7fffffffu);
+    }
+    // refit (propagateUp, BVHBuilder.wgsl:242-275): children have larger ids than their parent, so descending ids see final children
+    for (uint32_t id = internal; id-- > 0;) {
+        uint32_t* p = out.data() + 1 + size_t(id) * kNode2Stride;
+        const uint32_t* l = out.data() + 1 + size_t(p[3]) * kNode2Stride;
+        const uint32_t* r = out.data() + 1 + size_t(p[4]) * kNode2Stride;
+        const float mn[3] = {js_min_f(half_to_float(l[0] & 0xffffu), half_to_float(r[0] & 0xffffu)), js_min_f(half_to_float(l[0] >> 16), half_to_float(r[0] >> 16)),
+                             js_min_f(half_to_float(l[1] & 0xffffu), half_to_float(r[1] & 0xffffu))};
+        const float mx[3] = {js_max_f(half_to_float(l[1] >> 16), half_to_float(r[1] >> 16)), js_max_f(half_to_float(l[2] & 0xffffu), half_to_float(r[2] & 0xffffu)),
+                             js_max_f(half_to_float(l[2] >> 16), half_to_float(r[2] >> 16))};
+        store_bounds2(p, mn, mx);
     }
     return true;
 }

@@ -22,6 +22,13 @@ uint32_t float_to_half_rtne(float v);           // pinned rounding of WGSL pack2
 void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32_t* tri_index);
 // returns false on a malformed BVH2 (message in err)
 bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint32_t>& out, std::string& err);
+// by_area = true: the area-guided collapse of PT_ACCEL_AREA_COLLAPSE / PT_ACCEL_PLOC -- expand the internal entry of
+// largest surface area instead of the first one; reads the internal BVH2 bounds, so bvh2 must be a complete (refitted) BVH2
+bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std::vector<uint32_t>& out, std::string& err);
+// PLOC BVH2 (PT_ACCEL_PLOC) in the reference's BVH2 layout: u32[1 + 6(2N-1)], root 0, leaves = the LBVH's leaf words,
+// internal bounds = the reference's bottom-up refit on this topology.  The device build (pt_build.hip) equals it word for word.
+constexpr uint32_t kPlocRadius = 16;
+bool build_bvh2_ploc(const float* tris, uint32_t n, std::vector<uint32_t>& out, std::string& err);
 bool promote_to_bvh4_wide(const uint32_t* bvh2, uint64_t words, std::vector<uint32_t>& out, std::string& err);
 
 // ---- device layouts ----------------------------------------------

@@ -127,6 +127,8 @@ uint32_t megakernel_block();
 hipError_t launch_lbvh2(uint32_t* bvh2, const float* tris9, const uint32_t* morton, const uint32_t* tri_index,
                         uint32_t* parent, uint32_t* flags, uint32_t num_tris, bool refit, hipStream_t stream);
 hipError_t launch_lbvh2_refit(uint32_t* bvh2, const uint32_t* parent, uint32_t* flags, uint32_t num_tris, hipStream_t stream);
+// leaf records and the refit walk in one launch, over any topology given by parent[] (parent[root] = 0xFFFFFFFF, flags[0..N-2] zero)
+hipError_t launch_lbvh2_leaves(uint32_t* bvh2, const float* tris9, const uint32_t* tri_index, const uint32_t* parent, uint32_t* flags, uint32_t num_tris, hipStream_t stream);
 // ---- device-side scene build (pt_build.hip) -------------------------------------------------
 constexpr int kBuildCounters = 256;      // one append counter per BVH4 level (an LBVH2 over 30-bit codes + index bits is < 64 deep)
 struct BuildBuffers {
@@ -143,7 +145,15 @@ size_t build_temp_bytes(uint32_t num_tris);
 hipError_t launch_tri_records(const float* tris9, uint32_t num_tris, float4* records, uint32_t* edge_max, hipStream_t stream);
 hipError_t launch_morton_sort(const BuildBuffers& B, const float* tris9, uint32_t num_tris, hipStream_t stream);
 // synchronises the stream once per BVH4 level (the level sizes size the next launch); *num_nodes4 = M on return
-hipError_t collapse_on_device(const BuildBuffers& B, const uint32_t* bvh2, uint32_t num_tris, uint32_t* bvh4, uint32_t* num_nodes4, hipStream_t stream);
+// by_area: the area-guided collapse of PT_ACCEL_AREA_COLLAPSE / PT_ACCEL_PLOC (needs the internal BVH2 bounds)
+hipError_t collapse_on_device(const BuildBuffers& B, const uint32_t* bvh2, uint32_t num_tris, uint32_t* bvh4, uint32_t* num_nodes4, bool by_area, hipStream_t stream);
+// PLOC BVH2 (PT_ACCEL_PLOC) from B.tri_index (launch_morton_sort first): topology, parent[], leaf records and refit bounds.  `ploc` holds
+// ploc_words(n) words, B.temp at least ploc_temp_bytes(n) bytes; synchronises once per iteration (*iterations on return).
+// hipErrorInvalidValue: an iteration merged nothing
+size_t ploc_words(uint32_t num_tris);
+size_t ploc_temp_bytes(uint32_t num_tris);
+hipError_t build_ploc_on_device(const BuildBuffers& B, uint32_t* ploc, const float* tris9, uint32_t num_tris, uint32_t* bvh2, uint32_t* parent, uint32_t* flags,
+                                uint32_t* iterations, hipStream_t stream);
 // B.subtree[i] = 1 for internal node id i, B.ids = its exclusive prefix sum (the wide-node index)
 hipError_t launch_internal_scan(const BuildBuffers& B, const uint32_t* bvh4, uint32_t num_nodes4, hipStream_t stream);
 hipError_t launch_wide_nodes(const BuildBuffers& B, const uint32_t* bvh4, uint32_t num_nodes4, uint4* wide, uint32_t num_tris, uint32_t node_base16, hipStream_t stream);

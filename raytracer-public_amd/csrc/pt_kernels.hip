@@ -720,6 +720,13 @@ hipError_t launch_lbvh2(uint32_t* bvh2, const float* tris9, const uint32_t* mort
     return hipGetLastError();
 }
 
+// leaf records + the bottom-up walk over a parent[] of another builder's topology (PLOC: parent[0] invalid, flags zeroed by the caller)
+hipError_t launch_lbvh2_leaves(uint32_t* bvh2, const float* tris9, const uint32_t* tri_index, const uint32_t* parent, uint32_t* flags, uint32_t num_tris, hipStream_t stream) {
+    if (num_tris == 0) return hipSuccess;
+    hipLaunchKernelGGL((lbvh2_leaves_kernel<true, true>), dim3((num_tris + 255) / 256), dim3(256), 0, stream, bvh2, tris9, tri_index, parent, flags, num_tris);
+    return hipGetLastError();
+}
+
 // the bottom-up walk alone (the arrival flags are still zero from lbvh2_internal_kernel)
 hipError_t launch_lbvh2_refit(uint32_t* bvh2, const uint32_t* parent, uint32_t* flags, uint32_t num_tris, hipStream_t stream) {
     if (num_tris <= 1) return hipSuccess;

@@ -37,6 +37,8 @@ class PathTracer {
       mode: o.mode === undefined ? MODE_REFERENCE : o.mode,
       spp: o.spp || 1, maxBounces: o.maxBounces || 0, seed: o.seed === undefined ? 1 : o.seed,
       accumulate: !!o.accumulate, stats: !!o.stats, bruteForce: !!o.bruteForce,
+      // tree quality of buildBVH (include/mi355pt.h PT_ACCEL_*): 0 = the reference's tree; 1 = area-guided collapse; 2 = PLOC + area-guided collapse
+      accel: o.accel || 0,
     };
     // Several GPUs, still one image per render(): `gpus: N` (devices 0..N-1) or `devices: [..]` makes this PathTracer drive a
     // group of contexts -- pixel tiles interleaved over the GPUs, gathered on the first one over RCCL (pt_group_*, include/mi355pt.h).
@@ -71,8 +73,8 @@ class PathTracer {
   async buildBVH(trianglesData) {                // :671-749
     if (!this.device) return;                    // `if (!device) return`, :673
     const t0 = Date.now();
-    if (this.group) { native().groupSetTriangles(this.group, trianglesData); native().groupBuildBVH(this.group); }
-    else { native().setTriangles(this.device, trianglesData); native().buildBVH(this.device); }
+    if (this.group) { native().groupSetTriangles(this.group, trianglesData); native().groupBuildBVH(this.group, this.options.accel); }
+    else { native().setTriangles(this.device, trianglesData); native().buildBVH(this.device, this.options.accel); }
     this._hasBVH = true;
     console.log("BVH Build Time:", Date.now() - t0, "ms");   // :745-748 prints timings
   }

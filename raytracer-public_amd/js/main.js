@@ -14,6 +14,7 @@
 //        [--gpus N [--transport copy] | --devices 0,0,0]     one image per render() from N GPUs (pixel tiles, RCCL gather)
 //        [--bvh4-wide [--dump-wide data/BVH4_wide.bin]]      traverse the BVH4_wide promotion of the BVH2 (tests/test.cpp: config C3) instead of the collapsed BVH4
 //        [--accumulate]                                      progressive accumulation over the frames (config C5; no warm-up frame then)
+//        [--accel 0|1|2]                                     tree quality of buildBVH (0 = the reference's tree; 1 area-guided collapse; 2 PLOC)
 //        [--cam x,y,z --quat x,y,z,w] [--radiance frame.f32 --triangles tris.f32]
 "use strict";
 const fs = require("fs");
@@ -29,7 +30,7 @@ async function main() {
   const mode = Number(arg("mode", PT.MODE_REFERENCE));
   const devices = arg("devices", null);
   const accumulate = flag("accumulate");
-  const pathTracer = new PT.PathTracer(canvas, { mode: mode, spp: Number(arg("spp", 4)), maxBounces: Number(arg("bounces", 8)), seed: Number(arg("seed", 1)), accumulate: accumulate,
+  const pathTracer = new PT.PathTracer(canvas, { mode: mode, spp: Number(arg("spp", 4)), maxBounces: Number(arg("bounces", 8)), seed: Number(arg("seed", 1)), accumulate: accumulate, accel: Number(arg("accel", 0)),
                                                  gpus: Number(arg("gpus", 1)), devices: devices ? devices.split(",").map(Number) : null, transport: arg("transport", "rccl") });
   const camera = { position: arg("cam", "0,0,2.5").split(",").map(Number), rotation: arg("quat", "0,0,0,1").split(",").map(Number) };   // src/main.js:10-14
 

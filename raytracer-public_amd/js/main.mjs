@@ -4,6 +4,7 @@
 // requestAnimationFrame, the BVH2 dump written to data/BVH2.bin instead of POSTed to /api/write.  (No top-level await: Node 12.)
 //   node raytracer-public_amd/js/main.mjs [--frames N] [--width W --height H] [--glb path] [--tris N] [--mode 0|1|2 --spp S --bounces B --seed K]
 //        [--cam x,y,z --quat x,y,z,w] [--bvh2 data/BVH2.bin] [--dump data/BVH2.bin | --dump none] [--radiance frame.f32 --triangles tris.f32]
+//        [--accel 0|1|2]   tree quality of buildBVH (this build's extension; 0 = the reference's tree)
 // A GLB that exists and cannot be read ends the process with a non-zero status (the reference has no catch, src/main.js:20-23); only a file that
 // is not there falls back to the procedural stand-in.
 import * as PT from "./libs/PathTracer.js";
@@ -15,7 +16,7 @@ function arg(name, dflt) { const i = process.argv.indexOf("--" + name); return i
 
 async function main() {
   const canvas = { width: Number(arg("width", 1920)), height: Number(arg("height", 1080)) };        // index.html:10
-  const pathTracer = new PT.PathTracer(canvas, { mode: Number(arg("mode", PT.MODE_REFERENCE)), spp: Number(arg("spp", 4)), maxBounces: Number(arg("bounces", 8)), seed: Number(arg("seed", 1)) });   // src/main.js:8 (options: this build's extension)
+  const pathTracer = new PT.PathTracer(canvas, { mode: Number(arg("mode", PT.MODE_REFERENCE)), spp: Number(arg("spp", 4)), maxBounces: Number(arg("bounces", 8)), seed: Number(arg("seed", 1)), accel: Number(arg("accel", 0)) });   // src/main.js:8 (options: this build's extension)
   const camera = { position: arg("cam", "0,0,2.5").split(",").map(Number), rotation: arg("quat", "0,0,0,1").split(",").map(Number) };   // src/main.js:10-14
 
   await pathTracer.initialize();                                                                     // src/main.js:16

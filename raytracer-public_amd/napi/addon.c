@@ -212,10 +212,23 @@ static napi_value fn_set_triangles(napi_env env, napi_callback_info info) {   /*
     PT_CALL(ctx, pt_set_triangles(ctx, (const float*)d, (uint32_t)(len / 9)), "pt_set_triangles");
     return NULL;
 }
+/* optional second argument of buildBVH / groupBuildBVH: the tree-quality level (PT_ACCEL_*), 0 when absent or undefined */
+static int get_accel(napi_env env, napi_callback_info info, napi_value* argv, uint32_t* accel) {
+    size_t argc = 2;
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 1) { napi_throw_type_error(env, NULL, "wrong number of arguments"); return 0; }
+    *accel = 0;
+    if (argc >= 2) {
+        napi_valuetype t; napi_typeof(env, argv[1], &t);
+        if (t == napi_number) *accel = get_u32(env, argv[1]);
+        else if (t != napi_undefined) { napi_throw_type_error(env, NULL, "accel must be a number"); return 0; }
+    }
+    return 1;
+}
 static napi_value fn_build_bvh(napi_env env, napi_callback_info info) {       /* buildBVH, PathTracer.js:671-749 */
-    napi_value argv[1]; if (!get_args(env, info, 1, argv)) return NULL;
+    napi_value argv[2]; uint32_t accel; if (!get_accel(env, info, argv, &accel)) return NULL;
     PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    PT_CALL(ctx, pt_build_bvh(ctx), "pt_build_bvh");
+    if (accel == PT_ACCEL_REFERENCE) PT_CALL(ctx, pt_build_bvh(ctx), "pt_build_bvh");
+    else PT_CALL(ctx, pt_build_bvh_accel(ctx, accel), "pt_build_bvh_accel");
     return NULL;
 }
 static napi_value fn_read_bvh2(napi_env env, napi_callback_info info) {       /* readBVH2, PathTracer.js:485 */
@@ -441,9 +454,10 @@ static napi_value fn_group_set_triangles(napi_env env, napi_callback_info info) 
     return NULL;
 }
 static napi_value fn_group_build_bvh(napi_env env, napi_callback_info info) {
-    napi_value argv[1]; if (!get_args(env, info, 1, argv)) return NULL;
+    napi_value argv[2]; uint32_t accel; if (!get_accel(env, info, argv, &accel)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PTG_CALL(g, pt_group_build_bvh(g), "pt_group_build_bvh");
+    if (accel == PT_ACCEL_REFERENCE) PTG_CALL(g, pt_group_build_bvh(g), "pt_group_build_bvh");
+    else PTG_CALL(g, pt_group_build_bvh_accel(g, accel), "pt_group_build_bvh_accel");
     return NULL;
 }
 static napi_value group_set_bvh(napi_env env, napi_callback_info info, int four) {
