@@ -240,6 +240,46 @@ PT_API int pt_read_accum(PtContext* ctx, float* dst, uint64_t dst_floats);
  * afterwards restarts the accumulation, like it does for one that was rendered. */
 PT_API int pt_set_accum(PtContext* ctx, const PtAccumInfo* info, const float* src);
 
+/* ---- batched ray queries: what does a ray hit? (an extension beyond the reference) ------------------
+ * The reference asks this only in its debug tool (tests/test.py:149-230, traverse_bvh_debug: one ray over a whole tree).
+ *
+ * Closest hit (default): the renderer's single-ray traversal (render_rays_kernel, PT_MODE_REFERENCE) over the context's CURRENT tree,
+ * whatever set it -- pt_build_bvh / pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2: the same visit order, the same tie-breaking
+ * (first minimum in slot order), the same silent drop of pushes at 64 stack entries, the same Moller-Trumbore acceptance
+ * (t > 1e-7 and strictly t < best).  `best` starts at min(t_max, 1e30): with t_max = +inf a result is exactly the oracle's
+ * (oracle/pt_oracle.cpp::orc_trace_ray).  A smaller t_max prunes boxes and triangles at t >= t_max from the start.
+ *   hit:  t = the accepted test's t, bit for bit; prim = the triangle index; u, v = the barycentrics of that test (recomputed after the
+ *         traversal from the triangle's record with the same arithmetic: the same bits).
+ *   miss: t = +INFINITY, prim = 0xFFFFFFFF, u = v = 0.
+ * PT_TRACE_ANY_HIT: the first accepted hit in traversal order ends the ray (the renderer's shadow-ray semantics; t and prim equal
+ *   orc_trace_ray(..., anyhit = 1)).
+ * Rays with no traversal: a NaN in org, dir or t_max, or t_max <= 0: a miss.
+ * Scene contents: triangles only.  Spheres (pt_set_spheres) take no part in ray queries.
+ * Ordering: frames queued by pt_set_batch are launched first (as pt_flush does), so stream order is call order; a scene change after a
+ *   query does not change its results.  pt_trace_rays does not wait: the caller's buffers must stay allocated until a later
+ *   pt_synchronize has returned (the rule of pt_set_output_buffer).
+ * Errors: no triangles + tree: PT_ERR_NO_SCENE.  A NULL or non-16-byte-aligned pointer, unknown flags or n > UINT32_MAX:
+ *   PT_ERR_INVALID_ARG (checked before the scene).  n = 0: PT_OK, nothing is launched.
+ * PT_TRACE_STATS: the counting variant (one ray per thread) fills pt_get_stats like a PT_FLAG_STATS render: rays_closest or rays_shadow,
+ *   nodes_examined, tris_tested, stack_drops and max_stack, counted as the oracle counts them (samples = 0).
+ * PT_TRACE_SIMPLE_KERNEL: the one-ray-per-thread kernel instead of the persistent one (A/B checks); the results are the same. */
+typedef struct PtRay { float org[3]; float t_max; float dir[3]; uint32_t reserved; } PtRay;   /* 32 B, 16-byte aligned arrays; reserved: ignored */
+typedef struct PtHit { float t; uint32_t prim; float u, v; } PtHit;                           /* 16 B */
+enum {
+    PT_TRACE_ANY_HIT = 1u,
+    PT_TRACE_STATS = 2u,
+    PT_TRACE_SIMPLE_KERNEL = 4u
+};
+/* n rays from device memory, n hits into device memory (rays_device, hits_device: 16-byte aligned, on the context's device).
+ * Asynchronous on the context's stream (pt_get_stream). */
+PT_API int pt_trace_rays(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* hits_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the hits are written. */
+PT_API int pt_trace_rays_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, PtHit* hits);
+/* The rays PT_MODE_REFERENCE traces, with identical bits: one through each pixel centre of params (width, height, focal, aspect,
+ * cam_pos, cam_quat; renderer.wgsl:387-395), row-major (pixel (px, py) at py * width + px), t_max = +inf, reserved = 0.
+ * width * height PtRay records into rays_device (16-byte aligned).  Needs no scene.  Asynchronous on the context's stream. */
+PT_API int pt_camera_rays(PtContext* ctx, const PtRenderParams* params, void* rays_device);
+
 /* ---- pixel-tile sharding across GPUs (one context per GPU / rank) ------------------ */
 
 /* Number of 8x8 tiles / pixels-slots this rank owns for a W x H frame split tile_count ways. */

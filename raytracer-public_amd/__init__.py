@@ -13,6 +13,7 @@ context without a HIP device raises ``PtError``.
 import ctypes as C
 import math
 import os
+import sys
 
 import numpy as np
 
@@ -27,6 +28,9 @@ PT_FLAG_COMPACT = 8
 SCENE_DRAGON_CLASS, SCENE_SPONZA_CLASS = 0, 1
 # opt-in tree quality of build_bvh (include/mi355pt.h PT_ACCEL_*): 0 = the reference's tree
 PT_ACCEL_REFERENCE, PT_ACCEL_AREA_COLLAPSE, PT_ACCEL_PLOC = 0, 1, 2
+# batched ray queries (include/mi355pt.h pt_trace_rays)
+PT_TRACE_ANY_HIT, PT_TRACE_STATS, PT_TRACE_SIMPLE_KERNEL = 1, 2, 4
+PRIM_NONE = 0xFFFFFFFF
 
 
 class PtError(RuntimeError):
@@ -57,6 +61,16 @@ class PtStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class PtRay(C.Structure):
+    """include/mi355pt.h PtRay (32 B); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per ray."""
+    _fields_ = [("org", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class PtHit(C.Structure):
+    """include/mi355pt.h PtHit (16 B): t (+inf on a miss), prim (0xFFFFFFFF on a miss), barycentrics u, v."""
+    _fields_ = [("t", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
+
+
 class PtAccumInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
                 ("compact", C.c_uint32), ("samples", C.c_uint32), ("floats", C.c_uint64)]
@@ -71,6 +85,7 @@ EXPORTS = [
     "pt_read_bvh4", "pt_set_spheres", "pt_scene_info", "pt_render", "pt_last_render_ms", "pt_set_batch", "pt_flush", "pt_timing_begin", "pt_timing_collect", "pt_timing_collect_spans", "pt_set_compact_buffer", "pt_set_output_buffer", "pt_get_stats", "pt_read_radiance",
     "pt_read_rgba8", "pt_read_tonemapped", "pt_tile_layout", "pt_tile_ids", "pt_compact_radiance", "pt_deinterleave", "pt_deinterleave_batch", "pt_buffer_busy",
     "pt_accum_info", "pt_read_accum", "pt_set_accum",
+    "pt_trace_rays", "pt_trace_rays_host", "pt_camera_rays",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
     "pt_group_build_bvh_accel",
@@ -97,11 +112,46 @@ def _load():
     return lib
 
 
+# torch ships its own copy of the HIP runtime, and one process can drive the GPU through one copy only: libmi355pt binds to torch's when
+# torch was imported first (bench.py does that).  The torch route of the ray queries needs that, and checks it.
+_TORCH_FIRST = "torch" in sys.modules
 lib = _load()
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+def _aligned_zeros(shape, dtype, align=16):
+    """A zeroed numpy array whose data starts on an `align`-byte boundary (what the ray-query entry points require)."""
+    dtype = np.dtype(dtype)
+    n = int(np.prod(shape)) * dtype.itemsize
+    raw = np.zeros(n + align, np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off: off + n].view(dtype).reshape(shape)
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _torch_route():
+    if not _TORCH_FIRST:
+        raise RuntimeError("the torch route of the ray queries needs `import torch` before this package is imported: both must use "
+                           "the same HIP runtime (torch ships its own)")
+
+
+def pack_rays(origins, directions, t_max=None):
+    """numpy: (n, 8) float32 PtRay records (org xyz, t_max, dir xyz, 0) in a 16-byte aligned buffer; t_max None = +inf, a scalar or (n,)."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape: %s vs %s" % (o.shape, d.shape))
+    out = _aligned_zeros((o.shape[0], 8), np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = np.inf if t_max is None else np.broadcast_to(np.asarray(t_max, np.float32), (o.shape[0],))
+    out[:, 4:7] = d
+    return out
 
 
 def _check(rc, ctx=None):
@@ -425,6 +475,88 @@ class Context:
         data = np.ascontiguousarray(data, np.float32).reshape(-1)
         assert data.size == info.floats
         self._ck(lib.pt_set_accum(self.h, C.byref(info), _p(data, C.c_float)))
+
+    # ---- batched ray queries (an extension beyond the reference; include/mi355pt.h) ----
+    def trace_rays(self, origins, directions=None, t_max=None, any_hit=False, stats=False, simple=False):
+        """What does each ray hit?  Returns (t, prim, u, v): t = +inf and prim = 0xFFFFFFFF on a miss.
+
+        origins, directions: (n, 3) float32, or origins alone as (n, 8) PtRay records (directions=None; t_max then comes from the records).
+        numpy arrays take the host route (staged, returns when done).  torch tensors on the context's device take the device route:
+        zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's current stream both ways; the
+        results are torch tensors (prim as torch.uint32).  stats: the counting kernel, counters in stats() afterwards."""
+        flags = (PT_TRACE_ANY_HIT if any_hit else 0) | (PT_TRACE_STATS if stats else 0) | (PT_TRACE_SIMPLE_KERNEL if simple else 0)
+        if _is_torch(origins):
+            return self._trace_rays_torch(origins, directions, t_max, flags)
+        if directions is None:
+            rays = np.asarray(origins, np.float32).reshape(-1, 8)
+            if rays.ctypes.data % 16 or not rays.flags.c_contiguous or t_max is not None:
+                r2 = _aligned_zeros(rays.shape, np.float32); r2[...] = rays; rays = r2     # (the caller's records are never written)
+                if t_max is not None:
+                    rays[:, 3] = t_max
+        else:
+            rays = pack_rays(origins, directions, t_max)
+        n = rays.shape[0]
+        hits = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_trace_rays_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags),
+                                        hits.ctypes.data_as(C.POINTER(PtHit))))
+        f = hits.view(np.float32)
+        return f[:, 0].copy(), hits[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+
+    def trace_rays_device(self, rays_ptr, n, hits_ptr, flags=0):
+        """Raw device route: n PtRay records at rays_ptr -> n PtHit records at hits_ptr (16-byte aligned device pointers).  Asynchronous on
+        the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_trace_rays(self.h, C.c_void_p(rays_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(hits_ptr)))
+
+    def camera_rays_device(self, params, rays_ptr):
+        """Raw device route of camera_rays: width * height PtRay records at rays_ptr, asynchronous on the context's stream."""
+        self._ck(lib.pt_camera_rays(self.h, C.byref(params), C.c_void_p(rays_ptr)))
+
+    def _on_context_stream(self, device, launch):
+        """Run launch() on the context's stream, ordered after and before torch's current stream on `device` (events only, no host wait)."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        mine = self.get_stream()
+        if cur.cuda_stream == mine:
+            launch()
+            return
+        ext = torch.cuda.ExternalStream(mine, device=device)
+        before = torch.cuda.Event(); before.record(cur); ext.wait_event(before)
+        launch()
+        after = torch.cuda.Event(); after.record(ext); cur.wait_event(after)
+
+    def _trace_rays_torch(self, origins, directions, t_max, flags):
+        _torch_route()
+        import torch
+        dev = origins.device
+        if dev.type != "cuda":
+            raise ValueError("trace_rays: torch tensors must be on the context's GPU (got %s)" % dev)
+        if directions is None:
+            rays = origins.reshape(-1, 8)
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.data_ptr() % 16:
+                rays = rays.to(torch.float32).contiguous().clone()
+            if t_max is not None:
+                rays = rays.clone(); rays[:, 3] = t_max
+        else:
+            o = origins.reshape(-1, 3).to(torch.float32); d = directions.reshape(-1, 3).to(device=dev, dtype=torch.float32)
+            n = o.shape[0]
+            tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if t_max is None else \
+                torch.as_tensor(t_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+            rays = torch.cat([o, tm, d, torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
+        n = rays.shape[0]
+        hits = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        self._on_context_stream(dev, lambda: self.trace_rays_device(rays.data_ptr(), n, hits.data_ptr(), flags))
+        hf = hits.view(torch.float32)
+        return hf[:, 0], hits.view(torch.uint32)[:, 1], hf[:, 2], hf[:, 3]
+
+    def camera_rays(self, params, device=None):
+        """The rays PT_MODE_REFERENCE traces through each pixel centre of `params` (make_params): a torch (height * width, 8) float32 tensor of
+        PtRay records on the context's GPU, row-major, ordered with torch's current stream.  Feed it to trace_rays for depth / id buffers or picking."""
+        _torch_route()
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        rays = torch.empty((params.height * params.width, 8), dtype=torch.float32, device=dev)
+        self._on_context_stream(dev, lambda: self.camera_rays_device(params, rays.data_ptr()))
+        return rays
 
     def buffer_busy(self, device_ptr, nbytes):
         b = C.c_int()

@@ -90,6 +90,8 @@ struct PtContext {
     DevBuf<uint4> d_child_pos; DevBuf<unsigned char> d_build_temp; uint32_t* h_word = nullptr;
     DevBuf<uint32_t> d_ploc;         // PT_ACCEL_PLOC cluster buffers (ptk::ploc_words), allocated on first use
     DevBuf<float4> d_spheres; uint32_t num_spheres = 0;
+    // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
+    DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
 
     // frame
     DevBuf<float4> d_out, d_accum, d_compact, d_compact_accum;
@@ -608,7 +610,8 @@ void pt_destroy(PtContext* ctx) {
     (void)flush_pending(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->d_tris9.release(); ctx->d_scene.release(); ctx->d_bvh2.release(); ctx->d_bvh4.release();
-    ctx->d_spheres.release(); ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
+    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release();
+    ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
     ctx->d_out.release(); ctx->d_accum.release(); ctx->d_compact.release(); ctx->d_compact_accum.release();
     ctx->d_tiles.release(); ctx->d_u32tmp.release(); ctx->d_stats.release();
     ctx->d_wave_times.release();
@@ -1107,6 +1110,80 @@ int pt_render(PtContext* ctx, const PtRenderParams* p) {
     }
     if (ring) ctx->ring_used += 2;
     ctx->timed = !ring;
+    return PT_OK;
+}
+
+// ---- batched ray queries (include/mi355pt.h; pt_rayquery.hip) ----------------------------------------------------------------
+
+static_assert(sizeof(PtRay) == 32 && sizeof(PtHit) == 16, "PtRay / PtHit are read and written as 2 x 16 B and 16 B records");
+
+namespace {
+constexpr uint32_t kTraceFlags = PT_TRACE_ANY_HIT | PT_TRACE_STATS | PT_TRACE_SIMPLE_KERNEL;
+bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
+
+// arguments, then the scene; *proceed = false when there is nothing to launch (n = 0)
+int check_trace(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* hits) {
+    if (flags & ~kTraceFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
+    if (!aligned16(rays) || !aligned16(hits)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays and hits must be non-null and 16-byte aligned");
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+
+// the launch itself: rays / hits in device memory, on the context's stream, behind whatever pt_set_batch still holds
+int trace_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* hits) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
+    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
+    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
+    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
+    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
+    const bool anyhit = (flags & PT_TRACE_ANY_HIT) != 0, stats = (flags & PT_TRACE_STATS) != 0, simple = (flags & PT_TRACE_SIMPLE_KERNEL) != 0;
+    const uint32_t grid = ptk::rayquery_grid(ctx->num_cus);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple) {
+        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
+        PT_HIP(ctx, ctx->d_rq_spill.ensure(ptk::rayquery_spill_entries(grid)));
+    }
+    PT_HIP(ctx, ptk::launch_trace_rays(A, rays, hits, n, anyhit, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+} // namespace
+
+int pt_trace_rays(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* hits_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_trace(ctx, "pt_trace_rays", rays_device, n, flags, hits_device)) return rc;
+    return trace_on_stream(ctx, rays_device, uint32_t(n), flags, hits_device);
+}
+
+int pt_trace_rays_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, PtHit* hits) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_trace(ctx, "pt_trace_rays_host", rays, n, flags, hits)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = trace_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtHit), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_camera_rays(PtContext* ctx, const PtRenderParams* p, void* rays_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: null params");
+    if (!aligned16(rays_device)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: rays must be non-null and 16-byte aligned");
+    if (p->width == 0 || p->height == 0 || p->width > 32768 || p->height > 32768) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: bad resolution");
+    if (int rc = flush_pending(ctx)) return rc;
+    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
+    A.width = p->width; A.height = p->height; A.focal = p->focal; A.aspect = p->aspect;
+    std::memcpy(A.cam, p->cam_pos, 12); std::memcpy(A.quat, p->cam_quat, 16);
+    PT_HIP(ctx, ptk::launch_camera_rays(A, rays_device, ctx->stream));
     return PT_OK;
 }
 

@@ -1,6 +1,6 @@
 // pt_device.h -- device-side arithmetic shared by the HIP kernels (pt_kernels.hip,
-// pt_megakernel.hip): explicit-order f32 vector helpers, the reference's ray setup and slab
-// test, and the build-defined sampling functions of DESIGN.md section 4.
+// pt_megakernel.hip, pt_rayquery.hip): explicit-order f32 vector helpers, the reference's ray setup and slab
+// test, the build-defined sampling functions of DESIGN.md section 4 and the one-ray traversal of the simple kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -243,6 +243,103 @@ __device__ __forceinline__ const uint4* arena_record(const RenderArgs& A, uint32
 __device__ __forceinline__ F3 tri_normal_ref(const RenderArgs& A, uint32_t leaf_ref) {
     const uint4 n = arena_record(A, leaf_ref)[3];
     return f3(__uint_as_float(n.x), __uint_as_float(n.y), __uint_as_float(n.z));
+}
+
+
+// ------------------------------------------------------------------------------------
+// the one-ray traversal of the simple kernels
+// ------------------------------------------------------------------------------------
+struct Counters { uint32_t nodes, tris, drops, maxstack; };
+
+// One-ray BVH4 traversal over the wide layout.  Visit order, tie-breaking and the 64-entry
+// stack cap are those of traverseBVH4Packet (renderer.wgsl:210-346) run with a single active
+// lane: hit children keep slot order, the nearest one (first minimum) trades places with the
+// first hit and is entered next; a stacked child is re-validated at pop by tmin < best.
+// best_init: where `best` starts (kInfT in the renderer; a ray query's min(t_max, kInfT), pt_rayquery.hip).
+// (Used by the one-ray-per-lane kernels, pt_kernels.hip::render_rays_kernel and pt_rayquery.hip::trace_rays_simple_kernel.)
+template <bool ANYHIT, bool STATS>
+__device__ __forceinline__ bool traverse(const RenderArgs& A, const Ray& r, float& best_t, uint32_t& best_tri,
+                                         uint2* __restrict__ stk, Counters& cnt, float best_init = kInfT) {
+    best_t = best_init; best_tri = kInvalidRef;
+    if (A.root_ref == kInvalidRef || A.num_tris == 0u) return false;
+    if (STATS) { cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u; }   // the root record is fetched before its degenerate check (renderer.wgsl:240-244)
+    if (A.root_degenerate) return false;
+    float troot;
+    if (!slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best_t, troot)) return false;
+    uint32_t cur = A.root_ref;
+    int sp = 0;
+    for (;;) {
+        bool need_pop = false;
+        if (cur & kLeaf) {
+            const uint32_t ti4 = cur & 0x7fffffffu;               // packed reference: 4 * triangle index (16-byte units of 64 B records)
+            if (ti4 < 4u * A.num_tris) {                          // renderer.wgsl:262 (an out-of-range leaf points at record num_tris)
+                const uint32_t ti = ti4 >> 2;
+                const float4* tp = (const float4*)arena_record(A, cur);
+                const float4 a = tp[0], b = tp[1], c = tp[2];
+                if (STATS) cnt.tris += 1;
+                const F3 v0 = f3(a.x, b.x, c.x), e1 = f3(a.y, b.y, c.y), e2 = f3(a.z, b.z, c.z);     // axis-major record (pt_host.h::TriRecord)
+                const F3 p = cross3(r.d, e2);                    // renderer.wgsl:185-205
+                const float det = dot3(e1, p);
+                if (!(fabsf(det) < kTriEps)) {
+                    const float inv_det = 1.0f / det;
+                    const F3 s = r.o - v0;
+                    const float u = inv_det * dot3(s, p);
+                    if (!(u < 0.0f || u > 1.0f)) {
+                        const F3 q = cross3(s, e1);
+                        const float v = inv_det * dot3(r.d, q);
+                        if (!(v < 0.0f || (u + v) > 1.0f)) {
+                            const float t = inv_det * dot3(e2, q);
+                            if (t > kTriEps && t < best_t) {
+                                best_t = t; best_tri = ti;
+                                if (ANYHIT) return true;
+                            }
+                        }
+                    }
+                }
+            }
+            need_pop = true;
+        } else {
+            const uint4* np = arena_record(A, cur);
+            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+            float t0, t1, t2, t3;
+            // child-major record (pt_host.h::WideNode): piece k = child k's box words + its reference
+            const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
+            const bool h0 = (r0 < kDegenerateRef) && slab(r, n0.x, n0.y, n0.z, best_t, t0);
+            const bool h1 = (r1 < kDegenerateRef) && slab(r, n1.x, n1.y, n1.z, best_t, t1);
+            const bool h2 = (r2 < kDegenerateRef) && slab(r, n2.x, n2.y, n2.z, best_t, t2);
+            const bool h3 = (r3 < kDegenerateRef) && slab(r, n3.x, n3.y, n3.z, best_t, t3);
+            if (STATS) cnt.nodes += (r0 != kInvalidRef) + (r1 != kInvalidRef) + (r2 != kInvalidRef) + (r3 != kInvalidRef);
+            // nearest = first minimum in slot order (renderer.wgsl:315-318); first = first hit
+            int nslot = -1, fslot = -1; float tn = kInfT, tf = 0.0f; uint32_t rn = kInvalidRef, rf = kInvalidRef;
+            if (h0) { nslot = 0; tn = t0; rn = r0; fslot = 0; tf = t0; rf = r0; }
+            if (h1) { if (nslot < 0 || t1 < tn) { nslot = 1; tn = t1; rn = r1; } if (fslot < 0) { fslot = 1; tf = t1; rf = r1; } }
+            if (h2) { if (nslot < 0 || t2 < tn) { nslot = 2; tn = t2; rn = r2; } if (fslot < 0) { fslot = 2; tf = t2; rf = r2; } }
+            if (h3) { if (nslot < 0 || t3 < tn) { nslot = 3; tn = t3; rn = r3; } if (fslot < 0) { fslot = 3; tf = t3; rf = r3; } }
+            if (nslot < 0) {
+                need_pop = true;
+            } else {
+                // pushes far -> near (renderer.wgsl:336-342); the slot the nearest child left holds the first hit
+#define PT_PUSH(REF, TMIN) do { if (sp < kStackMax) { stk[sp] = make_uint2((REF), __float_as_uint(TMIN)); ++sp; } else if (STATS) { cnt.drops += 1; } } while (0)
+                if (h3) { if (nslot == 3) { if (fslot != 3) PT_PUSH(rf, tf); } else if (fslot != 3) PT_PUSH(r3, t3); }
+                if (h2) { if (nslot == 2) { if (fslot != 2) PT_PUSH(rf, tf); } else if (fslot != 2) PT_PUSH(r2, t2); }
+                if (h1) { if (nslot == 1) { if (fslot != 1) PT_PUSH(rf, tf); } else if (fslot != 1) PT_PUSH(r1, t1); }
+#undef PT_PUSH
+                if (STATS) { const uint32_t depth = (uint32_t)sp + (sp < kStackMax ? 1u : 0u); if (depth > cnt.maxstack) cnt.maxstack = depth; }   // entries incl. the nearest child, if its push fitted
+                if (sp < kStackMax) cur = rn;          // the push of the nearest child would have fitted
+                else { need_pop = true; if (STATS) cnt.drops += 1; }
+            }
+        }
+        if (need_pop) {
+            bool found = false;
+            while (sp > 0) {
+                --sp;
+                const uint2 e = stk[sp];
+                if (__uint_as_float(e.y) < best_t) { cur = e.x; found = true; break; }
+            }
+            if (!found) break;
+        }
+    }
+    return best_tri != kInvalidRef;
 }
 
 

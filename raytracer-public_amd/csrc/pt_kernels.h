@@ -35,6 +35,16 @@
 #ifndef PT_QUAD_LIVE
 #define PT_QUAD_LIVE 16            // paths a wavefront may hold when it re-seats them (16 quads per wavefront)
 #endif
+// batched ray queries (pt_rayquery.hip)
+#ifndef PT_RQ_SHORT_STACK
+#define PT_RQ_SHORT_STACK 12        // LDS stack entries per lane of trace_rays_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_RQ_WAVES_PER_SIMD
+#define PT_RQ_WAVES_PER_SIMD 6      // wavefronts of trace_rays_kernel per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_RQ_FILL
+#define PT_RQ_FILL 8                // idle lanes of a wavefront at which they take the next rays of its chunk
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -165,6 +175,17 @@ hipError_t launch_pack_shares(const float4* compact, uint64_t frame_stride_px, u
                               uint32_t rank, uint32_t count, const uint32_t rect[4], hipStream_t stream);
 hipError_t launch_unpack_frames(const float* gathered, uint64_t rank_stride_floats, uint64_t frame_stride_floats, uint32_t frames, float4* full, uint64_t full_stride_px,
                                 uint32_t width, uint32_t height, uint32_t count, const uint32_t rect[4], uint32_t spp, hipStream_t stream);
+// ---- batched ray queries (pt_rayquery.hip) -------------------------------------------------
+// rays: PtRay[n] (2 x float4 each), hits: PtHit[n] (uint4 each), both 16-byte aligned device memory.  simple or stats: one ray per thread
+// (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel with `grid` wavefronts at most, a queue block of
+// kRqQueueWords 64-bit words (zeroed by the launch) and rayquery_spill_entries(grid) 8-byte spill entries.
+constexpr uint32_t kRqQueueWords = 256;
+uint32_t rayquery_grid(int num_cus);
+size_t rayquery_spill_entries(uint32_t grid);
+hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, uint32_t n, bool anyhit, bool simple, bool stats,
+                             unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// A.width * A.height PtRay records of the PT_MODE_REFERENCE camera (A.focal, A.aspect, A.cam, A.quat), row-major
+hipError_t launch_camera_rays(const RenderArgs& A, void* rays, hipStream_t stream);
 hipError_t launch_rgba8(const float4* src, uint32_t* dst, uint32_t n, hipStream_t stream);
 hipError_t launch_tonemap(const float4* src, uint32_t* dst, uint32_t width, uint32_t height, int from_rgba8, hipStream_t stream);
 

@@ -106,19 +106,41 @@ class PathTracer {
   setBVH2(bvh2U32) { if (this.group) native().groupSetBVH2(this.group, bvh2U32); else native().setBVH2(this.device, bvh2U32); this._hasBVH = true; }
   setBVH4(bvh4U32) { if (this.group) native().groupSetBVH4(this.group, bvh4U32); else native().setBVH4(this.device, bvh4U32); this._hasBVH = true; }
 
-  async render() {                               // :756-822
-    if (!this._hasBVH) return;                   // `if (!this.buffers.BVH) return`, :757
+  _ubo() {
     const numTriangles = (this.trianglesData.length / 9) | 0;
     const fov = (70.0 * Math.PI) / 180;          // :761
     const focal = 1.0 / Math.tan(0.5 * fov);
-    const UBO = new Float32Array([               // :764-787, same 16 floats in the same order
+    return new Float32Array([                    // :764-787, same 16 floats in the same order
       this.canvas.width, this.canvas.height, focal, this.canvas.width / this.canvas.height,
       this.cameraPosition[0], this.cameraPosition[1], this.cameraPosition[2], numTriangles,
       this.cameraQuaternion[0], this.cameraQuaternion[1], this.cameraQuaternion[2], this.cameraQuaternion[3],
       this.frameCount, 0, 0, 0,
     ]);
+  }
+
+  async render() {                               // :756-822
+    if (!this._hasBVH) return;                   // `if (!this.buffers.BVH) return`, :757
+    const UBO = this._ubo();
     if (this.group) native().groupRender(this.group, UBO, this.options);   // every GPU traces its tiles; the gather follows on their streams
     else native().render(this.device, UBO, this.options);                  // asynchronous on the GPU, like queue.submit (:821)
+  }
+
+  // ---- batched ray queries: an extension beyond the reference (include/mi355pt.h pt_trace_rays, DESIGN.md section 13) ----
+  // rays: Float32Array, 8 floats per ray (origin xyz, tMax, direction xyz, 0).  Resolves to { t, prim, u, v } (Float32Array / Uint32Array):
+  // the closest hit (anyHit: the first hit in traversal order) over the current tree; a miss has t = Infinity, prim = 0xFFFFFFFF, u = v = 0.
+  // Triangles only (the spheres of a brute-force scene take no part).  On a group: member 0, which holds the whole scene.
+  async traceRays(rays, options) {
+    const anyHit = !!(options && options.anyHit);
+    return this.group ? native().groupTraceRays(this.group, rays, anyHit) : native().traceRays(this.device, rays, anyHit);
+  }
+  // What is under pixel (x, y) of the current camera (setCameraPosition / setCameraQuaternion)?  The ray render() traces through the
+  // pixel's centre in mode 1 (row 0 at the bottom of the image, as in the radiance); resolves to { hit, t, prim, point }, point = origin + t * direction.
+  async pick(x, y) {
+    const ray = native().cameraRay(this._ubo(), x, y);
+    const r = await this.traceRays(ray);
+    const hit = r.prim[0] !== 0xFFFFFFFF, t = r.t[0];
+    const point = hit ? [0, 1, 2].map((k) => Math.fround(ray[k] + Math.fround(t * ray[4 + k]))) : null;
+    return { hit: hit, t: t, prim: r.prim[0], point: point };
   }
 
   setCameraPosition(x, y, z) { this.cameraPosition = [x, y, z]; }           // :824

@@ -16,6 +16,7 @@
 //        [--accumulate]                                      progressive accumulation over the frames (config C5; no warm-up frame then)
 //        [--accel 0|1|2]                                     tree quality of buildBVH (0 = the reference's tree; 1 area-guided collapse; 2 PLOC)
 //        [--cam x,y,z --quat x,y,z,w] [--radiance frame.f32 --triangles tris.f32]
+//        [--pick X,Y]                                        after the frames: what is under pixel (X, Y), as one JSON line (ray query, an extension)
 "use strict";
 const fs = require("fs");
 const path = require("path");
@@ -99,6 +100,12 @@ async function main() {
   const radiance = arg("radiance", null), trisOut = arg("triangles", null);      // what a test compares with the oracle: the last frame (f32 RGBA) and the triangles it was traced over
   if (radiance) { const img = pathTracer.readRadiance(); fs.writeFileSync(radiance, Buffer.from(img.buffer, img.byteOffset, img.byteLength)); }
   if (trisOut) { const t = pathTracer.trianglesData; fs.writeFileSync(trisOut, Buffer.from(t.buffer, t.byteOffset, t.byteLength)); }
+  const pickAt = arg("pick", null);
+  if (pickAt) {
+    const xy = pickAt.split(",").map(Number);
+    const p = await pathTracer.pick(xy[0], xy[1]);
+    console.log(JSON.stringify({ pick: xy, hit: p.hit, t: p.t === Infinity ? null : p.t, prim: p.prim, point: p.point }));
+  }
   const out = arg("out", null);
   if (out) {      // what the tonemapper pass would have put on the canvas (tonemapper.wgsl)
     const rgba = pathTracer.readTonemapped(true);

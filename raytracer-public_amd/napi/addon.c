@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
+#include <math.h>
 
 #include "mi355pt.h"
 
@@ -314,6 +315,64 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {          /*
     return NULL;
 }
 
+/* ---- batched ray queries (an extension beyond the reference; include/mi355pt.h pt_trace_rays_host) ------------------------- */
+
+/* rays: Float32Array of 8 floats per ray (PtRay: org xyz, t_max, dir xyz, reserved) -> { t: Float32Array, prim: Uint32Array, u, v }.
+ * The records are copied into 16-byte aligned host memory (a typed array's data need not be aligned). */
+static napi_value trace_rays_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value any_v) {
+    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, "traceRays: 8 floats per ray"); return NULL; }
+    bool any = false; napi_get_value_bool(env, any_v, &any);
+    const size_t n = len / 8;
+    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
+    PtHit* hits = (PtHit*)aligned_alloc(16, (n ? n : 1) * sizeof(PtHit));
+    if (!rays || !hits) { free(rays); free(hits); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(rays, d, n * sizeof(PtRay));
+    int rc = pt_trace_rays_host(ctx, rays, n, any ? PT_TRACE_ANY_HIT : 0u, hits);
+    free(rays);
+    if (rc != 0) { free(hits); return throw_pt(env, ctx, rc, "pt_trace_rays_host"); }
+    napi_value o, t, prim, u, v; void *pt, *pp, *pu, *pv;
+    if (!(t = make_typed(env, napi_float32_array, 4, n, &pt)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
+        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(hits); return NULL; }
+    for (size_t i = 0; i < n; ++i) {
+        ((float*)pt)[i] = hits[i].t; ((uint32_t*)pp)[i] = hits[i].prim; ((float*)pu)[i] = hits[i].u; ((float*)pv)[i] = hits[i].v;
+    }
+    free(hits);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_trace_rays(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array rays, anyHit) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return trace_rays_on(env, ctx, argv[1], argv[2]);
+}
+
+/* The camera ray of PT_MODE_REFERENCE through the centre of pixel (x, y) of the UBO's camera, as one PtRay record (8 floats, t_max = +inf):
+ * renderer.wgsl:387-395 in the operation order of pt_device.h::primary_ray -- correctly rounded f32 division and square root, fmaf where it
+ * has fma, nothing contracted (-ffp-contract=off) -- so the same bits as the ray pt_camera_rays writes and mode 1 traces. */
+static napi_value fn_camera_ray(napi_env env, napi_callback_info info) {      /* (UBO Float32Array[16], x, y) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    void* u; size_t len; if (!get_typed(env, argv[0], napi_float32_array, &u, &len)) return NULL;
+    if (len < 16) { napi_throw_range_error(env, NULL, "UBO must hold 16 floats"); return NULL; }
+    const float* ubo = (const float*)u;
+    const float w = (float)(uint32_t)ubo[0], h = (float)(uint32_t)ubo[1], focal = ubo[2], aspect = ubo[3];
+    const float fx = (float)get_u32(env, argv[1]) + 0.5f, fy = (float)get_u32(env, argv[2]) + 0.5f;
+    const float px = fmaf(fx / w, 2.0f, -1.0f), py = fmaf(fy / h, 2.0f, -1.0f);
+    float vx = px * aspect, vy = py, vz = -focal;
+    const float inv = 1.0f / sqrtf((vx * vx + vy * vy) + vz * vz);
+    vx = vx * inv; vy = vy * inv; vz = vz * inv;
+    const float qx = ubo[8], qy = ubo[9], qz = ubo[10], qs = ubo[11];                       /* rotateVectorByQuat, renderer.wgsl:66-72 */
+    const float ux = qy * vz - qz * vy, uy = qz * vx - qx * vz, uz = qx * vy - qy * vx;     /* cross(q.xyz, v) */
+    const float wx = qy * uz - qz * uy, wy = qz * ux - qx * uz, wz = qx * uy - qy * ux;     /* cross(q.xyz, uv) */
+    void* r; napi_value out = make_typed(env, napi_float32_array, 4, 8, &r); if (!out) return NULL;
+    float* ray = (float*)r;
+    ray[0] = ubo[4]; ray[1] = ubo[5]; ray[2] = ubo[6]; ray[3] = INFINITY;
+    ray[4] = fmaf(2.0f, fmaf(qs, ux, wx), vx); ray[5] = fmaf(2.0f, fmaf(qs, uy, wy), vy); ray[6] = fmaf(2.0f, fmaf(qs, uz, wz), vz); ray[7] = 0.0f;
+    return out;
+}
+
 static napi_value fn_set_batch(napi_env env, napi_callback_info info) {       /* frames per persistent launch (1..256) */
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
@@ -480,6 +539,12 @@ static napi_value fn_group_read_bvh2(napi_env env, napi_callback_info info) {  /
     PT_CALL(c0, pt_read_bvh2(c0, (uint32_t*)out, (size / 4) * 4), "pt_read_bvh2");
     return ta;
 }
+static napi_value fn_group_trace_rays(napi_env env, napi_callback_info info) {      /* (group, rays, anyHit): on member 0, which holds the whole scene */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return trace_rays_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_set_batch(napi_env env, napi_callback_info info) {
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -536,6 +601,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render}, {"setBatch", fn_set_batch}, {"flush", fn_flush}, {"lastRenderMs", fn_last_ms}, {"synchronize", fn_sync}, {"getStats", fn_stats},
         {"readRadiance", fn_read_radiance}, {"readRGBA8", fn_read_rgba8}, {"readTonemapped", fn_read_tonemapped},
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
+        {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
         {"groupReadBVH2", fn_group_read_bvh2}, {"groupSetBatch", fn_group_set_batch}, {"groupRender", fn_group_render}, {"groupFlush", fn_group_flush},
