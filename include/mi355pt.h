@@ -280,6 +280,55 @@ PT_API int pt_trace_rays_host(PtContext* ctx, const PtRay* rays, uint64_t n, uin
  * width * height PtRay records into rays_device (16-byte aligned).  Needs no scene.  Asynchronous on the context's stream. */
 PT_API int pt_camera_rays(PtContext* ctx, const PtRenderParams* params, void* rays_device);
 
+/* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
+ * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
+ * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes
+ * every box from the new triangles, in place, on the device.  Child indices, leaf words, node counts and ids are untouched; the
+ * result is a BVH4 in the reference's layout (pt_read_bvh4), so every frame after an update can be checked against the oracle.
+ * The result depends on the topology and the current triangles only, not on earlier updates.
+ *
+ * Rules (host twins below, word for word):
+ *   BVH4 leaf (word 7 has the leaf bit, triangle t < num_tris): the component-wise min / max of the three vertices, each rounded to
+ *     nearest-even f16 and then stepped one f16 outwards, always (BVHBuilder.wgsl:63-102).  A leaf with t >= num_tris keeps its words.
+ *   BVH4 internal node: Math.min / Math.max over the exactly decoded boxes of its valid children (index != 0xFFFFFFFF and < numNodes)
+ *     in slot order, starting from +-inf, packed by truncation with f16 subnormals flushed to signed zero (PathTracer.js:42-51,
+ *     640-661).  A node whose four slots are all invalid keeps its words.  Only nodes reachable from the root are refitted; a tree in
+ *     which a node is reachable twice is refused by pt_set_bvh4 already.
+ *   Device layouts: the 64-byte triangle records are rewritten, and every internal node's 64-byte wide record is what the build writes
+ *     from the refitted BVH4 -- including the inverted box of an empty slot and the "fetched, never entered" mark of a child whose box
+ *     became degenerate.
+ *   BVH2 (when the context holds one): leaves by the leaf rule, internal nodes by the reference's propagateUp (the union of the two
+ *     children, stepped outwards once more; BVHBuilder.wgsl:242-275).  Deferred to the next pt_read_bvh2; nothing else reads it.
+ * Without a tree the call only replaces the triangles.
+ * Arguments: num_tris must equal the context's triangle count (pt_set_triangles changes it).  A NULL pointer, a device pointer that is
+ *   not 16-byte aligned, or another count: PT_ERR_INVALID_ARG (pointers are checked first).  No triangles uploaded yet: PT_ERR_NO_SCENE.
+ *   After either error the context is exactly as it was.  num_tris == 0 (an empty scene): PT_OK, nothing is launched.
+ * Ordering: frames queued by pt_set_batch are launched first (as pt_flush does): frames submitted before the update show the old
+ *   geometry, frames after it the new.  A running accumulation restarts, as on any scene change.
+ * The host's copies of what the tile cull and the kernel choice read -- the root box, its degenerate flag, the largest edge component --
+ *   come back in one 16-byte copy behind the refit.  pt_update_triangles waits for it; pt_update_triangles_device does not: the next
+ *   call that plans a launch (pt_render, pt_trace_rays, pt_traced_tile_rect) or changes the scene waits for that copy first.
+ * The first update (or pt_bvh_cost) after a tree was installed also derives the parent links the climb needs, once: on the device for
+ *   a tree this library built, by one read-back and a host walk for an installed one. */
+/* tris: f32[9 * num_tris] on the host, copied during the call; returns when the update is done. */
+PT_API int pt_update_triangles(PtContext* ctx, const float* tris, uint32_t num_tris);
+/* tris_device: f32[9 * num_tris] on the context's device, 16-byte aligned.  Asynchronous on the context's stream (pt_get_stream): the
+ * array is read by a copy queued there and may be reused once a later pt_synchronize has returned. */
+PT_API int pt_update_triangles_device(PtContext* ctx, const void* tris_device, uint32_t num_tris);
+/* Quality of the current tree: the sum, over the internal BVH4 nodes reachable from the root, of halfArea(node box) / halfArea(root
+ * box), with halfArea = dx*dy + dy*dz + dz*dx of the exactly decoded f16 bounds in f64.  A box that is degenerate (a min above its max)
+ * or has a NaN bound counts 0; the result is 0 when the root is a leaf or its half-area is 0 or not finite.  A refitted tree's cost
+ * grows with the deformation: rebuild when it exceeds the cost at build by a factor of the caller's choice (nothing rebuilds by itself).
+ * Device and host twin agree to a relative numNodes * 2^-51 (the order of the summation differs).  PT_ERR_NO_SCENE without a tree. */
+PT_API int pt_bvh_cost(PtContext* ctx, double* cost);
+/* Host twins (no context, no GPU), in place: the words the device refit leaves in pt_read_bvh4 / pt_read_bvh2 for the same topology and
+ * triangles.  bvh4: u32[1 + 8 * numNodes]; bvh2: u32[1 + 6 * numNodes] with both children of an internal node in range and different
+ * (a node where they are not keeps its words, as do its ancestors).  A buffer shorter than its node count or a BVH4 node reachable
+ * twice: PT_ERR_BAD_BVH; a NULL pointer: PT_ERR_INVALID_ARG. */
+PT_API int pt_refit_bvh4(const float* tris, uint32_t num_tris, uint32_t* bvh4, uint64_t words);
+PT_API int pt_refit_bvh2(const float* tris, uint32_t num_tris, uint32_t* bvh2, uint64_t words);
+PT_API int pt_bvh4_cost(const uint32_t* bvh4, uint64_t words, double* cost);
+
 /* ---- pixel-tile sharding across GPUs (one context per GPU / rank) ------------------ */
 
 /* Number of 8x8 tiles / pixels-slots this rank owns for a W x H frame split tile_count ways. */
@@ -375,6 +424,8 @@ PT_API int  pt_group_size(const PtGroup* group, uint32_t* num_members);
 PT_API int  pt_group_context(PtGroup* group, uint32_t rank, PtContext** ctx);
 /* scene, replicated on every member: pt_set_triangles / pt_build_bvh / pt_set_bvh2 / pt_set_bvh4 */
 PT_API int  pt_group_set_triangles(PtGroup* group, const float* tris, uint32_t num_tris);
+/* pt_update_triangles on every member (the same host array): every member ends up with the same refitted tree */
+PT_API int  pt_group_update_triangles(PtGroup* group, const float* tris, uint32_t num_tris);
 PT_API int  pt_group_build_bvh(PtGroup* group);
 /* pt_build_bvh_accel on every member: the build is deterministic, every member holds the same tree */
 PT_API int  pt_group_build_bvh_accel(PtGroup* group, uint32_t accel);

@@ -86,6 +86,7 @@ EXPORTS = [
     "pt_read_rgba8", "pt_read_tonemapped", "pt_tile_layout", "pt_tile_ids", "pt_compact_radiance", "pt_deinterleave", "pt_deinterleave_batch", "pt_buffer_busy",
     "pt_accum_info", "pt_read_accum", "pt_set_accum",
     "pt_trace_rays", "pt_trace_rays_host", "pt_camera_rays",
+    "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
     "pt_group_build_bvh_accel",
@@ -224,6 +225,30 @@ def bvh2_to_bvh4_wide(bvh2):
     return out
 
 
+def refit_bvh4(tris, bvh4):
+    """Host twin of Context.update_triangles: the BVH4 words for the same topology and the triangles `tris` (a new array)."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    out = np.array(bvh4, np.uint32).reshape(-1)
+    _check(lib.pt_refit_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), _p(out, C.c_uint32), C.c_uint64(out.size)))
+    return out
+
+
+def refit_bvh2(tris, bvh2):
+    """The BVH2 words Context.read_bvh2 returns after update_triangles(tris): leaf rule + the reference's propagateUp (a new array)."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    out = np.array(bvh2, np.uint32).reshape(-1)
+    _check(lib.pt_refit_bvh2(_p(tris, C.c_float), C.c_uint32(tris.size // 9), _p(out, C.c_uint32), C.c_uint64(out.size)))
+    return out
+
+
+def bvh4_cost(bvh4):
+    """Host twin of Context.bvh_cost: sum over reachable internal nodes of halfArea(node) / halfArea(root), f64."""
+    bvh4 = np.ascontiguousarray(bvh4, np.uint32).reshape(-1)
+    cost = C.c_double()
+    _check(lib.pt_bvh4_cost(_p(bvh4, C.c_uint32), C.c_uint64(bvh4.size), C.byref(cost)))
+    return cost.value
+
+
 def write_u32_file(path, words):
     words = np.ascontiguousarray(words, np.uint32)
     _check(lib.pt_file_write_u32(path.encode(), _p(words, C.c_uint32), C.c_uint64(words.size)))
@@ -313,6 +338,36 @@ class Context:
         tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
         self._ck(lib.pt_set_triangles(self.h, _p(tris, C.c_float), C.c_uint32(tris.size // 9)))
         self.num_tris = tris.size // 9
+
+    def update_triangles(self, tris):
+        """New vertices for the same triangles: the tree keeps its topology and is refitted in place on the device (no rebuild, and on
+        the device route no upload).  A numpy array takes the host route (returns when done).  A torch tensor on the context's GPU
+        (float32, 9N elements) takes the device route: zero-copy when contiguous and 16-byte aligned, no host synchronisation, ordered
+        with torch's current stream both ways; the tensor may be reused once synchronize() has returned."""
+        if _is_torch(tris):
+            _torch_route()
+            import torch
+            if tris.device.type != "cuda":
+                raise ValueError("update_triangles: torch tensors must be on the context's GPU (got %s)" % tris.device)
+            t = tris.reshape(-1)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+                t = t.to(torch.float32).contiguous().clone()
+            if t.numel() % 9:
+                raise ValueError("update_triangles: 9 floats per triangle")
+            self._on_context_stream(t.device, lambda: self.update_triangles_device(t.data_ptr(), t.numel() // 9))
+            return
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+        self._ck(lib.pt_update_triangles(self.h, _p(tris, C.c_float), C.c_uint32(tris.size // 9)))
+
+    def update_triangles_device(self, tris_ptr, num_tris):
+        """Raw device route: f32[9 * num_tris] at tris_ptr (16-byte aligned, on the context's device), asynchronous on the context's stream."""
+        self._ck(lib.pt_update_triangles_device(self.h, C.c_void_p(tris_ptr), C.c_uint32(num_tris)))
+
+    def bvh_cost(self):
+        """Quality of the current tree (grows as a refitted tree degrades): rebuild when it exceeds the cost at build by a factor you pick."""
+        cost = C.c_double()
+        self._ck(lib.pt_bvh_cost(self.h, C.byref(cost)))
+        return cost.value
 
     def set_spheres(self, xyzr):
         xyzr = np.ascontiguousarray(xyzr, np.float32).reshape(-1)
@@ -613,6 +668,10 @@ class Group:
         tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
         self._ck(lib.pt_group_set_triangles(self.h, _p(tris, C.c_float), C.c_uint32(tris.size // 9)))
         self.num_tris = tris.size // 9
+
+    def update_triangles(self, tris):
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+        self._ck(lib.pt_group_update_triangles(self.h, _p(tris, C.c_float), C.c_uint32(tris.size // 9)))
 
     def build_bvh(self, accel=PT_ACCEL_REFERENCE):
         if accel == PT_ACCEL_REFERENCE:

@@ -90,6 +90,17 @@ struct PtContext {
     DevBuf<uint4> d_child_pos; DevBuf<unsigned char> d_build_temp; uint32_t* h_word = nullptr;
     DevBuf<uint32_t> d_ploc;         // PT_ACCEL_PLOC cluster buffers (ptk::ploc_words), allocated on first use
     DevBuf<float4> d_spheres; uint32_t num_spheres = 0;
+    // refit in place (pt_update_triangles, pt_refit.hip).  The plan (ptk::RefitBuffers) is derived at the first update or pt_bvh_cost after
+    // a tree was installed; every call that installs a tree drops it.  tree_built: the BVH4 is this library's own build (every node
+    // reachable, d_ids still holds the wide indices of launch_internal_scan), so the plan is derived on the device.
+    bool tree_built = false, refit_ready = false, refit2_ready = false;
+    uint32_t num_wide = 0;            // wide nodes in the arena
+    DevBuf<uint2> d_refit_up, d_refit_self; DevBuf<uint4> d_refit_ref; DevBuf<uint32_t> d_refit_arrive, d_refit_parent2, d_refit_arrive2;
+    DevBuf<double> d_cost;
+    bool bvh2_stale = false;          // the BVH2 still holds the boxes of earlier triangles: refitted by the next pt_read_bvh2
+    // the host's copies after an update (root box, edge maximum) come back through a pinned block behind the refit; whoever reads them
+    // next waits for that copy (sync_refit_meta)
+    uint32_t* h_refit = nullptr; hipEvent_t ev_refit = nullptr; bool meta_pending = false, meta_has_root = false;
     // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
 
@@ -158,6 +169,23 @@ int bind(PtContext* ctx) {
     return PT_OK;
 }
 
+// The host's copies of what an update changed (pt_update_triangles): the root box with its degenerate flag -- the tile cull reads them --
+// and edges_small.  They follow the refit on the stream into a pinned block; the first call that reads them waits for that copy.
+int sync_refit_meta(PtContext* ctx) {
+    if (!ctx->meta_pending) return PT_OK;
+    PT_HIP(ctx, hipEventSynchronize(ctx->ev_refit));
+    ctx->meta_pending = false;
+    const uint32_t* h = ctx->h_refit;
+    ctx->edges_small = h[3] < 0x49800000u;          // 2^20 as f32 bits (pt_set_triangles)
+    if (ctx->meta_has_root && ctx->have_bvh) {
+        pt::WideBvh& w = ctx->wide_meta;
+        w.root_box[0] = h[0]; w.root_box[1] = h[1]; w.root_box[2] = h[2];
+        w.root_degenerate = pt::half_to_float(h[0] & 0xffffu) > pt::half_to_float(h[1] >> 16) || pt::half_to_float(h[0] >> 16) > pt::half_to_float(h[2] & 0xffffu) ||
+                            pt::half_to_float(h[1] & 0xffffu) > pt::half_to_float(h[2] >> 16);
+    }
+    return PT_OK;
+}
+
 // which pixels a running accumulation covers: tile rank (bits 0..11), tile count (12..23), compact tile-major layout (bit 31)
 uint32_t accum_share_key(uint32_t rank, uint32_t count, bool compact) { return (rank & 0xfffu) | ((count & 0xfffu) << 12) | (compact ? 0x80000000u : 0u); }
 
@@ -221,6 +249,7 @@ int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
 
 int upload_wide(PtContext* ctx, const uint32_t* bvh4, uint64_t words) {
     pt::WideBvh w; std::string err;
+    if (int rc = sync_refit_meta(ctx)) return rc;
     const uint32_t tris_now = ctx->have_tris ? ctx->num_tris : 0u;
     if (!pt::build_wide_bvh(bvh4, words, tris_now, uint32_t(tri_region_bytes(tris_now) / 16u), w, err)) return fail(ctx, PT_ERR_BAD_BVH, err);
     PT_HIP(ctx, ctx->d_bvh4.ensure(words));
@@ -230,6 +259,7 @@ int upload_wide(PtContext* ctx, const uint32_t* bvh4, uint64_t words) {
         PT_HIP(ctx, hipMemcpyAsync(ctx->wide(), w.nodes.data(), w.nodes.size() * sizeof(pt::WideNode), hipMemcpyHostToDevice, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host staging vectors die at return
     ctx->num_nodes4 = w.num_nodes4;
+    ctx->num_wide = uint32_t(w.nodes.size()); ctx->tree_built = false; ctx->refit_ready = false;
     w.nodes.clear(); w.nodes.shrink_to_fit();
     ctx->wide_meta = w;
     ctx->have_bvh = true;
@@ -618,6 +648,10 @@ void pt_destroy(PtContext* ctx) {
     ctx->d_bounds.release(); ctx->d_counters.release(); ctx->d_code_tmp.release(); ctx->d_index_tmp.release(); ctx->d_node2.release();
     ctx->d_subtree.release(); ctx->d_ids.release(); ctx->d_bnd.release(); ctx->d_child_pos.release(); ctx->d_build_temp.release();
     if (ctx->h_word) (void)hipHostFree(ctx->h_word);
+    ctx->d_refit_up.release(); ctx->d_refit_self.release(); ctx->d_refit_ref.release(); ctx->d_refit_arrive.release();
+    ctx->d_refit_parent2.release(); ctx->d_refit_arrive2.release(); ctx->d_cost.release();
+    if (ctx->h_refit) (void)hipHostFree(ctx->h_refit);
+    if (ctx->ev_refit) (void)hipEventDestroy(ctx->ev_refit);
     for (auto& sl : ctx->slots) {
         sl.queue.release(); sl.samples.release(); sl.spill.release(); sl.rays.release(); sl.trace_slots.release();
         if (sl.h_trace) (void)hipHostFree(sl.h_trace);
@@ -750,6 +784,7 @@ int pt_set_triangles(PtContext* ctx, const float* tris, uint32_t num_tris) {
     if (int rc = flush_pending(ctx)) return rc;
     if (num_tris && !tris) return fail(ctx, PT_ERR_INVALID_ARG, "pt_set_triangles: null triangles");
     if (num_tris >= 0x7fffffffu) return fail(ctx, PT_ERR_INVALID_ARG, "pt_set_triangles: too many triangles for the 31-bit leaf index");
+    if (int rc = sync_refit_meta(ctx)) return rc;
     PT_HIP(ctx, ctx->d_tris9.ensure(size_t(num_tris) * 9));
     ctx->scene_tris = ~0u;                          // new triangles: nothing in the arena is worth keeping
     if (int rc = ensure_scene(ctx, num_tris, uint64_t(num_tris) + 16u)) return rc;
@@ -766,6 +801,7 @@ int pt_set_triangles(PtContext* ctx, const float* tris, uint32_t num_tris) {
     ctx->num_tris = num_tris;
     ctx->have_tris = true;
     ctx->have_bvh = false; ctx->have_bvh2 = false; ctx->bvh2_refit_pending = false;
+    ctx->refit_ready = false; ctx->refit2_ready = false; ctx->bvh2_stale = false;
     ctx->accum_count = 0;
     return PT_OK;
 }
@@ -778,7 +814,7 @@ int pt_build_lbvh2(PtContext* ctx, const uint32_t* morton_sorted, const uint32_t
     uint32_t nn2 = 0; uint64_t bytes = 0;
     pt_compute_bvh2_sizing(n, &nn2, &bytes);
     PT_HIP(ctx, ctx->d_bvh2.ensure(bytes / 4));
-    ctx->num_nodes2 = nn2;
+    ctx->num_nodes2 = nn2; ctx->refit2_ready = false; ctx->bvh2_stale = false;
     PT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh2.ptr, &nn2, 4, hipMemcpyHostToDevice, ctx->stream));   // BVH2[0] = numNodes2, PathTracer.js:699
     if (n == 0) { PT_HIP(ctx, hipStreamSynchronize(ctx->stream)); ctx->have_bvh2 = true; return PT_OK; }
     if (!morton_sorted || !tri_index_sorted) return fail(ctx, PT_ERR_INVALID_ARG, "pt_build_lbvh2: null sorted arrays");
@@ -797,13 +833,133 @@ int pt_build_lbvh2(PtContext* ctx, const uint32_t* morton_sorted, const uint32_t
     return PT_OK;
 }
 
+// ---- animated geometry: new vertices, the same tree (pt_refit.hip) ------------------------------------------------------
+namespace {
+ptk::RefitBuffers refit_buffers(PtContext* ctx) {
+    ptk::RefitBuffers R;
+    R.up = ctx->d_refit_up.ptr; R.self = ctx->d_refit_self.ptr; R.child_ref = ctx->d_refit_ref.ptr; R.arrive = ctx->d_refit_arrive.ptr;
+    return R;
+}
+
+// the plan of the climb for the context's BVH4, once per installed tree
+int ensure_refit_plan(PtContext* ctx) {
+    if (ctx->refit_ready) return PT_OK;
+    const uint32_t m = ctx->num_nodes4;
+    PT_HIP(ctx, ctx->d_refit_up.ensure(m)); PT_HIP(ctx, ctx->d_refit_self.ensure(m));
+    PT_HIP(ctx, ctx->d_refit_ref.ensure(ctx->num_wide)); PT_HIP(ctx, ctx->d_refit_arrive.ensure(m));
+    if (m) PT_HIP(ctx, hipMemsetAsync(ctx->d_refit_arrive.ptr, 0, size_t(m) * 4, ctx->stream));
+    const uint32_t node_base16 = uint32_t(ctx->node_off / 16u);
+    if (ctx->tree_built) {
+        PT_HIP(ctx, ptk::launch_refit_prepare4(ctx->d_bvh4.ptr, m, ctx->d_ids.ptr, ctx->num_tris, node_base16, refit_buffers(ctx), ctx->stream));
+    } else if (m) {
+        // an installed tree (pt_set_bvh4, pt_set_bvh2) may hold nodes that no path from the root reaches, and its wide nodes are numbered
+        // by the host's walk (pt::build_wide_bvh): the same walk again, over the device's copy of the words
+        std::vector<uint32_t> words(1 + size_t(m) * 8), up, self, ref; std::string err;
+        PT_HIP(ctx, hipMemcpyAsync(words.data(), ctx->d_bvh4.ptr, words.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (!pt::refit_plan4(words.data(), words.size(), ctx->num_tris, node_base16, up, self, ref, err)) return fail(ctx, PT_ERR_BAD_BVH, err);
+        if (ref.size() / 4 != ctx->num_wide) return fail(ctx, PT_ERR_BAD_BVH, "refit plan: wide node count differs from the arena's");
+        PT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_up.ptr, up.data(), up.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        PT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_self.ptr, self.data(), self.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!ref.empty()) PT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_ref.ptr, ref.data(), ref.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host staging vectors die at return
+    }
+    ctx->refit_ready = true;
+    return PT_OK;
+}
+
+// BVH2 leaves and internal bounds from the current triangles (what an update left to the next pt_read_bvh2)
+int refit_bvh2_on_stream(PtContext* ctx) {
+    const uint32_t nn2 = ctx->num_nodes2;
+    if (!ctx->refit2_ready) {
+        PT_HIP(ctx, ctx->d_refit_parent2.ensure(nn2)); PT_HIP(ctx, ctx->d_refit_arrive2.ensure(nn2));
+        if (nn2) PT_HIP(ctx, hipMemsetAsync(ctx->d_refit_arrive2.ptr, 0, size_t(nn2) * 4, ctx->stream));
+        PT_HIP(ctx, ptk::launch_refit_prepare2(ctx->d_bvh2.ptr, nn2, ctx->d_refit_parent2.ptr, ctx->stream));
+        ctx->refit2_ready = true;
+    }
+    PT_HIP(ctx, ptk::launch_refit2(ctx->d_tris9.ptr, ctx->num_tris, ctx->d_bvh2.ptr, nn2, ctx->d_refit_parent2.ptr, ctx->d_refit_arrive2.ptr, ctx->stream));
+    ctx->bvh2_stale = false; ctx->bvh2_refit_pending = false;
+    return PT_OK;
+}
+
+int update_triangles(PtContext* ctx, const char* fn, const void* tris, uint32_t num_tris, bool from_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (!tris) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": null triangles");
+    if (from_device && (reinterpret_cast<uintptr_t>(tris) & 15u)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": the device array must be 16-byte aligned");
+    if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": no triangles uploaded (pt_set_triangles first)");
+    if (num_tris != ctx->num_tris) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": an update keeps the triangle count (pt_set_triangles changes it)");
+    if (int rc = flush_pending(ctx)) return rc;     // frames submitted before the update show the old geometry
+    if (num_tris == 0u) return PT_OK;
+    const bool tree = ctx->have_bvh && ctx->num_nodes4 != 0u;
+    if (tree) { if (int rc = ensure_refit_plan(ctx)) return rc; }
+    if (!ctx->h_refit) PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_refit, 16, hipHostMallocDefault));
+    if (!ctx->ev_refit) PT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_refit, hipEventDisableTiming));
+    PT_HIP(ctx, ctx->d_edge_max.ensure(1));
+    PT_HIP(ctx, hipMemsetAsync(ctx->d_edge_max.ptr, 0, sizeof(uint32_t), ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_tris9.ptr, tris, size_t(num_tris) * 36, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    PT_HIP(ctx, ptk::launch_tri_records(ctx->d_tris9.ptr, num_tris, ctx->trirec(), ctx->d_edge_max.ptr, ctx->stream));
+    if (tree) {
+        PT_HIP(ctx, ptk::launch_refit4(ctx->d_tris9.ptr, num_tris, ctx->d_bvh4.ptr, ctx->num_nodes4, refit_buffers(ctx), ctx->wide(), ctx->stream));
+        PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit, ctx->d_bvh4.ptr + 1, 12, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit + 3, ctx->d_edge_max.ptr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipEventRecord(ctx->ev_refit, ctx->stream));
+    ctx->meta_pending = true; ctx->meta_has_root = tree;
+    if (ctx->have_bvh2) ctx->bvh2_stale = true;
+    ctx->accum_count = 0;
+    if (!from_device) {                             // the host array may be pageable: done with it, and with the read-back, at return
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return sync_refit_meta(ctx);
+    }
+    return PT_OK;
+}
+} // namespace
+
+int pt_update_triangles(PtContext* ctx, const float* tris, uint32_t num_tris) { return update_triangles(ctx, "pt_update_triangles", tris, num_tris, false); }
+int pt_update_triangles_device(PtContext* ctx, const void* tris_device, uint32_t num_tris) { return update_triangles(ctx, "pt_update_triangles_device", tris_device, num_tris, true); }
+
+int pt_bvh_cost(PtContext* ctx, double* cost) {
+    if (int rc = bind(ctx)) return rc;
+    if (!cost) return fail(ctx, PT_ERR_INVALID_ARG, "pt_bvh_cost: null destination");
+    if (!ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, "pt_bvh_cost: no BVH on the device");
+    *cost = 0.0;
+    if (ctx->num_nodes4 == 0u) return PT_OK;
+    if (int rc = ensure_refit_plan(ctx)) return rc;
+    PT_HIP(ctx, ctx->d_cost.ensure(1));
+    PT_HIP(ctx, ptk::launch_bvh_cost(ctx->d_bvh4.ptr, ctx->num_nodes4, ctx->d_refit_self.ptr, ctx->d_cost.ptr, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(cost, ctx->d_cost.ptr, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_refit_bvh4(const float* tris, uint32_t num_tris, uint32_t* bvh4, uint64_t words) {
+    if (!bvh4 || (!tris && num_tris)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_refit_bvh4: null pointer");
+    std::string err;
+    if (!pt::refit_bvh4(tris, num_tris, bvh4, words, err)) return fail(nullptr, PT_ERR_BAD_BVH, err);
+    return PT_OK;
+}
+int pt_refit_bvh2(const float* tris, uint32_t num_tris, uint32_t* bvh2, uint64_t words) {
+    if (!bvh2 || (!tris && num_tris)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_refit_bvh2: null pointer");
+    std::string err;
+    if (!pt::refit_bvh2(tris, num_tris, bvh2, words, err)) return fail(nullptr, PT_ERR_BAD_BVH, err);
+    return PT_OK;
+}
+int pt_bvh4_cost(const uint32_t* bvh4, uint64_t words, double* cost) {
+    if (!bvh4 || !cost) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_bvh4_cost: null pointer");
+    std::string err;
+    if (!pt::bvh4_cost(bvh4, words, *cost, err)) return fail(nullptr, PT_ERR_BAD_BVH, err);
+    return PT_OK;
+}
+
 int pt_read_bvh2(PtContext* ctx, uint32_t* dst, uint64_t bytes) {
     if (int rc = bind(ctx)) return rc;
     if (!ctx->have_bvh2) return fail(ctx, PT_ERR_NO_SCENE, "pt_read_bvh2: no BVH2 on the device");
     if (!dst) return fail(ctx, PT_ERR_INVALID_ARG, "pt_read_bvh2: null destination");
     uint64_t have = 0; pt_compute_bvh2_sizing(ctx->num_tris, nullptr, &have);
     const uint64_t n = bytes < have ? bytes : have;
-    if (ctx->bvh2_refit_pending) {                  // BVHBuilder.wgsl:242-275, deferred by pt_build_bvh
+    if (ctx->bvh2_stale) {                          // pt_update_triangles since: leaves and internal bounds from the current triangles
+        if (int rc = refit_bvh2_on_stream(ctx)) return rc;
+    } else if (ctx->bvh2_refit_pending) {           // BVHBuilder.wgsl:242-275, deferred by pt_build_bvh
         PT_HIP(ctx, ptk::launch_lbvh2_refit(ctx->d_bvh2.ptr, ctx->d_parent.ptr, ctx->d_flags.ptr, ctx->num_tris, ctx->stream));
         ctx->bvh2_refit_pending = false;
     }
@@ -830,6 +986,7 @@ int pt_set_bvh2(PtContext* ctx, const uint32_t* bvh2, uint64_t words) {
     PT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh2.ptr, bvh2, bytes, hipMemcpyHostToDevice, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->num_nodes2 = nn2; ctx->have_bvh2 = true; ctx->bvh2_refit_pending = false;
+    ctx->refit2_ready = false; ctx->bvh2_stale = false;
     std::vector<uint32_t> b4; std::string err;
     if (!pt::collapse_to_bvh4(bvh2, ctx->num_tris, b4, err)) return fail(ctx, PT_ERR_BAD_BVH, err);
     ctx->accum_count = 0;
@@ -843,6 +1000,7 @@ int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     if (accel > PT_ACCEL_PLOC) return fail(ctx, PT_ERR_INVALID_ARG, "pt_build_bvh_accel: accel must be 0 (reference), 1 (area collapse) or 2 (PLOC)");
     if (int rc = flush_pending(ctx)) return rc;
     if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_build_bvh: no triangles uploaded");
+    if (int rc = sync_refit_meta(ctx)) return rc;
     const uint32_t n = ctx->num_tris;
     if (n == 0) {                                   // PathTracer.js:701-707: empty BVH4
         const uint32_t zero = 0;
@@ -874,6 +1032,7 @@ int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     B.node2 = ctx->d_node2.ptr; B.child_pos = ctx->d_child_pos.ptr; B.subtree = ctx->d_subtree.ptr; B.ids = ctx->d_ids.ptr; B.bnd = ctx->d_bnd.ptr;
     B.host_word = ctx->h_word;
     ctx->have_bvh = false; ctx->have_bvh2 = false;
+    ctx->refit_ready = false; ctx->refit2_ready = false; ctx->bvh2_stale = false;
     PT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh2.ptr, &nn2, 4, hipMemcpyHostToDevice, ctx->stream));   // BVH2[0] = numNodes2, PathTracer.js:699
     PT_HIP(ctx, ptk::launch_morton_sort(B, ctx->d_tris9.ptr, n, ctx->stream));
     if (accel == PT_ACCEL_PLOC) {                   // PLOC topology, LBVH leaves, the reference's refit
@@ -914,6 +1073,7 @@ int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     meta.root_ref = (root[7] & pt::kLeafFlag) ? pt::packed_leaf_ref(root[7] & 0x7fffffffu, n) : uint32_t(ctx->node_off / 16u);
     ctx->wide_meta = meta;
     ctx->num_nodes4 = m;
+    ctx->num_wide = internal; ctx->tree_built = true;
     ctx->have_bvh = true;
     ctx->accum_count = 0;
     return PT_OK;
@@ -974,6 +1134,7 @@ int pt_tile_ids(uint32_t width, uint32_t height, uint32_t tile_rank, uint32_t ti
 int pt_render(PtContext* ctx, const PtRenderParams* p) {
     if (int rc = bind(ctx)) return rc;
     if (!p) return fail(ctx, PT_ERR_INVALID_ARG, "pt_render: null params");
+    if (int rc = sync_refit_meta(ctx)) return rc;
     const bool brute = (p->flags & PT_FLAG_BRUTE_FORCE) != 0;
     if (!ctx->have_tris || (!ctx->have_bvh && !brute)) return fail(ctx, PT_ERR_NO_SCENE, "pt_render: scene not set (triangles + BVH)");   // PathTracer.js:757
     if (brute && p->mode == PT_MODE_REFERENCE_PACKET) return fail(ctx, PT_ERR_INVALID_ARG, "pt_render: brute-force scenes render in modes 1 and 2");
@@ -1134,6 +1295,7 @@ int check_trace(PtContext* ctx, const char* fn, const void* rays, uint64_t n, ui
 int trace_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* hits) {
     if (int rc = flush_pending(ctx)) return rc;
     if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
     ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
     A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
     A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
@@ -1482,6 +1644,7 @@ int pt_traced_tile_rect(PtContext* ctx, const PtRenderParams* p, uint32_t rect[4
     if (p->width == 0 || p->height == 0 || p->width > 32768 || p->height > 32768) return fail(ctx, PT_ERR_INVALID_ARG, "pt_traced_tile_rect: bad resolution");
     const uint32_t tiles_x = (p->width + pt::kTile - 1) / pt::kTile, tiles_y = (p->height + pt::kTile - 1) / pt::kTile;
     rect[0] = 0; rect[1] = 0; rect[2] = tiles_x; rect[3] = tiles_y;                       // nothing can be left out: the whole image
+    if (ctx->meta_pending) { if (int rc = bind(ctx)) return rc; if (int rc = sync_refit_meta(ctx)) return rc; }
     const bool brute = (p->flags & PT_FLAG_BRUTE_FORCE) != 0;
     if (brute || !ctx->have_bvh || ctx->wide_meta.root_ref == pt::kInvalid || ctx->wide_meta.root_degenerate || p->num_tris == 0u || ctx->tune.cull == 0u) return PT_OK;
     ptk::FrameParams f; std::memset(&f, 0, sizeof(f));

@@ -12,6 +12,7 @@
 // stable sort on the 30-bit code, the same DFS pre-order numbering.
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_bounds.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -141,7 +142,6 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 __device__ __forceinline__ bool leaf2(const uint32_t* __restrict__ bvh2, uint32_t node) { return (bvh2[1 + (size_t)node * 6 + 5] & kLeaf) != 0u; }
 
-__device__ __forceinline__ float half_exact(uint32_t h);
 // surface area of a BVH2 node from its stored f16 box words, decoded exactly: ((dx*dy) + (dy*dz)) + (dz*dx), f32, no fma
 // (-ffp-contract=off; pt_host.cpp::node_area2 is the same expression)
 __device__ __forceinline__ float node_area2(const uint32_t* __restrict__ bvh2, uint32_t node) {
@@ -209,25 +209,6 @@ __global__ __launch_bounds__(256) void collapse_expand_kernel(const uint32_t* __
     child_pos[level_begin + i] = cp;
 }
 
-// JS Math.min / Math.max on numbers (sign of zero ordered, first operand wins a tie otherwise): pt_host.cpp js_min_f / js_max_f
-__device__ __forceinline__ float js_min_f(float a, float b) { if (a < b) return a; if (b < a) return b; return (__float_as_uint(a) >> 31) ? a : b; }
-__device__ __forceinline__ float js_max_f(float a, float b) { if (a > b) return a; if (b > a) return b; return (__float_as_uint(a) >> 31) ? b : a; }
-__device__ __forceinline__ float half_exact(uint32_t h) {        // PathTracer.js:16-40, integer form (exact for subnormals whatever the FP mode)
-    const uint32_t sign = (h & 0x8000u) << 16, mag = h & 0x7fffu;
-    if (mag >= 0x7c00u) return __uint_as_float(sign | 0x7f800000u | ((mag & 0x3ffu) << 13));
-    if (mag >= 0x0400u) return __uint_as_float(sign | ((mag + (112u << 10)) << 13));
-    const float v = (float)mag * 5.9604644775390625e-8f;
-    return __uint_as_float(__float_as_uint(v) | sign);
-}
-__device__ __forceinline__ uint32_t half_trunc(float v) {        // PathTracer.js:42-51: truncate, flush below the normal range, saturate
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t e = (int32_t)((u >> 23) & 0xffu) - 112;
-    if (e <= 0) return sign;
-    if (e >= 31) return sign | 0x7c00u;
-    return sign | ((uint32_t)e << 10) | ((u >> 13) & 0x3ffu);
-}
-
 // bottom-up, one launch per level (deepest first): subtree size and bounds (PathTracer.js:640-661)
 __global__ __launch_bounds__(256) void collapse_up_kernel(const uint32_t* __restrict__ bvh2, const uint32_t* __restrict__ node2, const uint4* __restrict__ child_pos,
                                                            uint32_t* __restrict__ subtree, uint32_t* __restrict__ bnd, uint32_t level_begin, uint32_t level_count) {
@@ -292,10 +273,6 @@ __global__ __launch_bounds__(256) void collapse_down_kernel(const uint32_t* __re
 __global__ __launch_bounds__(256) void internal_flags_kernel(const uint32_t* __restrict__ bvh4, uint32_t m, uint32_t* __restrict__ flags) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) flags[i] = (bvh4[1 + (size_t)i * 8 + 7] & kLeaf) ? 0u : 1u;
-}
-
-__device__ __forceinline__ bool box_degenerate(uint32_t w0, uint32_t w1, uint32_t w2) {     // renderer.wgsl:244, 291: any(mn > mx)
-    return half_exact(w0 & 0xffffu) > half_exact(w1 >> 16) || half_exact(w0 >> 16) > half_exact(w2 & 0xffffu) || half_exact(w1 & 0xffffu) > half_exact(w2 >> 16);
 }
 
 __global__ __launch_bounds__(256) void wide_nodes_kernel(const uint32_t* __restrict__ bvh4, uint32_t m, const uint32_t* __restrict__ wide_index, uint4* __restrict__ wide,

@@ -290,6 +290,12 @@ int pt_group_set_triangles(PtGroup* g, const float* tris, uint32_t num_tris) {
     for (uint32_t r = 0; r < g->n; ++r) G_PT(g, r, pt_set_triangles(g->ctx[r], tris, num_tris));
     return PT_OK;
 }
+int pt_group_update_triangles(PtGroup* g, const float* tris, uint32_t num_tris) {
+    if (!g) return gfail(nullptr, PT_ERR_INVALID_ARG, "null group");
+    if (int rc = flush_group(g)) return rc;
+    for (uint32_t r = 0; r < g->n; ++r) G_PT(g, r, pt_update_triangles(g->ctx[r], tris, num_tris));      // deterministic, like pt_group_build_bvh
+    return PT_OK;
+}
 int pt_group_build_bvh(PtGroup* g) {
     if (!g) return gfail(nullptr, PT_ERR_INVALID_ARG, "null group");
     if (int rc = flush_group(g)) return rc;

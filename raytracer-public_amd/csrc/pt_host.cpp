@@ -416,6 +416,163 @@ bool build_wide_bvh(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uin
     return true;
 }
 
+// ------------------------------------------------------------------------------------
+// Refit in place (host twins of pt_refit.hip)
+// ------------------------------------------------------------------------------------
+namespace {
+// the device's v_min_f32 / v_max_f32 (pt_device.h::wmin / wmax): a NaN operand loses, -0 lies below +0
+inline float wmin_h(float a, float b) { if (a != a) return b; if (b != b) return a; return js_min_f(a, b); }
+inline float wmax_h(float a, float b) { if (a != a) return b; if (b != b) return a; return js_max_f(a, b); }
+// the leaf rule (BVHBuilder.wgsl:278-306): min / max of the three vertices, associated as the kernels do, stepped outwards
+inline void leaf_box_words(const float* t, uint32_t* p) {
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) { mn[a] = wmin_h(t[a], wmin_h(t[3 + a], t[6 + a])); mx[a] = wmax_h(t[a], wmax_h(t[3 + a], t[6 + a])); }
+    store_bounds2(p, mn, mx);
+}
+// reachable nodes of a reference-layout BVH4 in pre-order (build_wide_bvh's walk)
+bool reachable4(const uint32_t* bvh4, uint64_t words, std::vector<uint32_t>& order, std::string& err) {
+    order.clear();
+    if (words < 1) { err = "empty BVH buffer"; return false; }
+    const uint32_t m = bvh4[0];
+    if (m == 0) return true;
+    if (words < 1 + uint64_t(m) * kNode4Stride) { err = "BVH buffer shorter than its node count"; return false; }
+    std::vector<uint8_t> seen(m, 0);
+    std::vector<uint32_t> stack;
+    stack.push_back(0u); seen[0] = 1;
+    while (!stack.empty()) {
+        const uint32_t i = stack.back(); stack.pop_back();
+        order.push_back(i);
+        const uint32_t* r = bvh4 + 1 + size_t(i) * kNode4Stride;
+        if (r[7] & kLeafFlag) continue;
+        for (int s = 3; s >= 0; --s) {
+            const uint32_t c = r[3 + s];
+            if (c == kInvalid || c >= m) continue;
+            if (seen[c]) { err = "BVH node reachable twice (not a tree)"; return false; }
+            seen[c] = 1;
+            stack.push_back(c);
+        }
+    }
+    return true;
+}
+inline double half_area(const uint32_t* r) {
+    const double x0 = half_to_float(r[0] & 0xffffu), y0 = half_to_float(r[0] >> 16), z0 = half_to_float(r[1] & 0xffffu);
+    const double x1 = half_to_float(r[1] >> 16), y1 = half_to_float(r[2] & 0xffffu), z1 = half_to_float(r[2] >> 16);
+    if (!(x0 <= x1 && y0 <= y1 && z0 <= z1)) return 0.0;            // degenerate, or a NaN
+    const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
+    const double a = (dx * dy + dy * dz) + dz * dx;
+    return a == a ? a : 0.0;                                        // inf * 0
+}
+} // namespace
+
+bool refit_bvh4(const float* tris, uint32_t n, uint32_t* bvh4, uint64_t words, std::string& err) {
+    std::vector<uint32_t> order;
+    if (!reachable4(bvh4, words, order, err)) return false;
+    const uint32_t m = order.empty() ? 0u : bvh4[0];
+    for (size_t k = order.size(); k-- > 0;) {                       // children come after their parent in pre-order
+        uint32_t* r = bvh4 + 1 + size_t(order[k]) * kNode4Stride;
+        if (r[7] & kLeafFlag) {
+            const uint32_t t = r[7] & 0x7fffffffu;
+            if (t < n) leaf_box_words(tris + size_t(t) * 9, r);
+            continue;
+        }
+        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+        uint32_t valid = 0;
+        for (int s = 0; s < 4; ++s) {
+            const uint32_t c = r[3 + s];
+            if (c == kInvalid || c >= m) continue;
+            ++valid;
+            const uint32_t* cr = bvh4 + 1 + size_t(c) * kNode4Stride;
+            const float cmn[3] = {half_to_float(cr[0] & 0xffffu), half_to_float(cr[0] >> 16), half_to_float(cr[1] & 0xffffu)};
+            const float cmx[3] = {half_to_float(cr[1] >> 16), half_to_float(cr[2] & 0xffffu), half_to_float(cr[2] >> 16)};
+            for (int a = 0; a < 3; ++a) { mn[a] = js_min_f(mn[a], cmn[a]); mx[a] = js_max_f(mx[a], cmx[a]); }
+        }
+        if (!valid) continue;
+        r[0] = float_to_half_trunc(mn[0]) | (float_to_half_trunc(mn[1]) << 16);
+        r[1] = float_to_half_trunc(mn[2]) | (float_to_half_trunc(mx[0]) << 16);
+        r[2] = float_to_half_trunc(mx[1]) | (float_to_half_trunc(mx[2]) << 16);
+    }
+    return true;
+}
+
+bool refit_bvh2(const float* tris, uint32_t n, uint32_t* bvh2, uint64_t words, std::string& err) {
+    if (words < 1) { err = "empty BVH2 buffer"; return false; }
+    const uint32_t nn2 = bvh2[0];
+    if (words < 1 + uint64_t(nn2) * kNode2Stride) { err = "BVH2 buffer shorter than its node count"; return false; }
+    std::vector<uint32_t> parent(nn2, kInvalid), arrive(nn2, 0u);
+    auto rec = [&](uint32_t i) { return bvh2 + 1 + size_t(i) * kNode2Stride; };
+    for (uint32_t i = 0; i < nn2; ++i) {
+        const uint32_t* p = rec(i);
+        if (p[5] & kLeafFlag) continue;
+        const uint32_t l = p[3], r = p[4];
+        if (l >= nn2 || r >= nn2 || l == r) continue;
+        parent[l] = i; parent[r] = i;
+    }
+    for (uint32_t i = 0; i < nn2; ++i) {
+        uint32_t* p = rec(i);
+        if (!(p[5] & kLeafFlag)) continue;
+        const uint32_t t = p[5] & 0x7fffffffu;
+        if (t < n) leaf_box_words(tris + size_t(t) * 9, p);
+        for (uint32_t cur = i;;) {                                  // propagateUp (BVHBuilder.wgsl:242-275): the second child to arrive unions
+            const uint32_t par = parent[cur];
+            if (par >= nn2) break;
+            if (arrive[par]++ == 0u) break;
+            arrive[par] = 0u;
+            uint32_t* pp = rec(par);
+            const uint32_t* l = rec(pp[3]); const uint32_t* r = rec(pp[4]);
+            const float mn[3] = {wmin_h(half_to_float(l[0] & 0xffffu), half_to_float(r[0] & 0xffffu)), wmin_h(half_to_float(l[0] >> 16), half_to_float(r[0] >> 16)),
+                                 wmin_h(half_to_float(l[1] & 0xffffu), half_to_float(r[1] & 0xffffu))};
+            const float mx[3] = {wmax_h(half_to_float(l[1] >> 16), half_to_float(r[1] >> 16)), wmax_h(half_to_float(l[2] & 0xffffu), half_to_float(r[2] & 0xffffu)),
+                                 wmax_h(half_to_float(l[2] >> 16), half_to_float(r[2] >> 16))};
+            store_bounds2(pp, mn, mx);
+            cur = par;
+        }
+    }
+    return true;
+}
+
+bool bvh4_cost(const uint32_t* bvh4, uint64_t words, double& cost, std::string& err) {
+    cost = 0.0;
+    std::vector<uint32_t> order;
+    if (!reachable4(bvh4, words, order, err)) return false;
+    if (order.empty()) return true;
+    const double root = half_area(bvh4 + 1);
+    if (!(root > 0.0) || root == double(INFINITY)) return true;
+    std::sort(order.begin(), order.end());
+    for (uint32_t i : order) {
+        const uint32_t* r = bvh4 + 1 + size_t(i) * kNode4Stride;
+        if (!(r[7] & kLeafFlag)) cost += half_area(r) / root;
+    }
+    return true;
+}
+
+bool refit_plan4(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uint32_t node_base16,
+                 std::vector<uint32_t>& up, std::vector<uint32_t>& self, std::vector<uint32_t>& child_ref, std::string& err) {
+    std::vector<uint32_t> order;
+    if (!reachable4(bvh4, words, order, err)) return false;
+    const uint32_t m = order.empty() ? 0u : bvh4[0];
+    up.assign(size_t(m) * 2, 0u); self.assign(size_t(m) * 2, kInvalid); child_ref.clear();
+    for (uint32_t i = 0; i < m; ++i) up[size_t(i) * 2] = kInvalid;
+    uint32_t internal = 0;
+    for (uint32_t i : order)                                        // wide indices: the reachable internal nodes in pre-order
+        if (!(bvh4[1 + size_t(i) * kNode4Stride + 7] & kLeafFlag)) self[size_t(i) * 2 + 1] = internal++;
+    child_ref.assign(size_t(internal) * 4, kInvalid);
+    for (uint32_t i : order) {
+        const uint32_t* r = bvh4 + 1 + size_t(i) * kNode4Stride;
+        if (r[7] & kLeafFlag) { self[size_t(i) * 2] = kLeafFlag; continue; }
+        uint32_t valid = 0;
+        for (uint32_t s = 0; s < 4; ++s) {
+            const uint32_t c = r[3 + s];
+            if (c == kInvalid || c >= m) continue;
+            const uint32_t w7 = bvh4[1 + size_t(c) * kNode4Stride + 7];
+            child_ref[size_t(self[size_t(i) * 2 + 1]) * 4 + s] = (w7 & kLeafFlag) ? packed_leaf_ref(w7 & 0x7fffffffu, num_tris) : node_base16 + 4u * self[size_t(c) * 2 + 1];
+            up[size_t(c) * 2] = i; up[size_t(c) * 2 + 1] = s;
+            ++valid;
+        }
+        self[size_t(i) * 2] = valid;
+    }
+    return true;
+}
+
 void build_tri_records(const float* tris, uint32_t n, TriRecord* out) {
     for (uint32_t t = 0; t < n; ++t) {
         const float* p = tris + size_t(t) * 9;

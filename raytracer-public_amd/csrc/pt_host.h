@@ -65,6 +65,19 @@ struct WideBvh {
 // no ray enters but which counts as an examined record, exactly as in the reference.
 bool build_wide_bvh(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uint32_t node_base16, WideBvh& out, std::string& err);
 
+// ---- refit in place (pt_update_triangles; host twins of pt_refit.hip, word for word) ------------------------------------------
+// New boxes for an unchanged topology.  BVH4: the nodes reachable from the root (the walk of build_wide_bvh; a node reachable
+// twice is an error); a leaf whose triangle index is >= n, an internal node without a valid child and every unreachable node keep
+// their words.  BVH2: every leaf, and every internal node both of whose children (two different nodes in range) are refitted.
+bool refit_bvh4(const float* tris, uint32_t n, uint32_t* bvh4, uint64_t words, std::string& err);
+bool refit_bvh2(const float* tris, uint32_t n, uint32_t* bvh2, uint64_t words, std::string& err);
+// sum over the reachable internal nodes of halfArea(node box) / halfArea(root box), boxes decoded exactly, f64, in node order
+bool bvh4_cost(const uint32_t* bvh4, uint64_t words, double& cost, std::string& err);
+// What the device climb needs for an installed tree (pt_kernels.h::RefitBuffers): up[2M] = (parent, slot), self[2M] = (kind, wide
+// index), child_ref[4 * internal] = the packed references of each wide record, by the wide indices build_wide_bvh assigns.
+bool refit_plan4(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uint32_t node_base16,
+                 std::vector<uint32_t>& up, std::vector<uint32_t>& self, std::vector<uint32_t>& child_ref, std::string& err);
+
 // 64-byte triangle record (one cache line, like a wide node): v0, e1 = v1-v0, e2 = v2-v0, n = normalize(cross(e1,e2)) -- the same
 // f32 operations renderer.wgsl:179-180,269 performs per visit, done once at upload.  Pieces 0..2 are axis-major: piece a (16 bytes)
 // holds component a of the three vectors of the intersection test, (v0[a], e1[a], e2[a], 0) -- three lanes of a quad that fetch one

@@ -186,6 +186,25 @@ hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, 
                              unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // A.width * A.height PtRay records of the PT_MODE_REFERENCE camera (A.focal, A.aspect, A.cam, A.quat), row-major
 hipError_t launch_camera_rays(const RenderArgs& A, void* rays, hipStream_t stream);
+// ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
+// What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
+// launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):
+constexpr uint32_t kRefitLeaf = 0x80000000u, kRefitDead = 0xFFFFFFFFu;
+struct RefitBuffers {
+    uint2* up;              // [M] per BVH4 node: (parent id, slot in the parent); parent 0xFFFFFFFF for the root and for nodes that are not reachable
+    uint2* self;            // [M] (kind, wide index): kind = number of valid children (0..4) of an internal node, kRefitLeaf, or kRefitDead (not reachable)
+    uint4* child_ref;       // [internal nodes, by wide index] the packed references of the four slots (0xFFFFFFFF = empty): the part of a wide record no update changes
+    uint32_t* arrive;       // [M] arrival counts, zero between updates (the thread that completes a count zeroes it)
+};
+// wide_index: launch_internal_scan's B.ids
+hipError_t launch_refit_prepare4(const uint32_t* bvh4, uint32_t num_nodes4, const uint32_t* wide_index, uint32_t num_tris, uint32_t node_base16, const RefitBuffers& R, hipStream_t stream);
+// leaf boxes from tris9 and internal boxes bottom-up in one launch, then the wide records from the refitted BVH4 in a second
+hipError_t launch_refit4(const float* tris9, uint32_t num_tris, uint32_t* bvh4, uint32_t num_nodes4, const RefitBuffers& R, uint4* wide, hipStream_t stream);
+// parent2[nn2] from the child words of the BVH2; then leaves and the reference's propagateUp over it (arrive[nn2] zero, left zero)
+hipError_t launch_refit_prepare2(const uint32_t* bvh2, uint32_t nn2, uint32_t* parent2, hipStream_t stream);
+hipError_t launch_refit2(const float* tris9, uint32_t num_tris, uint32_t* bvh2, uint32_t nn2, const uint32_t* parent2, uint32_t* arrive, hipStream_t stream);
+// *out = sum over reachable internal nodes of halfArea(node) / halfArea(root) (f64)
+hipError_t launch_bvh_cost(const uint32_t* bvh4, uint32_t num_nodes4, const uint2* self, double* out, hipStream_t stream);
 hipError_t launch_rgba8(const float4* src, uint32_t* dst, uint32_t n, hipStream_t stream);
 hipError_t launch_tonemap(const float4* src, uint32_t* dst, uint32_t width, uint32_t height, int from_rgba8, hipStream_t stream);
 

@@ -14,6 +14,7 @@
 
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_bounds.h"
 
 namespace ptk {
 static_assert(kBgPrimary == 0.01f, "renderer.wgsl:410: packed tile shares (pt_group, bench.py) rebuild pixels outside the traced rectangle from this constant in every render mode");
@@ -346,15 +347,8 @@ __global__ __launch_bounds__(256) void render_packet_kernel(const RenderArgs A) 
 }
 
 // ------------------------------------------------------------------------------------
-// LBVH2 build (BVHBuilder.wgsl).  f32 -> f16 is round-to-nearest-even (v_cvt_f16_f32).
+// LBVH2 build (BVHBuilder.wgsl).  f32 -> f16 is round-to-nearest-even (v_cvt_f16_f32): step_f16, pt_bounds.h.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t f16_bits_rtne(float v) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)v); }
-__device__ __forceinline__ uint32_t step_f16(float v, bool up) {        // BVHBuilder.wgsl:63-81, returns f16 bits
-    const uint32_t bits = f16_bits_rtne(v);
-    uint32_t ord = (bits & 0x8000u) ? ((~bits) & 0xFFFFu) : (bits ^ 0x8000u);
-    ord = up ? ord + 1u : ord - 1u;
-    return ((ord & 0x8000u) ? (ord ^ 0x8000u) : ((~ord) & 0xFFFFu)) & 0xFFFFu;
-}
 __device__ __forceinline__ void store_bounds2(uint32_t* bvh2, uint32_t node, F3 mn, F3 mx) {   // BVHBuilder.wgsl:83-102
     uint32_t* p = bvh2 + 1 + (size_t)node * 6;
     const uint32_t w0 = step_f16(mn.x, false) | (step_f16(mn.y, false) << 16);

@@ -102,6 +102,18 @@ class PathTracer {
     this.setBVH2(bvh2U32);
   }
 
+  // ---- animated geometry: an extension beyond the reference (include/mi355pt.h pt_update_triangles, DESIGN.md section 14) ----
+  // New vertices for the same triangles (a Float32Array of the same length): the tree keeps its topology and is refitted in place on
+  // the GPU -- no rebuild.  Frames rendered before show the old geometry, frames after the new.
+  updateTriangles(trianglesData) {
+    if (!this.device) return;
+    if (this.group) native().groupUpdateTriangles(this.group, trianglesData); else native().updateTriangles(this.device, trianglesData);
+    this.trianglesData = trianglesData;
+  }
+  // Quality of the current tree: sum over internal nodes of halfArea(node) / halfArea(root).  It grows as a refitted tree degrades:
+  // rebuild (buildBVH) when it exceeds the cost at build by a factor of your choice.  On a group: member 0 (every member holds the same tree).
+  bvhCost() { return this.group ? native().groupBvhCost(this.group) : native().bvhCost(this.device); }
+
   // install a prebuilt BVH (data/BVH2.bin or data/BVH4_wide.bin) instead of rebuilding
   setBVH2(bvh2U32) { if (this.group) native().groupSetBVH2(this.group, bvh2U32); else native().setBVH2(this.device, bvh2U32); this._hasBVH = true; }
   setBVH4(bvh4U32) { if (this.group) native().groupSetBVH4(this.group, bvh4U32); else native().setBVH4(this.device, bvh4U32); this._hasBVH = true; }
@@ -173,4 +185,17 @@ class PathTracer {
   }
 }
 
-module.exports = { PathTracer, MODE_REFERENCE_PACKET, MODE_REFERENCE, MODE_PATH, native };
+// The drivers' `--animate AMP` displacement (tools/README.md): every vertex of `base` moves in y by AMP times a triangle wave of its own x,
+//   u = (2 x + 0.25) + 0.125 frame;   y += AMP (4 |u - floor(u) - 0.5| - 1),
+// every step rounded to f32 (Math.fround), in that order -- add, multiply, floor and abs only, so numpy float32 gives the same bits.
+function animateWave(base, amp, frame, out) {
+  const f = Math.fround, a = f(amp), phase = f(f(0.125) * f(frame));
+  for (let i = 0; i < base.length; i += 3) {
+    const u = f(f(f(2 * base[i]) + 0.25) + phase);
+    const tri = f(f(4 * Math.abs(f(f(u - Math.floor(u)) - 0.5))) - 1);
+    out[i] = base[i]; out[i + 1] = f(base[i + 1] + f(a * tri)); out[i + 2] = base[i + 2];
+  }
+  return out;
+}
+
+module.exports = { PathTracer, animateWave, MODE_REFERENCE_PACKET, MODE_REFERENCE, MODE_PATH, native };

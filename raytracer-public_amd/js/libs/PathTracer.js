@@ -5,5 +5,5 @@
 import cjs from "../PathTracer.js";
 export const PathTracer = cjs.PathTracer;
 export const MODE_REFERENCE_PACKET = cjs.MODE_REFERENCE_PACKET, MODE_REFERENCE = cjs.MODE_REFERENCE, MODE_PATH = cjs.MODE_PATH;
-export const native = cjs.native;
+export const native = cjs.native, animateWave = cjs.animateWave;
 export default cjs;

@@ -16,6 +16,8 @@
 //        [--accumulate]                                      progressive accumulation over the frames (config C5; no warm-up frame then)
 //        [--accel 0|1|2]                                     tree quality of buildBVH (0 = the reference's tree; 1 area-guided collapse; 2 PLOC)
 //        [--cam x,y,z --quat x,y,z,w] [--radiance frame.f32 --triangles tris.f32]
+//        [--animate AMP]                                     before every render() the scene as built is displaced (a triangle wave in y over x, amplitude AMP,
+//                                                            phase by the frame count; tools/README.md) and the tree refitted in place: updateTriangles, no rebuild
 //        [--pick X,Y]                                        after the frames: what is under pixel (X, Y), as one JSON line (ray query, an extension)
 "use strict";
 const fs = require("fs");
@@ -83,6 +85,8 @@ async function main() {
   const batch = Number(arg("batch", 1));                      // >1: frames are traced in batches by one launch each
   if (batch > 1) pathTracer.setBatch(batch);
   let frameIndex = 0;
+  const animate = Number(arg("animate", 0));                  // --animate AMP: the scene as built, displaced by the wave of the frame count before every render()
+  const baseTriangles = animate ? Float32Array.from(pathTracer.trianglesData) : null, movedTriangles = animate ? new Float32Array(baseTriangles.length) : null;
   if (!accumulate) { await pathTracer.render(); pathTracer.synchronize(); }        // warm-up (first-touch allocations); an accumulation counts every frame it renders
   const t0 = Date.now();
   for (let f = 0; f < frames; f++) {
@@ -90,6 +94,7 @@ async function main() {
     pathTracer.setCameraPosition(camera.position[0], camera.position[1], camera.position[2]);
     pathTracer.setCameraQuaternion(camera.rotation[0], camera.rotation[1], camera.rotation[2], camera.rotation[3]);
     pathTracer.setFrameCount(frameIndex);
+    if (animate) pathTracer.updateTriangles(PT.animateWave(baseTriangles, animate, frameIndex, movedTriangles));   // new vertices, the same tree: refit in place
     await pathTracer.render();
   }
   pathTracer.synchronize();

@@ -5,6 +5,7 @@
 //   node raytracer-public_amd/js/main.mjs [--frames N] [--width W --height H] [--glb path] [--tris N] [--mode 0|1|2 --spp S --bounces B --seed K]
 //        [--cam x,y,z --quat x,y,z,w] [--bvh2 data/BVH2.bin] [--dump data/BVH2.bin | --dump none] [--radiance frame.f32 --triangles tris.f32]
 //        [--accel 0|1|2]   tree quality of buildBVH (this build's extension; 0 = the reference's tree)
+//        [--animate AMP]   displace the scene before every render() and refit the tree in place (updateTriangles; tools/README.md has the formula)
 // A GLB that exists and cannot be read ends the process with a non-zero status (the reference has no catch, src/main.js:20-23); only a file that
 // is not there falls back to the procedural stand-in.
 import * as PT from "./libs/PathTracer.js";
@@ -59,12 +60,15 @@ async function main() {
   // ---------- Render Loop ----------  src/main.js:48-76
   const frames = Number(arg("frames", 30));
   let frameIndex = 0;
+  const animate = Number(arg("animate", 0));                  // --animate AMP: the scene as built, displaced by the wave of the frame count before every render()
+  const baseTriangles = animate ? Float32Array.from(pathTracer.trianglesData) : null, movedTriangles = animate ? new Float32Array(baseTriangles.length) : null;
   const t0 = Date.now();
   for (let f = 0; f < frames; f++) {
     frameIndex++;
     pathTracer.setCameraPosition(camera.position[0], camera.position[1], camera.position[2]);
     pathTracer.setCameraQuaternion(camera.rotation[0], camera.rotation[1], camera.rotation[2], camera.rotation[3]);
     pathTracer.setFrameCount(frameIndex);
+    if (animate) pathTracer.updateTriangles(PT.animateWave(baseTriangles, animate, frameIndex, movedTriangles));   // new vertices, the same tree: refit in place
     await pathTracer.render();
   }
   pathTracer.synchronize();

@@ -213,6 +213,21 @@ static napi_value fn_set_triangles(napi_env env, napi_callback_info info) {   /*
     PT_CALL(ctx, pt_set_triangles(ctx, (const float*)d, (uint32_t)(len / 9)), "pt_set_triangles");
     return NULL;
 }
+/* new vertices, the same tree: refit in place (pt_update_triangles); the array is copied during the call */
+static napi_value fn_update_triangles(napi_env env, napi_callback_info info) {
+    napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    void* d; size_t len; if (!get_typed(env, argv[1], napi_float32_array, &d, &len)) return NULL;
+    if (len % 9) { napi_throw_type_error(env, NULL, "updateTriangles: 9 floats per triangle"); return NULL; }
+    PT_CALL(ctx, pt_update_triangles(ctx, (const float*)d, (uint32_t)(len / 9)), "pt_update_triangles");
+    return NULL;
+}
+static napi_value fn_bvh_cost(napi_env env, napi_callback_info info) {
+    napi_value argv[1]; if (!get_args(env, info, 1, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    double cost = 0; PT_CALL(ctx, pt_bvh_cost(ctx, &cost), "pt_bvh_cost");
+    napi_value v; NAPI_OK(napi_create_double(env, cost, &v)); return v;
+}
 /* optional second argument of buildBVH / groupBuildBVH: the tree-quality level (PT_ACCEL_*), 0 when absent or undefined */
 static int get_accel(napi_env env, napi_callback_info info, napi_value* argv, uint32_t* accel) {
     size_t argc = 2;
@@ -512,6 +527,21 @@ static napi_value fn_group_set_triangles(napi_env env, napi_callback_info info) 
     PTG_CALL(g, pt_group_set_triangles(g, (const float*)d, (uint32_t)(len / 9)), "pt_group_set_triangles");
     return NULL;
 }
+static napi_value fn_group_update_triangles(napi_env env, napi_callback_info info) {
+    napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    void* d; size_t len; if (!get_typed(env, argv[1], napi_float32_array, &d, &len)) return NULL;
+    if (len % 9) { napi_throw_type_error(env, NULL, "updateTriangles: 9 floats per triangle"); return NULL; }
+    PTG_CALL(g, pt_group_update_triangles(g, (const float*)d, (uint32_t)(len / 9)), "pt_group_update_triangles");
+    return NULL;
+}
+static napi_value fn_group_bvh_cost(napi_env env, napi_callback_info info) {      /* member 0: every member holds the same tree */
+    napi_value argv[1]; if (!get_args(env, info, 1, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    double cost = 0; PT_CALL(ctx, pt_bvh_cost(ctx, &cost), "pt_bvh_cost");
+    napi_value v; NAPI_OK(napi_create_double(env, cost, &v)); return v;
+}
 static napi_value fn_group_build_bvh(napi_env env, napi_callback_info info) {
     napi_value argv[2]; uint32_t accel; if (!get_accel(env, info, argv, &accel)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -596,14 +626,14 @@ static napi_value init(napi_env env, napi_value exports) {
         {"computeBVH2Sizing", fn_bvh2_sizing}, {"computeBVH4Sizing", fn_bvh4_sizing},
         {"mortonSort", fn_morton_sort}, {"collapse", fn_collapse}, {"bvh4Wide", fn_bvh4_wide},
         {"writeU32File", fn_write_u32}, {"readU32File", fn_read_u32}, {"proceduralScene", fn_procedural},
-        {"setTriangles", fn_set_triangles}, {"buildBVH", fn_build_bvh}, {"readBVH2", fn_read_bvh2}, {"readBVH4", fn_read_bvh4},
+        {"setTriangles", fn_set_triangles}, {"updateTriangles", fn_update_triangles}, {"bvhCost", fn_bvh_cost}, {"buildBVH", fn_build_bvh}, {"readBVH2", fn_read_bvh2}, {"readBVH4", fn_read_bvh4},
         {"setBVH4", fn_set_bvh4}, {"setBVH2", fn_set_bvh2}, {"setSpheres", fn_set_spheres}, {"sceneInfo", fn_scene_info},
         {"render", fn_render}, {"setBatch", fn_set_batch}, {"flush", fn_flush}, {"lastRenderMs", fn_last_ms}, {"synchronize", fn_sync}, {"getStats", fn_stats},
         {"readRadiance", fn_read_radiance}, {"readRGBA8", fn_read_rgba8}, {"readTonemapped", fn_read_tonemapped},
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
         {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
-        {"groupSetTriangles", fn_group_set_triangles}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
+        {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
         {"groupReadBVH2", fn_group_read_bvh2}, {"groupSetBatch", fn_group_set_batch}, {"groupRender", fn_group_render}, {"groupFlush", fn_group_flush},
         {"groupSynchronize", fn_group_sync}, {"groupReadRadiance", fn_group_read_radiance}, {"groupReadRGBA8", fn_group_read_rgba8}, {"groupReadTonemapped", fn_group_read_tonemapped},
     };
