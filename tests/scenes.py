@@ -37,6 +37,45 @@ def cornell():
     return tris, spheres
 
 
+def _quad(a, b, c, d):
+    return [a, b, c, a, c, d]
+
+
+def room():
+    """The cornell() box (open towards +z) with two tilted panels standing free inside: seen from the opening most paths run long, so
+    Russian roulette decides how they end (14 triangles)."""
+    v = []
+    v += _quad((-0.75, -0.9, -0.15), (-0.15, -0.9, -0.6), (-0.1, 0.3, -0.55), (-0.7, 0.3, -0.1))
+    v += _quad((0.15, -0.85, 0.1), (0.8, -0.85, -0.35), (0.75, 0.05, -0.45), (0.1, 0.05, 0.0))
+    return np.concatenate([cornell()[0], np.array(v, np.float32).reshape(-1)])
+
+
+def closed_box():
+    """cornell() with its front closed: twelve triangles with shared edges; from inside no ray escapes and no light gets in."""
+    front = _quad((-1, -1, 1), (1, -1, 1), (1, 1, 1), (-1, 1, 1))
+    return np.concatenate([cornell()[0], np.array(front, np.float32).reshape(-1)])
+
+
+def back_faces(seed=4):
+    """Twelve large triangles whose stored normals point away from a camera at (0, 0, 2.5) looking down -z (n.z < 0, tilted by at most
+    about 20 degrees): every primary hit is a back face, nf = -n."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(12):
+        c = np.array([rng.uniform(-1.2, 1.2), rng.uniform(-0.9, 0.9), rng.uniform(-1.0, 0.8)])
+        ang = rng.uniform(0, 2 * np.pi) + np.array([0.0, 2.1, 4.2]) + rng.uniform(-0.3, 0.3, 3)
+        r = rng.uniform(0.5, 1.0, 3)
+        p = np.stack([c[0] + r * np.cos(ang), c[1] + r * np.sin(ang), c[2] + rng.uniform(-0.12, 0.12, 3)], 1)
+        n = np.cross(p[1] - p[0], p[2] - p[0])
+        if n[2] > 0:
+            p = p[[0, 2, 1]]
+        out.append(p)
+    return np.array(out, np.float32).reshape(-1)
+
+
+BIG_TRIANGLE = np.array([-3, -2, -1, 3, -2, -1.5, 0, 3, -0.5], np.float32)     # alone in space: no secondary or shadow ray can meet anything
+
+
 def _f16_down(v):
     h = np.float16(v)
     return h if np.float32(h) <= np.float32(v) else np.nextafter(h, np.float16(-np.inf))
