@@ -1,0 +1,530 @@
+"""An exhaustive audit of a BVH as the traversal sees it: every triangle of every tree, not the rays a test happens to sample.
+
+Two checks, both O(N) on the reference side, numpy and float64 only -- no oracle, no product code:
+
+1. verify_bvh4 / verify_bvh2: a proof on the words read back from the device (read_bvh4 / read_bvh2).  Topology (every reachable node
+   reached once, every triangle in exactly one reachable leaf, child counts, pre-order for trees this library builds); transitive
+   containment (the three vertices of every triangle inside the exactly decoded f16 box of EVERY ancestor on its root path, the one
+   exemption being the f16 subnormal flush of DESIGN.md section 3); and no stale or loose box (every box is what the rules of
+   DESIGN.md sections 3 and 14 give, stated in the ordered-integer form of f16).  Vectorised level by level.
+2. aimed_rays / judge: four rays aimed at every triangle, traced by the code under test and judged by float64 Moeller-Trumbore
+   (pathref.pair) against that triangle alone, and against the triangle the code reported.
+
+The megakernel's own traversal (pt_megakernel_loop.inc) cannot be reached by caller rays, so check 2 does not cover it; it stays covered by
+the sampled pathref renders and by bit equality with the other kernels over the same arena, which check 1 does cover.
+
+Test helper, not product code and not a conftest."""
+import time
+
+import numpy as np
+
+import pathref
+from refit_cases import INVALID, LEAF, halves, ord16, unord16
+
+TINY = 2.0 ** -14                    # the smallest normal f16: bounds below it are flushed to a signed zero by half_trunc
+ORD_PINF, ORD_NINF = int(ord16(0x7C00)), int(ord16(0xFC00))
+MISS = 0xFFFFFFFF
+
+
+def decode(words):
+    """(.., 3) box words -> (.., 6) float64, every f16 exactly: mn.x mn.y mn.z mx.x mx.y mx.z"""
+    return halves(words).astype(np.uint16).view(np.float16).astype(np.float64)
+
+
+def leaf_rule(tris, t):
+    """RTNE f16 of the min / max of the three vertices (-0 below +0), one f16 step outwards, always.  -> (len(t), 6) ordered integers."""
+    v = np.asarray(tris, np.float32).reshape(-1, 3, 3)[t]
+    with np.errstate(over="ignore"):
+        o = ord16(v.astype(np.float16).view(np.uint16))
+    return np.concatenate([o.min(1) - 1, o.max(1) + 1], -1)
+
+
+class _Tree:
+    def __init__(self, words, stride):
+        w = np.asarray(words, np.uint32)
+        self.m = m = int(w[0])
+        self.K = K = stride - 4
+        assert len(w) >= 1 + stride * m, "the buffer is shorter than its node count says"
+        rec = w[1:1 + stride * m].reshape(m, stride)
+        self.kids = rec[:, 3:3 + K].astype(np.int64)
+        self.meta = rec[:, 3 + K]
+        self.leaf = (self.meta & LEAF) != 0
+        self.tri = (self.meta & 0x7FFFFFFF).astype(np.int64)
+        self.o = ord16(halves(rec[:, :3]))
+        self.val = decode(rec[:, :3])
+        self.ok = (self.kids != INVALID) & (self.kids < m) & ~self.leaf[:, None]      # the children the traversal fetches
+
+    def rule(self, nodes, child_o):
+        """The box of internal `nodes` from the ordered boxes `child_o` of their children: BVH4 the union from +-inf with the subnormal
+        flush (collapse_up_kernel, half_trunc), BVH2 the union stepped once outwards (propagateUp)."""
+        k = self.kids[nodes]
+        ok = self.ok[nodes]
+        ko = child_o[np.where(ok, k, 0)]
+        lo = np.where(ok[..., None], ko[..., :3], 1 << 20).min(1)
+        hi = np.where(ok[..., None], ko[..., 3:], -(1 << 20)).max(1)
+        if self.K == 2:
+            return np.concatenate([lo - 1, hi + 1], -1)
+        h = unord16(np.concatenate([np.minimum(lo, ORD_PINF), np.maximum(hi, ORD_NINF)], -1))
+        return ord16(np.where((h & 0x7C00) == 0, h & 0x8000, h))
+
+
+class TreeReport:
+    """What verify_bvh4 / verify_bvh2 found.  errors: topology, as text.  outside / exempt: (tri, node, stick-out) of every (triangle,
+    ancestor) pair whose box the triangle leaves -- beyond, or within, the flush exemption.  stale: nodes whose box is not the rule's
+    (stale_loose: it contains the rule's box; otherwise it is too tight somewhere).  parent, depth (-1: not reachable), leaf_of (per triangle)."""
+
+    def perfect(self, exact=True):
+        return not self.errors and len(self.outside) == 0 and (not exact or len(self.stale) == 0)
+
+    def summary(self):
+        return "%s: %d nodes (%d reachable, depth %d), %d triangles; %d topology errors, %d (triangle, ancestor) pairs outside, %d within the flush exemption (%d triangles), %d stale boxes (%d loose); %.2f s" % (
+            self.kind, self.m, int((self.depth >= 0).sum()), int(self.depth.max()), self.n, len(self.errors), len(self.outside), len(self.exempt),
+            len(np.unique(self.exempt["tri"])), len(self.stale), int(self.stale_loose.sum()), self.seconds)
+
+    def leaves_box_of(self, tri):
+        """The ancestors whose box triangle `tri` leaves beyond the exemption."""
+        return self.outside["node"][self.outside["tri"] == tri]
+
+
+PAIR = np.dtype([("tri", np.int64), ("node", np.int64), ("stick", np.float64)])
+
+
+def _verify(tris, words, stride, built, kind):
+    t0 = time.time()
+    tr = _Tree(words, stride)
+    V = np.asarray(tris, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    n, m, K = len(V), tr.m, tr.K
+    r = TreeReport()
+    r.kind, r.n, r.m, r.errors = kind, n, m, []
+    err = r.errors.append
+
+    # ---- the walk from the root, a level per step ----
+    parent = np.full(m, -1, np.int64); depth = np.full(m, -1, np.int64); visits = np.zeros(m, np.int64)
+    levels = []
+    front = np.zeros(1, np.int64)
+    depth[0] = 0; visits[0] = 1
+    while len(front):
+        levels.append(front)
+        inner = front[~tr.leaf[front]]
+        ok = tr.ok[inner]
+        c = tr.kids[inner][ok]
+        p = np.repeat(inner, K).reshape(-1, K)[ok]
+        np.add.at(visits, c, 1)
+        new = depth[c] < 0
+        cu, first = np.unique(c[new], return_index=True)
+        depth[cu] = len(levels); parent[cu] = p[new][first]
+        front = cu
+    reach = depth >= 0
+    r.parent, r.depth = parent, depth
+    if (visits > 1).any():
+        err("%d nodes are reached more than once, first %s" % (int((visits > 1).sum()), np.flatnonzero(visits > 1)[:5].tolist()))
+
+    # ---- topology ----
+    rleaf = np.flatnonzero(reach & tr.leaf & (tr.tri < n))
+    count = np.bincount(tr.tri[rleaf], minlength=n)
+    if not np.all(count == 1):
+        err("%d triangles sit in no reachable leaf, %d in several; first %s" % (int((count == 0).sum()), int((count > 1).sum()), np.flatnonzero(count != 1)[:5].tolist()))
+    leaf_of = np.full(n, -1, np.int64)
+    leaf_of[tr.tri[rleaf][::-1]] = rleaf[::-1]
+    r.leaf_of = leaf_of
+    rinner = np.flatnonzero(reach & ~tr.leaf)
+    present = tr.kids[rinner] != INVALID
+    cnt = tr.ok[rinner].sum(1)
+    if not np.all(tr.ok[rinner] == present):
+        err("internal nodes name children beyond the node count")
+    if K == 2 and not np.all(cnt == 2):
+        err("BVH2 internal nodes without exactly two children: %s" % rinner[cnt != 2][:5].tolist())
+    if K == 4 and not (np.all(cnt >= 2) and np.all(cnt <= 4) and np.all(present[:, :-1] >= present[:, 1:])):
+        err("BVH4 internal nodes without 2..4 children packed to the front: %s" % rinner[(cnt < 2) | (present[:, :-1] < present[:, 1:]).any(1)][:5].tolist())
+    if built:
+        if not reach.all():
+            err("%d nodes of a built tree are not reachable" % int((~reach).sum()))
+        if (tr.leaf & (tr.tri >= n)).any():
+            err("a built tree has leaves beyond the triangle count")
+        if not np.all(tr.meta[~tr.leaf] == 0):
+            err("internal nodes with a non-zero last word")
+        if K == 4:
+            if not np.all(tr.kids[tr.leaf] == INVALID):
+                err("leaves with child words")
+            # DFS pre-order: the first child is the next node, every further child starts where its sibling's subtree ended
+            size = np.ones(m, np.int64)
+            for lv in levels[:0:-1]:
+                np.add.at(size, parent[lv], size[lv])
+            k = tr.kids[rinner]
+            good = k[:, 0] == rinner + 1
+            for s in range(1, 4):
+                here = tr.ok[rinner][:, s]
+                prev = np.where(here, k[:, s - 1], 0)
+                good &= ~here | (k[:, s] == prev + size[prev])
+            if not good.all():
+                err("not in DFS pre-order at nodes %s" % rinner[~good][:5].tolist())
+        else:
+            if m != 2 * n - 1 or not np.array_equal(tr.leaf, np.arange(m) >= n - 1):
+                err("BVH2 layout: internal nodes 0..N-2, leaves N-1.. expected")
+
+    # ---- no stale or loose boxes: the rules, from the triangles upwards and from the stored children ----
+    eo = tr.o.copy()
+    eo[rleaf] = leaf_rule(tris, tr.tri[rleaf])
+    has = tr.ok.any(1)
+    for lv in levels[::-1]:
+        nodes = lv[~tr.leaf[lv] & has[lv]]
+        if len(nodes):
+            eo[nodes] = tr.rule(nodes, eo)
+    local = tr.o.copy()
+    nodes = rinner[has[rinner]]
+    if len(nodes):
+        local[nodes] = tr.rule(nodes, tr.o)
+    local[rleaf] = eo[rleaf]
+    # a box is right if it is the rule over its stored children, or the rule over the triangles below it: by induction from the leaves a
+    # tree without a flag equals the rule's tree word for word, and damage is flagged where it is, not at every ancestor it leaks into
+    bad = reach & (tr.o != local).any(1) & (tr.o != eo).any(1)
+    r.stale = np.flatnonzero(bad)
+    r.stale_loose = np.all(tr.o[r.stale, :3] <= eo[r.stale, :3], 1) & np.all(tr.o[r.stale, 3:] >= eo[r.stale, 3:], 1)
+    r.expected = eo
+
+    # ---- transitive containment: every triangle climbs its root path ----
+    vlo, vhi = V.min(1), V.max(1)
+    act = np.flatnonzero(leaf_of >= 0)
+    cur = leaf_of[act]
+    found = []
+    while len(act):
+        b = tr.val[cur]
+        lo, hi = b[:, :3], b[:, 3:]
+        with np.errstate(invalid="ignore"):
+            out = np.concatenate([~(lo <= vlo[act]), ~(hi >= vhi[act])], 1)
+            stick = np.concatenate([lo - vlo[act], vhi[act] - hi], 1)
+        rows = np.flatnonzero(out.any(1))
+        if len(rows):
+            st = np.where(out[rows], np.where(np.isnan(stick[rows]), np.inf, stick[rows]), 0.0)
+            flushed = (b[rows] == 0) & (st < TINY)                           # a bound that is exactly +-0, exceeded by less than 2^-14
+            e = np.zeros(len(rows), np.dtype(PAIR.descr + [("exempt", bool)]))
+            e["tri"], e["node"], e["stick"], e["exempt"] = act[rows], cur[rows], st.max(1), np.all(~out[rows] | flushed, 1)
+            found.append(e)
+        cur = parent[cur]
+        keep = cur >= 0
+        act, cur = act[keep], cur[keep]
+    f = np.concatenate(found) if found else np.zeros(0, np.dtype(PAIR.descr + [("exempt", bool)]))
+    r.exempt = f[f["exempt"]][["tri", "node", "stick"]]
+    r.outside = f[~f["exempt"]][["tri", "node", "stick"]]
+    r.seconds = time.time() - t0
+    return r
+
+
+def verify_bvh4(tris, bvh4, built=True):
+    """The words of read_bvh4().  built=False: a tree installed with set_bvh4, held only to what DESIGN.md section 14 promises -- nodes
+    no path from the root reaches may exist, ids need not be in pre-order."""
+    return _verify(tris, bvh4, 8, built, "BVH4")
+
+
+def verify_bvh2(tris, bvh2, built=True):
+    return _verify(tris, bvh2, 6, built, "BVH2")
+
+
+def assert_tree(r, name, exact=True):
+    """A perfect tree.  exact=False for an installed tree whose boxes were made by other rules (a BVH4_wide promotion before its first
+    update keeps the BVH2's boxes): containment and topology only."""
+    print("%s %s" % (name, r.summary()))
+    assert not r.errors, "%s: %s" % (name, "; ".join(r.errors))
+    assert len(r.outside) == 0, "%s: %d (triangle, ancestor) pairs outside beyond the flush exemption, first (tri, node, stick-out) %s" % (name, len(r.outside), r.outside[:5].tolist())
+    if exact:
+        assert len(r.stale) == 0, "%s: %d boxes are not the rule's (%d of them loose), first nodes %s" % (name, len(r.stale), int(r.stale_loose.sum()), r.stale[:5].tolist())
+
+
+# ---- aimed rays -----------------------------------------------------------------------------------------------------------------------
+H_REL = 1e-4
+BARY = np.array([[1 / 3, 1 / 3, 1 / 3], [0.9, 0.05, 0.05], [0.05, 0.9, 0.05], [0.05, 0.05, 0.9]])
+
+
+class Rays:
+    """O, D (R, 3) and t_max (R,) in f32; tri (R,): the triangle ray i is aimed at (rays of a triangle are consecutive); P: the aimed point, f64."""
+
+
+def aimed_rays(tris, k=4, h=H_REL):
+    """k <= 4 rays per triangle: at the centroid and at the points with barycentrics (0.9, 0.05, 0.05) and its permutations.  Origin
+    p + s h' n, direction -s n (n the unit geometric normal, s = +1 for even and -1 for odd triangles), t_max = 2 h',
+    h' = h max(1, |p|inf); everything rounded to f32 before anybody sees it.
+
+    h = 1e-4, chosen from the reference alone.  It has to clear pathref's margins: t and t_max - t are both h', against
+    mt = max(D_T, COND_ULPS 2^-24 kappa e / |d|), which for a ray along the normal is about 1e-6 (|o| + |v0| + e) e^2 / 2A.  At unit scale
+    that is below 1e-4 up to e^2 / 2A of about 30 (longest edge squared over twice the area); a sliver beyond that gets h' = 2 mt instead
+    (0.5 % of the triangles of a random soup, by up to 27 times; never more than 1000 times, beyond which the triangle stays not
+    auditable).  And it has to keep occluders rare: a segment of 2e-4 meets another triangle of the 120,000-triangle soup (size 0.2 in
+    [-1, 1]^3, about 30 triangle crossings per unit length) in well under 1 % of the rays.
+    Measured -- rays not auditable / answered by an occluder, a duplicate or a triangle at a margin / triangles without any auditable
+    ray; float64 reference over the host twins and the oracle's traversal (tests/test_tree_audit.py), closest hit:
+      soups 1 .. 2,500, 30,000 and 120,000 (size 0.2)  0 % / 0 - 0.03 % / 0 %     (120,000: 0 of 1,500 sampled rays answered by an occluder, by brute force)
+      dragon-class 1,500 - 3,000, sponza-class 12,000  0 % / 0 % / 0 %            (0.15 % occluders after eight waves of amplitude 0.32)
+      room, cornell, f16 grid                          0 % / 0 % / 0 %            (exactly axis-parallel rays)
+      soup of size 2 in [980, 1020]^3                  0.49 % / 0.11 % / 0 %      (|o| / e conditions a pair: at size 0.2 a third of the corner rays are not auditable)
+      soup x 27,000                                    0 % / 0 % / 0 %
+      a cluster of 1 % collapsed to a point            1 % / 0 % / 1 %            (zero area: unhittable by the specification)
+      C2 (871,414) and C4 (262,144), reference only    0 % not auditable, 0 % without an auditable ray
+    The DEGENERATE families are outside what any h can audit and are classed, not capped (test_tree_audit.check_family): tiny 100 % not
+    auditable (|e1 x e2| of 1e-11 against the 1e-7 determinant threshold); identical 99.7 % answered by a duplicate; coplanar 94 %,
+    signed_zero 53 %, two_clusters 80 % answered by a coplanar or nearer triangle; mixed_zero 6.8 % without area, 25 % answered by another."""
+    T = np.asarray(tris, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    n = len(T)
+    c = np.cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+    ln = np.sqrt((c * c).sum(1))
+    with np.errstate(all="ignore"):
+        nrm = np.where((ln > 0)[:, None] & np.isfinite(ln)[:, None], c / ln[:, None], np.array([0.0, 0.0, 1.0]))
+    P = np.einsum("kj,njc->nkc", BARY[:k], T)
+    s = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    hh = h * np.maximum(1.0, np.abs(P).max(-1))
+    # a sliver's own margin of t (pathref's mt for a unit direction along the normal, |det| = |e1 x e2|) can exceed that: such a ray starts
+    # twice its margin away instead, as long as that stays a small step (a tenth of the scale); beyond it the triangle is left not auditable
+    E = np.stack([T[:, 1] - T[:, 0], T[:, 2] - T[:, 0]], 1)
+    em = np.sqrt((E ** 2).sum(-1).max(1))
+    with np.errstate(all="ignore"):
+        mt = pathref.COND_ULPS * pathref.U32 * (em * em / ln)[:, None] * (np.sqrt((P ** 2).sum(-1)) + hh + np.sqrt((T[:, 0] ** 2).sum(1))[:, None] + em[:, None])
+    hh = np.where(np.isfinite(mt) & (2 * mt > hh) & (2 * mt <= 1000 * hh), 2 * mt, hh)
+    r = Rays()
+    r.O = (P + (s[:, None] * hh)[..., None] * nrm[:, None, :]).astype(np.float32).reshape(-1, 3)
+    r.D = np.repeat((-s[:, None] * nrm).astype(np.float32), k, 0)
+    r.t_max = (2 * hh).astype(np.float32).reshape(-1)
+    r.tri = np.repeat(np.arange(n), k)
+    r.P = P.reshape(-1, 3)
+    r.k, r.n, r.own = k, n, None
+    return r
+
+
+def margins(tris, O, D, prim, t_max):
+    """pathref._candidates for the pair (ray i, triangle prim[i]) alone, elementwise: -> dict(acc, loose, tight, t, u, v, mt)."""
+    det, u, v, t = pathref.pair(tris, O, D, prim)
+    T = np.asarray(tris, np.float32).reshape(-1, 3, 3)[np.asarray(prim, np.int64)].astype(np.float64)
+    o = np.asarray(O, np.float32).astype(np.float64); d = np.asarray(D, np.float32).astype(np.float64)
+    e1, e2 = T[:, 1] - T[:, 0], T[:, 2] - T[:, 0]
+    em = np.sqrt(np.maximum((e1 ** 2).sum(1), (e2 ** 2).sum(1)))
+    v0n = np.sqrt((T[:, 0] ** 2).sum(1)); dn = np.sqrt((d * d).sum(1)); on = np.sqrt((o * o).sum(1))
+    b0 = np.minimum(np.asarray(t_max, np.float32).astype(np.float64), pathref.INF_T)
+    eps = pathref.EPS_T
+    with np.errstate(all="ignore"):
+        adet = np.abs(det)
+        kap = dn * em * (on + v0n + em) / adet
+        mb = np.maximum(pathref.D_B, pathref.COND_ULPS * pathref.U32 * kap)
+        mt = np.maximum(pathref.D_T, pathref.COND_ULPS * pathref.U32 * kap * em / dn)
+        bary = np.minimum(np.minimum(u, 1 - u), np.minimum(v, 1 - u - v))
+        acc = (adet >= eps) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t > eps) & (t < b0)
+        loose = (adet >= eps - pathref.D_DET) & (bary > -mb) & (t > eps - mt) & (t < b0 + mt)
+        tight = (adet >= eps + pathref.D_DET) & (bary >= mb) & (t >= eps + mt) & (t <= b0 - mt)
+    return dict(acc=acc, loose=loose | acc, tight=tight, t=t, u=u, v=v, mt=mt, det=det)
+
+
+class Judgement:
+    """Per ray: auditable (the reference accepts its own triangle with every margin to spare), own (the code reported it), occluder (it
+    reported another triangle the reference accepts for certain no farther), fragile (it reported a triangle at a margin of the
+    reference: a knife edge by pathref's rules, not comparable), lost.  lost_tris: the triangles of the lost rays."""
+
+    def summary(self):
+        return "%d triangles (%d audited), %d rays: not auditable %.3f %%, answered by an occluder or duplicate %.3f %% (%d rays), at a margin %.3f %%, ill-conditioned values %.3f %%; triangles without an auditable ray %.3f %%; lost rays %d (triangles %d); reference %.2f s" % (
+            self.n, self.n - int(round(self.share_blind_tris * self.n)), self.R, 100 * self.share_not_auditable, 100 * self.share_occluder, int((self.auditable & (self.occluder | self.fragile)).sum()), 100 * self.fragile.mean() if self.R else 0.0,
+            100 * self.poor.mean() if self.R else 0.0, 100 * self.share_blind_tris, len(self.lost), len(self.lost_tris), self.seconds)
+
+
+def judge(tris, rays, got, any_hit=False):
+    """got = (t, prim, u, v) as trace_rays returns them.  O(rays): float64 Moeller-Trumbore of each ray against its own triangle and
+    against the reported one, nothing else."""
+    t0 = time.time()
+    t, prim, u, v = [np.asarray(a) for a in got]
+    n, R = rays.n, len(rays.tri)
+    if rays.own is None:                                                         # the same for every kernel and hit type: once per ray set
+        rays.own = margins(tris, rays.O, rays.D, rays.tri, rays.t_max)
+    own = rays.own
+    j = Judgement()
+    j.n, j.R, j.any_hit, j.tri = n, R, any_hit, rays.tri
+    aud = j.auditable = own["tight"]
+    got_hit = prim != MISS
+    inrange = got_hit & (prim < n)
+    is_own = got_hit & (prim.astype(np.int64) == rays.tri)
+    oth = np.flatnonzero(inrange & ~is_own)
+    j.occluder = np.zeros(R, bool); j.fragile = np.zeros(R, bool); j.poor = np.zeros(R, bool); j.values_off = np.zeros(0, np.int64)
+    phantom = got_hit & ~inrange
+    if any_hit:
+        # it must hit, and the reference must accept the reported triangle below t_max
+        h = np.flatnonzero(inrange)
+        okh, th = pathref.loosely_accepts(tris, rays.O[h], rays.D[h], prim[h], rays.t_max[h])
+        good = np.zeros(R, bool); good[h] = okh
+        j.occluder[oth] = good[oth]
+        j.lost = np.flatnonzero(aud & ~good)
+        phantom |= got_hit & ~good & ~aud
+    else:
+        m = margins(tris, rays.O[oth], rays.D[oth], prim[oth], rays.t_max[oth])
+        ti, mti = own["t"][oth], own["mt"][oth]
+        with np.errstate(invalid="ignore"):
+            sure = m["tight"] & (m["t"] <= ti + pathref.D_T)
+            edge = ~sure & m["loose"] & (~aud[oth] | (m["t"] < (ti + mti) + m["mt"]))
+        j.occluder[oth] = sure
+        j.fragile[oth] = edge
+        phantom[oth[~sure & ~edge & ~aud[oth]]] = True                         # a ray that is not auditable is still explained
+        j.lost = np.flatnonzero(aud & ~is_own & ~j.occluder & ~j.fragile)
+        # values, where plain f32 can deliver them: the reference's own f32 evaluation of the pair within TOL / 4 (QueryRef.poor's rule)
+        s = np.flatnonzero(aud & is_own)
+        _, u32, v32, t32 = pathref.pair(tris, rays.O[s], rays.D[s], rays.tri[s], np.float32)
+        q = pathref.TOL / 4
+        tr, ur, vr = own["t"][s], own["u"][s], own["v"][s]
+        with np.errstate(invalid="ignore"):
+            j.poor[s] = ~((np.abs(u32 - ur) <= q) & (np.abs(v32 - vr) <= q) & (np.abs(t32 - tr) <= q * np.maximum(tr, 1)))
+            off = ~j.poor[s] & ~((np.abs(t[s] - tr) <= pathref.TOL * np.maximum(tr, 1)) & (np.abs(u[s] - ur) <= pathref.TOL) & (np.abs(v[s] - vr) <= pathref.TOL))
+        j.values_off = s[off]
+    j.phantom = np.flatnonzero(phantom)
+    j.lost_tris = np.unique(rays.tri[j.lost])
+    j.share_not_auditable = float((~aud).mean()) if R else 0.0
+    j.share_occluder = float((aud & (j.occluder | j.fragile)).mean()) if R else 0.0
+    j.share_blind_tris = float((np.bincount(rays.tri[aud], minlength=n) == 0).mean()) if n else 0.0
+    j.seconds = time.time() - t0
+    return j
+
+
+def assert_judged(j, name, tree=None, capped=True):
+    """No lost triangle, no hit the reference cannot explain, values within pathref.TOL; and (capped) the rays this audit cannot use --
+    not auditable, or answered by an occluder -- at most pathref.FRAGILE_CAP of the case, as are triangles without any auditable ray."""
+    lost, flushed = j.lost_tris, np.zeros(0, np.int64)
+    if tree is not None:
+        # a loss the containment proof attributes to the subnormal flush is the reference's behaviour: counted within the cap, not a failure
+        mine = np.isin(lost, tree.exempt["tri"]) & ~np.isin(lost, tree.outside["tri"])
+        lost, flushed = lost[~mine], lost[mine]
+    print("%s%s %s%s" % (name, " any hit" if j.any_hit else "", j.summary(), "; %d of the lost triangles stick out of a flushed bound" % len(flushed) if len(flushed) else ""))
+    if len(lost):
+        why = ""
+        if tree is not None:
+            why = "; boxes they leave (tri -> nodes): %s" % {int(t): tree.leaves_box_of(t).tolist() for t in lost[:10]}
+        raise AssertionError("%s: %d lost triangles, first %s%s" % (name, len(lost), lost[:20].tolist(), why))
+    assert len(j.phantom) == 0, "%s: %d rays report a triangle the reference cannot accept, first rays %s" % (name, len(j.phantom), j.phantom[:10].tolist())
+    assert len(j.values_off) == 0, "%s: t, u or v beyond pathref.TOL on %d rays, first %s" % (name, len(j.values_off), j.values_off[:10].tolist())
+    if capped:
+        cap = pathref.FRAGILE_CAP
+        unused = j.share_not_auditable + j.share_occluder + float(np.isin(j.tri[j.lost], flushed).sum()) / max(j.R, 1)
+        assert unused <= cap, "%s: %.2f %% of the rays are not auditable, answered by an occluder or lost to the flush (cap 2 %%): change the scene or h" % (name, 100 * unused)
+        assert j.share_blind_tris <= cap, "%s: %.2f %% of the triangles have no auditable ray (cap 2 %%)" % (name, 100 * j.share_blind_tris)
+
+
+def segment_meets_box(rays, idx, lo, hi, bounded=True, rel=1e-6):
+    """Does the segment of ray idx[i] (origin to t_max; the whole ray if not `bounded`) meet the box?  float64 slabs -> (certainly yes,
+    certainly no); a segment within `rel` of touching is neither.  For the detection tests: a triangle is lost exactly when its ray misses
+    a box on its path.  The kernels prune a box entered beyond t_max; the oracle's probe has no t_max, so
+    HostContext, which cuts the answer off afterwards, walks the whole ray (`prunes_at_t_max`)."""
+    o = rays.O[idx].astype(np.float64); d = rays.D[idx].astype(np.float64); tm = rays.t_max[idx].astype(np.float64)
+    with np.errstate(all="ignore"):
+        t1, t2 = (lo - o) / d, (hi - o) / d
+        par = d == 0
+        near = np.where(par, np.where((o >= lo) & (o <= hi), -np.inf, np.inf), np.minimum(t1, t2)).max(1)
+        far = np.where(par, np.where((o >= lo) & (o <= hi), np.inf, -np.inf), np.maximum(t1, t2)).min(1)
+    a, b = np.maximum(near, 0.0), np.minimum(far, tm) if bounded else far
+    slack = rel * np.maximum(1.0, np.abs(o).max(1))
+    return a <= b - slack, a > b + slack
+
+
+# ---- a context's tree through both checks ---------------------------------------------------------------------------------------------
+KERNELS = [False, True]              # simple=False: the persistent ray-query kernel; True: one ray per lane
+
+
+def audit_context(ctx, tris, name, built=True, exact=True, bvh2=True, capped=True, kernels=KERNELS, rays=None):
+    """The three steps for the tree `ctx` holds over `tris` (anything with read_bvh4 / read_bvh2 / trace_rays: a device context, or the
+    host twins with the oracle's traversal standing in): the words through verify_*, the aimed rays through every kernel, closest and
+    any hit, through judge.  -> (BVH4 report, {(simple, any_hit): judgement})."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    r4 = verify_bvh4(tris, ctx.read_bvh4(), built)
+    assert_tree(r4, name, exact)
+    if bvh2:
+        assert_tree(verify_bvh2(tris, ctx.read_bvh2(), built), name, exact)
+    rays = aimed_rays(tris) if rays is None else rays
+    out = {}
+    for simple in kernels:
+        for any_hit in (False, True):
+            got = ctx.trace_rays(rays.O, rays.D, t_max=rays.t_max, any_hit=any_hit, simple=simple)
+            out[simple, any_hit] = j = judge(tris, rays, got, any_hit)
+            assert_judged(j, "%s simple %d" % (name, simple), r4, capped)
+    return r4, out
+
+
+class HostContext:
+    """The calls of a device context that the audit uses, answered by the host twins of the build and the refit and by the oracle's
+    traversal (one orc.trace_ray per ray; t_max applied as DESIGN.md section 13 defines it: a hit iff the unbounded closest hit lies below)."""
+
+    prunes_at_t_max = False
+
+    def __init__(self, rt, orc):
+        self.rt, self.orc, self.b4, self.b2 = rt, orc, None, None
+
+    def set_triangles(self, tris):
+        self.tris = np.array(tris, np.float32).reshape(-1)
+        self.n = self.tris.size // 9
+        self.b4 = self.b2 = None
+
+    def build_bvh(self, accel=0):
+        self.b2 = self.rt.build_bvh2_ploc(self.tris) if accel == 2 else self.orc.build_lbvh2(self.tris)
+        self.b4 = self.rt.collapse_bvh2_to_bvh4_accel(self.b2, self.n, accel)[0]
+
+    def set_bvh4(self, bvh4):
+        self.b4, self.b2 = np.array(bvh4, np.uint32), None
+
+    def set_bvh2(self, bvh2):
+        self.b2 = np.array(bvh2, np.uint32)
+        self.b4 = self.rt.collapse_lbvh2_to_bvh4(self.b2, self.n)[0]
+
+    def update_triangles(self, tris):
+        self.tris = np.array(tris, np.float32).reshape(-1)
+        self.b4 = self.rt.refit_bvh4(self.tris, self.b4)
+        if self.b2 is not None:
+            self.b2 = self.rt.refit_bvh2(self.tris, self.b2)
+
+    def read_bvh4(self):
+        return self.b4
+
+    def read_bvh2(self):
+        return self.b2
+
+    def trace_rays(self, O, D, t_max=None, any_hit=False, simple=False):
+        R = len(O)
+        t = np.full(R, np.inf, np.float32); prim = np.full(R, MISS, np.uint32)
+        tm = np.full(R, np.inf, np.float32) if t_max is None else np.asarray(t_max, np.float32)
+        for i in range(R):
+            h, tt, _, tri = self.orc.trace_ray(self.tris, self.b4, O[i], D[i], anyhit=any_hit)
+            if h and any_hit and not tt < tm[i]:
+                h, tt, _, tri = self.orc.trace_ray(self.tris, self.b4, O[i], D[i], anyhit=False)
+            if h and tt < tm[i]:
+                t[i], prim[i] = tt, tri
+        hit = np.flatnonzero(prim != MISS)
+        u = np.zeros(R, np.float32); v = np.zeros(R, np.float32)
+        if len(hit):                                                            # the oracle's probe returns no barycentrics: the f32 evaluation of the winning pair
+            _, uu, vv, _ = pathref.pair(self.tris, O[hit], D[hit], prim[hit], np.float32)
+            u[hit], v[hit] = uu, vv
+        return t, prim, u, v
+
+
+# ---- scenes both audit files use ------------------------------------------------------------------------------------------------------
+def f16_grid(cells=16):
+    """Three axis-aligned planes of cells x cells quads whose vertices are multiples of 1 / 8: exactly representable in f16, every leaf box
+    two f16 steps thick in one axis, every aimed ray exactly axis-parallel.  One plane is z = 0: its leaves' boxes are [-0, 2^-24] in z
+    and the flush makes that [-0, +0] in the nodes above them -- boxes of zero thickness that still contain their triangles, where the slab
+    test's tmax >= tmin holds with equality (with > for >= every triangle of that plane is lost)."""
+    g = np.linspace(-1.0, 1.0, cells + 1)
+    a, b = np.meshgrid(g[:-1], g[:-1], indexing="ij")
+    s = 2.0 / cells
+    out = []
+    for axis, c in ((2, 0.0), (0, 0.25), (1, 0.75)):
+        q = np.zeros((cells * cells, 4, 3))
+        u, w = [x for x in range(3) if x != axis]
+        q[:, :, axis] = c
+        for k, (du, dw) in enumerate(((0, 0), (s, 0), (s, s), (0, s))):
+            q[:, k, u] = a.reshape(-1) + du; q[:, k, w] = b.reshape(-1) + dw
+        out.append(q[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3, 3))
+    t = np.concatenate(out).astype(np.float32)
+    assert np.array_equal(t, t.astype(np.float16).astype(np.float32))
+    return t.reshape(-1)
+
+
+def soup(n, seed, size=0.2):
+    """The soups of the build tests (tests/test_bvh_invariants.py)."""
+    rng = np.random.default_rng(seed)
+    c = rng.random((n, 1, 3), dtype=np.float32) * 2 - 1
+    return (c + (rng.random((n, 3, 3), dtype=np.float32) - 0.5) * size).astype(np.float32).reshape(-1)
+
+
+def collapse_cluster(tris, centre, count):
+    """The `count` triangles nearest to `centre`, every vertex moved to the centroid of the cluster: zero-area triangles, unhittable by the specification."""
+    T = np.array(tris, np.float32).reshape(-1, 3, 3)
+    d = ((T.mean(1) - np.asarray(centre, np.float32)) ** 2).sum(1)
+    pick = np.argsort(d, kind="stable")[:count]
+    T[pick] = T[pick].reshape(-1, 3).mean(0)
+    return T.reshape(-1), pick
