@@ -280,6 +280,64 @@ PT_API int pt_trace_rays_host(PtContext* ctx, const PtRay* rays, uint64_t n, uin
  * width * height PtRay records into rays_device (16-byte aligned).  Needs no scene.  Asynchronous on the context's stream. */
 PT_API int pt_camera_rays(PtContext* ctx, const PtRenderParams* params, void* rays_device);
 
+/* ---- batched closest-point queries: which triangle is nearest to a point? (an extension beyond the reference)
+ * For every point the nearest triangle of the scene within r_max, over the context's CURRENT tree, whatever set it (pt_build_bvh /
+ * pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2, refitted by pt_update_triangles or not).
+ *   found:   prim = the triangle with the smallest squared distance d2, evaluated in f32 (below); dist = sqrtf(d2), correctly rounded;
+ *            u, v = the closest point as v0 + u*e1 + v*e2 with e1 = v1 - v0, e2 = v2 - v0 as the triangle record stores them (each
+ *            rounded to f32 once at upload).  u, v are recomputed after the walk from the winning record with the same operations (the
+ *            same bits), as the ray queries do, so the walk keeps no registers for them.
+ *   nothing: dist = +INFINITY, prim = 0xFFFFFFFF, u = v = 0.
+ * Point-triangle arithmetic (f32, every operation rounded once, no contraction; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z), on
+ *   (ap = p - v0, e1, e2), operation by operation in DESIGN.md section 15 and csrc/pt_closest.h: the unconstrained minimum by one
+ *   Gram-Schmidt step (f = e2 - (b / a) e1; vq = (f . ap) / (f . f), uq = (d1 - vq * b) / a), Eberly's seven regions from the signs of
+ *   uq, vq and 1 - (uq + vq), folded onto the face or the edge that holds the minimum, and on an edge a quotient clamped to exactly 0
+ *   and 1.  Three reciprocals: 1 / a, 1 / (f . f), and 1 / den of the edges v0 v2 and v1 v2.  u, v >= 0 and u + v <= 1 + 2^-22.
+ *   d2 = dot(diff, diff) with diff = ap - (e1*u + e2*v).  NaN operands fail every comparison, reach the edge v1 v2 and leave a NaN d2,
+ *   as does a triangle collapsed to a point (0 / 0); a NaN d2 is never accepted.  A triangle collapsed to a segment still gets a point
+ *   of that segment.
+ * r_max: the best squared distance starts at r_max * r_max (+inf stays +inf); a triangle is accepted only when d2 < best2, strictly, and
+ *   the first minimum in visit order wins.  A point with a NaN in p or r_max, or with r_max <= 0, finds nothing and is not walked.
+ * The walk: the ray queries' walk with a squared lower bound of the distance to a child's box, bound2, in place of tmin.  A child is
+ *   entered only if bound2 < best2; passing children keep slot order, the first minimum trades places with the first passing child and
+ *   is entered next, the others are pushed far -> near; a stacked child is re-validated at pop by bound2 < best2.  Empty and degenerate
+ *   slots hold the inverted box (bound2 = +inf) and reject themselves; a leaf with t >= num_tris is skipped; a degenerate root box
+ *   means that every point finds nothing, as every ray misses.  The stack holds 64 entries; a push at the cap is dropped (and counted).
+ * bound2: per axis g = max(mn - (p + s), (p - s) - mx, 0) with s = 2^-12 and mn, mx the box's f16 bounds; bound2 = (gx*gx + gy*gy) + gz*gz.
+ *   The slack s covers the f16 subnormal flush of the internal boxes (a triangle may stick out of an ancestor's box by less than 2^-14)
+ *   and every rounding of bound2 and of d2: for vertex coordinates within [-4, 4] and point coordinates within [-32, 32] no triangle with
+ *   a smaller d2 is ever pruned (proof: DESIGN.md section 15).
+ * Exactness: wherever the walk drops nothing at the cap (stack_drops = 0) and every triangle is reachable from the root, dist has the
+ *   bits of the brute-force minimum over all triangles, and prim is a triangle with exactly that d2.
+ * PT_CLOSEST_BRUTE_FORCE: every triangle in index order, no tree (the precedent of PT_FLAG_BRUTE_FORCE): the tree-independent check.
+ * PT_CLOSEST_STATS: the counting variant (one point per thread) fills pt_get_stats: rays_closest = the number of points, nodes_examined,
+ *   tris_tested, stack_drops and max_stack by the rules of the ray queries' counters (rays_shadow = samples = 0).  With
+ *   PT_CLOSEST_BRUTE_FORCE only rays_closest and tris_tested are counted.
+ * PT_CLOSEST_SIMPLE_KERNEL: the one-point-per-thread kernel instead of the persistent one (A/B checks); the results are the same.
+ * Scene contents: triangles only.  Spheres (pt_set_spheres) take no part.
+ * Ordering, errors and alignment: as pt_trace_rays.  Frames queued by pt_set_batch are launched first; pt_closest_points does not wait
+ *   (the caller's buffers must stay allocated until a later pt_synchronize has returned); a scene change after a query does not change
+ *   its results.  A NULL or non-16-byte-aligned pointer, unknown flags or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the
+ *   scene).  No triangles + tree: PT_ERR_NO_SCENE.  n = 0: PT_OK, nothing is launched. */
+typedef struct PtPoint   { float p[3]; float r_max; } PtPoint;                  /* 16 B, 16-byte aligned arrays */
+typedef struct PtClosest { float dist; uint32_t prim; float u, v; } PtClosest;  /* 16 B */
+enum {
+    PT_CLOSEST_STATS = 1u,
+    PT_CLOSEST_SIMPLE_KERNEL = 2u,
+    PT_CLOSEST_BRUTE_FORCE = 4u
+};
+/* n points from device memory, n results into device memory (both 16-byte aligned, on the context's device).  Asynchronous on the
+ * context's stream (pt_get_stream). */
+PT_API int pt_closest_points(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* out_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the results are written. */
+PT_API int pt_closest_points_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out);
+/* Host twin (no context, no GPU): the same PtClosest bits and, with PT_CLOSEST_STATS and stats != NULL, the same counters as the device
+ * gives for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).  bvh4 = NULL (words = 0) only with PT_CLOSEST_BRUTE_FORCE;
+ * stats may be NULL; PT_CLOSEST_SIMPLE_KERNEL is accepted and changes nothing.  tris: f32[9 * num_tris]; bvh4: u32[1 + 8 * numNodes]
+ * (a malformed one: PT_ERR_BAD_BVH); a NULL points or out pointer with n > 0, or unknown flags: PT_ERR_INVALID_ARG. */
+PT_API int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                                  const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out, PtStats* stats);
+
 /* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
  * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
  * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes

@@ -30,6 +30,8 @@ SCENE_DRAGON_CLASS, SCENE_SPONZA_CLASS = 0, 1
 PT_ACCEL_REFERENCE, PT_ACCEL_AREA_COLLAPSE, PT_ACCEL_PLOC = 0, 1, 2
 # batched ray queries (include/mi355pt.h pt_trace_rays)
 PT_TRACE_ANY_HIT, PT_TRACE_STATS, PT_TRACE_SIMPLE_KERNEL = 1, 2, 4
+# batched closest-point queries (include/mi355pt.h pt_closest_points)
+PT_CLOSEST_STATS, PT_CLOSEST_SIMPLE_KERNEL, PT_CLOSEST_BRUTE_FORCE = 1, 2, 4
 PRIM_NONE = 0xFFFFFFFF
 
 
@@ -71,6 +73,16 @@ class PtHit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
 
 
+class PtPoint(C.Structure):
+    """include/mi355pt.h PtPoint (16 B); arrays of it must be 16-byte aligned.  As numpy / torch data: 4 float32 per point (x, y, z, r_max)."""
+    _fields_ = [("p", C.c_float * 3), ("r_max", C.c_float)]
+
+
+class PtClosest(C.Structure):
+    """include/mi355pt.h PtClosest (16 B): dist (+inf when nothing is found), prim (0xFFFFFFFF then), u, v of the closest point."""
+    _fields_ = [("dist", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
+
+
 class PtAccumInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
                 ("compact", C.c_uint32), ("samples", C.c_uint32), ("floats", C.c_uint64)]
@@ -86,6 +98,7 @@ EXPORTS = [
     "pt_read_rgba8", "pt_read_tonemapped", "pt_tile_layout", "pt_tile_ids", "pt_compact_radiance", "pt_deinterleave", "pt_deinterleave_batch", "pt_buffer_busy",
     "pt_accum_info", "pt_read_accum", "pt_set_accum",
     "pt_trace_rays", "pt_trace_rays_host", "pt_camera_rays",
+    "pt_closest_points", "pt_closest_points_host", "pt_closest_points_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -153,6 +166,31 @@ def pack_rays(origins, directions, t_max=None):
     out[:, 3] = np.inf if t_max is None else np.broadcast_to(np.asarray(t_max, np.float32), (o.shape[0],))
     out[:, 4:7] = d
     return out
+
+
+def pack_points(points, r_max=None):
+    """numpy: (n, 4) float32 PtPoint records (x, y, z, r_max) in a 16-byte aligned buffer; r_max None = +inf, a scalar or (n,)."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    out = _aligned_zeros((p.shape[0], 4), np.float32)
+    out[:, 0:3] = p
+    out[:, 3] = np.inf if r_max is None else np.broadcast_to(np.asarray(r_max, np.float32), (p.shape[0],))
+    return out
+
+
+def _point_records(points, r_max):
+    """(n, 3) points + r_max, or (n, 4) PtPoint records (r_max None: taken from the records) -> aligned (n, 4) float32 records."""
+    a = np.asarray(points, np.float32)
+    if a.ndim == 2 and a.shape[1] == 4:
+        if a.ctypes.data % 16 or not a.flags.c_contiguous or r_max is not None:
+            r2 = _aligned_zeros(a.shape, np.float32); r2[...] = a; a = r2          # (the caller's records are never written)
+            if r_max is not None:
+                a[:, 3] = r_max
+        return a
+    return pack_points(a, r_max)
+
+
+def _closest_flags(stats, simple, brute_force):
+    return (PT_CLOSEST_STATS if stats else 0) | (PT_CLOSEST_SIMPLE_KERNEL if simple else 0) | (PT_CLOSEST_BRUTE_FORCE if brute_force else 0)
 
 
 def _check(rc, ctx=None):
@@ -231,6 +269,27 @@ def refit_bvh4(tris, bvh4):
     out = np.array(bvh4, np.uint32).reshape(-1)
     _check(lib.pt_refit_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), _p(out, C.c_uint32), C.c_uint64(out.size)))
     return out
+
+
+def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.closest_points (no GPU): the nearest triangle of `tris` to each point over the tree set_bvh4(bvh4) installs, with
+    the device's bits.  bvh4 None needs brute_force=True.  Returns (dist, prim, u, v), and the counters as a dict in fifth place with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    pts = _point_records(points, r_max)
+    n = pts.shape[0]
+    out = _aligned_zeros((n, 4), np.uint32)
+    st = PtStats()
+    if bvh4 is None:
+        bp, words = None, 0
+    else:
+        bvh4 = np.ascontiguousarray(bvh4, np.uint32).reshape(-1)
+        bp, words = _p(bvh4, C.c_uint32), bvh4.size
+    _check(lib.pt_closest_points_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                      pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(_closest_flags(stats, simple, brute_force)),
+                                      out.ctypes.data_as(C.POINTER(PtClosest)), C.byref(st) if stats else None))
+    f = out.view(np.float32)
+    res = (f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy())
+    return res + (st.as_dict(),) if stats else res
 
 
 def refit_bvh2(tris, bvh2):
@@ -612,6 +671,55 @@ class Context:
         rays = torch.empty((params.height * params.width, 8), dtype=torch.float32, device=dev)
         self._on_context_stream(dev, lambda: self.camera_rays_device(params, rays.data_ptr()))
         return rays
+
+    # ---- batched closest-point queries (an extension beyond the reference; include/mi355pt.h) ----
+    def closest_points(self, points, r_max=None, stats=False, simple=False, brute_force=False):
+        """Which triangle is nearest to each point?  Returns (dist, prim, u, v): dist = +inf and prim = 0xFFFFFFFF when nothing lies within
+        r_max; the closest point is v0 + u * (v1 - v0) + v * (v2 - v0) of triangle prim.
+
+        points: (n, 3) float32, or (n, 4) PtPoint records (r_max=None: taken from the records).  numpy arrays take the host route (staged,
+        returns when done).  torch tensors on the context's device take the device route: zero-copy for contiguous (n, 4) float32 records,
+        no host synchronisation, ordered with torch's current stream both ways; the results are torch tensors (prim as torch.uint32).
+        stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle in index order, no tree."""
+        flags = _closest_flags(stats, simple, brute_force)
+        if _is_torch(points):
+            return self._closest_points_torch(points, r_max, flags)
+        pts = _point_records(points, r_max)
+        n = pts.shape[0]
+        out = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_closest_points_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags),
+                                            out.ctypes.data_as(C.POINTER(PtClosest))))
+        f = out.view(np.float32)
+        return f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+
+    def closest_points_device(self, ptr, n, out_ptr, flags=0):
+        """Raw device route: n PtPoint records at ptr -> n PtClosest records at out_ptr (16-byte aligned device pointers).  Asynchronous on
+        the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_closest_points(self.h, C.c_void_p(ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(out_ptr)))
+
+    def _closest_points_torch(self, points, r_max, flags):
+        _torch_route()
+        import torch
+        dev = points.device
+        if dev.type != "cuda":
+            raise ValueError("closest_points: torch tensors must be on the context's GPU (got %s)" % dev)
+        if points.dim() == 2 and points.shape[1] == 4:
+            pts = points
+            if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.data_ptr() % 16:
+                pts = pts.to(torch.float32).contiguous().clone()
+            if r_max is not None:
+                pts = pts.clone(); pts[:, 3] = r_max
+        else:
+            p = points.reshape(-1, 3).to(torch.float32)
+            n = p.shape[0]
+            rm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if r_max is None else \
+                torch.as_tensor(r_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+            pts = torch.cat([p, rm], dim=1).contiguous()
+        n = pts.shape[0]
+        out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        self._on_context_stream(dev, lambda: self.closest_points_device(pts.data_ptr(), n, out.data_ptr(), flags))
+        of = out.view(torch.float32)
+        return of[:, 0], out.view(torch.uint32)[:, 1], of[:, 2], of[:, 3]
 
     def buffer_busy(self, device_ptr, nbytes):
         b = C.c_int()

@@ -1349,6 +1349,86 @@ int pt_camera_rays(PtContext* ctx, const PtRenderParams* p, void* rays_device) {
     return PT_OK;
 }
 
+// ---- batched closest-point queries (include/mi355pt.h; pt_pointquery.hip) -----------------------------------------------------
+
+static_assert(sizeof(PtPoint) == 16 && sizeof(PtClosest) == 16, "PtPoint / PtClosest are read and written as 16 B records");
+
+namespace {
+constexpr uint32_t kClosestFlags = PT_CLOSEST_STATS | PT_CLOSEST_SIMPLE_KERNEL | PT_CLOSEST_BRUTE_FORCE;
+
+int check_closest(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t flags, const void* out) {
+    if (flags & ~kClosestFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
+    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+
+// the launch itself: points / results in device memory, on the context's stream, behind whatever pt_set_batch still holds
+int closest_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* out) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
+    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
+    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
+    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
+    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
+    const bool stats = (flags & PT_CLOSEST_STATS) != 0, simple = (flags & PT_CLOSEST_SIMPLE_KERNEL) != 0, brute = (flags & PT_CLOSEST_BRUTE_FORCE) != 0;
+    const uint32_t grid = ptk::pointquery_grid(ctx->num_cus);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple && !brute) {
+        // shared with the ray queries (the launches are ordered by the stream): room for whichever kernel needs more
+        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
+        PT_HIP(ctx, ctx->d_rq_spill.ensure(std::max(ptk::pointquery_spill_entries(grid), ptk::rayquery_spill_entries(ptk::rayquery_grid(ctx->num_cus)))));
+    }
+    PT_HIP(ctx, ptk::launch_closest_points(A, points, out, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+} // namespace
+
+int pt_closest_points(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* out_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_closest(ctx, "pt_closest_points", points_device, n, flags, out_device)) return rc;
+    return closest_on_stream(ctx, points_device, uint32_t(n), flags, out_device);
+}
+
+int pt_closest_points_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_closest(ctx, "pt_closest_points_host", points, n, flags, out)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = closest_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                           const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out, PtStats* stats) {
+    if (flags & ~kClosestFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: unknown flags");
+    const bool brute = (flags & PT_CLOSEST_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && (!points || !out)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: null pointer");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: more than 2^32 - 1 points");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::closest_points(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n,
+                            reinterpret_cast<uint32_t*>(out), (flags & PT_CLOSEST_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->rays_closest = counters[0]; stats->nodes_examined = counters[1]; stats->tris_tested = counters[2];
+        stats->stack_drops = counters[3]; stats->max_stack = counters[4];
+    }
+    return PT_OK;
+}
+
 int pt_set_batch(PtContext* ctx, uint32_t frames_per_launch) {
     if (int rc = bind(ctx)) return rc;
     if (int rc = flush_pending(ctx)) return rc;

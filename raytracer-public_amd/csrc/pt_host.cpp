@@ -3,10 +3,12 @@
 // (BVH4_wide), plus the re-layout of the reference's buffers into the device formats the
 // HIP kernels read.  Strict f32/f64 (-ffp-contract=off); no HIP calls.
 #include "pt_host.h"
+#include "pt_closest.h"
 
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <thread>
 
 namespace pt {
 
@@ -587,6 +589,137 @@ void build_tri_records(const float* tris, uint32_t n, TriRecord* out) {
         for (int k = 0; k < 3; ++k) { r.axis[k][0] = p[k]; r.axis[k][1] = e1[k]; r.axis[k][2] = e2[k]; r.axis[k][3] = 0.0f; r.n[k] = n[k]; }
         r.n[3] = 0.0f;
     }
+}
+
+// ------------------------------------------------------------------------------------
+// Closest-point queries (host twin of pt_pointquery.hip): the same records, operations, order and cap
+// ------------------------------------------------------------------------------------
+namespace {
+constexpr int kStackCap = 64;
+struct PointWalk {
+    const TriRecord* rec; uint32_t num_tris;
+    const WideBvh* wide; uint32_t node_base16;
+};
+struct WalkCounters { uint64_t nodes = 0, tris = 0, drops = 0, maxstack = 0; };
+
+inline float record_d2(const TriRecord& r, const float p[3]) {
+    const float ax = p[0] - r.axis[0][0], ay = p[1] - r.axis[1][0], az = p[2] - r.axis[2][0];
+    float u, v;
+    ptcp::closest_uv(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
+    return ptcp::closest_d2(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
+}
+// pt_pointquery.hip::box_bound2: per axis max(mn - (p + s), (p - s) - mx, 0), each difference rounded once
+inline float box_bound2_h(const float hi[3], const float lo[3], const uint32_t w[3]) {
+    const float mn[3] = {half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)};
+    const float mx[3] = {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)};
+    float g[3];
+    for (int k = 0; k < 3; ++k) g[k] = wmax_h(wmax_h(mn[k] - hi[k], lo[k] - mx[k]), 0.0f);
+    return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+}
+
+void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& best_tri, WalkCounters& cnt) {
+    const WideBvh& wb = *W.wide;
+    best_tri = kInvalid;
+    if (wb.root_ref == kInvalid || W.num_tris == 0u) return;
+    cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
+    if (wb.root_degenerate) return;
+    const float hi[3] = {p[0] + ptcp::kSlack, p[1] + ptcp::kSlack, p[2] + ptcp::kSlack};
+    const float lo[3] = {p[0] - ptcp::kSlack, p[1] - ptcp::kSlack, p[2] - ptcp::kSlack};
+    if (!(box_bound2_h(hi, lo, wb.root_box) < best2)) return;
+    struct Entry { uint32_t ref; float b2; } stk[kStackCap];
+    uint32_t cur = wb.root_ref;
+    int sp = 0;
+    for (;;) {
+        bool need_pop = false;
+        if (cur & kLeafFlag) {
+            const uint32_t ti4 = cur & 0x7fffffffu;
+            if (ti4 < 4u * W.num_tris) {
+                cnt.tris += 1;
+                const float d2 = record_d2(W.rec[ti4 >> 2], p);
+                if (d2 < best2) { best2 = d2; best_tri = ti4 >> 2; }
+            }
+            need_pop = true;
+        } else {
+            const WideNode& nd = wb.nodes[(cur - W.node_base16) >> 2];
+            float t[4]; bool h[4]; uint32_t r[4];
+            for (int k = 0; k < 4; ++k) {
+                r[k] = nd.child[k].ref; t[k] = box_bound2_h(hi, lo, nd.child[k].box); h[k] = t[k] < best2;
+                cnt.nodes += (r[k] != kInvalid);
+            }
+            int nslot = -1, fslot = -1;
+            for (int k = 0; k < 4; ++k) if (h[k]) { if (nslot < 0 || t[k] < t[nslot]) nslot = k; if (fslot < 0) fslot = k; }
+            if (nslot < 0) {
+                need_pop = true;
+            } else {
+                // pushes far -> near; the slot the nearest child left holds the first passing child
+                for (int k = 3; k >= 1; --k) {
+                    if (!h[k] || fslot == k) continue;
+                    const int src = (nslot == k) ? fslot : k;
+                    if (sp < kStackCap) { stk[sp].ref = r[src]; stk[sp].b2 = t[src]; ++sp; } else cnt.drops += 1;
+                }
+                const uint64_t depth = uint64_t(sp) + (sp < kStackCap ? 1u : 0u);
+                if (depth > cnt.maxstack) cnt.maxstack = depth;
+                if (sp < kStackCap) cur = r[nslot];
+                else { need_pop = true; cnt.drops += 1; }
+            }
+        }
+        if (need_pop) {
+            bool found = false;
+            while (sp > 0) {
+                --sp;
+                if (stk[sp].b2 < best2) { cur = stk[sp].ref; found = true; break; }
+            }
+            if (!found) break;
+        }
+    }
+}
+} // namespace
+
+bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+                    uint32_t* out, uint64_t* counters, std::string& err) {
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers);
+    auto run = [&](uint64_t w) {
+        WalkCounters& cnt = per[w];
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            const float* q = points + i * 4;
+            float best2 = q[3] * q[3]; uint32_t tri = kInvalid;
+            if (ptcp::point_walked(q[0], q[1], q[2], q[3])) {
+                if (bvh4) walk_point_h(W, q, best2, tri, cnt);
+                else {
+                    for (uint32_t t = 0; t < num_tris; ++t) { const float d2 = record_d2(rec[t], q); if (d2 < best2) { best2 = d2; tri = t; } }
+                    cnt.tris += num_tris;
+                }
+            }
+            uint32_t* o = out + i * 4;
+            if (tri == kInvalid) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; continue; }
+            const TriRecord& r = rec[tri];
+            float u, v;
+            ptcp::closest_uv(q[0] - r.axis[0][0], q[1] - r.axis[1][0], q[2] - r.axis[2][0],
+                             r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
+            o[0] = bits_of(std::sqrt(best2)); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
+        }
+    };
+    if (workers == 1) run(0);
+    else {
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------

@@ -88,6 +88,13 @@ struct TriRecord { float axis[3][4]; float n[4]; };
 static_assert(sizeof(TriRecord) == 64, "TriRecord must be 64 bytes");
 void build_tri_records(const float* tris, uint32_t n, TriRecord* out);
 
+// ---- closest-point queries (pt_closest_points; host twin of pt_pointquery.hip, bit for bit) --------------------------------------
+// points: n x (x, y, z, r_max); out: n x (dist bits, prim, u bits, v bits).  bvh4 = nullptr: every triangle in index order; else the walk
+// of the kernels over build_wide_bvh(bvh4) and build_tri_records(tris), with the arithmetic of pt_closest.h.  counters (optional):
+// points, nodes examined, triangles tested, stack drops, max stack -- as the device's PT_CLOSEST_STATS counts them.
+bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+                    uint32_t* out, uint64_t* counters, std::string& err);
+
 // ---- procedural stand-in scenes ---------------------------------------------------
 bool procedural_scene(uint32_t kind, uint32_t seed, uint32_t num_tris, float* out, std::string& err);
 

@@ -45,6 +45,16 @@
 #ifndef PT_RQ_FILL
 #define PT_RQ_FILL 8                // idle lanes of a wavefront at which they take the next rays of its chunk
 #endif
+// batched closest-point queries (pt_pointquery.hip)
+#ifndef PT_PQ_SHORT_STACK
+#define PT_PQ_SHORT_STACK 12        // LDS stack entries per lane of closest_points_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_PQ_WAVES_PER_SIMD
+#define PT_PQ_WAVES_PER_SIMD 6      // wavefronts of closest_points_kernel per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_PQ_FILL
+#define PT_PQ_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -186,6 +196,15 @@ hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, 
                              unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // A.width * A.height PtRay records of the PT_MODE_REFERENCE camera (A.focal, A.aspect, A.cam, A.quat), row-major
 hipError_t launch_camera_rays(const RenderArgs& A, void* rays, hipStream_t stream);
+// ---- batched closest-point queries (pt_pointquery.hip) ----------------------------------------
+// points: PtPoint[n] (float4 each), out: PtClosest[n] (uint4 each), both 16-byte aligned device memory.  brute: every triangle in index
+// order; simple or stats: one point per thread (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel
+// with `grid` wavefronts at most, a queue block of kRqQueueWords 64-bit words (zeroed by the launch) and pointquery_spill_entries(grid)
+// 8-byte spill entries.
+uint32_t pointquery_grid(int num_cus);
+size_t pointquery_spill_entries(uint32_t grid);
+hipError_t launch_closest_points(const RenderArgs& A, const void* points, void* out, uint32_t n, bool simple, bool stats, bool brute,
+                                 unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
 // What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
 // launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):

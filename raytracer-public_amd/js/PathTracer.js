@@ -155,6 +155,29 @@ class PathTracer {
     return { hit: hit, t: t, prim: r.prim[0], point: point };
   }
 
+  // ---- batched closest-point queries: an extension beyond the reference (include/mi355pt.h pt_closest_points, DESIGN.md section 15) ----
+  // points: Float32Array, 4 floats per point (x, y, z, rMax; rMax = Infinity for no limit).  Resolves to { dist, prim, u, v } (Float32Array /
+  // Uint32Array): the nearest triangle within rMax over the current tree and the closest point on it as v0 + u (v1 - v0) + v (v2 - v0);
+  // nothing within rMax: dist = Infinity, prim = 0xFFFFFFFF, u = v = 0.  options.bruteForce: every triangle, no tree; options.simple: the
+  // one-point-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
+  async closestPoints(points, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
+    return this.group ? native().groupClosestPoints(this.group, points, flags) : native().closestPoints(this.device, points, flags);
+  }
+  // The nearest triangle to (x, y, z): resolves to { found, dist, prim, u, v, point }.  point = v0 + u (v1 - v0) + v (v2 - v0) from
+  // `trianglesData`, the Float32Array the scene was built from (9 floats per triangle), when the caller passes it; null without it or
+  // when nothing is found (this object does not keep a copy of what every route uploaded).
+  async nearest(x, y, z, trianglesData) {
+    const r = await this.closestPoints(Float32Array.of(x, y, z, Infinity));
+    const found = r.prim[0] !== 0xFFFFFFFF;
+    let point = null;
+    if (found && trianglesData) {
+      const t = trianglesData, o = r.prim[0] * 9, u = r.u[0], v = r.v[0];
+      point = [0, 1, 2].map((k) => t[o + k] + u * Math.fround(t[o + 3 + k] - t[o + k]) + v * Math.fround(t[o + 6 + k] - t[o + k]));
+    }
+    return { found: found, dist: r.dist[0], prim: r.prim[0], u: r.u[0], v: r.v[0], point: point };
+  }
+
   setCameraPosition(x, y, z) { this.cameraPosition = [x, y, z]; }           // :824
   setCameraQuaternion(x, y, z, w) { this.cameraQuaternion = [x, y, z, w]; } // :828
   setFrameCount(frameCount) { this.frameCount = frameCount; }               // :832

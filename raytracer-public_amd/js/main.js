@@ -18,6 +18,7 @@
 //        [--cam x,y,z --quat x,y,z,w] [--radiance frame.f32 --triangles tris.f32]
 //        [--animate AMP]                                     before every render() the scene as built is displaced (a triangle wave in y over x, amplitude AMP,
 //                                                            phase by the frame count; tools/README.md) and the tree refitted in place: updateTriangles, no rebuild
+//        [--nearest X,Y,Z]                                   after the frames: the point of the scene nearest to (X, Y, Z), as one JSON line (closest-point query, an extension)
 //        [--pick X,Y]                                        after the frames: what is under pixel (X, Y), as one JSON line (ray query, an extension)
 "use strict";
 const fs = require("fs");
@@ -110,6 +111,12 @@ async function main() {
     const xy = pickAt.split(",").map(Number);
     const p = await pathTracer.pick(xy[0], xy[1]);
     console.log(JSON.stringify({ pick: xy, hit: p.hit, t: p.t === Infinity ? null : p.t, prim: p.prim, point: p.point }));
+  }
+  const nearestTo = arg("nearest", null);
+  if (nearestTo) {
+    const xyz = nearestTo.split(",").map(Number);
+    const q = await pathTracer.nearest(xyz[0], xyz[1], xyz[2], pathTracer.trianglesData);      // the triangles the frames were traced over
+    console.log(JSON.stringify({ nearest: xyz, found: q.found, dist: q.dist === Infinity ? null : q.dist, prim: q.prim, u: q.u, v: q.v, point: q.point }));
   }
   const out = arg("out", null);
   if (out) {      // what the tonemapper pass would have put on the canvas (tonemapper.wgsl)

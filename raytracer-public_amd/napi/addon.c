@@ -364,6 +364,40 @@ static napi_value fn_trace_rays(napi_env env, napi_callback_info info) {      /*
     return trace_rays_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- batched closest-point queries (an extension beyond the reference; include/mi355pt.h pt_closest_points_host) ---------------- */
+
+/* points: Float32Array of 4 floats per point (PtPoint: x, y, z, rMax) -> { dist: Float32Array, prim: Uint32Array, u, v }; flags: PT_CLOSEST_*.
+ * The records are copied into 16-byte aligned host memory, as the rays are. */
+static napi_value closest_points_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
+    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 4) { napi_throw_range_error(env, NULL, "closestPoints: 4 floats per point"); return NULL; }
+    const uint32_t flags = get_u32(env, flags_v);
+    const size_t n = len / 4;
+    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
+    PtClosest* res = (PtClosest*)aligned_alloc(16, (n ? n : 1) * sizeof(PtClosest));
+    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(pts, d, n * sizeof(PtPoint));
+    int rc = pt_closest_points_host(ctx, pts, n, flags, res);
+    free(pts);
+    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_closest_points_host"); }
+    napi_value o, dist, prim, u, v; void *pd, *pp, *pu, *pv;
+    if (!(dist = make_typed(env, napi_float32_array, 4, n, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
+        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(res); return NULL; }
+    for (size_t i = 0; i < n; ++i) {
+        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
+    }
+    free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_closest_points(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array points, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return closest_points_on(env, ctx, argv[1], argv[2]);
+}
+
 /* The camera ray of PT_MODE_REFERENCE through the centre of pixel (x, y) of the UBO's camera, as one PtRay record (8 floats, t_max = +inf):
  * renderer.wgsl:387-395 in the operation order of pt_device.h::primary_ray -- correctly rounded f32 division and square root, fmaf where it
  * has fma, nothing contracted (-ffp-contract=off) -- so the same bits as the ray pt_camera_rays writes and mode 1 traces. */
@@ -575,6 +609,12 @@ static napi_value fn_group_trace_rays(napi_env env, napi_callback_info info) {  
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return trace_rays_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_closest_points(napi_env env, napi_callback_info info) {  /* (group, points, flags): on member 0, which holds the whole scene */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return closest_points_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_set_batch(napi_env env, napi_callback_info info) {
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -632,6 +672,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readRadiance", fn_read_radiance}, {"readRGBA8", fn_read_rgba8}, {"readTonemapped", fn_read_tonemapped},
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
         {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
+        {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
         {"groupReadBVH2", fn_group_read_bvh2}, {"groupSetBatch", fn_group_set_batch}, {"groupRender", fn_group_render}, {"groupFlush", fn_group_flush},
