@@ -338,6 +338,60 @@ PT_API int pt_closest_points_host(PtContext* ctx, const PtPoint* points, uint64_
 PT_API int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
                                   const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out, PtStats* stats);
 
+/* ---- batched ambient-occlusion queries: how open is the hemisphere above a surface point? (an extension beyond the reference;
+ * DESIGN.md section 16) ---------------------------------------------------------------------------------------------------------
+ * For every surfel (a point p with a normal n) `samples` cosine-distributed rays around n are walked any-hit over the context's CURRENT
+ * tree, whatever set it, and the rays that reach nothing within r_max are counted: visibility = unoccluded / samples.  The result is an
+ * integer that equals, bit for bit, what pt_occlusion_rays -> pt_trace_rays(PT_TRACE_ANY_HIT) -> counting the misses gives; the ray
+ * records and hit records of that composition (48 bytes per ray) never reach memory.
+ * All arithmetic is f32, every operation rounded once, no contraction; dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * Sample ray s (s < samples) of surfel i:
+ *   key = sample_key(seed, index_base + i, s) with index_base + i taken mod 2^32; u1 = rnd(key, 0, 2), u2 = rnd(key, 0, 3);
+ *   dir = cosine_dir(n, u1, u2) -- the counter RNG and the cosine sampling of DESIGN.md section 4, the functions behind the oracle's
+ *   orc_rnd(seed, pixel, sidx, 0, dim) and orc_cosine_dir.  n is used as given: callers pass unit normals, the library does not normalise.
+ *   org.a = p.a + n.a * bias per component; t_max = r_max; reserved = 0.
+ * Which surfels are traced: a surfel is traced iff p, n and r_max hold no NaN and r_max > 0 (+inf is allowed).  An untraced surfel yields
+ *   {visibility 0, unoccluded 0, samples 0}; pt_occlusion_rays writes `samples` records {org = p, t_max = 0, dir = n} for it (rays that
+ *   pt_trace_rays does not traverse).
+ * Occlusion: a sample is occluded iff pt_trace_rays(PT_TRACE_ANY_HIT) on that ray record reports a hit: the same walk, the same acceptance
+ *   rule, best = min(t_max, 1e30), the same 64-entry cap, and no traversal for a ray with a NaN (a NaN dir, e.g. from a zero normal, is a
+ *   miss and counts as unoccluded).  unoccluded = the number of misses; samples = params.samples;
+ *   visibility = (float)unoccluded / (float)samples, one correctly rounded division; reserved = 0.
+ * Arguments: samples in 1..65536 and n * samples <= 2^32 - 1, a bias that is not NaN and not negative, else PT_ERR_INVALID_ARG.  A NULL or
+ *   non-16-byte-aligned pointer, unknown flags, NULL params or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the scene).  No triangles
+ *   + tree: PT_ERR_NO_SCENE (pt_occlusion_rays needs none; pt_hit_surfels needs the triangles).  n = 0: PT_OK, nothing is launched.
+ * Ordering: as pt_trace_rays.  Frames queued by pt_set_batch are launched first; pt_occlusion does not wait and synchronises nothing on the
+ *   host (the caller's buffers must stay allocated until a later pt_synchronize has returned); a scene change after the call does not
+ *   change its result.
+ * PT_OCCLUSION_STATS: the counting variant (one sample ray per thread) fills pt_get_stats: rays_shadow = samples * the number of traced
+ *   surfels; nodes_examined, tris_tested, stack_drops and max_stack exactly what pt_trace_rays(ANY_HIT | STATS) reports for the rays of the
+ *   traced surfels; rays_closest = samples = 0.
+ * PT_OCCLUSION_SIMPLE_KERNEL: the one-ray-per-thread kernel instead of the persistent one (A/B checks); the results are the same.
+ * pt_hit_surfels: hits -> surfels, so that camera rays -> pt_trace_rays -> surfels -> pt_occlusion stays on the device.  A hit with
+ *   prim < the triangle count: P.a = org.a + dir.a * t; nf = the triangle record's stored normal if dot3(normal, dir) < 0, else its negation
+ *   (the path tracer's rule); the surfel is {P, r_max, nf, 0}.  A miss, or prim out of range: {org, 0, dir, 0}, an
+ *   untraced surfel. */
+typedef struct PtSurfel    { float p[3]; float r_max; float n[3]; uint32_t reserved; } PtSurfel;        /* 32 B: the shape of PtRay (org, t_max, dir) */
+typedef struct PtOcclusion { float visibility; uint32_t unoccluded; uint32_t samples; uint32_t reserved; } PtOcclusion;  /* 16 B */
+typedef struct PtOcclusionParams { uint32_t samples; uint32_t seed; uint32_t index_base; float bias; uint32_t flags; } PtOcclusionParams;
+enum {
+    PT_OCCLUSION_STATS = 1u,
+    PT_OCCLUSION_SIMPLE_KERNEL = 2u
+};
+/* n surfels from device memory, n results into device memory (both 16-byte aligned, on the context's device).  Asynchronous on the
+ * context's stream (pt_get_stream). */
+PT_API int pt_occlusion(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* out_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the results are written. */
+PT_API int pt_occlusion_host(PtContext* ctx, const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtOcclusion* out);
+/* The sample rays themselves: n * samples PtRay records into rays_device, sample s of surfel i at i * samples + s.  Needs no scene. */
+PT_API int pt_occlusion_rays(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* rays_device);
+/* Host twin (no context, no GPU): the same bits.  params->flags: the known flags are accepted and change nothing. */
+PT_API int pt_occlusion_rays_host(const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtRay* rays);
+/* n rays + their n hits -> n surfels, all in device memory (16-byte aligned).  Asynchronous on the context's stream. */
+PT_API int pt_hit_surfels(PtContext* ctx, const void* rays_device, const void* hits_device, uint64_t n, float r_max, void* surfels_device);
+/* The same from host arrays (16-byte aligned): staged; returns when the surfels are written. */
+PT_API int pt_hit_surfels_host(PtContext* ctx, const PtRay* rays, const PtHit* hits, uint64_t n, float r_max, PtSurfel* out);
+
 /* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
  * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
  * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes

@@ -32,6 +32,8 @@ PT_ACCEL_REFERENCE, PT_ACCEL_AREA_COLLAPSE, PT_ACCEL_PLOC = 0, 1, 2
 PT_TRACE_ANY_HIT, PT_TRACE_STATS, PT_TRACE_SIMPLE_KERNEL = 1, 2, 4
 # batched closest-point queries (include/mi355pt.h pt_closest_points)
 PT_CLOSEST_STATS, PT_CLOSEST_SIMPLE_KERNEL, PT_CLOSEST_BRUTE_FORCE = 1, 2, 4
+# batched ambient-occlusion queries (include/mi355pt.h pt_occlusion)
+PT_OCCLUSION_STATS, PT_OCCLUSION_SIMPLE_KERNEL = 1, 2
 PRIM_NONE = 0xFFFFFFFF
 
 
@@ -83,6 +85,21 @@ class PtClosest(C.Structure):
     _fields_ = [("dist", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
 
 
+class PtSurfel(C.Structure):
+    """include/mi355pt.h PtSurfel (32 B, the shape of PtRay); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per surfel
+    (p xyz, r_max, n xyz, 0)."""
+    _fields_ = [("p", C.c_float * 3), ("r_max", C.c_float), ("n", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class PtOcclusion(C.Structure):
+    """include/mi355pt.h PtOcclusion (16 B): visibility = unoccluded / samples; all zero for a surfel that is not traced."""
+    _fields_ = [("visibility", C.c_float), ("unoccluded", C.c_uint32), ("samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PtOcclusionParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("index_base", C.c_uint32), ("bias", C.c_float), ("flags", C.c_uint32)]
+
+
 class PtAccumInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
                 ("compact", C.c_uint32), ("samples", C.c_uint32), ("floats", C.c_uint64)]
@@ -99,6 +116,7 @@ EXPORTS = [
     "pt_accum_info", "pt_read_accum", "pt_set_accum",
     "pt_trace_rays", "pt_trace_rays_host", "pt_camera_rays",
     "pt_closest_points", "pt_closest_points_host", "pt_closest_points_bvh4",
+    "pt_occlusion", "pt_occlusion_host", "pt_occlusion_rays", "pt_occlusion_rays_host", "pt_hit_surfels", "pt_hit_surfels_host",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -187,6 +205,39 @@ def _point_records(points, r_max):
                 a[:, 3] = r_max
         return a
     return pack_points(a, r_max)
+
+
+def pack_surfels(points, normals, r_max=None):
+    """numpy: (n, 8) float32 PtSurfel records (p xyz, r_max, n xyz, 0) in a 16-byte aligned buffer; r_max None = +inf, a scalar or (n,)."""
+    return pack_rays(points, normals, r_max)
+
+
+def _records8(a, what):
+    """(n, 8) float32 records in a 16-byte aligned, contiguous numpy buffer (the caller's array when it already is one)."""
+    a = np.asarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError("%s: expected (n, 8) float32 records, got shape %s" % (what, a.shape))
+    if a.ctypes.data % 16 or not a.flags.c_contiguous:
+        r2 = _aligned_zeros(a.shape, np.float32); r2[...] = a; a = r2
+    return a
+
+
+def _occlusion_params(samples, seed, bias, index_base, stats=False, simple=False):
+    p = PtOcclusionParams()
+    p.samples, p.seed, p.index_base, p.bias = int(samples), int(seed) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, float(bias)
+    p.flags = (PT_OCCLUSION_STATS if stats else 0) | (PT_OCCLUSION_SIMPLE_KERNEL if simple else 0)
+    return p
+
+
+def occlusion_rays_host(surfels, samples, seed=0, bias=1e-4, index_base=0):
+    """Host twin of Context.occlusion_rays (no GPU): the n * samples sample rays of (n, 8) PtSurfel records as (n * samples, 8) float32 PtRay
+    records, sample s of surfel i at i * samples + s, with the bits the device produces."""
+    sf = _records8(surfels, "occlusion_rays_host")
+    n = sf.shape[0]
+    p = _occlusion_params(samples, seed, bias, index_base)
+    rays = _aligned_zeros((n * max(int(samples), 0) if 0 < int(samples) <= 65536 else 0, 8), np.float32)
+    _check(lib.pt_occlusion_rays_host(sf.ctypes.data_as(C.POINTER(PtSurfel)), C.c_uint64(n), C.byref(p), rays.ctypes.data_as(C.POINTER(PtRay))))
+    return rays
 
 
 def _closest_flags(stats, simple, brute_force):
@@ -720,6 +771,114 @@ class Context:
         self._on_context_stream(dev, lambda: self.closest_points_device(pts.data_ptr(), n, out.data_ptr(), flags))
         of = out.view(torch.float32)
         return of[:, 0], out.view(torch.uint32)[:, 1], of[:, 2], of[:, 3]
+
+    # ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h) ----
+    def occlusion(self, surfels, samples, seed=0, bias=1e-4, index_base=0, stats=False, simple=False):
+        """How open is the hemisphere above each surfel?  Returns (visibility, unoccluded, samples) per surfel: `samples` cosine-distributed
+        rays around the normal, walked any-hit up to r_max; all zero for a surfel that is not traced (a NaN, or r_max <= 0).
+
+        surfels: (n, 8) float32 PtSurfel records (pack_surfels).  A numpy array takes the host route (staged, returns when done).  A torch
+        tensor on the context's device takes the device route: zero-copy for contiguous float32 records, no host synchronisation, ordered
+        with torch's current stream both ways; the results are torch tensors (the counts as torch.uint32).  stats: the counting kernel,
+        counters in stats() afterwards; simple: the one-ray-per-thread kernel."""
+        p = _occlusion_params(samples, seed, bias, index_base, stats, simple)
+        if _is_torch(surfels):
+            out = self._occlusion_torch(surfels, p)
+            import torch
+            return out.view(torch.float32)[:, 0], out.view(torch.uint32)[:, 1], out.view(torch.uint32)[:, 2]
+        sf = _records8(surfels, "occlusion")
+        n = sf.shape[0]
+        out = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_occlusion_host(self.h, sf.ctypes.data_as(C.POINTER(PtSurfel)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtOcclusion))))
+        return out.view(np.float32)[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+    def _surfel_tensor(self, surfels, what):
+        _torch_route()
+        import torch
+        if surfels.device.type != "cuda":
+            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, surfels.device))
+        sf = surfels.reshape(-1, 8)
+        if sf.dtype != torch.float32 or not sf.is_contiguous() or sf.data_ptr() % 16:
+            sf = sf.to(torch.float32).contiguous().clone()
+        return sf
+
+    def _occlusion_torch(self, surfels, p):
+        """a torch (n, 8) float32 tensor of PtSurfel records -> a torch (n, 4) int32 tensor of PtOcclusion records on the same device"""
+        import torch
+        sf = self._surfel_tensor(surfels, "occlusion")
+        n = sf.shape[0]
+        out = torch.empty((n, 4), dtype=torch.int32, device=sf.device)
+        self._on_context_stream(sf.device, lambda: self.occlusion_device(sf.data_ptr(), n, p, out.data_ptr()))
+        return out
+
+    def occlusion_device(self, surfels_ptr, n, params, out_ptr):
+        """Raw device route: n PtSurfel records at surfels_ptr -> n PtOcclusion records at out_ptr (16-byte aligned device pointers; params:
+        PtOcclusionParams).  Asynchronous on the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_occlusion(self.h, C.c_void_p(surfels_ptr), C.c_uint64(n), C.byref(params), C.c_void_p(out_ptr)))
+
+    def occlusion_rays(self, surfels, samples, seed=0, bias=1e-4, index_base=0):
+        """The sample rays occlusion() walks, as (n * samples, 8) float32 PtRay records; sample s of surfel i is record i * samples + s.  A torch
+        tensor of surfels takes the device route and gives a torch tensor on the same device (feed it to trace_rays); a numpy array is answered
+        by the host twin, occlusion_rays_host, with the same bits.  Needs no scene."""
+        if not _is_torch(surfels):
+            return occlusion_rays_host(surfels, samples, seed, bias, index_base)
+        import torch
+        sf = self._surfel_tensor(surfels, "occlusion_rays")
+        n = sf.shape[0]
+        p = _occlusion_params(samples, seed, bias, index_base)
+        rays = torch.empty((n * int(samples), 8), dtype=torch.float32, device=sf.device)
+        self._on_context_stream(sf.device, lambda: self.occlusion_rays_device(sf.data_ptr(), n, p, rays.data_ptr()))
+        return rays
+
+    def occlusion_rays_device(self, surfels_ptr, n, params, rays_ptr):
+        """Raw device route of occlusion_rays: n * params.samples PtRay records at rays_ptr, asynchronous on the context's stream."""
+        self._ck(lib.pt_occlusion_rays(self.h, C.c_void_p(surfels_ptr), C.c_uint64(n), C.byref(params), C.c_void_p(rays_ptr)))
+
+    def hit_surfels(self, rays, hits, r_max=float("inf")):
+        """Rays + their hits -> (n, 8) float32 PtSurfel records: the hit point with the triangle's normal turned against the ray and r_max; a
+        miss gives a surfel that is not traced.  rays: (n, 8) PtRay records; hits: (n, 4) PtHit records (int32 / uint32 / float32 words), or the
+        (t, prim, u, v) tuple trace_rays returns.  numpy takes the host route, torch tensors the device route (nothing leaves the device)."""
+        if isinstance(hits, (tuple, list)):
+            t, prim, u, v = hits
+            if _is_torch(rays):
+                import torch
+                hits = torch.stack([t.view(torch.int32), prim.view(torch.int32), u.view(torch.int32), v.view(torch.int32)], dim=1)
+            else:
+                hits = np.stack([np.asarray(t, np.float32).view(np.uint32), np.asarray(prim, np.uint32),
+                                 np.asarray(u, np.float32).view(np.uint32), np.asarray(v, np.float32).view(np.uint32)], axis=1)
+        if _is_torch(rays):
+            import torch
+            r = self._surfel_tensor(rays, "hit_surfels")
+            h = hits.reshape(-1, 4)
+            if h.element_size() != 4:
+                raise ValueError("hit_surfels: hits must be 4-byte words")
+            h = h.view(torch.int32)
+            if not h.is_contiguous() or h.data_ptr() % 16:
+                h = h.contiguous().clone()
+            n = r.shape[0]
+            if h.shape[0] != n:
+                raise ValueError("hit_surfels: %d rays but %d hits" % (n, h.shape[0]))
+            out = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+            self._on_context_stream(r.device, lambda: self.hit_surfels_device(r.data_ptr(), h.data_ptr(), n, r_max, out.data_ptr()))
+            return out
+        r = _records8(rays, "hit_surfels")
+        h = np.asarray(hits)
+        if h.dtype.itemsize != 4:
+            raise ValueError("hit_surfels: hits must be 4-byte words")
+        h = h.reshape(-1, 4).view(np.uint32)
+        if h.ctypes.data % 16 or not h.flags.c_contiguous:
+            h2 = _aligned_zeros(h.shape, np.uint32); h2[...] = h; h = h2
+        n = r.shape[0]
+        if h.shape[0] != n:
+            raise ValueError("hit_surfels: %d rays but %d hits" % (n, h.shape[0]))
+        out = _aligned_zeros((n, 8), np.float32)
+        self._ck(lib.pt_hit_surfels_host(self.h, r.ctypes.data_as(C.POINTER(PtRay)), h.ctypes.data_as(C.POINTER(PtHit)), C.c_uint64(n),
+                                         C.c_float(r_max), out.ctypes.data_as(C.POINTER(PtSurfel))))
+        return out
+
+    def hit_surfels_device(self, rays_ptr, hits_ptr, n, r_max, surfels_ptr):
+        """Raw device route of hit_surfels: n PtSurfel records at surfels_ptr, asynchronous on the context's stream."""
+        self._ck(lib.pt_hit_surfels(self.h, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), C.c_uint64(n), C.c_float(r_max), C.c_void_p(surfels_ptr)))
 
     def buffer_busy(self, device_ptr, nbytes):
         b = C.c_int()

@@ -103,6 +103,7 @@ struct PtContext {
     uint32_t* h_refit = nullptr; hipEvent_t ev_refit = nullptr; bool meta_pending = false, meta_has_root = false;
     // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
+    DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
 
     // frame
     DevBuf<float4> d_out, d_accum, d_compact, d_compact_accum;
@@ -640,7 +641,7 @@ void pt_destroy(PtContext* ctx) {
     (void)flush_pending(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->d_tris9.release(); ctx->d_scene.release(); ctx->d_bvh2.release(); ctx->d_bvh4.release();
-    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release();
+    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release(); ctx->d_oc_surfels.release();
     ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
     ctx->d_out.release(); ctx->d_accum.release(); ctx->d_compact.release(); ctx->d_compact_accum.release();
     ctx->d_tiles.release(); ctx->d_u32tmp.release(); ctx->d_stats.release();
@@ -1426,6 +1427,127 @@ int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t*
         stats->rays_closest = counters[0]; stats->nodes_examined = counters[1]; stats->tris_tested = counters[2];
         stats->stack_drops = counters[3]; stats->max_stack = counters[4];
     }
+    return PT_OK;
+}
+
+// ---- batched ambient-occlusion queries (include/mi355pt.h; pt_occlusion.hip) --------------------------------------------------
+
+static_assert(sizeof(PtSurfel) == 32 && sizeof(PtOcclusion) == 16, "PtSurfel / PtOcclusion are read and written as 2 x 16 B and 16 B records");
+
+namespace {
+constexpr uint32_t kOcclusionFlags = PT_OCCLUSION_STATS | PT_OCCLUSION_SIMPLE_KERNEL;
+
+// the parameter block and the batch size; the pointers and the scene are checked by the callers (pointers before the scene)
+int check_occlusion_params(PtContext* ctx, const char* fn, uint64_t n, const PtOcclusionParams* p) {
+    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": null params");
+    if (p->flags & ~kOcclusionFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 surfels");
+    if (p->samples < 1u || p->samples > 65536u) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": samples must be 1..65536");
+    if (n * uint64_t(p->samples) > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 sample rays (n * samples)");
+    if (!(p->bias >= 0.0f)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": bias must be >= 0");
+    return PT_OK;
+}
+int check_occlusion(PtContext* ctx, const char* fn, const void* surfels, uint64_t n, const PtOcclusionParams* p, const void* out, bool need_scene) {
+    if (int rc = check_occlusion_params(ctx, fn, n, p)) return rc;
+    if (!aligned16(surfels) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": surfels and results must be non-null and 16-byte aligned");
+    if (need_scene && (!ctx->have_tris || !ctx->have_bvh)) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+void scene_args(PtContext* ctx, ptk::RenderArgs& A) {
+    std::memset(&A, 0, sizeof(A));
+    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
+    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
+    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
+    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
+}
+
+// the launch itself: surfels / results in device memory, on the context's stream, behind whatever pt_set_batch still holds
+int occlusion_on_stream(PtContext* ctx, const void* surfels, uint32_t n, const PtOcclusionParams& p, void* out) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool stats = (p.flags & PT_OCCLUSION_STATS) != 0, simple = (p.flags & PT_OCCLUSION_SIMPLE_KERNEL) != 0;
+    const uint32_t grid = ptk::occlusion_grid(ctx->num_cus);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple) {
+        // shared with the ray and closest-point queries (the launches are ordered by the stream): room for whichever kernel needs more
+        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
+        PT_HIP(ctx, ctx->d_rq_spill.ensure(std::max(ptk::occlusion_spill_entries(grid), ptk::rayquery_spill_entries(ptk::rayquery_grid(ctx->num_cus)))));
+    }
+    PT_HIP(ctx, ptk::launch_occlusion(A, surfels, out, n, p.samples, p.seed, p.index_base, p.bias, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+} // namespace
+
+int pt_occlusion(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* out_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_occlusion(ctx, "pt_occlusion", surfels_device, n, params, out_device, true)) return rc;
+    return occlusion_on_stream(ctx, surfels_device, uint32_t(n), *params, out_device);
+}
+
+int pt_occlusion_host(PtContext* ctx, const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtOcclusion* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_occlusion(ctx, "pt_occlusion_host", surfels, n, params, out, true)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, surfels, size_t(n) * sizeof(PtSurfel), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = occlusion_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtOcclusion), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_occlusion_rays(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* rays_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_occlusion(ctx, "pt_occlusion_rays", surfels_device, n, params, rays_device, false)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    PT_HIP(ctx, ptk::launch_occlusion_rays(surfels_device, rays_device, uint32_t(n), params->samples, params->seed, params->index_base, params->bias, ctx->stream));
+    return PT_OK;
+}
+
+int pt_occlusion_rays_host(const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtRay* rays) {
+    if (int rc = check_occlusion_params(nullptr, "pt_occlusion_rays_host", n, params)) return rc;
+    if (n && (!surfels || !rays)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_occlusion_rays_host: null pointer");
+    pt::occlusion_rays(reinterpret_cast<const float*>(surfels), n, params->samples, params->seed, params->index_base, params->bias, reinterpret_cast<float*>(rays));
+    return PT_OK;
+}
+
+int pt_hit_surfels(PtContext* ctx, const void* rays_device, const void* hits_device, uint64_t n, float r_max, void* surfels_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels: more than 2^32 - 1 rays");
+    if (!aligned16(rays_device) || !aligned16(hits_device) || !aligned16(surfels_device))
+        return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels: rays, hits and surfels must be non-null and 16-byte aligned");
+    if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_hit_surfels: no triangles set");
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
+    A.tris = ctx->trirec(); A.num_tris = ctx->num_tris;
+    PT_HIP(ctx, ptk::launch_hit_surfels(A, rays_device, hits_device, uint32_t(n), r_max, surfels_device, ctx->stream));
+    return PT_OK;
+}
+
+int pt_hit_surfels_host(PtContext* ctx, const PtRay* rays, const PtHit* hits, uint64_t n, float r_max, PtSurfel* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels_host: more than 2^32 - 1 rays");
+    if (!aligned16(rays) || !aligned16(hits) || !aligned16(out))
+        return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels_host: rays, hits and surfels must be non-null and 16-byte aligned");
+    if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_hit_surfels_host: no triangles set");
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n))); PT_HIP(ctx, ctx->d_oc_surfels.ensure(size_t(n) * 2));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_hits.ptr, hits, size_t(n) * sizeof(PtHit), hipMemcpyHostToDevice, ctx->stream));
+    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
+    A.tris = ctx->trirec(); A.num_tris = ctx->num_tris;
+    PT_HIP(ctx, ptk::launch_hit_surfels(A, ctx->d_rq_rays.ptr, ctx->d_rq_hits.ptr, uint32_t(n), r_max, ctx->d_oc_surfels.ptr, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_oc_surfels.ptr, size_t(n) * sizeof(PtSurfel), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
 

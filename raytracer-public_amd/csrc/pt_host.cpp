@@ -994,4 +994,76 @@ bool procedural_scene(uint32_t kind, uint32_t seed, uint32_t num_tris, float* ou
     return false;
 }
 
+// ---- ambient-occlusion sample rays: pt_device.h's sampling functions restated for the host, operation by operation ----
+// f32 throughout, every operation rounded once (the library is built with -ffp-contract=off), fmaf exactly where the device code has it.
+namespace {
+inline uint32_t mix32_h(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
+inline uint32_t sample_key_h(uint32_t seed, uint32_t pixel, uint32_t sidx) {
+    uint32_t h = mix32_h(seed + 0x9E3779B9u);
+    h = mix32_h(h ^ pixel);
+    return mix32_h(h ^ sidx);
+}
+inline float rnd_h(uint32_t key, uint32_t bounce, uint32_t dim) {
+    const uint32_t h = mix32_h(key ^ (bounce * 8u + dim + 1u) * 0x9E3779B1u);
+    return float(h >> 8) * (1.0f / 16777216.0f);
+}
+inline void sincos_2pi_h(float u, float& c, float& s) {
+    const float q = u * 4.0f;
+    const float kf = std::floor(q + 0.5f);
+    const float y = (q - kf) * 1.57079632679489662f;
+    const float y2 = y * y;
+    float sp = std::fmaf(y2, 2.7557319e-6f, -1.9841270e-4f);
+    sp = std::fmaf(y2, sp, 8.3333333e-3f);
+    sp = std::fmaf(y2, sp, -1.6666667e-1f);
+    sp = std::fmaf(y2, sp, 1.0f);
+    const float sy = y * sp;
+    float cp = std::fmaf(y2, -2.7557319e-7f, 2.4801587e-5f);
+    cp = std::fmaf(y2, cp, -1.3888889e-3f);
+    cp = std::fmaf(y2, cp, 4.1666667e-2f);
+    cp = std::fmaf(y2, cp, -0.5f);
+    const float cy = std::fmaf(y2, cp, 1.0f);
+    const int k = int(kf) & 3;
+    c = (k == 0) ? cy : (k == 1) ? -sy : (k == 2) ? -cy : sy;
+    s = (k == 0) ? sy : (k == 1) ? cy : (k == 2) ? -sy : -cy;
+}
+inline void cosine_local_h(float u1, float u2, float l[3]) {
+    float c, s; sincos_2pi_h(u2, c, s);
+    const float r = std::sqrt(u1);
+    l[0] = r * c; l[1] = r * s; l[2] = std::sqrt(1.0f - u1);
+}
+// the branch-free orthonormal basis of n (Duff et al.), (t * l.x + bt * l.y) + n * l.z per component
+inline void cosine_world_h(const float n[3], const float l[3], float out[3]) {
+    const float sign = std::copysign(1.0f, n[2]);
+    const float a = -1.0f / (sign + n[2]);
+    const float b = n[0] * n[1] * a;
+    const float t[3] = {1.0f + sign * n[0] * n[0] * a, sign * b, -sign * n[0]};
+    const float bt[3] = {b, sign + n[1] * n[1] * a, -n[1]};
+    for (int k = 0; k < 3; ++k) out[k] = (t[k] * l[0] + bt[k] * l[1]) + n[k] * l[2];
+}
+} // namespace
+
+void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, float* rays) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* sf = surfels + i * 8;
+        const float* p = sf; const float r_max = sf[3]; const float* nr = sf + 4;
+        const bool nan = std::isnan(p[0]) || std::isnan(p[1]) || std::isnan(p[2]) || std::isnan(nr[0]) || std::isnan(nr[1]) || std::isnan(nr[2]);
+        const bool traced = !nan && (r_max > 0.0f);
+        const uint32_t pixel = index_base + uint32_t(i);
+        for (uint32_t s = 0; s < samples; ++s) {
+            float* r = rays + (i * samples + s) * 8;
+            if (!traced) {
+                r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = 0.0f; r[4] = nr[0]; r[5] = nr[1]; r[6] = nr[2]; r[7] = 0.0f;
+                continue;
+            }
+            const uint32_t key = sample_key_h(seed, pixel, s);
+            const float u1 = rnd_h(key, 0u, 2u), u2 = rnd_h(key, 0u, 3u);
+            float l[3], d[3];
+            cosine_local_h(u1, u2, l);
+            cosine_world_h(nr, l, d);
+            for (int k = 0; k < 3; ++k) { r[k] = p[k] + nr[k] * bias; r[4 + k] = d[k]; }
+            r[3] = r_max; r[7] = 0.0f;
+        }
+    }
+}
+
 } // namespace pt

@@ -106,4 +106,8 @@ uint32_t tile_count_of(uint32_t width, uint32_t height, uint32_t rank, uint32_t 
 // the rank's tiles inside the tile rectangle rect = {tx0, ty0, tx1, ty1} (half-open): what a packed share holds
 uint32_t rect_tile_count_of(uint32_t rank, uint32_t count, const uint32_t rect[4]);
 
+// ---- ambient-occlusion sample rays (host twin of pt_occlusion.hip::occlusion_rays_kernel; pt_occlusion_rays_host) ----
+// surfels: 8 floats each (p, r_max, n, reserved); rays: n * samples records of 8 floats (org, t_max, dir, 0), item i * samples + s.
+void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, float* rays);
+
 } // namespace pt

@@ -55,6 +55,16 @@
 #ifndef PT_PQ_FILL
 #define PT_PQ_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
 #endif
+// batched ambient-occlusion queries (pt_occlusion.hip)
+#ifndef PT_OC_SHORT_STACK
+#define PT_OC_SHORT_STACK 12        // LDS stack entries per lane of occlusion_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_OC_WAVES_PER_SIMD
+#define PT_OC_WAVES_PER_SIMD 6      // wavefronts of occlusion_kernel per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_OC_FILL
+#define PT_OC_FILL 8                // idle lanes of a wavefront at which they take the next items of its chunk
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -205,6 +215,20 @@ uint32_t pointquery_grid(int num_cus);
 size_t pointquery_spill_entries(uint32_t grid);
 hipError_t launch_closest_points(const RenderArgs& A, const void* points, void* out, uint32_t n, bool simple, bool stats, bool brute,
                                  unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// ---- batched ambient-occlusion queries (pt_occlusion.hip) -------------------------------------
+// surfels: PtSurfel[n] (2 x float4 each), out: PtOcclusion[n] (uint4 each), 16-byte aligned device memory; n * samples <= 2^32 - 1.  The launch
+// zeroes `out`, counts the unoccluded samples of every traced surfel into word 1 of its record and completes the records in a finishing
+// kernel.  simple or stats: one sample ray per thread (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent
+// kernel with `grid` wavefronts at most, a queue block of kRqQueueWords 64-bit words (zeroed by the launch) and
+// occlusion_spill_entries(grid) 8-byte spill entries.
+uint32_t occlusion_grid(int num_cus);
+size_t occlusion_spill_entries(uint32_t grid);
+hipError_t launch_occlusion(const RenderArgs& A, const void* surfels, void* out, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias,
+                            bool simple, bool stats, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// the n * samples sample rays as PtRay records (item i * samples + s); needs no scene
+hipError_t launch_occlusion_rays(const void* surfels, void* rays, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, hipStream_t stream);
+// PtRay[n] + PtHit[n] -> PtSurfel[n] (A.tris, A.num_tris)
+hipError_t launch_hit_surfels(const RenderArgs& A, const void* rays, const void* hits, uint32_t n, float r_max, void* surfels, hipStream_t stream);
 // ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
 // What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
 // launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):

@@ -178,6 +178,31 @@ class PathTracer {
     return { found: found, dist: r.dist[0], prim: r.prim[0], u: r.u[0], v: r.v[0], point: point };
   }
 
+  // ---- batched ambient-occlusion queries: an extension beyond the reference (include/mi355pt.h pt_occlusion, DESIGN.md section 16) ----
+  // surfels: Float32Array, 8 floats per surfel (point xyz, rMax, unit normal xyz, 0).  options: { samples (16), seed (0), bias (1e-4),
+  // indexBase (0), simple }.  Resolves to { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }: of `samples`
+  // cosine-distributed rays around the normal, how many reach nothing within rMax; all zero for a surfel that is not traced (a NaN, rMax <= 0).
+  // On a group: member 0, which holds the whole scene.
+  async occlusion(surfels, options) {
+    const o = options || {};
+    return this.group ? native().groupOcclusion(this.group, surfels, o) : native().occlusion(this.device, surfels, o);
+  }
+  // rays + what traceRays resolved to for them -> Float32Array of surfels (8 floats each): the hit point, rMax, the triangle's normal turned
+  // against the ray; a miss gives a surfel that occlusion() does not trace.
+  async hitSurfels(rays, hits, rMax) {
+    const r = rMax === undefined ? Infinity : rMax;
+    return this.group ? native().groupHitSurfels(this.group, rays, hits.t, hits.prim, hits.u, hits.v, r) : native().hitSurfels(this.device, rays, hits.t, hits.prim, hits.u, hits.v, r);
+  }
+  // An ambient-occlusion frame of the current camera: camera rays -> traceRays -> hitSurfels -> occlusion.  Resolves to a Float32Array of
+  // width * height visibilities, row-major like the radiance; 0 where the camera ray misses.
+  async ambientOcclusion(samples, rMax, options) {
+    const w = this.canvas.width, h = this.canvas.height, ubo = this._ubo();
+    const rays = new Float32Array(w * h * 8);
+    for (let y = 0; y < h; y++) for (let x = 0; x < w; x++) rays.set(native().cameraRay(ubo, x, y), (y * w + x) * 8);
+    const surfels = await this.hitSurfels(rays, await this.traceRays(rays), rMax);
+    return (await this.occlusion(surfels, Object.assign({ samples: samples }, options || {}))).visibility;
+  }
+
   setCameraPosition(x, y, z) { this.cameraPosition = [x, y, z]; }           // :824
   setCameraQuaternion(x, y, z, w) { this.cameraQuaternion = [x, y, z, w]; } // :828
   setFrameCount(frameCount) { this.frameCount = frameCount; }               // :832

@@ -19,6 +19,8 @@
 //        [--animate AMP]                                     before every render() the scene as built is displaced (a triangle wave in y over x, amplitude AMP,
 //                                                            phase by the frame count; tools/README.md) and the tree refitted in place: updateTriangles, no rebuild
 //        [--nearest X,Y,Z]                                   after the frames: the point of the scene nearest to (X, Y, Z), as one JSON line (closest-point query, an extension)
+//        [--ao S [--ao-radius R]]                            after the frames: an ambient-occlusion frame of the camera, S samples per pixel within R (default: no limit), grey
+//                                                            (v, v, v, 1) with v = visibility, 0 where the camera ray misses; --out writes it (linear, v * 255 rounded), --radiance the floats
 //        [--pick X,Y]                                        after the frames: what is under pixel (X, Y), as one JSON line (ray query, an extension)
 "use strict";
 const fs = require("fs");
@@ -103,8 +105,20 @@ async function main() {
   const spp = mode === PT.MODE_PATH ? pathTracer.options.spp : 1;
   console.log((frames / sec).toFixed(1) + " FPS, " + (canvas.width * canvas.height * spp * frames / sec / 1e6).toFixed(1) + " Msamples/s (" + frames + " frames)");
 
+  const aoSamples = Number(arg("ao", 0));
+  let aoFrame = null;
+  if (aoSamples > 0) {       // camera rays -> traceRays -> hitSurfels -> occlusion (an extension)
+    pathTracer.setCameraPosition(camera.position[0], camera.position[1], camera.position[2]);
+    pathTracer.setCameraQuaternion(camera.rotation[0], camera.rotation[1], camera.rotation[2], camera.rotation[3]);
+    const radius = arg("ao-radius", null);
+    const vis = await pathTracer.ambientOcclusion(aoSamples, radius === null ? Infinity : Number(radius), { seed: Number(arg("seed", 1)) });
+    aoFrame = new Float32Array(vis.length * 4);
+    let sum = 0;
+    for (let i = 0; i < vis.length; i++) { aoFrame[4 * i] = aoFrame[4 * i + 1] = aoFrame[4 * i + 2] = vis[i]; aoFrame[4 * i + 3] = 1; sum += vis[i]; }
+    console.log(JSON.stringify({ ao: aoSamples, radius: radius === null ? null : Number(radius), width: canvas.width, height: canvas.height, meanVisibility: sum / vis.length }));
+  }
   const radiance = arg("radiance", null), trisOut = arg("triangles", null);      // what a test compares with the oracle: the last frame (f32 RGBA) and the triangles it was traced over
-  if (radiance) { const img = pathTracer.readRadiance(); fs.writeFileSync(radiance, Buffer.from(img.buffer, img.byteOffset, img.byteLength)); }
+  if (radiance) { const img = aoFrame || pathTracer.readRadiance(); fs.writeFileSync(radiance, Buffer.from(img.buffer, img.byteOffset, img.byteLength)); }
   if (trisOut) { const t = pathTracer.trianglesData; fs.writeFileSync(trisOut, Buffer.from(t.buffer, t.byteOffset, t.byteLength)); }
   const pickAt = arg("pick", null);
   if (pickAt) {
@@ -120,7 +134,9 @@ async function main() {
   }
   const out = arg("out", null);
   if (out) {      // what the tonemapper pass would have put on the canvas (tonemapper.wgsl)
-    const rgba = pathTracer.readTonemapped(true);
+    let rgba = null;
+    if (aoFrame) { rgba = new Uint8Array(aoFrame.length); for (let i = 0; i < aoFrame.length; i++) rgba[i] = Math.round(aoFrame[i] * 255); }
+    else rgba = pathTracer.readTonemapped(true);
     const header = Buffer.from("P6\n" + canvas.width + " " + canvas.height + "\n255\n");
     const rgb = Buffer.alloc(canvas.width * canvas.height * 3);
     for (let i = 0, o = 0; i < rgba.length; i += 4) { rgb[o++] = rgba[i]; rgb[o++] = rgba[i + 1]; rgb[o++] = rgba[i + 2]; }

@@ -398,6 +398,68 @@ static napi_value fn_closest_points(napi_env env, napi_callback_info info) {    
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h pt_occlusion_host, pt_hit_surfels_host) ---- */
+
+/* surfels: Float32Array of 8 floats per surfel (PtSurfel: p xyz, rMax, n xyz, reserved); opt: { samples, seed, bias, indexBase, simple }
+ * -> { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }.  Copied into 16-byte aligned host memory, as the rays are. */
+static napi_value occlusion_on(napi_env env, PtContext* ctx, napi_value surfels_v, napi_value opt) {
+    void* d; size_t len; if (!get_typed(env, surfels_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, "occlusion: 8 floats per surfel"); return NULL; }
+    PtOcclusionParams p; memset(&p, 0, sizeof p);
+    p.samples = prop_u32(env, opt, "samples", 16); p.seed = prop_u32(env, opt, "seed", 0); p.index_base = prop_u32(env, opt, "indexBase", 0);
+    p.bias = (float)prop_f64(env, opt, "bias", 1e-4);
+    p.flags = prop_u32(env, opt, "simple", 0) ? PT_OCCLUSION_SIMPLE_KERNEL : 0u;
+    const size_t n = len / 8;
+    PtSurfel* sf = (PtSurfel*)aligned_alloc(16, (n ? n : 1) * sizeof(PtSurfel));
+    PtOcclusion* res = (PtOcclusion*)aligned_alloc(16, (n ? n : 1) * sizeof(PtOcclusion));
+    if (!sf || !res) { free(sf); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(sf, d, n * sizeof(PtSurfel));
+    int rc = pt_occlusion_host(ctx, sf, n, &p, res);
+    free(sf);
+    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_occlusion_host"); }
+    napi_value o, vis, un, sm; void *pv, *pu, *ps;
+    if (!(vis = make_typed(env, napi_float32_array, 4, n, &pv)) || !(un = make_typed(env, napi_uint32_array, 4, n, &pu)) ||
+        !(sm = make_typed(env, napi_uint32_array, 4, n, &ps))) { free(res); return NULL; }
+    for (size_t i = 0; i < n; ++i) { ((float*)pv)[i] = res[i].visibility; ((uint32_t*)pu)[i] = res[i].unoccluded; ((uint32_t*)ps)[i] = res[i].samples; }
+    free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "visibility", vis); napi_set_named_property(env, o, "unoccluded", un); napi_set_named_property(env, o, "samples", sm);
+    return o;
+}
+static napi_value fn_occlusion(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array surfels, options) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return occlusion_on(env, ctx, argv[1], argv[2]);
+}
+/* rays: Float32Array (8 floats per ray); t, prim, u, v: what traceRays resolved to; rMax -> Float32Array of 8 floats per surfel */
+static napi_value hit_surfels_on(napi_env env, PtContext* ctx, napi_value* a) {
+    void *d, *pt, *pp, *pu, *pv; size_t len, nt, np, nu, nv;
+    if (!get_typed(env, a[0], napi_float32_array, &d, &len) || !get_typed(env, a[1], napi_float32_array, &pt, &nt) ||
+        !get_typed(env, a[2], napi_uint32_array, &pp, &np) || !get_typed(env, a[3], napi_float32_array, &pu, &nu) ||
+        !get_typed(env, a[4], napi_float32_array, &pv, &nv)) return NULL;
+    const size_t n = len / 8;
+    if (len % 8 || nt != n || np != n || nu != n || nv != n) { napi_throw_range_error(env, NULL, "hitSurfels: 8 floats per ray and one hit per ray"); return NULL; }
+    const float r_max = (float)get_f64(env, a[5]);
+    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
+    PtHit* hits = (PtHit*)aligned_alloc(16, (n ? n : 1) * sizeof(PtHit));
+    PtSurfel* sf = (PtSurfel*)aligned_alloc(16, (n ? n : 1) * sizeof(PtSurfel));
+    if (!rays || !hits || !sf) { free(rays); free(hits); free(sf); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(rays, d, n * sizeof(PtRay));
+    for (size_t i = 0; i < n; ++i) { hits[i].t = ((float*)pt)[i]; hits[i].prim = ((uint32_t*)pp)[i]; hits[i].u = ((float*)pu)[i]; hits[i].v = ((float*)pv)[i]; }
+    int rc = pt_hit_surfels_host(ctx, rays, hits, n, r_max, sf);
+    free(rays); free(hits);
+    if (rc != 0) { free(sf); return throw_pt(env, ctx, rc, "pt_hit_surfels_host"); }
+    void* out; napi_value ta = make_typed(env, napi_float32_array, 4, n * 8, &out);
+    if (ta && n) memcpy(out, sf, n * sizeof(PtSurfel));
+    free(sf);
+    return ta;
+}
+static napi_value fn_hit_surfels(napi_env env, napi_callback_info info) {    /* (ctx, rays, t, prim, u, v, rMax) */
+    napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return hit_surfels_on(env, ctx, argv + 1);
+}
+
 /* The camera ray of PT_MODE_REFERENCE through the centre of pixel (x, y) of the UBO's camera, as one PtRay record (8 floats, t_max = +inf):
  * renderer.wgsl:387-395 in the operation order of pt_device.h::primary_ray -- correctly rounded f32 division and square root, fmaf where it
  * has fma, nothing contracted (-ffp-contract=off) -- so the same bits as the ray pt_camera_rays writes and mode 1 traces. */
@@ -615,6 +677,18 @@ static napi_value fn_group_closest_points(napi_env env, napi_callback_info info)
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_occlusion(napi_env env, napi_callback_info info) {       /* (group, surfels, options): on member 0, which holds the whole scene */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return occlusion_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_group_hit_surfels(napi_env env, napi_callback_info info) {     /* (group, rays, t, prim, u, v, rMax): on member 0 */
+    napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return hit_surfels_on(env, ctx, argv + 1);
+}
 static napi_value fn_group_set_batch(napi_env env, napi_callback_info info) {
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -673,6 +747,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
         {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
         {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
+        {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
         {"groupReadBVH2", fn_group_read_bvh2}, {"groupSetBatch", fn_group_set_batch}, {"groupRender", fn_group_render}, {"groupFlush", fn_group_flush},
