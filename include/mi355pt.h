@@ -576,8 +576,19 @@ PT_API int pt_debug_counters(PtContext* ctx, unsigned long long* dst24);
  * [3] traversal steps, [4] shade passes, [5] refill passes, [6] steps / [8] traversing lanes / [15] shade passes when the queue ran dry, [7] traversing lanes summed
  * over the steps, [9] of them at a leaf, [16..18] tick / steps / lanes when the wavefront re-seated its paths one per quad (0: never), [20] the variant that wrote it
  * (1 COUNTERS, 2 TIMELINE); COUNTERS only: [10..13] cycle shares (shade, refill, step, step before queue-dry), [14] longest path that ended after queue-dry, [19].
- * *n_waves = wavefronts written (<= max_waves).  Read it after pt_synchronize. */
+ * *n_waves = wavefronts written (<= max_waves).  Read it after pt_synchronize.  Both kinds of launch trace every tile of the root box's rectangle
+ * (their lane counts are compared with each other and with the oracle's): not the production launch, which also leaves out the tiles the tile cover
+ * drops (pt_debug_traced_tiles). */
 PT_API int pt_debug_wave_times(PtContext* ctx, unsigned long long* dst, uint32_t max_waves, uint32_t* n_waves);
+/* Which 8x8 tiles a megakernel launch of this one frame would trace, without launching anything: the tiles of the params' tile share inside the
+ * root box's screen rectangle (pt_traced_tile_rect) that the tile cover keeps -- the union of the screen rectangles of the live boxes of a
+ * breadth-first cut of the tree.  Follows knob "CULL" (0: every tile, 1: the rectangle, 2 = default: the cover) and
+ * PT_FLAG_STATS / knob "TIMELINE" (instrumented launches keep the rectangle). bitmask_out (optional, `words` >= ceil(tiles / 32) words): bit ty * tiles_x + tx
+ * set for a traced tile.  *rect_tiles = owned tiles inside the rectangle, *traced_tiles = those of them that are traced.  This is the plan of a view
+ * that stays: a small launch (fewer than 2^24 pixel-samples x (bounces + 1)) keeps the rectangle the first time it sees a set of cameras (or a refitted tree) and pays for their cover -- one small kernel and a
+ * host wait -- when the view repeats; this call computes the cover at once and leaves it for the launches that follow.  The frames pt_set_batch holds
+ * are not touched. */
+PT_API int pt_debug_traced_tiles(PtContext* ctx, const PtRenderParams* params, uint32_t* bitmask_out, uint32_t words, uint32_t* rect_tiles, uint32_t* traced_tiles);
 
 #ifdef __cplusplus
 }

@@ -123,7 +123,7 @@ EXPORTS = [
     "pt_group_build_bvh_accel",
     "pt_group_set_bvh2", "pt_group_set_bvh4", "pt_group_set_batch", "pt_group_render", "pt_group_flush", "pt_group_synchronize", "pt_group_read_radiance",
     "pt_group_read_rgba8", "pt_group_read_tonemapped",
-    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan",     # diagnostics section of the header
+    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_traced_tiles",     # diagnostics section of the header
 ]
 
 
@@ -556,6 +556,16 @@ class Context:
     def debug_set_tune(self, name, value=None):
         """Diagnostics: override one launch heuristic of the megakernel on this context (None restores the default)."""
         self._ck(lib.pt_debug_set_tune(self.h, name.encode(), C.c_uint32(0xFFFFFFFF if value is None else value)))
+
+    def debug_traced_tiles(self, params):
+        """Diagnostics: (mask, rect_tiles, traced_tiles) -- mask[ty, tx] is True for the 8x8 tiles a megakernel launch of this frame traces;
+        rect_tiles counts the owned tiles inside the root box's rectangle, traced_tiles those of them that the tile cover keeps."""
+        tx, ty = (params.width + 7) // 8, (params.height + 7) // 8
+        words = (tx * ty + 31) // 32
+        bits = np.zeros(words, np.uint32); nr = C.c_uint32(); nt = C.c_uint32()
+        self._ck(lib.pt_debug_traced_tiles(self.h, C.byref(params), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(nr), C.byref(nt)))
+        mask = np.unpackbits(bits.view(np.uint8), bitorder="little")[: tx * ty].astype(bool).reshape(ty, tx)
+        return mask, nr.value, nt.value
 
     def timing_collect_spans(self, capacity):
         """(start_ms, dur_ms) of the launches recorded since timing_begin; starts are relative to the first launch."""

@@ -101,6 +101,23 @@ struct PtContext {
     // the host's copies after an update (root box, edge maximum) come back through a pinned block behind the refit; whoever reads them
     // next waits for that copy (sync_refit_meta)
     uint32_t* h_refit = nullptr; hipEvent_t ev_refit = nullptr; bool meta_pending = false, meta_has_root = false;
+    // Tile cover (pt_cover.hip).  The cut of the wide tree is taken whenever a tree is installed (install_cut); tree_version counts
+    // everything that changes a box (install, refit).  A cover -- the tiles the cut's live boxes reach from a set of cameras -- is
+    // computed on a stream of its own that waits for nothing, read back through a pinned block, and kept until the cameras, the
+    // resolution or the tree change: with an unchanged camera a launch adds no kernel, no copy and no host wait.  The last kCovers results
+    // are kept (least recently used goes first), so a few alternating views -- stereo eyes, a diagnostics call between launches -- do
+    // not evict each other.
+    DevBuf<uint32_t> d_cut; uint32_t cut_count = 0, tree_version = 0;
+    hipStream_t cover_stream = nullptr; DevBuf<uint32_t> d_cover; uint32_t* h_cover = nullptr; size_t h_cover_cap = 0;
+    struct Cover {
+        bool valid = false, computed = false, usable = false;      // valid: the view has been seen; computed: its mask is there; usable: every box could be projected (else the launch keeps the rectangle)
+        uint32_t tree_version = 0, width = 0, height = 0, id = 0; uint64_t used = 0;
+        std::vector<ptk::CoverCam> cams; std::vector<uint32_t> mask;
+    };
+    static constexpr int kCovers = 4;
+    Cover covers[kCovers]; uint64_t cover_clock = 0;
+    std::vector<ptk::CoverCam> cover_cams;                 // the distinct cameras of the launch being planned
+    uint32_t cover_ids = 0;
     // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
     DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
@@ -115,9 +132,10 @@ struct PtContext {
         hipStream_t side = nullptr; hipEvent_t resolved = nullptr, done = nullptr; bool used = false;
         uint64_t resolved_seq = 0;                                      // launch sequence number of the latest record of `resolved` (pt_buffer_busy)
         DevBuf<uint32_t> queue; DevBuf<float4> samples; DevBuf<uint2> spill; DevBuf<uint4> rays;
-        // owned-tile slots that the launch in this slot traces (the others are culled: every camera ray misses the root box)
+        // owned-tile slots that the launch in this slot traces (the others are culled: every camera ray misses the root box, or every box
+        // of the tree's cut), followed by the tile cover's bitmask (RenderArgs::trace_slots); key word 8 = the cover's id (0: rectangle only)
         DevBuf<uint32_t> trace_slots; uint32_t* h_trace = nullptr; size_t h_trace_cap = 0; hipEvent_t trace_copied = nullptr;
-        uint32_t cull_key[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint32_t num_trace_tiles = 0; bool cull_valid = false;
+        uint32_t cull_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; uint32_t num_trace_tiles = 0; bool cull_valid = false;
         DevBuf<ptk::FrameParams> frame_params; DevBuf<float4*> frame_outs;      // per-frame parameters / targets of the launch in this slot
         const void* primed_ptr = nullptr; size_t primed_samples = 0;   // what the resident prefill covers
     };
@@ -248,6 +266,22 @@ int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
     return PT_OK;
 }
 
+// The cut of the tree that was just installed in the arena (wide_meta, num_wide and node_off describe it), for the tile cover.  No
+// cut (cut_count 0: launches cull by the root box's rectangle alone) when the root is a leaf or the tree is empty.  Waits for the
+// stream, as every call that installs a tree does anyway.
+int install_cut(PtContext* ctx) {
+    ++ctx->tree_version; ctx->cut_count = 0;
+    const uint32_t base16 = uint32_t(ctx->node_off / 16u), root = ctx->wide_meta.root_ref;
+    if (root == pt::kInvalid || (root & pt::kLeafFlag) || ctx->num_wide == 0u || root < base16) return PT_OK;
+    PT_HIP(ctx, ctx->d_cut.ensure(ptk::kCutMax + 1u));
+    if (!ctx->h_word) PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_word, 64, hipHostMallocDefault));
+    PT_HIP(ctx, ptk::launch_tile_cut(ctx->wide(), ctx->num_wide, base16, (root - base16) / 4u, ctx->d_cut.ptr, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->h_word, ctx->d_cut.ptr + ptk::kCutMax, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cut_count = std::min(ctx->h_word[0], ptk::kCutMax);
+    return PT_OK;
+}
+
 int upload_wide(PtContext* ctx, const uint32_t* bvh4, uint64_t words) {
     pt::WideBvh w; std::string err;
     if (int rc = sync_refit_meta(ctx)) return rc;
@@ -264,7 +298,7 @@ int upload_wide(PtContext* ctx, const uint32_t* bvh4, uint64_t words) {
     w.nodes.clear(); w.nodes.shrink_to_fit();
     ctx->wide_meta = w;
     ctx->have_bvh = true;
-    return PT_OK;
+    return install_cut(ctx);
 }
 
 // Tiles whose every camera ray provably misses the root box need no tracing: their samples keep the primed miss value.  The
@@ -412,21 +446,107 @@ LaunchPlan plan_launch(const PtTune& tune, const PlanInput& in) {
 
 // Which owned tiles are traced at all: the union over the launch's frames of the root box's screen rectangle (root_box_rect).  Returns false for
 // "every owned tile"; otherwise `traced` lists the owned-tile slots inside `rect`.
-bool traced_tiles(const PtContext* ctx, const ptk::RenderArgs& A, uint32_t nf, bool sharded, TileRect& rect, std::vector<uint32_t>& traced) {
-    traced.clear(); rect = {0, 0, 0, 0};
-    if (!(ctx->have_bvh && ctx->wide_meta.root_ref != pt::kInvalid && !ctx->wide_meta.root_degenerate && A.num_tris != 0u && ctx->tune.cull != 0u)) return false;
+// `cover` (optional): the launch's tile cover, one bit per tile of the frame (tile_cover below) -- a tile inside the rectangle is listed only if
+// its bit is set.
+bool launch_rect(const PtContext* ctx, const ptk::FrameParams* frames, uint32_t nf, uint32_t width, uint32_t height, uint32_t num_tris, TileRect& rect) {
+    rect = {0, 0, 0, 0};
+    if (!(ctx->have_bvh && ctx->wide_meta.root_ref != pt::kInvalid && !ctx->wide_meta.root_degenerate && num_tris != 0u && ctx->tune.cull != 0u)) return false;
     for (uint32_t i = 0; i < nf; ++i) {
         TileRect r;
-        if (!root_box_rect(ctx->wide_meta, ctx->pending_frames[i], A.width, A.height, r)) return false;
+        if (!root_box_rect(ctx->wide_meta, frames[i], width, height, r)) return false;
         if (i == 0) rect = r;
         else { rect.tx0 = std::min(rect.tx0, r.tx0); rect.ty0 = std::min(rect.ty0, r.ty0); rect.tx1 = std::max(rect.tx1, r.tx1); rect.ty1 = std::max(rect.ty1, r.ty1); }
     }
-    const uint32_t tiles_y = (A.height + pt::kTile - 1) / pt::kTile;
-    if (rect.tx0 == 0u && rect.ty0 == 0u && rect.tx1 >= A.tiles_x && rect.ty1 >= tiles_y) return false;     // nothing to leave out
-    auto inside = [&](uint32_t tile) { const uint32_t tx = tile % A.tiles_x, ty = tile / A.tiles_x; return tx >= rect.tx0 && tx < rect.tx1 && ty >= rect.ty0 && ty < rect.ty1; };
-    if (sharded) { for (uint32_t sl = 0; sl < A.num_tiles; ++sl) if (inside(ctx->tiles_host[sl])) traced.push_back(sl); }
-    else { for (uint32_t ty = rect.ty0; ty < rect.ty1; ++ty) for (uint32_t tx = rect.tx0; tx < rect.tx1; ++tx) traced.push_back(ty * A.tiles_x + tx); }
     return true;
+}
+bool traced_tiles(const PtContext* ctx, const ptk::RenderArgs& A, uint32_t nf, bool sharded, const uint32_t* cover, TileRect& rect, std::vector<uint32_t>& traced) {
+    traced.clear();
+    if (!launch_rect(ctx, ctx->pending_frames.data(), nf, A.width, A.height, A.num_tris, rect)) return false;
+    const uint32_t tiles_y = (A.height + pt::kTile - 1) / pt::kTile;
+    if (!cover && rect.tx0 == 0u && rect.ty0 == 0u && rect.tx1 >= A.tiles_x && rect.ty1 >= tiles_y) return false;     // nothing to leave out
+    auto inside = [&](uint32_t tile) {
+        const uint32_t tx = tile % A.tiles_x, ty = tile / A.tiles_x;
+        return tx >= rect.tx0 && tx < rect.tx1 && ty >= rect.ty0 && ty < rect.ty1 && (!cover || ((cover[tile >> 5] >> (tile & 31u)) & 1u));
+    };
+    if (sharded) { for (uint32_t sl = 0; sl < A.num_tiles; ++sl) if (inside(ctx->tiles_host[sl])) traced.push_back(sl); }
+    else {          // whole frames: the rectangle's tiles in row-major order, no division per tile
+        for (uint32_t ty = rect.ty0; ty < rect.ty1; ++ty) for (uint32_t tx = rect.tx0; tx < rect.tx1; ++tx) {
+            const uint32_t tile = ty * A.tiles_x + tx;
+            if (!cover || ((cover[tile >> 5] >> (tile & 31u)) & 1u)) traced.push_back(tile);
+        }
+    }
+    return true;
+}
+
+// The tile cover of `nf` frames: for every distinct camera among them, the tiles that the screen rectangles of the cut's live boxes touch
+// (ptk::launch_tile_cover), as a bitmask over the frame's tiles; *mask = nullptr when the launch has to keep the rectangle -- no cut, the
+// root box itself cannot be projected (launch_rect fails: everything is traced), or one of the cut's boxes cannot.  The last result is kept:
+// the same cameras, resolution and tree version cost a comparison.  A new one runs on the context's cover stream, which waits for no other
+// stream (every call that changes the tree has been waited for on the host before a launch is planned: sync_refit_meta, the builds), and
+// the host waits for its read-back only.
+// For a small launch (`now` false, flush_pending_stats) that wait is paid for a view that REPEATS: the first launch that shows a set of cameras (or the first after a refit) only notes it and keeps the
+// rectangle -- exactly the earlier behaviour, so a camera that moves every frame, or a mesh that is updated every frame, pays nothing (measured:
+// the wait cost the reference's 0.18 ms frame a third with a new camera per render() call); the second launch of the same
+// view computes the cover, and every later one finds it.  `now`: compute at the first sight (pt_debug_traced_tiles: the plan of a view that stays).
+int tile_cover(PtContext* ctx, const ptk::FrameParams* frames, uint32_t nf, uint32_t width, uint32_t height, uint32_t num_tris, bool now, const uint32_t** mask, uint32_t* id) {
+    *mask = nullptr; *id = 0u;
+    if (ctx->cut_count == 0u || nf == 0u) return PT_OK;
+    TileRect rect;
+    if (!launch_rect(ctx, frames, nf, width, height, num_tris, rect)) return PT_OK;
+    std::vector<ptk::CoverCam>& cams = ctx->cover_cams;
+    cams.clear();
+    for (uint32_t i = 0; i < nf; ++i) {
+        ptk::CoverCam c; std::memset(&c, 0, sizeof c);
+        std::memcpy(c.cam, frames[i].cam, 12); c.focal = frames[i].focal; std::memcpy(c.quat, frames[i].quat, 16); c.aspect = frames[i].aspect;
+        bool seen = false;
+        for (size_t k = cams.size(); k-- > 0 && !seen;) seen = std::memcmp(&cams[k], &c, sizeof c) == 0;      // a batch usually repeats its last camera
+        if (!seen) cams.push_back(c);
+    }
+    PtContext::Cover* found = nullptr; PtContext::Cover* victim = &ctx->covers[0];
+    for (PtContext::Cover& c : ctx->covers) {
+        if (c.valid && c.tree_version == ctx->tree_version && c.width == width && c.height == height && c.cams.size() == cams.size() &&
+            std::memcmp(c.cams.data(), cams.data(), cams.size() * sizeof(ptk::CoverCam)) == 0) { found = &c; break; }
+        if (!c.valid || (victim->valid && c.used < victim->used)) victim = &c;
+    }
+    PtContext::Cover& cv = found ? *found : *victim;
+    cv.used = ++ctx->cover_clock;
+    if (!found) {           // first sight: remembered, nothing computed yet
+        cv.valid = true; cv.computed = false; cv.usable = false;
+        cv.cams = cams; cv.tree_version = ctx->tree_version; cv.width = width; cv.height = height;
+        if (!now) return PT_OK;
+    }
+    if (!cv.computed) {
+        if (int rc = sync_refit_meta(ctx)) return rc;
+        const uint32_t tiles = ((width + pt::kTile - 1) / pt::kTile) * ((height + pt::kTile - 1) / pt::kTile), words = (tiles + 31u) / 32u;
+        if (!ctx->cover_stream) {
+            int lo = 0, hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);       // short kernels next to persistent launches, like the resolve passes
+            PT_HIP(ctx, hipStreamCreateWithPriority(&ctx->cover_stream, hipStreamNonBlocking, hi));
+        }
+        PT_HIP(ctx, ctx->d_cover.ensure(words + 1u));
+        if (ctx->h_cover_cap < words + 1u) {
+            if (ctx->h_cover) (void)hipHostFree(ctx->h_cover);
+            ctx->h_cover = nullptr; ctx->h_cover_cap = 0;
+            PT_HIP(ctx, hipHostMalloc((void**)&ctx->h_cover, (size_t(words) + 1u) * sizeof(uint32_t), hipHostMallocDefault));
+            ctx->h_cover_cap = words + 1u;
+        }
+        cv.valid = false;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_cover.ptr, 0, (size_t(words) + 1u) * sizeof(uint32_t), ctx->cover_stream));
+        for (size_t first = 0; first < cams.size(); first += ptk::kCoverCams) {
+            ptk::CoverCams group; std::memset(&group, 0, sizeof group);
+            const uint32_t n = uint32_t(std::min<size_t>(ptk::kCoverCams, cams.size() - first));
+            std::memcpy(group.c, cams.data() + first, n * sizeof(ptk::CoverCam));
+            PT_HIP(ctx, ptk::launch_tile_cover(ctx->wide(), ctx->d_cut.ptr, ctx->cut_count, group, n, width, height, ctx->d_cover.ptr, words, ctx->cover_stream));
+        }
+        PT_HIP(ctx, hipMemcpyAsync(ctx->h_cover, ctx->d_cover.ptr, (size_t(words) + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->cover_stream));
+        PT_HIP(ctx, hipStreamSynchronize(ctx->cover_stream));
+        cv.mask.assign(ctx->h_cover, ctx->h_cover + words);
+        cv.usable = ctx->h_cover[words] == 0u;
+        cv.id = ++ctx->cover_ids; if (cv.id == 0u) cv.id = ++ctx->cover_ids;
+        cv.valid = true; cv.computed = true;
+    }
+    if (cv.usable) { *mask = cv.mask.data(); *id = cv.id; }
+    return PT_OK;
 }
 
 // Streams, events and buffers of the frame slots a launch of this plan may use: every slot is sized for a full batch of the current setting (largest
@@ -460,18 +580,22 @@ int prepare_slots(PtContext* ctx, const LaunchPlan& P, const ptk::RenderArgs& A,
 
 // The list of traced tiles of a launch into the slot's device array, through a pinned staging buffer of the slot; rebuilt only when the rectangle
 // (or the tile share) changes.  The copy itself is queued by the caller's launch step (on the slot's stream, behind what it still waits for).
-int stage_traced_tiles(PtContext* ctx, PtContext::FrameSlot& sl, const uint32_t key[8], const std::vector<uint32_t>& traced) {
-    if (sl.cull_valid && std::memcmp(key, sl.cull_key, 8 * sizeof(uint32_t)) == 0) return PT_OK;
+// Behind the list goes the tile cover's bitmask (`words` words; cover == nullptr: all ones, the rectangle alone decides), which resolve_kernel reads.
+int stage_traced_tiles(PtContext* ctx, PtContext::FrameSlot& sl, const uint32_t key[9], const std::vector<uint32_t>& traced, const uint32_t* cover, uint32_t words) {
+    if (sl.cull_valid && std::memcmp(key, sl.cull_key, 9 * sizeof(uint32_t)) == 0) return PT_OK;
     if (!sl.trace_copied) PT_HIP(ctx, hipEventCreateWithFlags(&sl.trace_copied, hipEventDisableTiming));
     else PT_HIP(ctx, hipEventSynchronize(sl.trace_copied));                   // the previous copy out of the staging buffer is done
-    if (sl.h_trace_cap < traced.size()) {
+    const size_t need = traced.size() + words;
+    if (sl.h_trace_cap < need) {
         if (sl.h_trace) (void)hipHostFree(sl.h_trace);
         sl.h_trace = nullptr; sl.h_trace_cap = 0;
-        PT_HIP(ctx, hipHostMalloc((void**)&sl.h_trace, std::max<size_t>(traced.size(), 1024) * sizeof(uint32_t), hipHostMallocDefault));
-        sl.h_trace_cap = std::max<size_t>(traced.size(), 1024);
+        PT_HIP(ctx, hipHostMalloc((void**)&sl.h_trace, std::max<size_t>(need, 1024) * sizeof(uint32_t), hipHostMallocDefault));
+        sl.h_trace_cap = std::max<size_t>(need, 1024);
     }
-    PT_HIP(ctx, sl.trace_slots.ensure(std::max<size_t>(traced.size(), 1)));
+    PT_HIP(ctx, sl.trace_slots.ensure(std::max<size_t>(need, 1)));
     if (!traced.empty()) std::memcpy(sl.h_trace, traced.data(), traced.size() * sizeof(uint32_t));
+    if (cover) std::memcpy(sl.h_trace + traced.size(), cover, size_t(words) * sizeof(uint32_t));
+    else std::memset(sl.h_trace + traced.size(), 0xff, size_t(words) * sizeof(uint32_t));
     sl.cull_valid = false;
     return PT_OK;
 }
@@ -493,7 +617,18 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     // ---- plan ---------------------------------------------------------------------------------------------------------------
     std::vector<uint32_t> traced;                 // owned-tile slots inside the rectangle (cull == false: all of them)
     TileRect rect;
-    const bool cull = traced_tiles(ctx, A, nf, sharded, rect, traced);
+    // knob CULL: 0 no culling, 1 the root box's rectangle, 2 (default) the tile cover inside it.  Instrumented launches keep the rectangle: the
+    // oracle traces the culled rays too, and stats_culled below can only account for rays that miss the ROOT box (one node record each).  So do
+    // TIMELINE launches: their lane-step counts are the COUNTERS variant's of the same frame (tests/test_gpu_edges.py)
+    // A new view's cover costs the host about 0.1 ms of waiting.  A launch of at least 2^24 ray segments (pixel-samples x
+    // (bounces + 1): a millisecond of tracing or more -- one path-traced 1080p frame has 2^26) takes it at once, because the tiles it saves are worth
+    // more; a smaller launch (the reference's own 0.15 ms frame) only notes the view and takes the cover if the view repeats.
+    const bool cover_now = uint64_t(A.num_tiles) * 64u * A.spp * nf * (uint64_t(A.max_bounces) + 1u) >= (1ull << 24);
+    const uint32_t* cover = nullptr; uint32_t cover_id = 0u;
+    if (!stats && PtTune::pick(ctx->tune.timeline, 0u) == 0u && PtTune::pick(ctx->tune.cull, 2u) >= 2u) {
+        if (int rc = tile_cover(ctx, ctx->pending_frames.data(), nf, A.width, A.height, A.num_tris, cover_now, &cover, &cover_id)) return rc;
+    }
+    const bool cull = traced_tiles(ctx, A, nf, sharded, cover, rect, traced);
     A.num_trace_tiles = cull ? uint32_t(traced.size()) : A.num_tiles;
     ctx->stats_culled = 0;
     if (stats && cull) {                          // the oracle traces these rays too: one closest ray, one root record, one sample each
@@ -529,8 +664,9 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     A.prime = stats ? 1u : 0u;                   // instrumented launches start from a freshly primed prefix
     A.samples = sl.samples.ptr; A.queue = sl.queue.ptr; A.spill = sl.spill.ptr; A.raybuf = sl.rays.ptr;
     A.trace_slots = nullptr;
-    const uint32_t cull_key[8] = {rect.tx0, rect.ty0, rect.tx1, rect.ty1, A.width, A.height, ctx->pending_rank | (ctx->pending_count << 16), A.num_trace_tiles};
-    if (cull) { if (int rc = stage_traced_tiles(ctx, sl, cull_key, traced)) return rc; }
+    const uint32_t cull_key[9] = {rect.tx0, rect.ty0, rect.tx1, rect.ty1, A.width, A.height, ctx->pending_rank | (ctx->pending_count << 16), A.num_trace_tiles, cover_id};
+    const uint32_t cover_words = (A.tiles_x * ((A.height + pt::kTile - 1) / pt::kTile) + 31u) / 32u;
+    if (cull) { if (int rc = stage_traced_tiles(ctx, sl, cull_key, traced, cover, cover_words)) return rc; }
     // knob TIMELINE = 1 (diagnostics): an ordinary launch -- its plan, its slot, its overlap with its neighbours all as in production -- runs the TIMELINE variant
     // of the kernel and leaves the per-wavefront record of pt_debug_wave_times (the last such launch's: read it after a pt_synchronize)
     const bool timeline = !stats && PtTune::pick(ctx->tune.timeline, 0u) != 0u;
@@ -547,7 +683,7 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     if (sl.used) PT_HIP(ctx, hipStreamWaitEvent(sl.side, sl.resolved, 0));
     if (cull) {
         if (!sl.cull_valid) {
-            if (!traced.empty()) PT_HIP(ctx, hipMemcpyAsync(sl.trace_slots.ptr, sl.h_trace, traced.size() * sizeof(uint32_t), hipMemcpyHostToDevice, sl.side));
+            PT_HIP(ctx, hipMemcpyAsync(sl.trace_slots.ptr, sl.h_trace, (traced.size() + cover_words) * sizeof(uint32_t), hipMemcpyHostToDevice, sl.side));
             PT_HIP(ctx, hipEventRecord(sl.trace_copied, sl.side));
             std::memcpy(sl.cull_key, cull_key, sizeof cull_key); sl.cull_valid = true; sl.num_trace_tiles = A.num_trace_tiles;
         }
@@ -653,6 +789,9 @@ void pt_destroy(PtContext* ctx) {
     ctx->d_refit_parent2.release(); ctx->d_refit_arrive2.release(); ctx->d_cost.release();
     if (ctx->h_refit) (void)hipHostFree(ctx->h_refit);
     if (ctx->ev_refit) (void)hipEventDestroy(ctx->ev_refit);
+    if (ctx->cover_stream) { (void)hipStreamSynchronize(ctx->cover_stream); (void)hipStreamDestroy(ctx->cover_stream); }
+    ctx->d_cut.release(); ctx->d_cover.release();
+    if (ctx->h_cover) (void)hipHostFree(ctx->h_cover);
     for (auto& sl : ctx->slots) {
         sl.queue.release(); sl.samples.release(); sl.spill.release(); sl.rays.release(); sl.trace_slots.release();
         if (sl.h_trace) (void)hipHostFree(sl.h_trace);
@@ -902,6 +1041,7 @@ int update_triangles(PtContext* ctx, const char* fn, const void* tris, uint32_t 
     if (tree) {
         PT_HIP(ctx, ptk::launch_refit4(ctx->d_tris9.ptr, num_tris, ctx->d_bvh4.ptr, ctx->num_nodes4, refit_buffers(ctx), ctx->wide(), ctx->stream));
         PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit, ctx->d_bvh4.ptr + 1, 12, hipMemcpyDeviceToHost, ctx->stream));
+        ++ctx->tree_version;        // new boxes at the places the cut names: the next launch takes a new tile cover
     }
     PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit + 3, ctx->d_edge_max.ptr, 4, hipMemcpyDeviceToHost, ctx->stream));
     PT_HIP(ctx, hipEventRecord(ctx->ev_refit, ctx->stream));
@@ -1077,7 +1217,7 @@ int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     ctx->num_wide = internal; ctx->tree_built = true;
     ctx->have_bvh = true;
     ctx->accum_count = 0;
-    return PT_OK;
+    return install_cut(ctx);
 }
 
 int pt_read_bvh4(PtContext* ctx, uint32_t* dst, uint64_t bytes) {
@@ -1662,6 +1802,44 @@ int pt_debug_wave_times(PtContext* ctx, unsigned long long* dst, uint32_t max_wa
     const uint32_t n = ctx->wave_times_n < max_waves ? ctx->wave_times_n : max_waves;
     if (n) PT_HIP(ctx, hipMemcpy(dst, ctx->d_wave_times.ptr, size_t(n) * ptk::kWaveTimeWords * 8u, hipMemcpyDeviceToHost));
     if (n_waves) *n_waves = n;
+    return PT_OK;
+}
+
+/* diagnostics: which tiles a megakernel launch of this one frame traces -- the plan of flush_pending_stats (rectangle, tile cover, knob CULL,
+ * PT_FLAG_STATS), without launching anything and without touching the frames pt_set_batch still holds */
+int pt_debug_traced_tiles(PtContext* ctx, const PtRenderParams* p, uint32_t* bitmask_out, uint32_t words, uint32_t* rect_tiles, uint32_t* traced_tiles_out) {
+    if (int rc = bind(ctx)) return rc;
+    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_traced_tiles: null params");
+    if (p->width == 0 || p->height == 0 || p->width > 32768 || p->height > 32768) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_traced_tiles: bad resolution");
+    const uint32_t count = p->tile_count ? p->tile_count : 1u;
+    if (p->tile_rank >= count) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_traced_tiles: tile_rank >= tile_count");
+    const uint32_t tiles_x = (p->width + pt::kTile - 1) / pt::kTile, tiles_y = (p->height + pt::kTile - 1) / pt::kTile, need = (tiles_x * tiles_y + 31u) / 32u;
+    if (bitmask_out && words < need) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_traced_tiles: the bitmask needs one bit per tile of the frame");
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::FrameParams f; std::memset(&f, 0, sizeof(f));
+    std::memcpy(f.cam, p->cam_pos, 12); std::memcpy(f.quat, p->cam_quat, 16); f.focal = p->focal; f.aspect = p->aspect;
+    const bool brute = (p->flags & PT_FLAG_BRUTE_FORCE) != 0, stats = (p->flags & PT_FLAG_STATS) != 0;
+    TileRect rect = {0, 0, tiles_x, tiles_y};
+    const uint32_t* cover = nullptr; uint32_t cover_id = 0u;
+    if (!brute && launch_rect(ctx, &f, 1u, p->width, p->height, p->num_tris, rect)) {
+        if (!stats && PtTune::pick(ctx->tune.timeline, 0u) == 0u && PtTune::pick(ctx->tune.cull, 2u) >= 2u) {
+            if (int rc = tile_cover(ctx, &f, 1u, p->width, p->height, p->num_tris, true, &cover, &cover_id)) return rc;
+        }
+    } else rect = {0, 0, tiles_x, tiles_y};
+    std::vector<uint32_t> owned;
+    pt::tile_list(p->width, p->height, p->tile_rank, count, owned);
+    if (bitmask_out) std::memset(bitmask_out, 0, size_t(words) * sizeof(uint32_t));
+    uint32_t in_rect = 0, traced = 0;
+    for (uint32_t tile : owned) {
+        const uint32_t tx = tile % tiles_x, ty = tile / tiles_x;
+        if (!(tx >= rect.tx0 && tx < rect.tx1 && ty >= rect.ty0 && ty < rect.ty1)) continue;
+        ++in_rect;
+        if (cover && !((cover[tile >> 5] >> (tile & 31u)) & 1u)) continue;
+        ++traced;
+        if (bitmask_out) bitmask_out[tile >> 5] |= 1u << (tile & 31u);
+    }
+    if (rect_tiles) *rect_tiles = in_rect;
+    if (traced_tiles_out) *traced_tiles_out = traced;
     return PT_OK;
 }
 

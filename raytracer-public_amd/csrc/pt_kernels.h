@@ -124,7 +124,9 @@ struct RenderArgs {
     // Queue enumeration vs sample storage.  The queue hands out (frame, traced tile, sample) batches of 64 pixel-samples;
     // `trace_slots` lists the owned-tile slots that are traced at all (nullptr = every owned tile): tiles whose every camera ray
     // provably misses the root box are left out (pt_api.cpp: screen rectangle of the root box) and keep the primed miss value.
-    // Samples are stored by (frame, owned-tile slot, sample), whatever subset is traced.
+    // Samples are stored by (frame, owned-tile slot, sample), whatever subset is traced.  Behind the num_trace_tiles slots the array holds
+    // the launch's tile cover, one bit per tile of the frame (tile ty * tiles_x + tx; pt_cover.hip): a tile inside trace_rect whose bit
+    // is clear is not traced either (resolve_kernel reads the bit; the trace only sees the list).
     const uint32_t* trace_slots; uint32_t num_trace_tiles;
     uint32_t  trace_rect[4];                  // tiles [tx0, tx1) x [ty0, ty1) that are traced when trace_slots is set: the rest keeps the primed value (resolve_kernel writes it without reading)
     uint32_t  trace_bpf, trace_bpf_magic;     // traced batches per frame (num_trace_tiles * spp) and floor(2^32 / that)
@@ -248,6 +250,19 @@ hipError_t launch_refit_prepare2(const uint32_t* bvh2, uint32_t nn2, uint32_t* p
 hipError_t launch_refit2(const float* tris9, uint32_t num_tris, uint32_t* bvh2, uint32_t nn2, const uint32_t* parent2, uint32_t* arrive, hipStream_t stream);
 // *out = sum over reachable internal nodes of halfArea(node) / halfArea(root) (f64)
 hipError_t launch_bvh_cost(const uint32_t* bvh4, uint32_t num_nodes4, const uint2* self, double* out, hipStream_t stream);
+// ---- tile cover (pt_cover.hip): which tiles of a frame a camera ray can reach the scene in at all ------------------------------
+// The cut: a breadth-first frontier of the wide tree, at most kCutMax entries, each (wide node index << 2) | child slot -- the place
+// of a child piece in the arena, not a copy of its box.  cut[kCutMax] receives the number of entries.
+constexpr uint32_t kCutMax = 4096;
+hipError_t launch_tile_cut(const uint4* wide, uint32_t num_wide, uint32_t node_base16, uint32_t root_index, uint32_t* cut, hipStream_t stream);
+// The cover of up to kCoverCams cameras: the bits (tile ty * tiles_x + tx) of every tile that the screen rectangle of a cut entry's
+// live box touches (projection and margin of pt_api.cpp::root_box_rect) are OR-ed into mask[0 .. words); mask[words] becomes nonzero
+// when a box cannot be projected (a corner beside or behind the eye, a value that is not finite): the caller traces the rectangle then.
+constexpr uint32_t kCoverCams = 16;
+struct CoverCam { float cam[3]; float focal; float quat[4]; float aspect; };
+struct CoverCams { CoverCam c[kCoverCams]; };
+hipError_t launch_tile_cover(const uint4* wide, const uint32_t* cut, uint32_t count, const CoverCams& cams, uint32_t num_cams, uint32_t width, uint32_t height,
+                             uint32_t* mask, uint32_t words, hipStream_t stream);
 hipError_t launch_rgba8(const float4* src, uint32_t* dst, uint32_t n, hipStream_t stream);
 hipError_t launch_tonemap(const float4* src, uint32_t* dst, uint32_t width, uint32_t height, int from_rgba8, hipStream_t stream);
 
