@@ -1432,6 +1432,13 @@ int check_trace(PtContext* ctx, const char* fn, const void* rays, uint64_t n, ui
     return PT_OK;
 }
 
+// The queue block and the spill area of the persistent query kernels (pt_walk.h), shared by the ray, closest-point and occlusion queries:
+// their launches are ordered by the stream, and DevBuf::ensure only ever grows a buffer, so the area fits whichever kernel asked for most.
+hipError_t ensure_walk_buffers(PtContext* ctx, uint32_t grid, int short_stack) {
+    const hipError_t e = ctx->d_rq_queue.ensure(ptk::kRqQueueWords);
+    return e != hipSuccess ? e : ctx->d_rq_spill.ensure(ptk::walk_spill_entries(grid, short_stack));
+}
+
 // the launch itself: rays / hits in device memory, on the context's stream, behind whatever pt_set_batch still holds
 int trace_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* hits) {
     if (int rc = flush_pending(ctx)) return rc;
@@ -1443,14 +1450,13 @@ int trace_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags
     A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
     A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
     const bool anyhit = (flags & PT_TRACE_ANY_HIT) != 0, stats = (flags & PT_TRACE_STATS) != 0, simple = (flags & PT_TRACE_SIMPLE_KERNEL) != 0;
-    const uint32_t grid = ptk::rayquery_grid(ctx->num_cus);
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_RQ_WAVES_PER_SIMD);
     if (stats) {
         ctx->stats_culled = 0;
         PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
         A.stats = ctx->d_stats.ptr;
     } else if (!simple) {
-        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
-        PT_HIP(ctx, ctx->d_rq_spill.ensure(ptk::rayquery_spill_entries(grid)));
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_RQ_SHORT_STACK));
     }
     PT_HIP(ctx, ptk::launch_trace_rays(A, rays, hits, n, anyhit, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
     if (stats) ctx->last_stats = true;
@@ -1516,15 +1522,13 @@ int closest_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t f
     A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
     A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
     const bool stats = (flags & PT_CLOSEST_STATS) != 0, simple = (flags & PT_CLOSEST_SIMPLE_KERNEL) != 0, brute = (flags & PT_CLOSEST_BRUTE_FORCE) != 0;
-    const uint32_t grid = ptk::pointquery_grid(ctx->num_cus);
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_PQ_WAVES_PER_SIMD);
     if (stats) {
         ctx->stats_culled = 0;
         PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
         A.stats = ctx->d_stats.ptr;
     } else if (!simple && !brute) {
-        // shared with the ray queries (the launches are ordered by the stream): room for whichever kernel needs more
-        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
-        PT_HIP(ctx, ctx->d_rq_spill.ensure(std::max(ptk::pointquery_spill_entries(grid), ptk::rayquery_spill_entries(ptk::rayquery_grid(ctx->num_cus)))));
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_PQ_SHORT_STACK));
     }
     PT_HIP(ctx, ptk::launch_closest_points(A, points, out, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
     if (stats) ctx->last_stats = true;
@@ -1608,15 +1612,13 @@ int occlusion_on_stream(PtContext* ctx, const void* surfels, uint32_t n, const P
     if (int rc = sync_refit_meta(ctx)) return rc;
     ptk::RenderArgs A; scene_args(ctx, A);
     const bool stats = (p.flags & PT_OCCLUSION_STATS) != 0, simple = (p.flags & PT_OCCLUSION_SIMPLE_KERNEL) != 0;
-    const uint32_t grid = ptk::occlusion_grid(ctx->num_cus);
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_OC_WAVES_PER_SIMD);
     if (stats) {
         ctx->stats_culled = 0;
         PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
         A.stats = ctx->d_stats.ptr;
     } else if (!simple) {
-        // shared with the ray and closest-point queries (the launches are ordered by the stream): room for whichever kernel needs more
-        PT_HIP(ctx, ctx->d_rq_queue.ensure(ptk::kRqQueueWords));
-        PT_HIP(ctx, ctx->d_rq_spill.ensure(std::max(ptk::occlusion_spill_entries(grid), ptk::rayquery_spill_entries(ptk::rayquery_grid(ctx->num_cus)))));
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_OC_SHORT_STACK));
     }
     PT_HIP(ctx, ptk::launch_occlusion(A, surfels, out, n, p.samples, p.seed, p.index_base, p.bias, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
     if (stats) ctx->last_stats = true;

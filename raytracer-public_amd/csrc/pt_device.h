@@ -1,5 +1,5 @@
 // pt_device.h -- device-side arithmetic shared by the HIP kernels (pt_kernels.hip,
-// pt_megakernel.hip, pt_rayquery.hip): explicit-order f32 vector helpers, the reference's ray setup and slab
+// pt_megakernel.hip, pt_rayquery.hip, pt_walk.h): explicit-order f32 vector helpers, the reference's ray setup and slab
 // test, the build-defined sampling functions of DESIGN.md section 4 and the one-ray traversal of the simple kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -65,7 +65,6 @@ constexpr float kTriEps = 1e-7f;        // renderer.wgsl:178
 constexpr uint32_t kLeaf = 0x80000000u;
 constexpr uint32_t kInvalidRef = 0xFFFFFFFFu;
 constexpr uint32_t kDegenerateRef = 0xFFFFFFFEu;   // child slot whose record the reference fetches and rejects (renderer.wgsl:289-291): counted, never entered
-constexpr int kStackMax = 64;           // renderer.wgsl:8
 
 struct Ray { F3 o, d, inv; };
 
@@ -250,6 +249,76 @@ __device__ __forceinline__ F3 tri_normal_ref(const RenderArgs& A, uint32_t leaf_
 // the one-ray traversal of the simple kernels
 // ------------------------------------------------------------------------------------
 struct Counters { uint32_t nodes, tris, drops, maxstack; };
+
+// the oracle's counters (PtStats order) of a simple kernel, summed over the wavefront first: one atomic per counter and wavefront.
+// `n` items are counted into A.stats[slot_of_n] (0: closest-hit rays and points, 1: any-hit rays).
+__device__ __forceinline__ void add_stats(const RenderArgs& A, int slot_of_n, uint32_t n, const Counters& cnt) {
+    uint32_t nodes = cnt.nodes, tris = cnt.tris, drops = cnt.drops, maxstack = cnt.maxstack;
+    for (int off = 32; off > 0; off >>= 1) {
+        n += __shfl_xor(n, off, 64); nodes += __shfl_xor(nodes, off, 64); tris += __shfl_xor(tris, off, 64);
+        drops += __shfl_xor(drops, off, 64); maxstack = max(maxstack, (uint32_t)__shfl_xor(maxstack, off, 64));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        atomicAdd(&A.stats[slot_of_n], (unsigned long long)n);
+        atomicAdd(&A.stats[2], (unsigned long long)nodes);
+        atomicAdd(&A.stats[3], (unsigned long long)tris);
+        atomicAdd(&A.stats[4], (unsigned long long)drops);
+        atomicMax(&A.stats[5], (unsigned long long)maxstack);
+    }
+}
+
+// Branch-free Moller-Trumbore (renderer.wgsl:185-205) on a fetched triangle record (three axis-major pieces: v0[a], e1[a], e2[a]): the
+// operations and comparisons of traverse(), rejections combined at the end.  Returns whether the ray hits the triangle at t > kTriEps; the
+// caller compares t with its `best`.  The all-zero record behind the last triangle (an out-of-range leaf) is rejected: |det| < eps.
+__device__ __forceinline__ bool tri_hit(F3 o, F3 d, const uint4 n0, const uint4 n1, const uint4 n2, float& t) {
+    const F3 v0 = f3(__uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x));
+    const F3 e1 = f3(__uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y));
+    const F3 e2 = f3(__uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z));
+    const F3 pv = cross3(d, e2);
+    const float det = dot3(e1, pv);
+    const bool ok_det = !(fabsf(det) < kTriEps);
+    const float inv_det = 1.0f / det;
+    const F3 sv = o - v0;
+    const float u = inv_det * dot3(sv, pv);
+    const bool ok_u = !((u < 0.0f) | (u > 1.0f));
+    const F3 q = cross3(sv, e1);
+    const float v = inv_det * dot3(d, q);
+    const bool ok_v = !((v < 0.0f) | ((u + v) > 1.0f));
+    t = inv_det * dot3(e2, q);
+    return ok_det & ok_u & ok_v & (t > kTriEps);
+}
+
+// The order in which the visited children (h) of a wide node are walked, by key (t), and the stack-cap rule: they keep slot order, except
+// that the nearest one -- the first minimum in slot order (renderer.wgsl:315-318) -- trades places with the first of them.  The others go
+// onto the stack far -> near (renderer.wgsl:336-342; the slot the nearest child left holds the first one): store(at, ref, key) writes
+// entry `at`, `sp` counts the entries, and a push at kStackMax entries is dropped without a word.  Returns whether `enter`, the nearest
+// child, is walked next: a child is visited and its own push would have fitted.
+// tn0 is what the running minimum holds before the first visited child.  It is never compared (`nslot < 0` comes first), but the constant
+// decides the register allocation of the persistent kernels: kInfT in the ray walks (70 VGPRs; 68 with 0) and 0 in the point walk (60
+// VGPRs; 63 with kInfT) are the values those loops were written with, and the resource tests pin their lines.
+// The helper counts in a local and store() keeps no state of its own on purpose: with `sp` behind the functor's reference the compiler
+// folds the two pushes of a slot into one behind a select, 54 instructions more per persistent kernel (profiles/query_walk_isa.txt).
+// traverse() below and pt_pointquery.hip::walk_point keep their own copy of these lines: on this helper render_rays_kernel compiles to
+// other code (the same file), and its instruction count is held where it is.
+template <class Store>
+__device__ __forceinline__ bool order_children(bool h0, bool h1, bool h2, bool h3, float t0, float t1, float t2, float t3,
+                                               uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, float tn, int& sp, uint32_t& enter, Store store) {
+    bool fits = false;
+    int nslot = -1, fslot = -1, n = sp; float tf = 0.0f; uint32_t rn = kInvalidRef, rf = kInvalidRef;
+    if (h0) { nslot = 0; tn = t0; rn = r0; fslot = 0; tf = t0; rf = r0; }
+    if (h1) { if (nslot < 0 || t1 < tn) { nslot = 1; tn = t1; rn = r1; } if (fslot < 0) { fslot = 1; tf = t1; rf = r1; } }
+    if (h2) { if (nslot < 0 || t2 < tn) { nslot = 2; tn = t2; rn = r2; } if (fslot < 0) { fslot = 2; tf = t2; rf = r2; } }
+    if (h3) { if (nslot < 0 || t3 < tn) { nslot = 3; tn = t3; rn = r3; } if (fslot < 0) { fslot = 3; tf = t3; rf = r3; } }
+    if (nslot >= 0) {
+        auto push = [&](uint32_t ref, float key) __attribute__((always_inline)) { if (n < kStackMax) { store(n, ref, key); ++n; } };
+        if (h3) { if (nslot == 3) { if (fslot != 3) push(rf, tf); } else if (fslot != 3) push(r3, t3); }
+        if (h2) { if (nslot == 2) { if (fslot != 2) push(rf, tf); } else if (fslot != 2) push(r2, t2); }
+        if (h1) { if (nslot == 1) { if (fslot != 1) push(rf, tf); } else if (fslot != 1) push(r1, t1); }
+        fits = n < kStackMax;       // the push of the nearest child would have fitted
+    }
+    sp = n; enter = rn;
+    return fits;
+}
 
 // One-ray BVH4 traversal over the wide layout.  Visit order, tie-breaking and the 64-entry
 // stack cap are those of traverseBVH4Packet (renderer.wgsl:210-346) run with a single active

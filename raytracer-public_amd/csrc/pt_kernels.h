@@ -71,6 +71,7 @@
 
 namespace ptk {
 
+constexpr int kStackMax = 64;            // stack entries of a traversal, in every kernel (renderer.wgsl:8): a push beyond them is dropped
 constexpr uint32_t kWaveTimeWords = 24;  // STATS diagnostics: 64-bit words per wavefront in RenderArgs::wave_times
 #define PT_MAX_BATCH 256    // frames per persistent launch (their per-frame parameters live in a small device array)
 // Per-frame part of the UBO for a batched launch (several consecutive frames traced by one persistent launch).
@@ -197,13 +198,16 @@ hipError_t launch_pack_shares(const float4* compact, uint64_t frame_stride_px, u
                               uint32_t rank, uint32_t count, const uint32_t rect[4], hipStream_t stream);
 hipError_t launch_unpack_frames(const float* gathered, uint64_t rank_stride_floats, uint64_t frame_stride_floats, uint32_t frames, float4* full, uint64_t full_stride_px,
                                 uint32_t width, uint32_t height, uint32_t count, const uint32_t rect[4], uint32_t spp, hipStream_t stream);
+// ---- the persistent walk of the batched queries (pt_walk.h) ----------------------------------
+// What the three queries below share on the launch side: a queue block of kRqQueueWords 64-bit words (zeroed by each launch) and a spill
+// area of 8-byte entries, both the context's, for a grid of one-wavefront workgroups.  The knobs differ per kernel (PT_RQ_*, PT_PQ_*, PT_OC_*).
+constexpr uint32_t kRqQueueWords = 256;
+inline uint32_t walk_grid(int num_cus, uint32_t waves_per_simd) { return (uint32_t)num_cus * 4u * waves_per_simd; }
+inline size_t walk_spill_entries(uint32_t grid, int short_stack) { return (size_t)(kStackMax - short_stack) * grid * 64u; }
 // ---- batched ray queries (pt_rayquery.hip) -------------------------------------------------
 // rays: PtRay[n] (2 x float4 each), hits: PtHit[n] (uint4 each), both 16-byte aligned device memory.  simple or stats: one ray per thread
-// (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel with `grid` wavefronts at most, a queue block of
-// kRqQueueWords 64-bit words (zeroed by the launch) and rayquery_spill_entries(grid) 8-byte spill entries.
-constexpr uint32_t kRqQueueWords = 256;
-uint32_t rayquery_grid(int num_cus);
-size_t rayquery_spill_entries(uint32_t grid);
+// (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel with `grid` wavefronts at most
+// (walk_grid(.., PT_RQ_WAVES_PER_SIMD)), the queue block and walk_spill_entries(grid, PT_RQ_SHORT_STACK) spill entries.
 hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, uint32_t n, bool anyhit, bool simple, bool stats,
                              unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // A.width * A.height PtRay records of the PT_MODE_REFERENCE camera (A.focal, A.aspect, A.cam, A.quat), row-major
@@ -211,20 +215,16 @@ hipError_t launch_camera_rays(const RenderArgs& A, void* rays, hipStream_t strea
 // ---- batched closest-point queries (pt_pointquery.hip) ----------------------------------------
 // points: PtPoint[n] (float4 each), out: PtClosest[n] (uint4 each), both 16-byte aligned device memory.  brute: every triangle in index
 // order; simple or stats: one point per thread (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel
-// with `grid` wavefronts at most, a queue block of kRqQueueWords 64-bit words (zeroed by the launch) and pointquery_spill_entries(grid)
-// 8-byte spill entries.
-uint32_t pointquery_grid(int num_cus);
-size_t pointquery_spill_entries(uint32_t grid);
+// with `grid` wavefronts at most (walk_grid(.., PT_PQ_WAVES_PER_SIMD)), the queue block and walk_spill_entries(grid, PT_PQ_SHORT_STACK)
+// spill entries.
 hipError_t launch_closest_points(const RenderArgs& A, const void* points, void* out, uint32_t n, bool simple, bool stats, bool brute,
                                  unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- batched ambient-occlusion queries (pt_occlusion.hip) -------------------------------------
 // surfels: PtSurfel[n] (2 x float4 each), out: PtOcclusion[n] (uint4 each), 16-byte aligned device memory; n * samples <= 2^32 - 1.  The launch
 // zeroes `out`, counts the unoccluded samples of every traced surfel into word 1 of its record and completes the records in a finishing
 // kernel.  simple or stats: one sample ray per thread (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent
-// kernel with `grid` wavefronts at most, a queue block of kRqQueueWords 64-bit words (zeroed by the launch) and
-// occlusion_spill_entries(grid) 8-byte spill entries.
-uint32_t occlusion_grid(int num_cus);
-size_t occlusion_spill_entries(uint32_t grid);
+// kernel with `grid` wavefronts at most (walk_grid(.., PT_OC_WAVES_PER_SIMD)), the queue block and
+// walk_spill_entries(grid, PT_OC_SHORT_STACK) spill entries.
 hipError_t launch_occlusion(const RenderArgs& A, const void* surfels, void* out, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias,
                             bool simple, bool stats, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // the n * samples sample rays as PtRay records (item i * samples + s); needs no scene

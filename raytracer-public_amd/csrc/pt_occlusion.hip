@@ -10,8 +10,8 @@
 //
 // Item i * samples + s is sample ray s of surfel i.  Its ray is a pure function of the surfel record and (seed, index_base + i, s)
 // (sample_ray below), so the persistent kernel, the simple kernel and occlusion_rays_kernel produce the same bits, and a sample is occluded
-// exactly when pt_trace_rays(PT_TRACE_ANY_HIT) reports a hit for the record occlusion_rays_kernel writes: the walk below is the walk of
-// pt_rayquery.hip::trace_rays_kernel<true>, kept as a private copy so that the resource line of that kernel does not depend on this file.
+// exactly when pt_trace_rays(PT_TRACE_ANY_HIT) reports a hit for the record occlusion_rays_kernel writes: occlusion_kernel and
+// pt_rayquery.hip::trace_rays_kernel<true> are the same walk (pt_walk.h::persistent_walk) and the same tests (pt_device.h).
 // Records: PtSurfel = two float4 (p.xyz, r_max | n.xyz, reserved), PtOcclusion = one uint4 (visibility bits, unoccluded, samples, 0).
 // The counter of surfel i is word 1 of its output record: zeroed by the launch, incremented by vector atomics, completed by the finish kernel.
 #include <hip/hip_runtime.h>
@@ -20,13 +20,9 @@
 
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_walk.h"
 
 namespace ptk {
-
-constexpr int kOcShort = PT_OC_SHORT_STACK;     // LDS stack entries per lane; entries from this depth on live in the spill area
-constexpr uint32_t kOcChunk = 64;               // items per queue claim: one per lane of the claiming wavefront
-constexpr uint32_t kOcXcds = 8;                 // chunk ranges with a queue counter each (MI355X: 8 XCDs)
-constexpr uint32_t kOcQueueStride = 32;         // counters 256 bytes apart
 
 struct Surfel { F3 p, n; float r_max; };
 __device__ __forceinline__ Surfel load_surfel(const float4* __restrict__ surfels, uint32_t i) {
@@ -89,161 +85,59 @@ __global__ __launch_bounds__(256) void occlusion_simple_kernel(const RenderArgs 
         }
     }
     count_misses(out, miss, sid, threadIdx.x & 63u);
-    if (STATS) {      // the oracle's counters (PtStats order), summed over the wavefront first: one atomic per counter and wavefront
-        uint32_t nodes = cnt.nodes, tris = cnt.tris, drops = cnt.drops, maxstack = cnt.maxstack;
-        for (int off = 32; off > 0; off >>= 1) {
-            n_rays += __shfl_xor(n_rays, off, 64); nodes += __shfl_xor(nodes, off, 64); tris += __shfl_xor(tris, off, 64);
-            drops += __shfl_xor(drops, off, 64); maxstack = max(maxstack, (uint32_t)__shfl_xor(maxstack, off, 64));
-        }
-        if ((threadIdx.x & 63u) == 0u) {
-            atomicAdd(&A.stats[1], (unsigned long long)n_rays);
-            atomicAdd(&A.stats[2], (unsigned long long)nodes);
-            atomicAdd(&A.stats[3], (unsigned long long)tris);
-            atomicAdd(&A.stats[4], (unsigned long long)drops);
-            atomicMax(&A.stats[5], (unsigned long long)maxstack);
-        }
-    }
+    if (STATS) add_stats(A, 1, n_rays, cnt);
 }
 
 // ------------------------------------------------------------------------------------
 // persistent kernel: one wavefront per workgroup, one sample ray per lane, lanes refilled from the wavefront's chunk
 // ------------------------------------------------------------------------------------
-// Queue, chunks, refill, the 64 B step, the stack (entries 0 .. kOcShort-1 in LDS, one column per lane; deeper entries in the spill area at
-// [entry - kOcShort][grid lane]) and the end of the wavefront are those of trace_rays_kernel<true> (pt_rayquery.hip); what differs is where
-// a ray comes from (32 bytes of surfel instead of 32 bytes of ray: no ray record is ever written) and where it goes (a count instead of a
-// 16-byte hit record).  A lane keeps neither the hit triangle nor the ray's number: only the surfel id it counts for.
+// persistent_walk's Q (pt_walk.h) of a sample ray: RayWalk<true> of pt_rayquery.hip, except where a ray comes from (32 bytes of surfel
+// instead of 32 bytes of ray: no ray record is ever written) and where it goes (a count instead of a 16-byte hit record).  A lane keeps
+// neither the hit triangle nor the ray's number: only the surfel id it counts for.  The counting is wave-wide (count_misses), so it sits
+// in the two hooks: behind a hand-out for the rays that end where they start, behind a step for those that ended in it without a hit.
+struct OcclusionWalk {
+    static constexpr bool kWaveHooks = true;
+    static constexpr float kKeyInit = kInfT;      // pt_device.h::order_children
+    const float4* __restrict__ surfels; uint4* __restrict__ out;
+    uint32_t samples, samples_magic, seed, index_base; float bias;
+    uint32_t sid = 0; float best = 0.0f;
+    bool miss = false;          // this lane's new ray ends where it starts: it is not walked, or it misses the root box
+    bool occluded = false;      // this lane's ray ended in this step at a hit
+    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
+
+    __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
+        uint32_t s; divmod_magic(item, samples, samples_magic, sid, s);
+        const Surfel sf = load_surfel(surfels, sid);
+        if (!surfel_traced(sf)) return false;
+        sample_ray(sf, seed, index_base + sid, s, bias, o, d);
+        best = wmin(sf.r_max, kInfT);
+        inv = safe_inv(d); sel = ray_selectors(inv);
+        Ray r; r.o = o; r.d = d; r.inv = inv;
+        float troot;
+        if (scene_ok && ray_walks(o, d) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) return true;
+        miss = true;
+        return false;
+    }
+    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& tmin) const { return lane_of(slab_sel(o, inv, sel, w0, w1, w2, best, tmin)); }
+    __device__ __forceinline__ bool leaf(uint32_t, const uint4 n0, const uint4 n1, const uint4 n2) {
+        float t;
+        if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) occluded = true;      // any hit ends the ray
+        return occluded;
+    }
+    __device__ __forceinline__ float bound() const { return best; }      // `best` never moves (the first hit ends the ray)
+    __device__ __forceinline__ void finish(const RenderArgs&) {}
+    __device__ __forceinline__ void after_refill(uint32_t lane) { count_misses(out, miss, sid, lane); miss = false; }
+    // the lanes whose ray ended in this step without a hit, combined per surfel
+    __device__ __forceinline__ void after_step(bool done, uint32_t lane) {
+        if (__ballot(done) != 0ull) count_misses(out, done && !occluded, sid, lane);
+        occluded = false;
+    }
+};
 __global__ __launch_bounds__(64) void occlusion_kernel(const RenderArgs A, const float4* __restrict__ surfels, uint4* __restrict__ out, uint32_t items,
                                                        uint32_t samples, uint32_t samples_magic, uint32_t seed, uint32_t index_base, float bias,
                                                        unsigned long long* __restrict__ queue, unsigned long long* __restrict__ spill, uint32_t fill) {
-    __shared__ unsigned long long lds_stack[kOcShort][64];
-    const uint32_t lane = threadIdx.x;
-    unsigned long long* const stk = &lds_stack[0][lane];
-    const size_t grid_lanes = (size_t)gridDim.x * 64u, my_lane = (size_t)blockIdx.x * 64u + lane;
-    const bool scene_ok = !(A.root_ref == kInvalidRef || A.num_tris == 0u || A.root_degenerate != 0u);
-
-    const uint32_t chunks = (uint32_t)(((unsigned long long)items + kOcChunk - 1u) / kOcChunk), per_xcd = (chunks + kOcXcds - 1u) / kOcXcds;
-    uint32_t xcd = (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & (kOcXcds - 1u), hops = 0;      // HW_REG_XCC_ID
-    unsigned long long ahead = 0;                         // lane 0: the claimed next chunk of range `xcd` (read where it is used)
-    if (lane == 0u) ahead = atomicAdd(&queue[xcd * kOcQueueStride], 1ull);
-    uint32_t next = 0, end = 0; bool dry = false;
-    bool trav = false;                                    // this lane traverses a ray
-    uint32_t sid = 0, cur = 0; int sp = 0; float best = 0.0f;
-    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
-
-    for (;;) {
-        unsigned long long idle = __ballot(!trav);
-        if (idle == ~0ull || (uint32_t)__popcll(idle) >= fill) {
-            while (idle != 0ull && !dry) {
-                if (next == end) {
-                    unsigned long long c = __shfl(ahead, 0, 64);
-                    auto used_up = [&](uint32_t x, unsigned long long k) __attribute__((always_inline)) {
-                        return (unsigned long long)x * per_xcd + k >= min((x + 1u) * per_xcd, chunks);
-                    };
-                    while (used_up(xcd, c)) {
-                        if (++hops >= kOcXcds) { dry = true; break; }
-                        xcd = (xcd + 1u) & (kOcXcds - 1u);
-                        // a plain read first: a range that is used up costs no claim (every wavefront looks at every range once at the end)
-                        unsigned long long seen = 0;
-                        if (lane == 0u) seen = __hip_atomic_load(&queue[xcd * kOcQueueStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        c = __shfl(seen, 0, 64);
-                        if (used_up(xcd, c)) continue;
-                        if (lane == 0u) ahead = atomicAdd(&queue[xcd * kOcQueueStride], 1ull);
-                        c = __shfl(ahead, 0, 64);
-                    }
-                    if (dry) break;
-                    if (lane == 0u) ahead = atomicAdd(&queue[xcd * kOcQueueStride], 1ull);
-                    const uint32_t chunk = xcd * per_xcd + (uint32_t)c;
-                    next = chunk * kOcChunk; end = (uint32_t)min((unsigned long long)next + kOcChunk, (unsigned long long)items);
-                }
-                const uint32_t take = min((uint32_t)__popcll(idle), end - next);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                bool miss = false;                        // this lane's new ray ends here: it is not walked, or it misses the root box
-                if (!trav && rank < take) {
-                    uint32_t s; divmod_magic(next + rank, samples, samples_magic, sid, s);
-                    const Surfel sf = load_surfel(surfels, sid);
-                    if (surfel_traced(sf)) {
-                        sample_ray(sf, seed, index_base + sid, s, bias, o, d);
-                        best = wmin(sf.r_max, kInfT); sp = 0;
-                        inv = safe_inv(d); sel = ray_selectors(inv);
-                        Ray r; r.o = o; r.d = d; r.inv = inv;
-                        float troot;
-                        if (scene_ok && ray_walks(o, d) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) { cur = A.root_ref; trav = true; }
-                        else miss = true;
-                    }
-                }
-                count_misses(out, miss, sid, lane);
-                next += take;
-                idle = __ballot(!trav);
-            }
-            if (idle == ~0ull) break;                     // the queue is dry and nothing traverses
-        }
-        bool need_pop = true, done = false, occluded = false;
-        if (trav) {
-            const uint4* np = arena_record(A, cur);
-            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-            if (cur & kLeaf) {
-                // branch-free Moller-Trumbore (renderer.wgsl:185-205): the operations and comparisons of traverse(), rejections combined at
-                // the end.  A leaf whose triangle index is out of range points at the all-zero record behind the last triangle: |det| < eps.
-                const F3 v0 = f3(__uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x));
-                const F3 e1 = f3(__uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y));
-                const F3 e2 = f3(__uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z));
-                const F3 pv = cross3(d, e2);
-                const float det = dot3(e1, pv);
-                const bool ok_det = !(fabsf(det) < kTriEps);
-                const float inv_det = 1.0f / det;
-                const F3 sv = o - v0;
-                const float u = inv_det * dot3(sv, pv);
-                const bool ok_u = !((u < 0.0f) | (u > 1.0f));
-                const F3 q = cross3(sv, e1);
-                const float v = inv_det * dot3(d, q);
-                const bool ok_v = !((v < 0.0f) | ((u + v) > 1.0f));
-                const float t = inv_det * dot3(e2, q);
-                if (ok_det & ok_u & ok_v & (t > kTriEps) & (t < best)) { done = true; occluded = true; }    // any hit ends the ray
-            } else {
-                // child-major record (pt_host.h::WideNode): piece k = child k's box words + its reference
-                const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
-                float t0, t1, t2, t3;
-                const bool h0 = lane_of(slab_sel(o, inv, sel, n0.x, n0.y, n0.z, best, t0));
-                const bool h1 = lane_of(slab_sel(o, inv, sel, n1.x, n1.y, n1.z, best, t1));
-                const bool h2 = lane_of(slab_sel(o, inv, sel, n2.x, n2.y, n2.z, best, t2));
-                const bool h3 = lane_of(slab_sel(o, inv, sel, n3.x, n3.y, n3.z, best, t3));
-                // nearest = first minimum in slot order (renderer.wgsl:315-318); first = first hit -- as traverse()
-                int nslot = -1, fslot = -1; float tn = kInfT, tf = 0.0f; uint32_t rn = kInvalidRef, rf = kInvalidRef;
-                if (h0) { nslot = 0; tn = t0; rn = r0; fslot = 0; tf = t0; rf = r0; }
-                if (h1) { if (nslot < 0 || t1 < tn) { nslot = 1; tn = t1; rn = r1; } if (fslot < 0) { fslot = 1; tf = t1; rf = r1; } }
-                if (h2) { if (nslot < 0 || t2 < tn) { nslot = 2; tn = t2; rn = r2; } if (fslot < 0) { fslot = 2; tf = t2; rf = r2; } }
-                if (h3) { if (nslot < 0 || t3 < tn) { nslot = 3; tn = t3; rn = r3; } if (fslot < 0) { fslot = 3; tf = t3; rf = r3; } }
-                if (nslot >= 0) {
-                    // pushes far -> near (renderer.wgsl:336-342); the slot the nearest child left holds the first hit; a push at 64 entries is dropped
-                    auto push = [&](uint32_t ref, float tmin) __attribute__((always_inline)) {
-                        if (sp < kStackMax) {
-                            const unsigned long long e = ((unsigned long long)__float_as_uint(tmin) << 32) | ref;
-                            if (__builtin_expect(sp < kOcShort, 1)) stk[sp * 64] = e;
-                            else spill[(size_t)(sp - kOcShort) * grid_lanes + my_lane] = e;
-                            ++sp;
-                        }
-                    };
-                    if (h3) { if (nslot == 3) { if (fslot != 3) push(rf, tf); } else if (fslot != 3) push(r3, t3); }
-                    if (h2) { if (nslot == 2) { if (fslot != 2) push(rf, tf); } else if (fslot != 2) push(r2, t2); }
-                    if (h1) { if (nslot == 1) { if (fslot != 1) push(rf, tf); } else if (fslot != 1) push(r1, t1); }
-                    if (sp < kStackMax) { cur = rn; need_pop = false; }       // the push of the nearest child would have fitted
-                }
-            }
-            if (need_pop && !done) {
-                // entries whose box the ray no longer reaches (tmin >= best) are skipped; `best` never moves here (the first hit ends the ray)
-                bool found = false;
-                while (sp > 0) {
-                    --sp;
-                    const unsigned long long e = sp < kOcShort ? stk[sp * 64] : spill[(size_t)(sp - kOcShort) * grid_lanes + my_lane];
-                    if (__uint_as_float((uint32_t)(e >> 32)) < best) { cur = (uint32_t)e; found = true; break; }
-                }
-                done = !found;
-            }
-            if (done) trav = false;
-        }
-        // the lanes whose ray ended in this step without a hit, combined per surfel
-        if (__ballot(done) != 0ull) count_misses(out, done && !occluded, sid, lane);
-    }
+    OcclusionWalk q{surfels, out, samples, samples_magic, seed, index_base, bias};
+    persistent_walk<PT_OC_SHORT_STACK>(A, items, queue, spill, fill, q);
 }
 
 // one thread per surfel: the record around the count
@@ -289,10 +183,6 @@ __global__ __launch_bounds__(256) void hit_surfels_kernel(const RenderArgs A, co
     surfels[(size_t)i * 2 + 1] = make_float4(nf.x, nf.y, nf.z, 0.0f);
 }
 
-static_assert(kRqQueueWords == kOcXcds * kOcQueueStride, "pt_kernels.h: the queue block holds one counter line per range");
-uint32_t occlusion_grid(int num_cus) { return (uint32_t)num_cus * 4u * PT_OC_WAVES_PER_SIMD; }
-size_t occlusion_spill_entries(uint32_t grid) { return (size_t)(kStackMax - kOcShort) * grid * 64u; }
-
 // floor(2^32 / d), saturated for d = 1 (divmod_magic's one correction covers the difference)
 static uint32_t magic_of(uint32_t d) { return (uint32_t)std::min<unsigned long long>((1ull << 32) / d, 0xFFFFFFFFull); }
 
@@ -308,11 +198,9 @@ hipError_t launch_occlusion(const RenderArgs& A, const void* surfels, void* out,
         if (stats) occlusion_simple_kernel<true><<<g, 256, 0, stream>>>(A, sf, o, items, samples, magic, seed, index_base, bias);
         else occlusion_simple_kernel<false><<<g, 256, 0, stream>>>(A, sf, o, items, samples, magic, seed, index_base, bias);
     } else {
-        e = hipMemsetAsync(queue, 0, kRqQueueWords * sizeof(unsigned long long), stream);
+        e = walk_begin(queue, items, grid, stream);
         if (e != hipSuccess) return e;
-        // no more wavefronts than there are chunks: the rest would only find the queue dry
-        const uint32_t g = (uint32_t)min((unsigned long long)grid, ((unsigned long long)items + kOcChunk - 1u) / kOcChunk);
-        occlusion_kernel<<<g, 64, 0, stream>>>(A, sf, o, items, samples, magic, seed, index_base, bias, queue, spill, PT_OC_FILL);
+        occlusion_kernel<<<grid, 64, 0, stream>>>(A, sf, o, items, samples, magic, seed, index_base, bias, queue, spill, PT_OC_FILL);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;

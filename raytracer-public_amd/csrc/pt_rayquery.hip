@@ -12,13 +12,9 @@
 
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_walk.h"
 
 namespace ptk {
-
-constexpr int kRqShort = PT_RQ_SHORT_STACK;     // LDS stack entries per lane; entries from this depth on live in the spill area
-constexpr uint32_t kRqChunk = 64;               // rays per queue claim: one per lane of the claiming wavefront
-constexpr uint32_t kRqXcds = 8;                 // chunk ranges with a queue counter each (MI355X: 8 XCDs)
-constexpr uint32_t kRqQueueStride = 32;         // counters 256 bytes apart
 
 __device__ __forceinline__ void load_ray(const float4* __restrict__ rays, uint32_t i, F3& o, F3& d, float& tmax) {
     const float4 a = rays[(size_t)i * 2], b = rays[(size_t)i * 2 + 1];
@@ -68,168 +64,50 @@ __global__ __launch_bounds__(256) void trace_rays_simple_kernel(const RenderArgs
         }
         hits[i] = hit_record(A, o, d, t, tri);
     }
-    if (STATS) {      // the oracle's counters (PtStats order), summed over the wavefront first: one atomic per counter and wavefront
-        uint32_t nodes = cnt.nodes, tris = cnt.tris, drops = cnt.drops, maxstack = cnt.maxstack;
-        for (int off = 32; off > 0; off >>= 1) {
-            n_rays += __shfl_xor(n_rays, off, 64); nodes += __shfl_xor(nodes, off, 64); tris += __shfl_xor(tris, off, 64);
-            drops += __shfl_xor(drops, off, 64); maxstack = max(maxstack, (uint32_t)__shfl_xor(maxstack, off, 64));
-        }
-        if ((threadIdx.x & 63u) == 0u) {
-            atomicAdd(&A.stats[ANYHIT ? 1 : 0], (unsigned long long)n_rays);
-            atomicAdd(&A.stats[2], (unsigned long long)nodes);
-            atomicAdd(&A.stats[3], (unsigned long long)tris);
-            atomicAdd(&A.stats[4], (unsigned long long)drops);
-            atomicMax(&A.stats[5], (unsigned long long)maxstack);
-        }
-    }
+    if (STATS) add_stats(A, ANYHIT ? 1 : 0, n_rays, cnt);
 }
 
 // ------------------------------------------------------------------------------------
 // persistent kernel: one wavefront per workgroup, one ray per lane, lanes refilled from the wavefront's chunk
 // ------------------------------------------------------------------------------------
-// A step is the unified 64 B arena fetch (pt_device.h::arena_record: four child pieces of a wide node, or a triangle record) followed by
-// the box tests of the four children (sign-selected slab, pt_device.h::slab_sel; empty and degenerate slots hold the inverted box and fail
-// by themselves) or a branch-free Moller-Trumbore.  The stack is (tmin bits << 32 | reference): entries 0 .. kRqShort-1 in LDS, one
-// column per lane (bank-conflict free), deeper entries in the spill area at [entry - kRqShort][grid lane].
-// When at least `fill` lanes are idle (or every lane is), the idle lanes take the next rays of the wavefront's chunk, in lane order;
-// a chunk of 64 rays is claimed with one atomic, one chunk ahead, from the range of the wavefront's XCD.  The wavefront ends when every
-// range is used up and no lane traverses.
+// persistent_walk's Q (pt_walk.h) of a ray: the key of a child is tmin of its slab test, `best` starts at min(t_max, kInfT).  A leaf whose
+// triangle index is out of range points at the all-zero record behind the last triangle, which tri_hit rejects.
+template <bool ANYHIT>
+struct RayWalk {
+    static constexpr bool kWaveHooks = false;
+    static constexpr float kKeyInit = kInfT;      // pt_device.h::order_children
+    const float4* __restrict__ rays; uint4* __restrict__ hits;
+    uint32_t rid = 0, btri = kInvalidRef; float best = 0.0f;
+    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
+
+    __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
+        rid = item;
+        float tmax;
+        load_ray(rays, rid, o, d, tmax);
+        best = wmin(tmax, kInfT); btri = kInvalidRef;
+        inv = safe_inv(d); sel = ray_selectors(inv);
+        Ray r; r.o = o; r.d = d; r.inv = inv;
+        float troot;
+        if (scene_ok && ray_traced(o, d, tmax) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) return true;
+        hits[rid] = hit_record(A, o, d, 0.0f, kInvalidRef);
+        return false;
+    }
+    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& tmin) const { return lane_of(slab_sel(o, inv, sel, w0, w1, w2, best, tmin)); }
+    __device__ __forceinline__ bool leaf(uint32_t cur, const uint4 n0, const uint4 n1, const uint4 n2) {
+        float t;
+        if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) { best = t; btri = cur; return ANYHIT; }
+        return false;
+    }
+    __device__ __forceinline__ float bound() const { return best; }      // entries whose box the ray no longer reaches (tmin >= best) are skipped
+    __device__ __forceinline__ void finish(const RenderArgs& A) { hits[rid] = hit_record(A, o, d, best, btri == kInvalidRef ? kInvalidRef : (btri & 0x7fffffffu) >> 2); }
+    __device__ __forceinline__ void after_refill(uint32_t) {}
+    __device__ __forceinline__ void after_step(bool, uint32_t) {}
+};
 template <bool ANYHIT>
 __global__ __launch_bounds__(64) void trace_rays_kernel(const RenderArgs A, const float4* __restrict__ rays, uint4* __restrict__ hits, uint32_t n,
                                                         unsigned long long* __restrict__ queue, unsigned long long* __restrict__ spill, uint32_t fill) {
-    __shared__ unsigned long long lds_stack[kRqShort][64];
-    const uint32_t lane = threadIdx.x;
-    unsigned long long* const stk = &lds_stack[0][lane];
-    const size_t grid_lanes = (size_t)gridDim.x * 64u, my_lane = (size_t)blockIdx.x * 64u + lane;
-    const bool scene_ok = !(A.root_ref == kInvalidRef || A.num_tris == 0u || A.root_degenerate != 0u);
-
-    // wave-uniform: the unhanded rays [next, end) of the current chunk.  The chunks are split into kRqXcds contiguous ranges with a counter
-    // each (on its own 256-byte line): a wavefront claims from the range of the XCD it runs on (HW_REG_XCC_ID) and moves on to the next
-    // range when that one is used up -- one counter for the whole grid serialises the claims (device-scope atomics on one address, about
-    // 20 ns each, measured as a ceiling of ~3.2 G rays/s whatever the rays did).  The next chunk is claimed when a chunk is taken, so that
-    // the atomic's round trip overlaps the chunk's work.
-    const uint32_t chunks = (uint32_t)(((unsigned long long)n + kRqChunk - 1u) / kRqChunk), per_xcd = (chunks + kRqXcds - 1u) / kRqXcds;
-    uint32_t xcd = (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & (kRqXcds - 1u), hops = 0;
-    unsigned long long ahead = 0;                         // lane 0: the claimed next chunk of range `xcd` (read where it is used)
-    if (lane == 0u) ahead = atomicAdd(&queue[xcd * kRqQueueStride], 1ull);
-    uint32_t next = 0, end = 0; bool dry = false;
-    bool trav = false;                                    // this lane traverses a ray
-    uint32_t rid = 0, cur = 0, btri = kInvalidRef; int sp = 0; float best = 0.0f;
-    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
-
-    for (;;) {
-        unsigned long long idle = __ballot(!trav);
-        if (idle == ~0ull || (uint32_t)__popcll(idle) >= fill) {
-            while (idle != 0ull && !dry) {
-                if (next == end) {
-                    unsigned long long c = __shfl(ahead, 0, 64);
-                    auto used_up = [&](uint32_t x, unsigned long long k) __attribute__((always_inline)) {
-                        return (unsigned long long)x * per_xcd + k >= min((x + 1u) * per_xcd, chunks);
-                    };
-                    while (used_up(xcd, c)) {
-                        if (++hops >= kRqXcds) { dry = true; break; }
-                        xcd = (xcd + 1u) & (kRqXcds - 1u);
-                        // a plain read first: a range that is used up costs no claim (every wavefront looks at every range once at the end)
-                        unsigned long long seen = 0;
-                        if (lane == 0u) seen = __hip_atomic_load(&queue[xcd * kRqQueueStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        c = __shfl(seen, 0, 64);
-                        if (used_up(xcd, c)) continue;
-                        if (lane == 0u) ahead = atomicAdd(&queue[xcd * kRqQueueStride], 1ull);
-                        c = __shfl(ahead, 0, 64);
-                    }
-                    if (dry) break;
-                    if (lane == 0u) ahead = atomicAdd(&queue[xcd * kRqQueueStride], 1ull);
-                    const uint32_t chunk = xcd * per_xcd + (uint32_t)c;
-                    next = chunk * kRqChunk; end = (uint32_t)min((unsigned long long)next + kRqChunk, (unsigned long long)n);
-                }
-                const uint32_t take = min((uint32_t)__popcll(idle), end - next);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (!trav && rank < take) {
-                    rid = next + rank;
-                    float tmax;
-                    load_ray(rays, rid, o, d, tmax);
-                    best = wmin(tmax, kInfT); btri = kInvalidRef; sp = 0;
-                    inv = safe_inv(d); sel = ray_selectors(inv);
-                    Ray r; r.o = o; r.d = d; r.inv = inv;
-                    float troot;
-                    if (scene_ok && ray_traced(o, d, tmax) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) { cur = A.root_ref; trav = true; }
-                    else hits[rid] = hit_record(A, o, d, 0.0f, kInvalidRef);
-                }
-                next += take;
-                idle = __ballot(!trav);
-            }
-            if (idle == ~0ull) break;                     // the queue is dry and nothing traverses
-        }
-        if (!trav) continue;
-        const uint4* np = arena_record(A, cur);
-        const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-        bool need_pop = true, done = false;
-        if (cur & kLeaf) {
-            // branch-free Moller-Trumbore (renderer.wgsl:185-205): the operations and comparisons of traverse(), rejections combined at
-            // the end.  A leaf whose triangle index is out of range points at the all-zero record behind the last triangle: |det| < eps.
-            const F3 v0 = f3(__uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x));
-            const F3 e1 = f3(__uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y));
-            const F3 e2 = f3(__uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z));
-            const F3 pv = cross3(d, e2);
-            const float det = dot3(e1, pv);
-            const bool ok_det = !(fabsf(det) < kTriEps);
-            const float inv_det = 1.0f / det;
-            const F3 sv = o - v0;
-            const float u = inv_det * dot3(sv, pv);
-            const bool ok_u = !((u < 0.0f) | (u > 1.0f));
-            const F3 q = cross3(sv, e1);
-            const float v = inv_det * dot3(d, q);
-            const bool ok_v = !((v < 0.0f) | ((u + v) > 1.0f));
-            const float t = inv_det * dot3(e2, q);
-            if (ok_det & ok_u & ok_v & (t > kTriEps) & (t < best)) {
-                best = t; btri = cur;
-                if (ANYHIT) done = true;
-            }
-        } else {
-            // child-major record (pt_host.h::WideNode): piece k = child k's box words + its reference
-            const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
-            float t0, t1, t2, t3;
-            const bool h0 = lane_of(slab_sel(o, inv, sel, n0.x, n0.y, n0.z, best, t0));
-            const bool h1 = lane_of(slab_sel(o, inv, sel, n1.x, n1.y, n1.z, best, t1));
-            const bool h2 = lane_of(slab_sel(o, inv, sel, n2.x, n2.y, n2.z, best, t2));
-            const bool h3 = lane_of(slab_sel(o, inv, sel, n3.x, n3.y, n3.z, best, t3));
-            // nearest = first minimum in slot order (renderer.wgsl:315-318); first = first hit -- as traverse()
-            int nslot = -1, fslot = -1; float tn = kInfT, tf = 0.0f; uint32_t rn = kInvalidRef, rf = kInvalidRef;
-            if (h0) { nslot = 0; tn = t0; rn = r0; fslot = 0; tf = t0; rf = r0; }
-            if (h1) { if (nslot < 0 || t1 < tn) { nslot = 1; tn = t1; rn = r1; } if (fslot < 0) { fslot = 1; tf = t1; rf = r1; } }
-            if (h2) { if (nslot < 0 || t2 < tn) { nslot = 2; tn = t2; rn = r2; } if (fslot < 0) { fslot = 2; tf = t2; rf = r2; } }
-            if (h3) { if (nslot < 0 || t3 < tn) { nslot = 3; tn = t3; rn = r3; } if (fslot < 0) { fslot = 3; tf = t3; rf = r3; } }
-            if (nslot >= 0) {
-                // pushes far -> near (renderer.wgsl:336-342); the slot the nearest child left holds the first hit; a push at 64 entries is dropped
-                auto push = [&](uint32_t ref, float tmin) __attribute__((always_inline)) {
-                    if (sp < kStackMax) {
-                        const unsigned long long e = ((unsigned long long)__float_as_uint(tmin) << 32) | ref;
-                        if (__builtin_expect(sp < kRqShort, 1)) stk[sp * 64] = e;
-                        else spill[(size_t)(sp - kRqShort) * grid_lanes + my_lane] = e;
-                        ++sp;
-                    }
-                };
-                if (h3) { if (nslot == 3) { if (fslot != 3) push(rf, tf); } else if (fslot != 3) push(r3, t3); }
-                if (h2) { if (nslot == 2) { if (fslot != 2) push(rf, tf); } else if (fslot != 2) push(r2, t2); }
-                if (h1) { if (nslot == 1) { if (fslot != 1) push(rf, tf); } else if (fslot != 1) push(r1, t1); }
-                if (sp < kStackMax) { cur = rn; need_pop = false; }       // the push of the nearest child would have fitted
-            }
-        }
-        if (need_pop && !done) {
-            // entries whose box the ray no longer reaches (tmin >= best) are skipped
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                const unsigned long long e = sp < kRqShort ? stk[sp * 64] : spill[(size_t)(sp - kRqShort) * grid_lanes + my_lane];
-                if (__uint_as_float((uint32_t)(e >> 32)) < best) { cur = (uint32_t)e; found = true; break; }
-            }
-            done = !found;
-        }
-        if (done) {
-            hits[rid] = hit_record(A, o, d, best, btri == kInvalidRef ? kInvalidRef : (btri & 0x7fffffffu) >> 2);
-            trav = false;
-        }
-    }
+    RayWalk<ANYHIT> q{rays, hits};
+    persistent_walk<PT_RQ_SHORT_STACK>(A, n, queue, spill, fill, q);
 }
 
 // the camera rays of PT_MODE_REFERENCE: one through each pixel centre (renderer.wgsl:387-395), row-major, t_max = +inf
@@ -241,10 +119,6 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const RenderArgs A, fl
     rays[(size_t)i * 2] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(0x7F800000u));
     rays[(size_t)i * 2 + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
 }
-
-static_assert(kRqQueueWords == kRqXcds * kRqQueueStride, "pt_kernels.h: the queue block holds one counter line per range");
-uint32_t rayquery_grid(int num_cus) { return (uint32_t)num_cus * 4u * PT_RQ_WAVES_PER_SIMD; }
-size_t rayquery_spill_entries(uint32_t grid) { return (size_t)(kStackMax - kRqShort) * grid * 64u; }
 
 hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, uint32_t n, bool anyhit, bool simple, bool stats,
                              unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream) {
@@ -261,12 +135,10 @@ hipError_t launch_trace_rays(const RenderArgs& A, const void* rays, void* hits, 
         }
         return hipGetLastError();
     }
-    hipError_t e = hipMemsetAsync(queue, 0, kRqQueueWords * sizeof(unsigned long long), stream);
+    hipError_t e = walk_begin(queue, n, grid, stream);
     if (e != hipSuccess) return e;
-    // no more wavefronts than there are chunks: the rest would only find the queue dry
-    const uint32_t g = (uint32_t)min((unsigned long long)grid, ((unsigned long long)n + kRqChunk - 1u) / kRqChunk);
-    if (anyhit) trace_rays_kernel<true><<<g, 64, 0, stream>>>(A, r, h, n, queue, spill, PT_RQ_FILL);
-    else trace_rays_kernel<false><<<g, 64, 0, stream>>>(A, r, h, n, queue, spill, PT_RQ_FILL);
+    if (anyhit) trace_rays_kernel<true><<<grid, 64, 0, stream>>>(A, r, h, n, queue, spill, PT_RQ_FILL);
+    else trace_rays_kernel<false><<<grid, 64, 0, stream>>>(A, r, h, n, queue, spill, PT_RQ_FILL);
     return hipGetLastError();
 }
 

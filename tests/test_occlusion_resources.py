@@ -1,27 +1,11 @@
 """What the compiler made of the ambient-occlusion kernels (pt_occlusion.hip), pinned -- compile-only, like test_rayquery_resources.py.
-The kernels of pt_rayquery.hip and the megakernel keep their own lines (test_rayquery_resources.py, test_kernel_resources.py): this file
-adds no kernel to theirs and changes no pt_device.h function they use."""
-import os
-import re
-import shutil
-import subprocess
+occlusion_kernel is the persistent walk that trace_rays_kernel<true> and closest_points_kernel are too (pt_walk.h), instantiated in its own
+translation unit; the kernels of pt_rayquery.hip and the megakernel keep their own lines (test_rayquery_resources.py,
+test_kernel_resources.py), and this file adds no kernel to theirs."""
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "raytracer-public_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
-FIELDS = r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
-
-
-def resources(target):
-    out = subprocess.run(["make", "-s", "-C", CSRC, target], capture_output=True, text=True, timeout=900)
-    text = out.stdout + out.stderr
-    seen = {}
-    for b in re.split(r"remark: Function Name: ", text)[1:]:
-        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+" + FIELDS + r": (\d+)", b)}
-    return seen
+from kres import HIPCC, resources
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc is missing")

@@ -1,26 +1,12 @@
 """What the compiler made of the closest-point kernels (pt_pointquery.hip), pinned -- compile-only, like test_rayquery_resources.py."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "raytracer-public_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
-FIELDS = r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
+from kres import CSRC, HIPCC, resources
+
 WAVES_PER_SIMD = 6          # pt_kernels.h PT_PQ_WAVES_PER_SIMD: what the launch grid of closest_points_kernel assumes
-
-
-def resources(target):
-    out = subprocess.run(["make", "-s", "-C", CSRC, target], capture_output=True, text=True, timeout=900)
-    text = out.stdout + out.stderr
-    seen = {}
-    for b in re.split(r"remark: Function Name: ", text)[1:]:
-        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+" + FIELDS + r": (\d+)", b)}
-    return seen
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc is missing")

@@ -1,26 +1,12 @@
 """What the compiler made of the ray-query kernels (pt_rayquery.hip), pinned -- compile-only, like test_kernel_resources.py -- and the
 C layout of the PtRay / PtHit records those kernels read and write as 16-byte pieces."""
 import os
-import re
 import shutil
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "raytracer-public_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
-FIELDS = r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
-
-
-def resources(target):
-    out = subprocess.run(["make", "-s", "-C", CSRC, target], capture_output=True, text=True, timeout=900)
-    text = out.stdout + out.stderr
-    seen = {}
-    for b in re.split(r"remark: Function Name: ", text)[1:]:
-        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+" + FIELDS + r": (\d+)", b)}
-    return seen
+from kres import HIPCC, ROOT, resources
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc is missing")

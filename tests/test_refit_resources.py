@@ -2,27 +2,14 @@
 sizes of the records those kernels rewrite; and the megakernel's and the ray-query kernel's resource lines, which a new translation
 unit must not move."""
 import os
-import re
 import shutil
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "raytracer-public_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
-FIELDS = r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\])"
+from kres import CSRC, HIPCC, resources
+
 KERNELS = ("refit_prepare4_kernel", "refit4_kernel", "refit_wide_kernel", "refit_prepare2_kernel", "refit2_kernel", "bvh_cost_kernel")
-
-
-def resources(target):
-    out = subprocess.run(["make", "-s", "-C", CSRC, target], capture_output=True, text=True, timeout=900)
-    text = out.stdout + out.stderr
-    seen = {}
-    for b in re.split(r"remark: Function Name: ", text)[1:]:
-        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+" + FIELDS + r": (\d+)", b)}
-    return seen
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc is missing")
