@@ -392,6 +392,67 @@ PT_API int pt_hit_surfels(PtContext* ctx, const void* rays_device, const void* h
 /* The same from host arrays (16-byte aligned): staged; returns when the surfels are written. */
 PT_API int pt_hit_surfels_host(PtContext* ctx, const PtRay* rays, const PtHit* hits, uint64_t n, float r_max, PtSurfel* out);
 
+/* ---- crossing counts, containment and signed distance: how many surfaces does a ray cross, is a point inside? (an extension beyond
+ * the reference) ---------------------------------------------------------------------------------------------
+ * pt_count_hits: for every ray the number of triangle records that the walk reaches and for which the Moller-Trumbore test of the ray
+ *   queries holds (two-sided, t > 1e-7, u and v edges inclusive as they stand) and t < best.  best = min(t_max, 1e30), constant for the
+ *   whole walk: no hit shrinks it and no hit ends the ray.
+ * The walk: the ray queries' walk over the context's CURRENT tree (built at any level, installed, refitted): children tested against
+ *   `best`, visited in the order of the ray queries (first minimum entered, the others pushed far -> near), a stacked entry re-validated
+ *   at pop against `best` (which always passes here), 64 stack entries with a push at the cap dropped (and counted), a leaf with
+ *   t >= num_tris skipped, a degenerate root box: 0.  Spheres (pt_set_spheres) take no part.
+ * Rays with no walk: a NaN in org, dir or t_max, or t_max <= 0: count 0.
+ * Three consequences of the walk being the shared one (tested as equalities):
+ *   1. count >= 1 exactly when pt_trace_rays(PT_TRACE_ANY_HIT) reports a hit for the same record -- always, with stack drops too: `best`
+ *      moves in neither walk, so the any-hit walk is a prefix of the counting walk.
+ *   2. the walk's count never exceeds the brute-force count on a tree whose leaves hold each triangle once.
+ *   3. the two are equal wherever nothing is dropped at the cap and no crossing is lost to an f16 box.
+ * PT_COUNT_BRUTE_FORCE: every triangle in index order, no tree.
+ * PT_COUNT_STATS: the counting variant (one ray per thread) fills pt_get_stats: rays_closest = n, rays_shadow = samples = 0,
+ *   nodes_examined, tris_tested, stack_drops and max_stack by the rules of the ray queries' counters.  With PT_COUNT_BRUTE_FORCE only
+ *   rays_closest and tris_tested are counted.
+ * PT_COUNT_SIMPLE_KERNEL: the one-ray-per-thread kernel instead of the persistent one (A/B checks); the results are the same.
+ * Ordering, errors and alignment: as pt_trace_rays (rays 16-byte aligned, counts 4-byte aligned).  n = 0: PT_OK, nothing is launched.
+ *
+ * pt_contains: crossing parity by majority vote over `samples` rays per point.  Sample ray s of point i is, bit for bit, record
+ *   i * samples + s of pt_occlusion_rays_host for the surfels {p, r_max = +inf, n = (0, 0, 1)} with bias = 0 and the same samples, seed and
+ *   index_base (a cosine-distributed direction around +z; t_max = +inf).  odd = the number of those rays whose pt_count_hits count is odd;
+ *   inside = (2 * odd > samples); samples = params.samples; reserved = 0.  The point's r_max field is ignored.  A point with a NaN in p is
+ *   not traced and yields {0, 0, 0, 0}.
+ *   Meaning: on a closed mesh this is the point-in-solid test.  On an open or self-intersecting mesh it is whatever the parity is;
+ *   odd / samples tells the caller how much the rays disagreed.  No mesh is repaired and no orientation is consulted.
+ *   Arguments: samples odd and in 1..255, n * samples <= 2^32 - 1, known flags, non-NULL params, else PT_ERR_INVALID_ARG; pointers
+ *   16-byte aligned; the scene as for pt_trace_rays.
+ *   PT_CONTAIN_STATS counts like pt_count_hits(PT_COUNT_STATS) over the rays of the traced points (rays_closest = samples * their number).
+ *   PT_CONTAIN_SIMPLE_KERNEL: the one-ray-per-thread kernel instead of the persistent one; the results are the same.
+ *
+ * pt_signed_distance: the PtClosest record of pt_closest_points(flags = 0) with the sign bit of dist set where pt_contains says inside
+ *   (-inf: inside, and nothing within r_max).  Three launches on the context's stream, no host wait: the closest points into out, the
+ *   containment into a buffer of the context, one thread per point for the sign.  params as for pt_contains. */
+typedef struct PtContainment { uint32_t inside; uint32_t odd; uint32_t samples; uint32_t reserved; } PtContainment;   /* 16 B */
+typedef struct PtContainParams { uint32_t samples; uint32_t seed; uint32_t index_base; uint32_t flags; } PtContainParams;
+enum { PT_COUNT_STATS = 1u, PT_COUNT_SIMPLE_KERNEL = 2u, PT_COUNT_BRUTE_FORCE = 4u };
+enum { PT_CONTAIN_STATS = 1u, PT_CONTAIN_SIMPLE_KERNEL = 2u };
+/* n rays from device memory (PtRay[n], 16-byte aligned), n counts into device memory (uint32_t[n], 4-byte aligned).  Asynchronous on
+ * the context's stream (pt_get_stream). */
+PT_API int pt_count_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* counts_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the counts are written. */
+PT_API int pt_count_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts);
+/* Host twin (no context, no GPU): the same counts and, with PT_COUNT_STATS and stats != NULL, the same counters as the device gives for
+ * the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).  bvh4 = NULL (words = 0) only with PT_COUNT_BRUTE_FORCE; a malformed
+ * bvh4: PT_ERR_BAD_BVH; a NULL rays or counts pointer with n > 0, or unknown flags: PT_ERR_INVALID_ARG. */
+PT_API int pt_count_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                              const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts, PtStats* stats);
+/* n points from device memory (PtPoint[n]), n PtContainment records into device memory (both 16-byte aligned).  Asynchronous. */
+PT_API int pt_contains(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device);
+PT_API int pt_contains_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out);
+/* Host twin (no context, no GPU): pt_occlusion_rays_host -> pt_count_hits_bvh4 -> parity -> majority; the same records and counters. */
+PT_API int pt_contains_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                            const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out, PtStats* stats);
+/* n points from device memory, n PtClosest records into device memory (both 16-byte aligned).  Asynchronous, no host wait. */
+PT_API int pt_signed_distance(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device);
+PT_API int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtClosest* out);
+
 /* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
  * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
  * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes

@@ -34,6 +34,8 @@ PT_TRACE_ANY_HIT, PT_TRACE_STATS, PT_TRACE_SIMPLE_KERNEL = 1, 2, 4
 PT_CLOSEST_STATS, PT_CLOSEST_SIMPLE_KERNEL, PT_CLOSEST_BRUTE_FORCE = 1, 2, 4
 # batched ambient-occlusion queries (include/mi355pt.h pt_occlusion)
 PT_OCCLUSION_STATS, PT_OCCLUSION_SIMPLE_KERNEL = 1, 2
+PT_COUNT_STATS, PT_COUNT_SIMPLE_KERNEL, PT_COUNT_BRUTE_FORCE = 1, 2, 4
+PT_CONTAIN_STATS, PT_CONTAIN_SIMPLE_KERNEL = 1, 2
 PRIM_NONE = 0xFFFFFFFF
 
 
@@ -100,6 +102,16 @@ class PtOcclusionParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("index_base", C.c_uint32), ("bias", C.c_float), ("flags", C.c_uint32)]
 
 
+class PtContainment(C.Structure):
+    """include/mi355pt.h PtContainment (16 B): inside = (2 * odd > samples), odd = sample rays with an odd crossing count; all zero for a
+    point that is not traced."""
+    _fields_ = [("inside", C.c_uint32), ("odd", C.c_uint32), ("samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PtContainParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("index_base", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class PtAccumInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
                 ("compact", C.c_uint32), ("samples", C.c_uint32), ("floats", C.c_uint64)]
@@ -117,6 +129,8 @@ EXPORTS = [
     "pt_trace_rays", "pt_trace_rays_host", "pt_camera_rays",
     "pt_closest_points", "pt_closest_points_host", "pt_closest_points_bvh4",
     "pt_occlusion", "pt_occlusion_host", "pt_occlusion_rays", "pt_occlusion_rays_host", "pt_hit_surfels", "pt_hit_surfels_host",
+    "pt_count_hits", "pt_count_hits_host", "pt_count_hits_bvh4", "pt_contains", "pt_contains_host", "pt_contains_bvh4",
+    "pt_signed_distance", "pt_signed_distance_host",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -244,6 +258,29 @@ def _closest_flags(stats, simple, brute_force):
     return (PT_CLOSEST_STATS if stats else 0) | (PT_CLOSEST_SIMPLE_KERNEL if simple else 0) | (PT_CLOSEST_BRUTE_FORCE if brute_force else 0)
 
 
+def _count_flags(stats, simple, brute_force):
+    return (PT_COUNT_STATS if stats else 0) | (PT_COUNT_SIMPLE_KERNEL if simple else 0) | (PT_COUNT_BRUTE_FORCE if brute_force else 0)
+
+
+def _contain_params(samples, seed, index_base, stats=False, simple=False):
+    p = PtContainParams()
+    p.samples, p.seed, p.index_base = int(samples) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF
+    p.flags = (PT_CONTAIN_STATS if stats else 0) | (PT_CONTAIN_SIMPLE_KERNEL if simple else 0)
+    return p
+
+
+def _ray_records(origins, directions, t_max):
+    """(n, 3) origins + directions + t_max, or (n, 8) PtRay records (t_max None: taken from the records) -> aligned (n, 8) float32 records."""
+    if directions is not None:
+        return pack_rays(origins, directions, t_max)
+    rays = np.asarray(origins, np.float32).reshape(-1, 8)
+    if rays.ctypes.data % 16 or not rays.flags.c_contiguous or t_max is not None:
+        r2 = _aligned_zeros(rays.shape, np.float32); r2[...] = rays; rays = r2     # (the caller's records are never written)
+        if t_max is not None:
+            rays[:, 3] = t_max
+    return rays
+
+
 def _check(rc, ctx=None):
     if rc != 0:
         msg = lib.pt_last_error(ctx)
@@ -340,6 +377,45 @@ def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=Fals
                                       out.ctypes.data_as(C.POINTER(PtClosest)), C.byref(st) if stats else None))
     f = out.view(np.float32)
     res = (f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy())
+    return res + (st.as_dict(),) if stats else res
+
+
+def _bvh4_arg(bvh4):
+    if bvh4 is None:
+        return None, None, 0
+    bvh4 = np.ascontiguousarray(bvh4, np.uint32).reshape(-1)
+    return bvh4, _p(bvh4, C.c_uint32), bvh4.size
+
+
+def count_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.count_hits (no GPU): how many triangles of `tris` each ray crosses over the tree set_bvh4(bvh4) installs, with
+    the device's counts.  bvh4 None needs brute_force=True.  Returns the (n,) uint32 counts, and the counters as a dict in second place
+    with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    rays = _ray_records(origins, directions, t_max)
+    n = rays.shape[0]
+    counts = np.zeros(n, np.uint32)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    _check(lib.pt_count_hits_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                  rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(_count_flags(stats, simple, brute_force)),
+                                  _p(counts, C.c_uint32), C.byref(st) if stats else None))
+    return (counts, st.as_dict()) if stats else counts
+
+
+def contains_bvh4(tris, bvh4, points, samples=3, seed=0, index_base=0, stats=False, simple=False):
+    """Host twin of Context.contains (no GPU): (inside, odd, samples) per point, and the counters as a dict in fourth place with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    pts = _point_records(points, None)
+    n = pts.shape[0]
+    out = _aligned_zeros((n, 4), np.uint32)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    p = _contain_params(samples, seed, index_base, stats, simple)
+    _check(lib.pt_contains_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p),
+                                out.ctypes.data_as(C.POINTER(PtContainment)), C.byref(st) if stats else None))
+    res = (out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy())
     return res + (st.as_dict(),) if stats else res
 
 
@@ -889,6 +965,122 @@ class Context:
     def hit_surfels_device(self, rays_ptr, hits_ptr, n, r_max, surfels_ptr):
         """Raw device route of hit_surfels: n PtSurfel records at surfels_ptr, asynchronous on the context's stream."""
         self._ck(lib.pt_hit_surfels(self.h, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), C.c_uint64(n), C.c_float(r_max), C.c_void_p(surfels_ptr)))
+
+    # ---- crossing counts, containment, signed distance (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 17) ----
+    def count_hits(self, origins, directions=None, t_max=None, stats=False, simple=False, brute_force=False):
+        """How many triangles does each ray cross (up to t_max)?  Returns the (n,) uint32 counts.
+
+        origins, directions: (n, 3) float32, or origins alone as (n, 8) PtRay records (directions=None; t_max then comes from the records).
+        numpy arrays take the host route (staged, returns when done).  torch tensors on the context's device take the device route:
+        zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's current stream both ways; the
+        result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle, no tree."""
+        flags = _count_flags(stats, simple, brute_force)
+        if _is_torch(origins):
+            _torch_route()
+            import torch
+            rays = self._ray_tensor(origins, directions, t_max, "count_hits")
+            n = rays.shape[0]
+            counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
+            self._on_context_stream(rays.device, lambda: self.count_hits_device(rays.data_ptr(), n, counts.data_ptr(), flags))
+            return counts.view(torch.uint32)
+        rays = _ray_records(origins, directions, t_max)
+        n = rays.shape[0]
+        counts = np.zeros(n, np.uint32)
+        self._ck(lib.pt_count_hits_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
+        return counts
+
+    def count_hits_device(self, rays_ptr, n, counts_ptr, flags=0):
+        """Raw device route: n PtRay records at rays_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the context's
+        stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_count_hits(self.h, C.c_void_p(rays_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
+
+    def _ray_tensor(self, origins, directions, t_max, what):
+        import torch
+        dev = origins.device
+        if dev.type != "cuda":
+            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
+        if directions is None:
+            rays = origins.reshape(-1, 8)
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.data_ptr() % 16:
+                rays = rays.to(torch.float32).contiguous().clone()
+            if t_max is not None:
+                rays = rays.clone(); rays[:, 3] = t_max
+            return rays
+        o = origins.reshape(-1, 3).to(torch.float32); d = directions.reshape(-1, 3).to(device=dev, dtype=torch.float32)
+        n = o.shape[0]
+        tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if t_max is None else \
+            torch.as_tensor(t_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+        return torch.cat([o, tm, d, torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
+
+    def _point_tensor(self, points, r_max, what):
+        import torch
+        dev = points.device
+        if dev.type != "cuda":
+            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
+        if points.dim() == 2 and points.shape[1] == 4:
+            pts = points
+            if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.data_ptr() % 16:
+                pts = pts.to(torch.float32).contiguous().clone()
+            if r_max is not None:
+                pts = pts.clone(); pts[:, 3] = r_max
+            return pts
+        p = points.reshape(-1, 3).to(torch.float32)
+        n = p.shape[0]
+        rm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if r_max is None else \
+            torch.as_tensor(r_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+        return torch.cat([p, rm], dim=1).contiguous()
+
+    def contains(self, points, samples=3, seed=0, index_base=0, stats=False, simple=False):
+        """Is each point inside the mesh?  Crossing parity by majority vote over `samples` (odd, 1..255) rays per point: returns
+        (inside, odd, samples) as uint32 -- on a closed mesh the point-in-solid test; on an open or self-intersecting mesh whatever the
+        parity is, with odd / samples telling how much the rays disagreed.  All zero for a point with a NaN.
+
+        points: (n, 3) float32 or (n, 4) PtPoint records (r_max is ignored).  numpy takes the host route; torch tensors on the context's
+        device stay there, on the context's stream, with no host synchronisation."""
+        p = _contain_params(samples, seed, index_base, stats, simple)
+        if _is_torch(points):
+            _torch_route()
+            import torch
+            pts = self._point_tensor(points, None, "contains")
+            n = pts.shape[0]
+            out = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
+            self._on_context_stream(pts.device, lambda: self.contains_device(pts.data_ptr(), n, p, out.data_ptr()))
+            o = out.view(torch.uint32)
+            return o[:, 0], o[:, 1], o[:, 2]
+        pts = _point_records(points, None)
+        n = pts.shape[0]
+        out = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_contains_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtContainment))))
+        return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+    def contains_device(self, points_ptr, n, params, out_ptr):
+        """Raw device route: n PtPoint records at points_ptr -> n PtContainment records at out_ptr (16-byte aligned device pointers; params:
+        PtContainParams).  Asynchronous on the context's stream."""
+        self._ck(lib.pt_contains(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.byref(params), C.c_void_p(out_ptr)))
+
+    def signed_distance(self, points, r_max=None, samples=3, seed=0, index_base=0, simple=False):
+        """closest_points with the sign of contains: returns (dist, prim, u, v), dist negative where the point is inside (-inf: inside, and
+        nothing within r_max).  Arguments as closest_points and contains; three launches on the context's stream, no host wait."""
+        p = _contain_params(samples, seed, index_base, False, simple)
+        if _is_torch(points):
+            _torch_route()
+            import torch
+            pts = self._point_tensor(points, r_max, "signed_distance")
+            n = pts.shape[0]
+            out = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
+            self._on_context_stream(pts.device, lambda: self.signed_distance_device(pts.data_ptr(), n, p, out.data_ptr()))
+            of = out.view(torch.float32)
+            return of[:, 0], out.view(torch.uint32)[:, 1], of[:, 2], of[:, 3]
+        pts = _point_records(points, r_max)
+        n = pts.shape[0]
+        out = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_signed_distance_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtClosest))))
+        f = out.view(np.float32)
+        return f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+
+    def signed_distance_device(self, points_ptr, n, params, out_ptr):
+        """Raw device route: n PtPoint records at points_ptr -> n PtClosest records at out_ptr (16-byte aligned; params: PtContainParams)."""
+        self._ck(lib.pt_signed_distance(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.byref(params), C.c_void_p(out_ptr)))
 
     def buffer_busy(self, device_ptr, nbytes):
         b = C.c_int()

@@ -121,6 +121,7 @@ struct PtContext {
     // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
     DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
+    DevBuf<uint4> d_cr_contain;         // pt_signed_distance: the PtContainment records between its containment launch and the sign kernel
 
     // frame
     DevBuf<float4> d_out, d_accum, d_compact, d_compact_accum;
@@ -777,7 +778,7 @@ void pt_destroy(PtContext* ctx) {
     (void)flush_pending(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->d_tris9.release(); ctx->d_scene.release(); ctx->d_bvh2.release(); ctx->d_bvh4.release();
-    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release(); ctx->d_oc_surfels.release();
+    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release(); ctx->d_oc_surfels.release(); ctx->d_cr_contain.release();
     ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
     ctx->d_out.release(); ctx->d_accum.release(); ctx->d_compact.release(); ctx->d_compact_accum.release();
     ctx->d_tiles.release(); ctx->d_u32tmp.release(); ctx->d_stats.release();
@@ -1689,6 +1690,177 @@ int pt_hit_surfels_host(PtContext* ctx, const PtRay* rays, const PtHit* hits, ui
     A.tris = ctx->trirec(); A.num_tris = ctx->num_tris;
     PT_HIP(ctx, ptk::launch_hit_surfels(A, ctx->d_rq_rays.ptr, ctx->d_rq_hits.ptr, uint32_t(n), r_max, ctx->d_oc_surfels.ptr, ctx->stream));
     PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_oc_surfels.ptr, size_t(n) * sizeof(PtSurfel), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+// ---- crossing counts, containment, signed distance (include/mi355pt.h; pt_crossings.hip) ---------------------------------------
+
+static_assert(sizeof(PtContainment) == 16 && sizeof(PtContainParams) == 16, "PtContainment is written as one 16 B record");
+
+namespace {
+constexpr uint32_t kCountFlags = PT_COUNT_STATS | PT_COUNT_SIMPLE_KERNEL | PT_COUNT_BRUTE_FORCE;
+constexpr uint32_t kContainFlags = PT_CONTAIN_STATS | PT_CONTAIN_SIMPLE_KERNEL;
+bool aligned4(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3u) == 0u; }
+
+int check_count(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* counts) {
+    if (flags & ~kCountFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
+    if (!aligned16(rays) || !aligned4(counts)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays must be non-null and 16-byte aligned, counts non-null and 4-byte aligned");
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+// the parameter block and the batch size; the pointers and the scene are checked by the callers (pointers before the scene)
+int check_contain_params(PtContext* ctx, const char* fn, uint64_t n, const PtContainParams* p) {
+    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": null params");
+    if (p->flags & ~kContainFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
+    if (p->samples < 1u || p->samples > 255u || (p->samples & 1u) == 0u) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": samples must be odd and in 1..255");
+    if (n * uint64_t(p->samples) > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 sample rays (n * samples)");
+    return PT_OK;
+}
+int check_contain(PtContext* ctx, const char* fn, const void* points, uint64_t n, const PtContainParams* p, const void* out) {
+    if (int rc = check_contain_params(ctx, fn, n, p)) return rc;
+    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+
+// the launches themselves: device memory, on the context's stream, behind whatever pt_set_batch still holds
+int count_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* counts) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool stats = (flags & PT_COUNT_STATS) != 0, simple = (flags & PT_COUNT_SIMPLE_KERNEL) != 0, brute = (flags & PT_COUNT_BRUTE_FORCE) != 0;
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_CR_WAVES_PER_SIMD);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple && !brute) {
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_CR_SHORT_STACK));
+    }
+    PT_HIP(ctx, ptk::launch_count_hits(A, rays, counts, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+int contains_on_stream(PtContext* ctx, const void* points, uint32_t n, const PtContainParams& p, void* out) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool stats = (p.flags & PT_CONTAIN_STATS) != 0, simple = (p.flags & PT_CONTAIN_SIMPLE_KERNEL) != 0;
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_CR_WAVES_PER_SIMD);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple) {
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_CR_SHORT_STACK));
+    }
+    PT_HIP(ctx, ptk::launch_contains(A, points, out, n, p.samples, p.seed, p.index_base, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+// three launches, no host wait: the closest points into `out`, the containment into the context's buffer, the sign
+int signed_on_stream(PtContext* ctx, const void* points, uint32_t n, const PtContainParams& p, void* out) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    PT_HIP(ctx, ctx->d_cr_contain.ensure(size_t(n)));
+    if (int rc = closest_on_stream(ctx, points, n, 0u, out)) return rc;
+    if (int rc = contains_on_stream(ctx, points, n, p, ctx->d_cr_contain.ptr)) return rc;
+    PT_HIP(ctx, ptk::launch_apply_sign(ctx->d_cr_contain.ptr, out, n, ctx->stream));
+    return PT_OK;
+}
+void stats_from(PtStats* stats, const uint64_t counters[5]) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->rays_closest = counters[0]; stats->nodes_examined = counters[1]; stats->tris_tested = counters[2];
+    stats->stack_drops = counters[3]; stats->max_stack = counters[4];
+}
+} // namespace
+
+int pt_count_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* counts_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_count(ctx, "pt_count_hits", rays_device, n, flags, counts_device)) return rc;
+    return count_on_stream(ctx, rays_device, uint32_t(n), flags, counts_device);
+}
+
+int pt_count_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_count(ctx, "pt_count_hits_host", rays, n, flags, counts)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure((size_t(n) + 3) / 4));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = count_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(counts, ctx->d_rq_hits.ptr, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_count_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                       const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts, PtStats* stats) {
+    if (flags & ~kCountFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: unknown flags");
+    const bool brute = (flags & PT_COUNT_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && (!rays || !counts)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: null pointer");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: more than 2^32 - 1 rays");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::count_hits(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(rays), n, counts,
+                        (flags & PT_COUNT_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
+int pt_contains(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_contain(ctx, "pt_contains", points_device, n, params, out_device)) return rc;
+    return contains_on_stream(ctx, points_device, uint32_t(n), *params, out_device);
+}
+
+int pt_contains_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_contain(ctx, "pt_contains_host", points, n, params, out)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = contains_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtContainment), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_contains_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                     const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out, PtStats* stats) {
+    if (int rc = check_contain_params(nullptr, "pt_contains_bvh4", n, params)) return rc;
+    if ((!tris && num_tris) || (n && (!points || !out)) || !bvh4) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_contains_bvh4: null pointer");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::contains(tris, num_tris, bvh4, words, reinterpret_cast<const float*>(points), n, params->samples, params->seed, params->index_base,
+                      reinterpret_cast<uint32_t*>(out), (params->flags & PT_CONTAIN_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
+int pt_signed_distance(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_contain(ctx, "pt_signed_distance", points_device, n, params, out_device)) return rc;
+    return signed_on_stream(ctx, points_device, uint32_t(n), *params, out_device);
+}
+
+int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtClosest* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_contain(ctx, "pt_signed_distance_host", points, n, params, out)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = signed_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <limits>
 #include <thread>
 
 namespace pt {
@@ -1064,6 +1065,177 @@ void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t
             r[3] = r_max; r[7] = 0.0f;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------
+// Crossing counts and containment (host twin of pt_crossings.hip): the same records, operations, order, cap and counters
+// ------------------------------------------------------------------------------------
+namespace {
+constexpr float kInfT_h = 1e30f, kTriEps_h = 1e-7f;
+struct RayH { float o[3], d[3], inv[3]; };
+
+// pt_device.h::slab: the min / max form of the one-ray kernels (the sign-selected form of the persistent kernels gives the same bits)
+inline bool slab_h(const RayH& r, const uint32_t w[3], float best, float& tmin_out) {
+    const float mn[3] = {half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)};
+    const float mx[3] = {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)};
+    float t1[3], t2[3];
+    for (int k = 0; k < 3; ++k) { t1[k] = (mn[k] - r.o[k]) * r.inv[k]; t2[k] = (mx[k] - r.o[k]) * r.inv[k]; }
+    const float tmin = wmax_h(wmax_h(wmin_h(t1[0], t2[0]), wmin_h(t1[1], t2[1])), wmin_h(t1[2], t2[2]));
+    const float tmax = wmin_h(wmin_h(wmax_h(t1[0], t2[0]), wmax_h(t1[1], t2[1])), wmax_h(t1[2], t2[2]));
+    tmin_out = tmin;
+    return (tmax >= wmax_h(tmin, 0.0f)) && (tmin < best);
+}
+// pt_device.h::tri_hit on a triangle record, operation by operation
+inline bool tri_hit_h(const RayH& r, const TriRecord& rec, float& t) {
+    const float v0[3] = {rec.axis[0][0], rec.axis[1][0], rec.axis[2][0]};
+    const float e1[3] = {rec.axis[0][1], rec.axis[1][1], rec.axis[2][1]};
+    const float e2[3] = {rec.axis[0][2], rec.axis[1][2], rec.axis[2][2]};
+    auto dot = [](const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    auto cross = [](const float a[3], const float b[3], float c[3]) {
+        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    float pv[3]; cross(r.d, e2, pv);
+    const float det = dot(e1, pv);
+    const bool ok_det = !(std::fabs(det) < kTriEps_h);
+    const float inv_det = 1.0f / det;
+    const float sv[3] = {r.o[0] - v0[0], r.o[1] - v0[1], r.o[2] - v0[2]};
+    const float u = inv_det * dot(sv, pv);
+    const bool ok_u = !((u < 0.0f) || (u > 1.0f));
+    float q[3]; cross(sv, e1, q);
+    const float v = inv_det * dot(r.d, q);
+    const bool ok_v = !((v < 0.0f) || ((u + v) > 1.0f));
+    t = inv_det * dot(e2, q);
+    return ok_det && ok_u && ok_v && (t > kTriEps_h);
+}
+
+uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt) {
+    const WideBvh& wb = *W.wide;
+    uint32_t count = 0;
+    if (wb.root_ref == kInvalid || W.num_tris == 0u) return 0u;
+    cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
+    if (wb.root_degenerate) return 0u;
+    float troot;
+    if (!slab_h(r, wb.root_box, best, troot)) return 0u;
+    struct Entry { uint32_t ref; float tmin; } stk[kStackCap];
+    uint32_t cur = wb.root_ref;
+    int sp = 0;
+    for (;;) {
+        bool need_pop = false;
+        if (cur & kLeafFlag) {
+            const uint32_t ti4 = cur & 0x7fffffffu;
+            if (ti4 < 4u * W.num_tris) {
+                cnt.tris += 1;
+                float t;
+                if (tri_hit_h(r, W.rec[ti4 >> 2], t) && t < best) ++count;
+            }
+            need_pop = true;
+        } else {
+            const WideNode& nd = wb.nodes[(cur - W.node_base16) >> 2];
+            float t[4] = {0, 0, 0, 0}; bool h[4]; uint32_t c[4];
+            for (int k = 0; k < 4; ++k) {
+                c[k] = nd.child[k].ref; h[k] = (c[k] < kDegenerate) && slab_h(r, nd.child[k].box, best, t[k]);
+                cnt.nodes += (c[k] != kInvalid);
+            }
+            int nslot = -1, fslot = -1;
+            for (int k = 0; k < 4; ++k) if (h[k]) { if (nslot < 0 || t[k] < t[nslot]) nslot = k; if (fslot < 0) fslot = k; }
+            if (nslot < 0) {
+                need_pop = true;
+            } else {
+                // pushes far -> near; the slot the nearest child left holds the first visited child
+                for (int k = 3; k >= 1; --k) {
+                    if (!h[k] || fslot == k) continue;
+                    const int src = (nslot == k) ? fslot : k;
+                    if (sp < kStackCap) { stk[sp].ref = c[src]; stk[sp].tmin = t[src]; ++sp; } else cnt.drops += 1;
+                }
+                const uint64_t depth = uint64_t(sp) + (sp < kStackCap ? 1u : 0u);
+                if (depth > cnt.maxstack) cnt.maxstack = depth;
+                if (sp < kStackCap) cur = c[nslot];
+                else { need_pop = true; cnt.drops += 1; }
+            }
+        }
+        if (need_pop) {
+            bool found = false;
+            while (sp > 0) {
+                --sp;
+                if (stk[sp].tmin < best) { cur = stk[sp].ref; found = true; break; }      // always passes: `best` never moves
+            }
+            if (!found) break;
+        }
+    }
+    return count;
+}
+} // namespace
+
+bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
+                uint32_t* counts, uint64_t* counters, std::string& err) {
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers);
+    auto run = [&](uint64_t w) {
+        WalkCounters& cnt = per[w];
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            const float* q = rays + i * 8;
+            RayH r;
+            for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
+            const float tmax = q[3];
+            const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
+            uint32_t count = 0;
+            if (!nan && tmax > 0.0f) {
+                const float best = wmin_h(tmax, kInfT_h);
+                if (bvh4) count = walk_count_h(W, r, best, cnt);
+                else {
+                    for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, rec[t], th) && th < best) ++count; }
+                    cnt.tris += num_tris;
+                }
+            }
+            counts[i] = count;
+        }
+    };
+    if (workers == 1) run(0);
+    else {
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+    return true;
+}
+
+bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+              uint32_t samples, uint32_t seed, uint32_t index_base, uint32_t* out, uint64_t* counters, std::string& err) {
+    // the surfels whose sample rays these are: {p, +inf, (0, 0, 1)}; a point with a NaN in p stays untraced (r_max = 0: rays that are not walked)
+    std::vector<float> surfels(size_t(n) * 8), rays(size_t(n) * samples * 8);
+    uint64_t traced = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* p = points + i * 4; float* sf = surfels.data() + i * 8;
+        const bool ok = !(std::isnan(p[0]) || std::isnan(p[1]) || std::isnan(p[2]));
+        sf[0] = p[0]; sf[1] = p[1]; sf[2] = p[2]; sf[3] = ok ? std::numeric_limits<float>::infinity() : 0.0f;
+        sf[4] = 0.0f; sf[5] = 0.0f; sf[6] = 1.0f; sf[7] = 0.0f;
+        traced += ok;
+    }
+    occlusion_rays(surfels.data(), n, samples, seed, index_base, 0.0f, rays.data());
+    std::vector<uint32_t> counts(size_t(n) * samples);
+    if (!count_hits(tris, num_tris, bvh4, words, rays.data(), n * samples, counts.data(), counters, err)) return false;
+    if (counters) counters[0] = traced * samples;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t* o = out + i * 4;
+        if (surfels[i * 8 + 3] == 0.0f) { o[0] = o[1] = o[2] = o[3] = 0u; continue; }
+        uint32_t odd = 0;
+        for (uint32_t s = 0; s < samples; ++s) odd += counts[i * samples + s] & 1u;
+        o[0] = 2u * odd > samples ? 1u : 0u; o[1] = odd; o[2] = samples; o[3] = 0u;
+    }
+    return true;
 }
 
 } // namespace pt

@@ -95,6 +95,17 @@ void build_tri_records(const float* tris, uint32_t n, TriRecord* out);
 bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                     uint32_t* out, uint64_t* counters, std::string& err);
 
+// ---- crossing counts and containment (pt_count_hits, pt_contains; host twin of pt_crossings.hip, bit for bit) --------------------------
+// rays: n x (org, t_max, dir, reserved); counts: n words.  bvh4 = nullptr: every triangle in index order; else the walk of the kernels over
+// build_wide_bvh(bvh4) and build_tri_records(tris): a record is counted when tri_hit holds and t < best = min(t_max, 1e30), which never
+// moves.  counters (optional): rays, nodes examined, triangles tested, stack drops, max stack -- as the device's PT_COUNT_STATS counts them.
+bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
+                uint32_t* counts, uint64_t* counters, std::string& err);
+// points: n x (x, y, z, ignored); out: n x (inside, odd, samples, 0): occlusion_rays of {p, +inf, (0, 0, 1)} with bias 0 -> count_hits ->
+// parity -> majority.  counters[0] = samples * the number of traced points.
+bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+              uint32_t samples, uint32_t seed, uint32_t index_base, uint32_t* out, uint64_t* counters, std::string& err);
+
 // ---- procedural stand-in scenes ---------------------------------------------------
 bool procedural_scene(uint32_t kind, uint32_t seed, uint32_t num_tris, float* out, std::string& err);
 

@@ -65,6 +65,16 @@
 #ifndef PT_OC_FILL
 #define PT_OC_FILL 8                // idle lanes of a wavefront at which they take the next items of its chunk
 #endif
+// crossing counts and containment (pt_crossings.hip): the ray queries' values taken over, not measured for these kernels
+#ifndef PT_CR_SHORT_STACK
+#define PT_CR_SHORT_STACK 12        // LDS stack entries per lane of count_hits_kernel / contains_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_CR_WAVES_PER_SIMD
+#define PT_CR_WAVES_PER_SIMD 6      // wavefronts of count_hits_kernel / contains_kernel per SIMD in the launch grid (what their registers and LDS allow)
+#endif
+#ifndef PT_CR_FILL
+#define PT_CR_FILL 8                // idle lanes of a wavefront at which they take the next items of its chunk
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -231,6 +241,18 @@ hipError_t launch_occlusion(const RenderArgs& A, const void* surfels, void* out,
 hipError_t launch_occlusion_rays(const void* surfels, void* rays, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, hipStream_t stream);
 // PtRay[n] + PtHit[n] -> PtSurfel[n] (A.tris, A.num_tris)
 hipError_t launch_hit_surfels(const RenderArgs& A, const void* rays, const void* hits, uint32_t n, float r_max, void* surfels, hipStream_t stream);
+// ---- crossing counts, containment, signed distance (pt_crossings.hip) ---------------------------
+// rays: PtRay[n] (2 x float4 each, 16-byte aligned), counts: uint32_t[n].  brute: every triangle in index order; simple or stats: one ray
+// per thread (stats: PtStats counters into A.stats, zeroed by the caller); else the persistent kernel with `grid` wavefronts at most
+// (walk_grid(.., PT_CR_WAVES_PER_SIMD)), the queue block and walk_spill_entries(grid, PT_CR_SHORT_STACK) spill entries.
+hipError_t launch_count_hits(const RenderArgs& A, const void* rays, void* counts, uint32_t n, bool simple, bool stats, bool brute,
+                             unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// points: PtPoint[n] (float4 each), out: PtContainment[n] (uint4 each), 16-byte aligned; samples odd, n * samples <= 2^32 - 1.  The launch
+// zeroes `out`, counts the odd sample rays of every traced point into word 1 of its record and completes the records in a finishing kernel.
+hipError_t launch_contains(const RenderArgs& A, const void* points, void* out, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base,
+                           bool simple, bool stats, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// PtClosest[n] in `out` gets the sign bit of dist where PtContainment[n] in `contain` says inside
+hipError_t launch_apply_sign(const void* contain, void* out, uint32_t n, hipStream_t stream);
 // ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
 // What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
 // launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):

@@ -178,6 +178,32 @@ class PathTracer {
     return { found: found, dist: r.dist[0], prim: r.prim[0], u: r.u[0], v: r.v[0], point: point };
   }
 
+  // ---- crossing counts, containment, signed distance: an extension beyond the reference (include/mi355pt.h pt_count_hits, DESIGN.md section 17) ----
+  // rays: Float32Array, 8 floats per ray (origin xyz, tMax, direction xyz, 0).  Resolves to a Uint32Array: how many triangles each ray
+  // crosses before tMax -- every one, not only the first.  options.bruteForce: every triangle, no tree; options.simple: the
+  // one-ray-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
+  async countHits(rays, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
+    return this.group ? native().groupCountHits(this.group, rays, flags) : native().countHits(this.device, rays, flags);
+  }
+  // points: Float32Array, 4 floats per point (x, y, z, ignored).  options: { samples (3; odd, 1..255), seed (0), indexBase (0), simple }.
+  // Resolves to { inside, odd, samples } (Uint32Array): crossing parity by majority vote over `samples` rays per point -- on a closed mesh
+  // the point-in-solid test; on an open or self-intersecting mesh whatever the parity is, odd / samples telling how much the rays disagreed.
+  async contains(points, options) {
+    const o = options || {};
+    return this.group ? native().groupContains(this.group, points, o) : native().contains(this.device, points, o);
+  }
+  // closestPoints with the sign of contains: { dist, prim, u, v }, dist negative inside (-Infinity: inside, and nothing within rMax)
+  async signedDistance(points, options) {
+    const o = options || {};
+    return this.group ? native().groupSignedDistance(this.group, points, o) : native().signedDistance(this.device, points, o);
+  }
+  // Is (x, y, z) inside the mesh?  Resolves to { inside, odd, samples }.
+  async inside(x, y, z, options) {
+    const r = await this.contains(Float32Array.of(x, y, z, Infinity), options);
+    return { inside: r.inside[0] !== 0, odd: r.odd[0], samples: r.samples[0] };
+  }
+
   // ---- batched ambient-occlusion queries: an extension beyond the reference (include/mi355pt.h pt_occlusion, DESIGN.md section 16) ----
   // surfels: Float32Array, 8 floats per surfel (point xyz, rMax, unit normal xyz, 0).  options: { samples (16), seed (0), bias (1e-4),
   // indexBase (0), simple }.  Resolves to { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }: of `samples`

@@ -431,6 +431,94 @@ static napi_value fn_occlusion(napi_env env, napi_callback_info info) {      /* 
     PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
     return occlusion_on(env, ctx, argv[1], argv[2]);
 }
+/* ---- crossing counts, containment, signed distance (an extension beyond the reference; include/mi355pt.h pt_count_hits_host,
+ * pt_contains_host, pt_signed_distance_host) ---------------------------------------------------------------------------------- */
+
+/* rays: Float32Array of 8 floats per ray -> Uint32Array of crossing counts; flags: PT_COUNT_*.  Copied into aligned host memory, as above. */
+static napi_value count_hits_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value flags_v) {
+    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, "countHits: 8 floats per ray"); return NULL; }
+    const uint32_t flags = get_u32(env, flags_v);
+    const size_t n = len / 8;
+    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
+    if (!rays) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(rays, d, n * sizeof(PtRay));
+    void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
+    if (!counts) { free(rays); return NULL; }
+    uint32_t none = 0;
+    int rc = pt_count_hits_host(ctx, rays, n, flags, n ? (uint32_t*)pc : &none);
+    free(rays);
+    if (rc != 0) return throw_pt(env, ctx, rc, "pt_count_hits_host");
+    return counts;
+}
+static void contain_params(napi_env env, napi_value opt, PtContainParams* p) {
+    memset(p, 0, sizeof *p);
+    p->samples = prop_u32(env, opt, "samples", 3); p->seed = prop_u32(env, opt, "seed", 0); p->index_base = prop_u32(env, opt, "indexBase", 0);
+    p->flags = prop_u32(env, opt, "simple", 0) ? PT_CONTAIN_SIMPLE_KERNEL : 0u;
+}
+/* points: Float32Array of 4 floats per point (rMax ignored); opt: { samples (3), seed, indexBase, simple }
+ * -> { inside: Uint32Array, odd: Uint32Array, samples: Uint32Array } */
+static napi_value contains_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value opt) {
+    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 4) { napi_throw_range_error(env, NULL, "contains: 4 floats per point"); return NULL; }
+    PtContainParams p; contain_params(env, opt, &p);
+    const size_t n = len / 4;
+    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
+    PtContainment* res = (PtContainment*)aligned_alloc(16, (n ? n : 1) * sizeof(PtContainment));
+    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(pts, d, n * sizeof(PtPoint));
+    int rc = pt_contains_host(ctx, pts, n, &p, res);
+    free(pts);
+    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_contains_host"); }
+    napi_value o, in, od, sm; void *pi, *po, *ps;
+    if (!(in = make_typed(env, napi_uint32_array, 4, n, &pi)) || !(od = make_typed(env, napi_uint32_array, 4, n, &po)) ||
+        !(sm = make_typed(env, napi_uint32_array, 4, n, &ps))) { free(res); return NULL; }
+    for (size_t i = 0; i < n; ++i) { ((uint32_t*)pi)[i] = res[i].inside; ((uint32_t*)po)[i] = res[i].odd; ((uint32_t*)ps)[i] = res[i].samples; }
+    free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "inside", in); napi_set_named_property(env, o, "odd", od); napi_set_named_property(env, o, "samples", sm);
+    return o;
+}
+/* points: Float32Array of 4 floats per point (x, y, z, rMax); opt as contains -> { dist, prim, u, v }, dist negative inside */
+static napi_value signed_distance_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value opt) {
+    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 4) { napi_throw_range_error(env, NULL, "signedDistance: 4 floats per point"); return NULL; }
+    PtContainParams p; contain_params(env, opt, &p);
+    const size_t n = len / 4;
+    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
+    PtClosest* res = (PtClosest*)aligned_alloc(16, (n ? n : 1) * sizeof(PtClosest));
+    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(pts, d, n * sizeof(PtPoint));
+    int rc = pt_signed_distance_host(ctx, pts, n, &p, res);
+    free(pts);
+    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_signed_distance_host"); }
+    napi_value o, dist, prim, u, v; void *pd, *pp, *pu, *pv;
+    if (!(dist = make_typed(env, napi_float32_array, 4, n, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
+        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(res); return NULL; }
+    for (size_t i = 0; i < n; ++i) {
+        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
+    }
+    free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_count_hits(napi_env env, napi_callback_info info) {          /* (ctx, Float32Array rays, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return count_hits_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_contains(napi_env env, napi_callback_info info) {            /* (ctx, Float32Array points, options) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return contains_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_signed_distance(napi_env env, napi_callback_info info) {     /* (ctx, Float32Array points, options) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return signed_distance_on(env, ctx, argv[1], argv[2]);
+}
 /* rays: Float32Array (8 floats per ray); t, prim, u, v: what traceRays resolved to; rMax -> Float32Array of 8 floats per surfel */
 static napi_value hit_surfels_on(napi_env env, PtContext* ctx, napi_value* a) {
     void *d, *pt, *pp, *pu, *pv; size_t len, nt, np, nu, nv;
@@ -683,6 +771,24 @@ static napi_value fn_group_occlusion(napi_env env, napi_callback_info info) {   
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return occlusion_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_count_hits(napi_env env, napi_callback_info info) {      /* (group, rays, flags): on member 0, which holds the whole scene */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return count_hits_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_group_contains(napi_env env, napi_callback_info info) {        /* (group, points, options): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return contains_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_group_signed_distance(napi_env env, napi_callback_info info) { /* (group, points, options): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return signed_distance_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_hit_surfels(napi_env env, napi_callback_info info) {     /* (group, rays, t, prim, u, v, rMax): on member 0 */
     napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -747,6 +853,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
         {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
         {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
+        {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
+        {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
         {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
