@@ -453,6 +453,67 @@ PT_API int pt_contains_bvh4(const float* tris, uint32_t num_tris, const uint32_t
 PT_API int pt_signed_distance(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device);
 PT_API int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtClosest* out);
 
+/* ---- radius queries: which triangles lie within r of a point -- all of them, each with its contact point? (an extension beyond the
+ * reference) ----------------------------------------------------------------------------------------------
+ * For every point the walk of pt_closest_points runs over the context's CURRENT tree with best2 held constant at r2, and every triangle it
+ * reaches with d2 < r2 is counted (pt_radius_count) and listed (pt_radius_search).  Every result is an integer or a bit pattern.
+ * Walked points: a point is walked iff p and r_max hold no NaN and r_max > 0 (ptcp::point_walked, as pt_closest_points); otherwise its
+ *   count is 0 and its list is empty.
+ * r2 = r_max * r_max in f32 (+inf stays +inf), constant for the whole walk.
+ * Accepted leaves: a reached leaf with tri < num_tris is accepted iff d2 < r2, strictly; d2 by the point-triangle arithmetic of
+ *   pt_closest_points (csrc/pt_closest.h: closest_uv, then closest_d2) on the triangle record as stored.  A NaN d2 is never accepted.
+ * The walk: pt_closest_points' with best2 replaced by r2 -- bound2 with the same slack s = 2^-12; a child is entered iff bound2 < r2;
+ *   passing children keep slot order, the first minimum trades places with the first passing child and is entered next, the others are
+ *   pushed far -> near; a stacked child is re-validated at pop by bound2 < r2 (which always passes here: the walk is the shared one); the
+ *   stack holds 64 entries and a push at the cap is dropped (and counted); a degenerate root box gives 0 for every point.  Spheres
+ *   (pt_set_spheres) take no part.
+ * The list: count[i] = the number of accepted leaves of point i; its list is those leaves IN VISIT ORDER, which is a property of the point
+ *   and the tree, not of the scheduling: every kernel variant and the host twin give the same order.
+ * Entries: one PtClosest per accepted leaf: dist = sqrtf(d2), prim = the triangle, u, v from the same operations -- the bits
+ *   pt_closest_points(PT_CLOSEST_BRUTE_FORCE) gives for that point if that triangle is the only one.
+ * pt_radius_search: offsets[0] = 0 and offsets[i + 1] - offsets[i] = count[i] in uint64_t (no wrap); offsets[n] = the total.  The entry
+ *   with global index g = offsets[i] + k is written iff g < capacity; entries at and beyond min(total, capacity) are not touched.  The
+ *   offsets are always complete: offsets[n] > capacity says that the list was truncated and how large the retry must be.
+ *   entries_device = NULL is allowed with capacity = 0 (offsets only).  Three launches on the context's stream, no host wait: the count
+ *   walk into a buffer of the context, an exclusive scan, a second walk of the same steps that stores entry k of point i at
+ *   offsets[i] + k.  No atomic appends anything, so the order never depends on scheduling.
+ * PT_RADIUS_BRUTE_FORCE: every triangle in index order, no tree; the list is then in index order.
+ * PT_RADIUS_STATS: the counting variant (one point per thread) fills pt_get_stats: rays_closest = n, nodes_examined, tris_tested,
+ *   stack_drops and max_stack by the rules of PT_CLOSEST_STATS, counted over the count walk only (rays_shadow = samples = 0).  With
+ *   PT_RADIUS_BRUTE_FORCE only rays_closest and tris_tested are counted.
+ * PT_RADIUS_SIMPLE_KERNEL: the one-point-per-thread kernels instead of the persistent one (A/B checks); the results are the same.
+ * Completeness: for vertex coordinates within [-4, 4] and point coordinates within [-32, 32], wherever every triangle is reachable from
+ *   the root and the walk drops nothing at the cap (stack_drops = 0), the set listed for a point equals the set PT_RADIUS_BRUTE_FORCE lists
+ *   (bound2 < best2 never prunes a triangle with d2 < best2).
+ *   STACK DROPS LOSE ENTRIES.  A radius that covers much of a deep tree pushes up to three siblings per level and nothing is ever pruned
+ *   behind it, so the 64-entry cap is nearer here than in any sibling query.  A dropped subtree is missing from the list without a mark
+ *   on the item; the only report is stack_drops of PT_RADIUS_STATS, as in the sibling queries.  A caller that needs every triangle for
+ *   large radii checks that counter, or uses PT_RADIUS_BRUTE_FORCE.  With drops the walk's list is still a subset of the brute-force set.
+ * Ordering, errors and alignment: as pt_closest_points.  Points and entries 16-byte aligned, offsets 8-byte, counts 4-byte; a NULL or
+ *   misaligned pointer (entries: unless capacity = 0), unknown flags or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the scene).
+ *   No triangles + tree: PT_ERR_NO_SCENE.  n = 0: PT_OK, no kernel is launched (pt_radius_search still sets offsets[0] = 0).  A scene
+ *   change after a call does not change its results. */
+enum { PT_RADIUS_STATS = 1u, PT_RADIUS_SIMPLE_KERNEL = 2u, PT_RADIUS_BRUTE_FORCE = 4u };
+/* n points from device memory (PtPoint[n], 16-byte aligned), n counts into device memory (uint32_t[n], 4-byte aligned).  Asynchronous on
+ * the context's stream (pt_get_stream). */
+PT_API int pt_radius_count(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* counts_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the counts are written. */
+PT_API int pt_radius_count_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint32_t* counts);
+/* n points from device memory -> offsets_device: uint64_t[n + 1] (8-byte aligned); entries_device: PtClosest[capacity] (16-byte aligned).
+ * Asynchronous on the context's stream, no host wait. */
+PT_API int pt_radius_search(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags,
+                            void* offsets_device, void* entries_device, uint64_t capacity);
+/* The same from host arrays: staged; the host reads the total between the scan and the second walk; returns when everything is written. */
+PT_API int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags,
+                                 uint64_t* offsets, PtClosest* entries, uint64_t capacity);
+/* Host twin (no context, no GPU): the same offsets, entry bits and order (and the same truncation at `capacity`) and, with PT_RADIUS_STATS
+ * and stats != NULL, the same counters as the device gives for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).
+ * bvh4 = NULL (words = 0) only with PT_RADIUS_BRUTE_FORCE; a malformed bvh4: PT_ERR_BAD_BVH; a NULL points pointer with n > 0, NULL
+ * offsets, NULL entries with capacity > 0, offsets not 8-byte aligned, or unknown flags: PT_ERR_INVALID_ARG.  points and entries need
+ * only the alignment of their types here. */
+PT_API int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
+                                 uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats);
+
 /* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
  * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
  * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes

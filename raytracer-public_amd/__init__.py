@@ -36,6 +36,8 @@ PT_CLOSEST_STATS, PT_CLOSEST_SIMPLE_KERNEL, PT_CLOSEST_BRUTE_FORCE = 1, 2, 4
 PT_OCCLUSION_STATS, PT_OCCLUSION_SIMPLE_KERNEL = 1, 2
 PT_COUNT_STATS, PT_COUNT_SIMPLE_KERNEL, PT_COUNT_BRUTE_FORCE = 1, 2, 4
 PT_CONTAIN_STATS, PT_CONTAIN_SIMPLE_KERNEL = 1, 2
+# radius queries (include/mi355pt.h pt_radius_search)
+PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
 PRIM_NONE = 0xFFFFFFFF
 
 
@@ -131,6 +133,7 @@ EXPORTS = [
     "pt_occlusion", "pt_occlusion_host", "pt_occlusion_rays", "pt_occlusion_rays_host", "pt_hit_surfels", "pt_hit_surfels_host",
     "pt_count_hits", "pt_count_hits_host", "pt_count_hits_bvh4", "pt_contains", "pt_contains_host", "pt_contains_bvh4",
     "pt_signed_distance", "pt_signed_distance_host",
+    "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -260,6 +263,16 @@ def _closest_flags(stats, simple, brute_force):
 
 def _count_flags(stats, simple, brute_force):
     return (PT_COUNT_STATS if stats else 0) | (PT_COUNT_SIMPLE_KERNEL if simple else 0) | (PT_COUNT_BRUTE_FORCE if brute_force else 0)
+
+
+def _radius_flags(stats, simple, brute_force):
+    return (PT_RADIUS_STATS if stats else 0) | (PT_RADIUS_SIMPLE_KERNEL if simple else 0) | (PT_RADIUS_BRUTE_FORCE if brute_force else 0)
+
+
+def _entry_columns(entries):
+    """(m, 4) uint32 PtClosest records -> (dist, prim, u, v)"""
+    f = entries.view(np.float32)
+    return f[:, 0].copy(), entries[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
 
 
 def _contain_params(samples, seed, index_base, stats=False, simple=False):
@@ -401,6 +414,34 @@ def count_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, stats=Fals
                                   rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(_count_flags(stats, simple, brute_force)),
                                   _p(counts, C.c_uint32), C.byref(st) if stats else None))
     return (counts, st.as_dict()) if stats else counts
+
+
+def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.radius_search (no GPU): every triangle of `tris` within r_max of each point over the tree set_bvh4(bvh4) installs,
+    with the device's bits and order.  bvh4 None needs brute_force=True.  Returns (offsets, dist, prim, u, v): offsets (n + 1,) uint64, the
+    list of point i at offsets[i]:offsets[i + 1], in visit order (index order with brute_force).  capacity None: every entry (the twin runs
+    twice, once for the total); else the first min(offsets[-1], capacity) entries, offsets complete.  The counters as a dict in sixth place
+    with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    pts = _point_records(points, r_max)
+    n = pts.shape[0]
+    offsets = np.zeros(n + 1, np.uint64)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    flags = _radius_flags(stats, simple, brute_force)
+
+    def call(entries, cap):
+        _check(lib.pt_radius_search_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                         pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                         entries.ctypes.data_as(C.POINTER(PtClosest)) if cap else None, C.c_uint64(cap),
+                                         C.byref(st) if stats else None))
+    if capacity is None:
+        call(None, 0)
+        capacity = int(offsets[n])
+    entries = _aligned_zeros((int(capacity), 4), np.uint32)
+    call(entries, int(capacity))
+    res = (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+    return res + (st.as_dict(),) if stats else res
 
 
 def contains_bvh4(tris, bvh4, points, samples=3, seed=0, index_base=0, stats=False, simple=False):
@@ -1057,6 +1098,90 @@ class Context:
         """Raw device route: n PtPoint records at points_ptr -> n PtContainment records at out_ptr (16-byte aligned device pointers; params:
         PtContainParams).  Asynchronous on the context's stream."""
         self._ck(lib.pt_contains(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.byref(params), C.c_void_p(out_ptr)))
+
+    # ---- radius queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 18) ----
+    def radius_count(self, points, r_max=None, stats=False, simple=False, brute_force=False):
+        """How many triangles lie within r_max of each point?  Returns the (n,) uint32 counts (0 for a point with a NaN or r_max <= 0).
+
+        points: (n, 3) float32, or (n, 4) PtPoint records (r_max=None: taken from the records).  numpy arrays take the host route (staged,
+        returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host synchronisation; the
+        result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0 means that triangles
+        were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
+        flags = _radius_flags(stats, simple, brute_force)
+        if _is_torch(points):
+            _torch_route()
+            import torch
+            pts = self._point_tensor(points, r_max, "radius_count")
+            n = pts.shape[0]
+            counts = torch.empty((n,), dtype=torch.int32, device=pts.device)
+            self._on_context_stream(pts.device, lambda: self.radius_count_device(pts.data_ptr(), n, counts.data_ptr(), flags))
+            return counts.view(torch.uint32)
+        pts = _point_records(points, r_max)
+        n = pts.shape[0]
+        counts = np.zeros(n, np.uint32)
+        self._ck(lib.pt_radius_count_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
+        return counts
+
+    def radius_count_device(self, points_ptr, n, counts_ptr, flags=0):
+        """Raw device route: n PtPoint records at points_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
+        context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_radius_count(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
+
+    def radius_search(self, points, r_max=None, capacity=None, stats=False, simple=False, brute_force=False):
+        """Which triangles lie within r_max of each point -- all of them, each with its contact point?  Returns (offsets, dist, prim, u, v):
+        the list of point i is entries offsets[i]:offsets[i + 1], in the walk's visit order (index order with brute_force); the contact point
+        of an entry is v0 + u * (v1 - v0) + v * (v2 - v0) of triangle prim, at distance dist.  offsets has n + 1 elements and is always
+        complete: offsets[-1] is the total, and offsets[-1] > capacity says that only the first `capacity` entries were written.
+
+        points: as radius_count.  numpy arrays take the host route (staged, returns when done): offsets is uint64 and the entry arrays hold
+        min(offsets[-1], capacity) elements; capacity=None starts with room for 16 entries per point and runs the query again when
+        offsets[-1] says that this was too little.
+        torch tensors on the context's device stay there, on the context's stream: offsets is int64, prim torch.uint32.  With `capacity` given
+        the torch route waits for nothing on the host and the entry tensors hold `capacity` elements, of which those from offsets[-1] on are
+        not written.  With capacity=None it reads offsets[-1] once to size the entries: that is the one host wait of this call (the counts
+        are then walked a second time); pass a capacity to avoid it.
+        stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack cap,
+        which large radii over deep trees reach sooner than any other query; brute_force lists every triangle within r_max regardless."""
+        flags = _radius_flags(stats, simple, brute_force)
+        if _is_torch(points):
+            _torch_route()
+            import torch
+            pts = self._point_tensor(points, r_max, "radius_search")
+            n = pts.shape[0]
+            dev = pts.device
+            offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+            if capacity is None:
+                self._on_context_stream(dev, lambda: self.radius_search_device(pts.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
+                capacity = int(offsets[-1].item())          # the one host wait
+            cap = int(capacity)
+            entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            self._on_context_stream(dev, lambda: self.radius_search_device(pts.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
+            ef = entries.view(torch.float32)
+            return offsets, ef[:, 0], entries.view(torch.uint32)[:, 1], ef[:, 2], ef[:, 3]
+        pts = _point_records(points, r_max)
+        n = pts.shape[0]
+        offsets = np.zeros(n + 1, np.uint64)
+
+        def call(entries, cap):
+            self._ck(lib.pt_radius_search_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                               entries.ctypes.data_as(C.POINTER(PtClosest)) if cap else None, C.c_uint64(cap)))
+        retry = capacity is None
+        if retry:
+            capacity = 16 * n + 64                  # a first guess; offsets[n] says how large the retry must be
+        entries = _aligned_zeros((int(capacity), 4), np.uint32)
+        call(entries, int(capacity))
+        if retry and int(offsets[n]) > capacity:
+            capacity = int(offsets[n])
+            entries = _aligned_zeros((capacity, 4), np.uint32)
+            call(entries, capacity)
+        return (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+
+    def radius_search_device(self, points_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
+        """Raw device route: n PtPoint records at points_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
+        `capacity` PtClosest records at entries_ptr (16-byte aligned; 0 with capacity 0: offsets only).  Three launches on the context's
+        stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_radius_search(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
+                                      C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
 
     def signed_distance(self, points, r_max=None, samples=3, seed=0, index_base=0, simple=False):
         """closest_points with the sign of contains: returns (dist, prim, u, v), dist negative where the point is inside (-inf: inside, and

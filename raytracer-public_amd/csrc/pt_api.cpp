@@ -122,6 +122,9 @@ struct PtContext {
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
     DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
     DevBuf<uint4> d_cr_contain;         // pt_signed_distance: the PtContainment records between its containment launch and the sign kernel
+    // radius queries (pt_radius_search): the counts between the count walk and the scan, the scan's scratch (grown like the staging buffers),
+    // and the staging of pt_radius_search_host's offsets and entries
+    DevBuf<uint32_t> d_rd_counts; DevBuf<unsigned char> d_rd_temp; DevBuf<unsigned long long> d_rd_offsets; DevBuf<uint4> d_rd_entries;
 
     // frame
     DevBuf<float4> d_out, d_accum, d_compact, d_compact_accum;
@@ -778,7 +781,7 @@ void pt_destroy(PtContext* ctx) {
     (void)flush_pending(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->d_tris9.release(); ctx->d_scene.release(); ctx->d_bvh2.release(); ctx->d_bvh4.release();
-    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release(); ctx->d_oc_surfels.release(); ctx->d_cr_contain.release();
+    ctx->d_spheres.release(); ctx->d_rq_queue.release(); ctx->d_rq_spill.release(); ctx->d_rq_rays.release(); ctx->d_rq_hits.release(); ctx->d_oc_surfels.release(); ctx->d_cr_contain.release(); ctx->d_rd_counts.release(); ctx->d_rd_temp.release(); ctx->d_rd_offsets.release(); ctx->d_rd_entries.release();
     ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
     ctx->d_out.release(); ctx->d_accum.release(); ctx->d_compact.release(); ctx->d_compact_accum.release();
     ctx->d_tiles.release(); ctx->d_u32tmp.release(); ctx->d_stats.release();
@@ -1862,6 +1865,139 @@ int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, c
     if (int rc = signed_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
     PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+// ---- radius queries (include/mi355pt.h; pt_radius.hip) -------------------------------------------------------------------------
+
+namespace {
+constexpr uint32_t kRadiusFlags = PT_RADIUS_STATS | PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_BRUTE_FORCE;
+bool aligned8(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 7u) == 0u; }
+
+// flags, batch size and the points; the other pointers are checked by the callers, and the scene behind them (check_radius_scene)
+int check_radius(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t flags) {
+    if (flags & ~kRadiusFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
+    if (!aligned16(points)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points must be non-null and 16-byte aligned");
+    return PT_OK;
+}
+int check_radius_search(PtContext* ctx, const char* fn, const void* offsets, const void* entries, uint64_t capacity) {
+    if (!aligned8(offsets)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": offsets must be non-null and 8-byte aligned");
+    if (capacity ? !aligned16(entries) : (entries && !aligned16(entries)))
+        return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": entries must be 16-byte aligned, and non-null unless capacity is 0");
+    return PT_OK;
+}
+int check_radius_scene(PtContext* ctx, const char* fn) {
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+
+// One walk on the context's stream, behind whatever pt_set_batch still holds: the count walk into `counts` (offsets = nullptr), or the fill
+// walk from `offsets` into `entries`.  PT_RADIUS_STATS counts over the count walk only; its fill walk is the one-point-per-thread kernel.
+int radius_walk_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* counts, const unsigned long long* offsets,
+                          void* entries, uint64_t capacity) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool fill = offsets != nullptr, brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
+    const bool stats = (flags & PT_RADIUS_STATS) != 0 && !fill, simple = (flags & (PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_STATS)) != 0;
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_RD_WAVES_PER_SIMD);
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple && !brute) {
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_RD_SHORT_STACK));
+    }
+    PT_HIP(ctx, ptk::launch_radius(A, points, n, counts, offsets, entries, capacity, simple, stats, brute,
+                                   ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+// the count walk into the context's buffer and the scan into `offsets`: two launches, no host wait
+int radius_offsets_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, unsigned long long* offsets) {
+    const size_t temp_bytes = ptk::radius_scan_temp_bytes(n);
+    PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_temp.ensure(temp_bytes));
+    if (int rc = radius_walk_on_stream(ctx, points, n, flags, ctx->d_rd_counts.ptr, nullptr, nullptr, 0)) return rc;
+    PT_HIP(ctx, ptk::launch_radius_scan(ctx->d_rd_counts.ptr, n, offsets, ctx->d_rd_temp.ptr, temp_bytes, ctx->stream));
+    return PT_OK;
+}
+} // namespace
+
+int pt_radius_count(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* counts_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_radius(ctx, "pt_radius_count", points_device, n, flags)) return rc;
+    if (!aligned4(counts_device)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_radius_count: counts must be non-null and 4-byte aligned");
+    if (int rc = check_radius_scene(ctx, "pt_radius_count")) return rc;
+    return radius_walk_on_stream(ctx, points_device, uint32_t(n), flags, counts_device, nullptr, nullptr, 0);
+}
+
+int pt_radius_count_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint32_t* counts) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_radius(ctx, "pt_radius_count_host", points, n, flags)) return rc;
+    if (!aligned4(counts)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_radius_count_host: counts must be non-null and 4-byte aligned");
+    if (int rc = check_radius_scene(ctx, "pt_radius_count_host")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n)));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = radius_walk_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_counts.ptr, nullptr, nullptr, 0)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(counts, ctx->d_rd_counts.ptr, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+// three launches, no host wait: the counts into the context's buffer, their scan into offsets, the entries
+int pt_radius_search(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_radius(ctx, "pt_radius_search", points_device, n, flags)) return rc;
+    if (int rc = check_radius_search(ctx, "pt_radius_search", offsets_device, entries_device, capacity)) return rc;
+    if (int rc = check_radius_scene(ctx, "pt_radius_search")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    unsigned long long* offsets = static_cast<unsigned long long*>(offsets_device);
+    if (n == 0) { PT_HIP(ctx, hipMemsetAsync(offsets, 0, sizeof(unsigned long long), ctx->stream)); return PT_OK; }
+    if (int rc = radius_offsets_on_stream(ctx, points_device, uint32_t(n), flags, offsets)) return rc;
+    if (capacity == 0) return PT_OK;
+    return radius_walk_on_stream(ctx, points_device, uint32_t(n), flags, nullptr, offsets, entries_device, capacity);
+}
+
+// staged: the host reads the total between the scan and the fill walk, so the staging buffer holds min(total, capacity) entries
+int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_radius(ctx, "pt_radius_search_host", points, n, flags)) return rc;
+    if (int rc = check_radius_search(ctx, "pt_radius_search_host", offsets, entries, capacity)) return rc;
+    if (int rc = check_radius_scene(ctx, "pt_radius_search_host")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) { offsets[0] = 0; return PT_OK; }
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_offsets.ensure(size_t(n) + 1));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = radius_offsets_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_rd_offsets.ptr, (size_t(n) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t held = std::min<uint64_t>(offsets[n], capacity);
+    if (held == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rd_entries.ensure(size_t(held)));
+    if (int rc = radius_walk_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, nullptr, ctx->d_rd_offsets.ptr, ctx->d_rd_entries.ptr, held)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(entries, ctx->d_rd_entries.ptr, size_t(held) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
+                          uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats) {
+    if (flags & ~kRadiusFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: unknown flags");
+    const bool brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && !points) || !offsets || (capacity && !entries) || (!bvh4 && !brute))
+        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: null pointer");
+    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: offsets must be 8-byte aligned");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: more than 2^32 - 1 points");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::radius_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, offsets,
+                           reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_RADIUS_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
     return PT_OK;
 }
 

@@ -618,9 +618,11 @@ inline float box_bound2_h(const float hi[3], const float lo[3], const uint32_t w
     return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
 }
 
-void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& best_tri, WalkCounters& cnt) {
+// The walk of both point queries: `best2` is what child boxes and stacked entries are compared with, and `leaf(tri)` is called for every
+// reached leaf with tri < num_tris, in visit order -- the closest-point query lowers best2 there, the radius query leaves it alone.
+template <class Leaf>
+void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounters& cnt, Leaf leaf) {
     const WideBvh& wb = *W.wide;
-    best_tri = kInvalid;
     if (wb.root_ref == kInvalid || W.num_tris == 0u) return;
     cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
     if (wb.root_degenerate) return;
@@ -636,8 +638,7 @@ void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& 
             const uint32_t ti4 = cur & 0x7fffffffu;
             if (ti4 < 4u * W.num_tris) {
                 cnt.tris += 1;
-                const float d2 = record_d2(W.rec[ti4 >> 2], p);
-                if (d2 < best2) { best2 = d2; best_tri = ti4 >> 2; }
+                leaf(ti4 >> 2);
             }
             need_pop = true;
         } else {
@@ -673,6 +674,13 @@ void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& 
             if (!found) break;
         }
     }
+}
+void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& best_tri, WalkCounters& cnt) {
+    best_tri = kInvalid;
+    walk_h(W, p, best2, cnt, [&](uint32_t tri) {
+        const float d2 = record_d2(W.rec[tri], p);
+        if (d2 < best2) { best2 = d2; best_tri = tri; }
+    });
 }
 } // namespace
 
@@ -713,6 +721,81 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
         std::vector<std::thread> pool;
         for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
         for (std::thread& t : pool) t.join();
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Radius queries (host twin of pt_radius.hip): the closest-point walk with best2 held at r_max^2, every accepted leaf counted and, in a
+// second walk of the same steps, listed at offsets[i] + k -- the device's two walks around its scan
+// ------------------------------------------------------------------------------------
+namespace {
+// d2 of one record with the u, v it was computed from (record_d2's operations)
+inline float record_uv_d2(const TriRecord& r, const float p[3], float& u, float& v) {
+    const float ax = p[0] - r.axis[0][0], ay = p[1] - r.axis[1][0], az = p[2] - r.axis[2][0];
+    ptcp::closest_uv(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
+    return ptcp::closest_d2(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
+}
+} // namespace
+
+bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+                   uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers), unused(workers);
+    // one point: the walk (or every triangle in index order), each accepted leaf handed to `accept`
+    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
+        if (!ptcp::point_walked(q[0], q[1], q[2], q[3])) return;
+        const float r2 = q[3] * q[3];
+        auto leaf = [&](uint32_t t) {
+            float u, v;
+            const float d2 = record_uv_d2(rec[t], q, u, v);
+            if (d2 < r2) accept(d2, t, u, v);
+        };
+        if (bvh4) { walk_h(W, q, r2, cnt, leaf); return; }      // r2 never moves: every stacked entry passes its re-validation
+        for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+        cnt.tris += num_tris;
+    };
+    auto parallel = [&](auto run) {
+        if (workers == 1) { run(uint64_t(0)); return; }
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    };
+    // the count walk: offsets[i + 1] holds the count of point i until the scan
+    offsets[0] = 0;
+    parallel([&](uint64_t w) {
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            uint64_t count = 0;
+            query(points + i * 4, per[w], [&](float, uint32_t, float, float) { ++count; });
+            offsets[i + 1] = count;
+        }
+    });
+    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
+    // the fill walk: the same steps, entry k of point i at offsets[i] + k where that is below the capacity
+    if (entries && capacity) {
+        parallel([&](uint64_t w) {
+            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+                uint64_t g = offsets[i];
+                if (g >= capacity) break;                       // the offsets only grow
+                query(points + i * 4, unused[w], [&](float d2, uint32_t tri, float u, float v) {
+                    if (g < capacity) { uint32_t* o = entries + g * 4; o[0] = bits_of(std::sqrt(d2)); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v); }
+                    ++g;
+                });
+            }
+        });
     }
     if (counters) {
         counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;

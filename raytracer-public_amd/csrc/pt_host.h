@@ -95,6 +95,15 @@ void build_tri_records(const float* tris, uint32_t n, TriRecord* out);
 bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                     uint32_t* out, uint64_t* counters, std::string& err);
 
+// ---- radius queries (pt_radius_count, pt_radius_search; host twin of pt_radius.hip, bit for bit) -------------------------------------
+// points: n x (x, y, z, r_max); offsets: n + 1 words, the exclusive prefix sums of the counts (offsets[n] = the total); entries: (dist bits,
+// prim, u bits, v bits) per accepted leaf, the list of point i in visit order from offsets[i] on, written only below `capacity` (entries =
+// nullptr with capacity 0: offsets only).  bvh4 = nullptr: every triangle in index order; else closest_points' walk with best2 held at
+// r_max^2.  counters (optional): points, nodes examined, triangles tested, stack drops, max stack of the count walk -- as the device's
+// PT_RADIUS_STATS counts them.
+bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
+                   uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
+
 // ---- crossing counts and containment (pt_count_hits, pt_contains; host twin of pt_crossings.hip, bit for bit) --------------------------
 // rays: n x (org, t_max, dir, reserved); counts: n words.  bvh4 = nullptr: every triangle in index order; else the walk of the kernels over
 // build_wide_bvh(bvh4) and build_tri_records(tris): a record is counted when tri_hit holds and t < best = min(t_max, 1e30), which never

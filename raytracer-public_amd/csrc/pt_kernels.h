@@ -75,6 +75,16 @@
 #ifndef PT_CR_FILL
 #define PT_CR_FILL 8                // idle lanes of a wavefront at which they take the next items of its chunk
 #endif
+// radius queries (pt_radius.hip): the point queries' values taken over, unmeasured for these kernels until tools/radius_bench.py has run
+#ifndef PT_RD_SHORT_STACK
+#define PT_RD_SHORT_STACK 12        // LDS stack entries per lane of radius_kernel<FILL>; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_RD_WAVES_PER_SIMD
+#define PT_RD_WAVES_PER_SIMD 6      // wavefronts of radius_kernel<FILL> per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_RD_FILL
+#define PT_RD_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -253,6 +263,21 @@ hipError_t launch_contains(const RenderArgs& A, const void* points, void* out, u
                            bool simple, bool stats, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // PtClosest[n] in `out` gets the sign bit of dist where PtContainment[n] in `contain` says inside
 hipError_t launch_apply_sign(const void* contain, void* out, uint32_t n, hipStream_t stream);
+// ---- radius queries (pt_radius.hip): every triangle within r_max of a point ----------------------------------------------------
+// points: PtPoint[n] (float4 each, 16-byte aligned).  One walk per launch, the closest-point walk with best2 held at r_max^2:
+//   offsets = nullptr: the count walk, counts[i] = the number of accepted leaves of point i (uint32_t[n]);
+//   offsets != nullptr: the fill walk, entry k of point i (a PtClosest record, in visit order) at entries[offsets[i] + k] where that index
+//   is below `capacity`; counts is not touched.
+// brute: every triangle in index order; simple or stats: one point per thread (stats: PtStats counters into A.stats, zeroed by the
+// caller); else the persistent kernel with `grid` wavefronts at most (walk_grid(.., PT_RD_WAVES_PER_SIMD)), the queue block and
+// walk_spill_entries(grid, PT_RD_SHORT_STACK) spill entries.
+hipError_t launch_radius(const RenderArgs& A, const void* points, uint32_t n, void* counts, const unsigned long long* offsets, void* entries,
+                         unsigned long long capacity, bool simple, bool stats, bool brute,
+                         unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// offsets[0 .. n] = the exclusive prefix sums of counts[0 .. n) in 64 bits, offsets[n] = the total (hipcub::DeviceScan over n + 1 items,
+// item n read as 0); temp: at least radius_scan_temp_bytes(n) bytes
+size_t radius_scan_temp_bytes(uint32_t n);
+hipError_t launch_radius_scan(const void* counts, uint32_t n, unsigned long long* offsets, void* temp, size_t temp_bytes, hipStream_t stream);
 // ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
 // What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
 // launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):

@@ -204,6 +204,34 @@ class PathTracer {
     return { inside: r.inside[0] !== 0, odd: r.odd[0], samples: r.samples[0] };
   }
 
+  // ---- radius queries: an extension beyond the reference (include/mi355pt.h pt_radius_search, DESIGN.md section 18) ----
+  // points: Float32Array, 4 floats per point (x, y, z, rMax); a number rMax replaces the fourth float of every point (the caller's array is
+  // not written).  radiusSearch resolves to { offsets, dist, prim, u, v }: the triangles within rMax of point i are entries
+  // offsets[i] .. offsets[i + 1] - 1 (offsets: Float64Array of n + 1 exact integers), each with its distance and its contact point
+  // v0 + u (v1 - v0) + v (v2 - v0), in the order the walk meets them (triangle order with options.bruteForce).  radiusCount resolves to a
+  // Uint32Array of the list lengths alone.  A point with a NaN or rMax <= 0 has an empty list.  options.bruteForce: every triangle, no
+  // tree; options.simple: the one-point-per-thread kernels.  A radius that covers much of a deep tree can lose triangles at the
+  // 64-entry stack cap (the header says when); bruteForce never does.  Triangles only.  On a group: member 0, which holds the whole scene.
+  _radiusPoints(points, rMax) {
+    if (rMax === undefined || rMax === null) return points;
+    const p = Float32Array.from(points);
+    for (let i = 3; i < p.length; i += 4) p[i] = rMax;
+    return p;
+  }
+  async radiusSearch(points, rMax, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0), p = this._radiusPoints(points, rMax);
+    return this.group ? native().groupRadiusSearch(this.group, p, flags) : native().radiusSearch(this.device, p, flags);
+  }
+  async radiusCount(points, rMax, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0), p = this._radiusPoints(points, rMax);
+    return this.group ? native().groupRadiusCount(this.group, p, flags) : native().radiusCount(this.device, p, flags);
+  }
+  // The triangles within r of (x, y, z): resolves to { count, dist, prim, u, v }.
+  async within(x, y, z, r, options) {
+    const s = await this.radiusSearch(Float32Array.of(x, y, z, r), undefined, options);
+    return { count: s.prim.length, dist: s.dist, prim: s.prim, u: s.u, v: s.v };
+  }
+
   // ---- batched ambient-occlusion queries: an extension beyond the reference (include/mi355pt.h pt_occlusion, DESIGN.md section 16) ----
   // surfels: Float32Array, 8 floats per surfel (point xyz, rMax, unit normal xyz, 0).  options: { samples (16), seed (0), bias (1e-4),
   // indexBase (0), simple }.  Resolves to { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }: of `samples`

@@ -398,6 +398,74 @@ static napi_value fn_closest_points(napi_env env, napi_callback_info info) {    
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- radius queries (an extension beyond the reference; include/mi355pt.h pt_radius_count_host, pt_radius_search_host) ---------------- */
+
+static PtPoint* radius_points(napi_env env, napi_value points_v, const char* what, size_t* n) {
+    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 4) { napi_throw_range_error(env, NULL, what); return NULL; }
+    *n = len / 4;
+    PtPoint* pts = (PtPoint*)aligned_alloc(16, (*n ? *n : 1) * sizeof(PtPoint));
+    if (!pts) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (*n) memcpy(pts, d, *n * sizeof(PtPoint));
+    return pts;
+}
+/* points: Float32Array of 4 floats per point (x, y, z, rMax) -> Uint32Array: the triangles within rMax of each point; flags: PT_RADIUS_* */
+static napi_value radius_count_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
+    size_t n; PtPoint* pts = radius_points(env, points_v, "radiusCount: 4 floats per point", &n); if (!pts) return NULL;
+    const uint32_t flags = get_u32(env, flags_v);
+    void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
+    if (!counts) { free(pts); return NULL; }
+    uint32_t none = 0;
+    int rc = pt_radius_count_host(ctx, pts, n, flags, n ? (uint32_t*)pc : &none);
+    free(pts);
+    if (rc != 0) return throw_pt(env, ctx, rc, "pt_radius_count_host");
+    return counts;
+}
+/* points as above -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), dist, prim, u, v }: every entry.  The first
+ * call has room for 16 entries per point; when offsets[n] says that this was too little, the query runs again with room for all. */
+static napi_value radius_search_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
+    size_t n; PtPoint* pts = radius_points(env, points_v, "radiusSearch: 4 floats per point", &n); if (!pts) return NULL;
+    const uint32_t flags = get_u32(env, flags_v);
+    uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
+    uint64_t cap = 16 * (uint64_t)n + 64;
+    PtClosest* res = (PtClosest*)aligned_alloc(16, (size_t)cap * sizeof(PtClosest));
+    if (!off || !res) { free(pts); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = pt_radius_search_host(ctx, pts, n, flags, off, res, cap);
+    if (rc == 0 && off[n] > cap) {
+        cap = off[n];
+        free(res);
+        res = (PtClosest*)aligned_alloc(16, (size_t)cap * sizeof(PtClosest));
+        if (!res) { free(pts); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        rc = pt_radius_search_host(ctx, pts, n, flags, off, res, cap);
+    }
+    free(pts);
+    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_radius_search_host"); }
+    const size_t m = (size_t)off[n];
+    napi_value o, offs, dist, prim, u, v; void *po, *pd, *pp, *pu, *pv;
+    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(dist = make_typed(env, napi_float32_array, 4, m, &pd)) ||
+        !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) || !(u = make_typed(env, napi_float32_array, 4, m, &pu)) ||
+        !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(off); free(res); return NULL; }
+    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
+    for (size_t i = 0; i < m; ++i) {
+        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
+    }
+    free(off); free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_radius_count(napi_env env, napi_callback_info info) {        /* (ctx, Float32Array points, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return radius_count_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_radius_search(napi_env env, napi_callback_info info) {       /* (ctx, Float32Array points, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return radius_search_on(env, ctx, argv[1], argv[2]);
+}
+
 /* ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h pt_occlusion_host, pt_hit_surfels_host) ---- */
 
 /* surfels: Float32Array of 8 floats per surfel (PtSurfel: p xyz, rMax, n xyz, reserved); opt: { samples, seed, bias, indexBase, simple }
@@ -789,6 +857,18 @@ static napi_value fn_group_signed_distance(napi_env env, napi_callback_info info
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return signed_distance_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_radius_count(napi_env env, napi_callback_info info) {   /* (group, points, flags): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return radius_count_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_group_radius_search(napi_env env, napi_callback_info info) {  /* (group, points, flags): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return radius_search_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_hit_surfels(napi_env env, napi_callback_info info) {     /* (group, rays, t, prim, u, v, rMax): on member 0 */
     napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -855,6 +935,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
         {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
         {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
+        {"radiusCount", fn_radius_count}, {"groupRadiusCount", fn_group_radius_count}, {"radiusSearch", fn_radius_search}, {"groupRadiusSearch", fn_group_radius_search},
         {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
