@@ -514,6 +514,47 @@ PT_API int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t
 PT_API int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
                                  uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats);
 
+/* ---- k-nearest queries: which k triangles are closest to a point, each with its contact point? (an extension beyond the reference;
+ * DESIGN.md section 19) -----------------------------------------------------------------------------------------------------------
+ * Records: PtPoint in, PtClosest out.  out holds n * k PtClosest, row i at out[i*k .. i*k + k-1].  Every result is an integer or a bit
+ * pattern.
+ * Per point: a point is walked exactly when ptcp::point_walked holds (p and r_max hold no NaN, r_max > 0, as pt_closest_points).
+ *   r2 = r_max * r_max in f32 (+inf stays +inf).  The lane keeps a list L of at most k pairs (d2, leaf reference), sorted ascending by d2.
+ *   worst2 = r2 while |L| < k; otherwise it is the d2 of L's last pair.  A reached leaf with tri < num_tris is accepted when d2 < worst2,
+ *   strictly; a NaN is never accepted; d2 comes from csrc/pt_closest.h (closest_uv, then closest_d2) on the record as stored.  An accepted
+ *   pair is inserted behind every pair with d2' <= d2, so equal distances keep visit order.  If L held k pairs, the last one falls off.
+ * The walk: pt_closest_points' with best2 replaced by worst2 -- a child is entered iff box_bound2 < worst2 (the same slack s = 2^-12);
+ *   bound() returns worst2, and a stacked child is re-validated at pop against it; the order of order_children (passing children keep slot
+ *   order, the first minimum trades places with the first passing child and is entered next, the others are pushed far -> near); 64 stack
+ *   entries, a push at the cap dropped and counted; a degenerate root finds nothing.  Spheres (pt_set_spheres) take no part.
+ * Output: row i, entry j < |L|: dist = sqrtf(d2), prim, and u, v recomputed from the record with the operations of the accepted test --
+ *   the bits pt_closest_points gives for that triangle.  Entries j >= |L|, and every entry of a point that is not walked: dist = +inf,
+ *   prim = 0xFFFFFFFF, u = v = 0.  Every one of the n * k records is written.  Nothing behind them is touched.
+ * Arguments: k = 0 or k > PT_NEAREST_MAX_K: PT_ERR_INVALID_ARG.  Pointers, alignment (16 bytes), unknown flags, n > UINT32_MAX, n = 0
+ *   (PT_OK, no kernel), ordering against queued frames, and scene changes after the call: as pt_closest_points.
+ * PT_NEAREST_BRUTE_FORCE: every triangle in index order with the same list rule.  Ties are then in index order.
+ * PT_NEAREST_STATS: rays_closest = n, nodes_examined, tris_tested, stack_drops, max_stack by the rules of PT_CLOSEST_STATS, served by the
+ *   one-point-per-thread kernel.  PT_NEAREST_SIMPLE_KERNEL: that kernel without counters (A/B checks); the results are the same.
+ * Consequences: k = 1 gives the bits of pt_closest_points on every point, prim included.  For vertex coordinates within [-4, 4] and point
+ *   coordinates within [-32, 32], wherever every triangle is reachable from the root and stack_drops = 0, the multiset of d2 in a row equals
+ *   brute force's k smallest d2 < r2 (a pruned subtree has d2 >= bound2 >= worst2 at that moment, and worst2 only falls); prim may differ
+ *   from brute force only among triangles whose d2 bits are equal.  The persistent kernel, the simple kernel and the host twin visit in the
+ *   same order, so they agree bit for bit, ties included.  With drops a row is still made of true (prim, dist, u, v) records within r_max,
+ *   but nearer triangles may be missing; the only report is stack_drops of PT_NEAREST_STATS. */
+#define PT_NEAREST_MAX_K 64
+enum { PT_NEAREST_STATS = 1u, PT_NEAREST_SIMPLE_KERNEL = 2u, PT_NEAREST_BRUTE_FORCE = 4u };
+/* n points from device memory (PtPoint[n]) -> n * k records into device memory (PtClosest[n * k]), both 16-byte aligned.  Asynchronous on
+ * the context's stream (pt_get_stream), no host wait, one launch (plus the zeroing of the walk's queue block). */
+PT_API int pt_nearest_k(PtContext* ctx, const void* points_device, uint64_t n, uint32_t k, uint32_t flags, void* out_device);
+/* The same from host arrays: staged through device buffers of the context like pt_closest_points_host; returns when the rows are written. */
+PT_API int pt_nearest_k_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t k, uint32_t flags, PtClosest* out);
+/* Host twin (no context, no GPU): the same rows and, with PT_NEAREST_STATS and stats != NULL, the same counters as the device gives for the
+ * tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).  Argument rules of pt_closest_points_bvh4: bvh4 = NULL (words = 0) only with
+ * PT_NEAREST_BRUTE_FORCE; a malformed bvh4: PT_ERR_BAD_BVH; a NULL points or out pointer with n > 0, unknown flags, or k out of range:
+ * PT_ERR_INVALID_ARG.  points and out need only the alignment of their types here. */
+PT_API int pt_nearest_k_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
+                             uint32_t k, uint32_t flags, PtClosest* out, PtStats* stats);
+
 /* ---- animated geometry: new vertices, the same tree (an extension beyond the reference) --------------
  * The reference rebuilds its tree whenever a vertex moves (PathTracer.buildBVH).  An update keeps the TOPOLOGY of the context's
  * current tree -- whatever installed it: pt_build_bvh, pt_build_bvh_accel of any level, pt_set_bvh4, pt_set_bvh2 -- and recomputes

@@ -38,6 +38,9 @@ PT_COUNT_STATS, PT_COUNT_SIMPLE_KERNEL, PT_COUNT_BRUTE_FORCE = 1, 2, 4
 PT_CONTAIN_STATS, PT_CONTAIN_SIMPLE_KERNEL = 1, 2
 # radius queries (include/mi355pt.h pt_radius_search)
 PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
+# k-nearest queries (include/mi355pt.h pt_nearest_k)
+PT_NEAREST_STATS, PT_NEAREST_SIMPLE_KERNEL, PT_NEAREST_BRUTE_FORCE = 1, 2, 4
+PT_NEAREST_MAX_K = 64
 PRIM_NONE = 0xFFFFFFFF
 
 
@@ -134,6 +137,7 @@ EXPORTS = [
     "pt_count_hits", "pt_count_hits_host", "pt_count_hits_bvh4", "pt_contains", "pt_contains_host", "pt_contains_bvh4",
     "pt_signed_distance", "pt_signed_distance_host",
     "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
+    "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -267,6 +271,16 @@ def _count_flags(stats, simple, brute_force):
 
 def _radius_flags(stats, simple, brute_force):
     return (PT_RADIUS_STATS if stats else 0) | (PT_RADIUS_SIMPLE_KERNEL if simple else 0) | (PT_RADIUS_BRUTE_FORCE if brute_force else 0)
+
+
+def _nearest_flags(stats, simple, brute_force):
+    return (PT_NEAREST_STATS if stats else 0) | (PT_NEAREST_SIMPLE_KERNEL if simple else 0) | (PT_NEAREST_BRUTE_FORCE if brute_force else 0)
+
+
+def _row_columns(rows, n, k):
+    """(n * k, 4) uint32 PtClosest records -> (dist, prim, u, v), each (n, k)"""
+    f = rows.view(np.float32)
+    return tuple(a.reshape(n, k).copy() for a in (f[:, 0], rows[:, 1], f[:, 2], f[:, 3]))
 
 
 def _entry_columns(entries):
@@ -441,6 +455,24 @@ def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=Fals
     entries = _aligned_zeros((int(capacity), 4), np.uint32)
     call(entries, int(capacity))
     res = (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+    return res + (st.as_dict(),) if stats else res
+
+
+def nearest_k_bvh4(tris, bvh4, points, k, r_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.nearest_k (no GPU): the k triangles of `tris` nearest to each point over the tree set_bvh4(bvh4) installs, with the
+    device's bits and order.  bvh4 None needs brute_force=True.  Returns (dist, prim, u, v), each (n, k): row i in ascending order of
+    distance, padded with dist = +inf and prim = 0xFFFFFFFF.  The counters as a dict in fifth place with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    pts = _point_records(points, r_max)
+    n, k = pts.shape[0], int(k)
+    rows = _aligned_zeros((n * min(max(k, 0), PT_NEAREST_MAX_K), 4), np.uint32)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    _check(lib.pt_nearest_k_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                 pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF),
+                                 C.c_uint32(_nearest_flags(stats, simple, brute_force)), rows.ctypes.data_as(C.POINTER(PtClosest)),
+                                 C.byref(st) if stats else None))
+    res = _row_columns(rows, n, k)
     return res + (st.as_dict(),) if stats else res
 
 
@@ -1182,6 +1214,41 @@ class Context:
         stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_radius_search(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
                                       C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    # ---- k-nearest queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 19) ----
+    def nearest_k(self, points, k, r_max=None, stats=False, simple=False, brute_force=False):
+        """Which k triangles are nearest to each point?  Returns (dist, prim, u, v), each of shape (n, k): row i holds the at most k
+        triangles within r_max in ascending order of distance (equal distances in the walk's visit order; index order with brute_force),
+        padded with dist = +inf and prim = 0xFFFFFFFF; the contact point of an entry is v0 + u * (v1 - v0) + v * (v2 - v0) of triangle prim.
+        1 <= k <= PT_NEAREST_MAX_K (64).
+
+        points: as closest_points.  numpy arrays take the host route (staged, returns when done).  torch tensors on the context's device take
+        the device route: zero-copy for contiguous (n, 4) float32 records, no host synchronisation, ordered with torch's current stream both
+        ways; the results are torch tensors (prim as torch.uint32).
+        stats: the counting kernel, counters in stats() afterwards (stack_drops > 0 means that nearer triangles may be missing);
+        brute_force: every triangle in index order, no tree."""
+        flags = _nearest_flags(stats, simple, brute_force)
+        k = int(k)
+        if _is_torch(points):
+            _torch_route()
+            import torch
+            pts = self._point_tensor(points, r_max, "nearest_k")
+            n = pts.shape[0]
+            rows = torch.empty((n, min(max(k, 1), PT_NEAREST_MAX_K), 4), dtype=torch.int32, device=pts.device)
+            self._on_context_stream(pts.device, lambda: self.nearest_k_device(pts.data_ptr(), n, k, rows.data_ptr(), flags))
+            rf = rows.view(torch.float32)
+            return rf[:, :, 0], rows.view(torch.uint32)[:, :, 1], rf[:, :, 2], rf[:, :, 3]
+        pts = _point_records(points, r_max)
+        n = pts.shape[0]
+        rows = _aligned_zeros((n * min(max(k, 0), PT_NEAREST_MAX_K), 4), np.uint32)
+        self._ck(lib.pt_nearest_k_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(flags),
+                                       rows.ctypes.data_as(C.POINTER(PtClosest))))
+        return _row_columns(rows, n, k)
+
+    def nearest_k_device(self, ptr, n, k, out_ptr, flags=0):
+        """Raw device route: n PtPoint records at ptr -> n * k PtClosest records at out_ptr, row i at record i * k (16-byte aligned device
+        pointers).  Asynchronous on the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_nearest_k(self.h, C.c_void_p(ptr), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(flags), C.c_void_p(out_ptr)))
 
     def signed_distance(self, points, r_max=None, samples=3, seed=0, index_base=0, simple=False):
         """closest_points with the sign of contains: returns (dist, prim, u, v), dist negative where the point is inside (-inf: inside, and

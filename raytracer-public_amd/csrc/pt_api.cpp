@@ -2001,6 +2001,79 @@ int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* 
     return PT_OK;
 }
 
+// ---- k-nearest queries (include/mi355pt.h; pt_knn.hip) --------------------------------------------------------------------------
+
+static_assert(PT_NEAREST_MAX_K == ptk::kNearestMaxK && PT_NEAREST_MAX_K == pt::kNearestMaxK, "one PT_NEAREST_MAX_K for the header, the kernels and the twin");
+
+namespace {
+constexpr uint32_t kNearestFlags = PT_NEAREST_STATS | PT_NEAREST_SIMPLE_KERNEL | PT_NEAREST_BRUTE_FORCE;
+
+int check_nearest(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t k, uint32_t flags, const void* out) {
+    if (flags & ~kNearestFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (k == 0u || k > PT_NEAREST_MAX_K) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": k must be 1 .. PT_NEAREST_MAX_K");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
+    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
+    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
+    return PT_OK;
+}
+
+// the launch itself: points / rows in device memory, on the context's stream, behind whatever pt_set_batch still holds
+int nearest_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t k, uint32_t flags, void* out) {
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0u) return PT_OK;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool stats = (flags & PT_NEAREST_STATS) != 0, simple = (flags & PT_NEAREST_SIMPLE_KERNEL) != 0, brute = (flags & PT_NEAREST_BRUTE_FORCE) != 0;
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, ptk::nearest_k_waves_per_simd(k));
+    if (stats) {
+        ctx->stats_culled = 0;
+        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
+        A.stats = ctx->d_stats.ptr;
+    } else if (!simple && !brute) {
+        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_NK_SHORT_STACK));
+    }
+    PT_HIP(ctx, ptk::launch_nearest_k(A, points, out, n, k, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (stats) ctx->last_stats = true;
+    return PT_OK;
+}
+} // namespace
+
+int pt_nearest_k(PtContext* ctx, const void* points_device, uint64_t n, uint32_t k, uint32_t flags, void* out_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_nearest(ctx, "pt_nearest_k", points_device, n, k, flags, out_device)) return rc;
+    return nearest_on_stream(ctx, points_device, uint32_t(n), k, flags, out_device);
+}
+
+// staged through the buffers of the ray and closest-point queries: n points in, n * k records out
+int pt_nearest_k_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t k, uint32_t flags, PtClosest* out) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_nearest(ctx, "pt_nearest_k_host", points, n, k, flags, out)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;           // as pt_closest_points_host: before the staging; nearest_on_stream then finds nothing queued
+    if (n == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n) * k));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = nearest_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), k, flags, ctx->d_rq_hits.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * k * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_nearest_k_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
+                      uint32_t k, uint32_t flags, PtClosest* out, PtStats* stats) {
+    if (flags & ~kNearestFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: unknown flags");
+    if (k == 0u || k > PT_NEAREST_MAX_K) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: k must be 1 .. PT_NEAREST_MAX_K");
+    const bool brute = (flags & PT_NEAREST_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && (!points || !out)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: null pointer");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: more than 2^32 - 1 points");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::nearest_k(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, k,
+                       reinterpret_cast<uint32_t*>(out), (flags & PT_NEAREST_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
 int pt_set_batch(PtContext* ctx, uint32_t frames_per_launch) {
     if (int rc = bind(ctx)) return rc;
     if (int rc = flush_pending(ctx)) return rc;

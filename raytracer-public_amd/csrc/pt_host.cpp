@@ -807,6 +807,71 @@ bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
 }
 
 // ------------------------------------------------------------------------------------
+// k-nearest queries (host twin of pt_knn.hip): the closest-point walk with best2 replaced by worst2 -- r_max^2 while the list holds fewer
+// than k pairs, the d2 of its last pair after that -- and a list of at most k pairs (d2, triangle) in ascending order of d2, equal
+// distances in visit order
+// ------------------------------------------------------------------------------------
+bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n, uint32_t k,
+               uint32_t* out, uint64_t* counters, std::string& err) {
+    if (k == 0u || k > kNearestMaxK) { err = "nearest_k: k must be 1 .. 64"; return false; }
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers);
+    auto run = [&](uint64_t w) {
+        WalkCounters& cnt = per[w];
+        struct Pair { float d2; uint32_t tri; } lst[kNearestMaxK];
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            const float* q = points + i * 4;
+            float worst2 = q[3] * q[3];
+            uint32_t count = 0;
+            // pt_knn.hip::nk_insert: behind every pair with d2' <= d2, the tail shifted down from the end, the pair behind the k-th lost
+            auto leaf = [&](uint32_t t) {
+                const float d2 = record_d2(rec[t], q);
+                if (!(d2 < worst2)) return;
+                uint32_t j = count < k ? count : k - 1u;
+                for (; j > 0u && lst[j - 1u].d2 > d2; --j) lst[j] = lst[j - 1u];
+                lst[j].d2 = d2; lst[j].tri = t;
+                if (count < k) ++count;
+                if (count == k) worst2 = lst[k - 1u].d2;
+            };
+            if (ptcp::point_walked(q[0], q[1], q[2], q[3])) {
+                if (bvh4) walk_h(W, q, worst2, cnt, leaf);
+                else {
+                    for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+                    cnt.tris += num_tris;
+                }
+            }
+            uint32_t* o = out + i * k * 4;
+            for (uint32_t j = 0; j < count; ++j, o += 4) {
+                float u, v;
+                (void)record_uv_d2(rec[lst[j].tri], q, u, v);
+                o[0] = bits_of(std::sqrt(lst[j].d2)); o[1] = lst[j].tri; o[2] = bits_of(u); o[3] = bits_of(v);
+            }
+            for (uint32_t j = count; j < k; ++j, o += 4) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; }
+        }
+    };
+    if (workers == 1) run(0);
+    else {
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
 // Tiles: 8x8 pixels; tile (tx,ty) belongs to rank (tx + ty) % count.  A rank's tiles are
 // listed row-major; the list index is the tile's slot in the rank's compact buffer.
 // ------------------------------------------------------------------------------------

@@ -104,6 +104,15 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
 bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                    uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
 
+// ---- k-nearest queries (pt_nearest_k; host twin of pt_knn.hip, bit for bit) -----------------------------------------------------------
+// points: n x (x, y, z, r_max); out: n * k records of four words (dist bits, prim, u bits, v bits), row i at out + i * k * 4: the at most k
+// triangles nearest to point i within r_max in ascending order of distance, equal distances in visit order (index order without a tree),
+// padded with (+inf bits, 0xFFFFFFFF, 0, 0).  1 <= k <= kNearestMaxK, else false.  bvh4 = nullptr: every triangle in index order; else
+// closest_points' walk with best2 replaced by the k-th best d2 so far.  counters (optional): as closest_points.
+constexpr uint32_t kNearestMaxK = 64;    // include/mi355pt.h: PT_NEAREST_MAX_K
+bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n, uint32_t k,
+               uint32_t* out, uint64_t* counters, std::string& err);
+
 // ---- crossing counts and containment (pt_count_hits, pt_contains; host twin of pt_crossings.hip, bit for bit) --------------------------
 // rays: n x (org, t_max, dir, reserved); counts: n words.  bvh4 = nullptr: every triangle in index order; else the walk of the kernels over
 // build_wide_bvh(bvh4) and build_tri_records(tris): a record is counted when tri_hit holds and t < best = min(t_max, 1e30), which never

@@ -85,6 +85,24 @@
 #ifndef PT_RD_FILL
 #define PT_RD_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
 #endif
+// k-nearest queries (pt_knn.hip).  The short stack and the fill are the point queries' values taken over: tools/knn_bench.py ran with them
+// (profiles/knn_ab.json), no other value has been tried, so as choices they are unmeasured.  The waves per SIMD follow from the LDS of a one-wavefront workgroup, 8 * 64 * (PT_NK_SHORT_STACK + KCAP)
+// bytes: floor(floor(163,840 / LDS) / 4), capped at the point queries' 6 -- 8,192 B, 14,336 B and 38,912 B for the tiers 4, 16 and 64.
+#ifndef PT_NK_SHORT_STACK
+#define PT_NK_SHORT_STACK 12        // LDS stack entries per lane of nearest_k_kernel<KCAP>; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_NK_FILL
+#define PT_NK_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
+#endif
+#ifndef PT_NK_WAVES_PER_SIMD_4
+#define PT_NK_WAVES_PER_SIMD_4 5    // wavefronts of nearest_k_kernel<4> per SIMD in the launch grid (what its LDS allows)
+#endif
+#ifndef PT_NK_WAVES_PER_SIMD_16
+#define PT_NK_WAVES_PER_SIMD_16 2   // the same of nearest_k_kernel<16>
+#endif
+#ifndef PT_NK_WAVES_PER_SIMD_64
+#define PT_NK_WAVES_PER_SIMD_64 1   // the same of nearest_k_kernel<64>
+#endif
 #ifndef PT_FILL_THRESHOLD
 #define PT_FILL_THRESHOLD 4        // hand out ready camera rays when this many lanes of a wavefront are without a path (a fetch from the ray buffer is cheap: 4 beats 8 by 2 %)
 #endif
@@ -278,6 +296,16 @@ hipError_t launch_radius(const RenderArgs& A, const void* points, uint32_t n, vo
 // item n read as 0); temp: at least radius_scan_temp_bytes(n) bytes
 size_t radius_scan_temp_bytes(uint32_t n);
 hipError_t launch_radius_scan(const void* counts, uint32_t n, unsigned long long* offsets, void* temp, size_t temp_bytes, hipStream_t stream);
+// ---- k-nearest queries (pt_knn.hip): the k closest triangles to each point ----------------------------------------------------------
+// points: PtPoint[n] (float4 each, 16-byte aligned); out: PtClosest[n * k] (uint4 each), row i at out[i * k], sorted by distance and padded
+// with (+inf, 0xFFFFFFFF, 0, 0); 1 <= k <= kNearestMaxK.  One launch, the closest-point walk with best2 replaced by the k-th best squared
+// distance so far.  brute: every triangle in index order; simple or stats: one point per thread (stats: PtStats counters into A.stats,
+// zeroed by the caller); else the persistent kernel of the smallest capacity tier (4, 16, 64) that holds k, with `grid` wavefronts at most
+// (walk_grid(.., nearest_k_waves_per_simd(k))), the queue block and walk_spill_entries(grid, PT_NK_SHORT_STACK) spill entries.
+constexpr uint32_t kNearestMaxK = 64;    // include/mi355pt.h: PT_NEAREST_MAX_K
+uint32_t nearest_k_waves_per_simd(uint32_t k);
+hipError_t launch_nearest_k(const RenderArgs& A, const void* points, void* out, uint32_t n, uint32_t k, bool simple, bool stats, bool brute,
+                            unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- refit in place (pt_refit.hip): pt_update_triangles, pt_bvh_cost ------------------------------------------------------
 // What the climb needs beyond the reference's BVH4, derived once per installed tree (on the device for a tree this library built,
 // launch_refit_prepare4; on the host for an installed one, pt::refit_plan4 -- the same contents):

@@ -232,6 +232,24 @@ class PathTracer {
     return { count: s.prim.length, dist: s.dist, prim: s.prim, u: s.u, v: s.v };
   }
 
+  // ---- k-nearest queries: an extension beyond the reference (include/mi355pt.h pt_nearest_k, DESIGN.md section 19) ----
+  // points: Float32Array, 4 floats per point (x, y, z, rMax; rMax = Infinity for no limit); k: 1 .. 64.  Resolves to { k, dist, prim, u, v }
+  // (Float32Array / Uint32Array of n * k): row i at [i * k, i * k + k) holds the at most k triangles within rMax in ascending order of
+  // distance, each with its contact point v0 + u (v1 - v0) + v (v2 - v0), padded with dist = Infinity, prim = 0xFFFFFFFF, u = v = 0.
+  // options.rMax: a number that replaces the fourth float of every point (the caller's array is not written); options.bruteForce: every
+  // triangle, no tree; options.simple: the one-point-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
+  async nearestK(points, k, options) {
+    const o = options || {}, flags = (o.simple ? 2 : 0) | (o.bruteForce ? 4 : 0), p = this._radiusPoints(points, o.rMax);
+    return this.group ? native().groupNearestK(this.group, p, k, flags) : native().nearestK(this.device, p, k, flags);
+  }
+  // The k triangles nearest to (x, y, z): resolves to { count, dist, prim, u, v } without the padding, nearest first.
+  async kNearest(x, y, z, k, options) {
+    const r = await this.nearestK(Float32Array.of(x, y, z, Infinity), k, options);
+    let count = 0;
+    while (count < r.prim.length && r.prim[count] !== 0xFFFFFFFF) ++count;
+    return { count: count, dist: r.dist.slice(0, count), prim: r.prim.slice(0, count), u: r.u.slice(0, count), v: r.v.slice(0, count) };
+  }
+
   // ---- batched ambient-occlusion queries: an extension beyond the reference (include/mi355pt.h pt_occlusion, DESIGN.md section 16) ----
   // surfels: Float32Array, 8 floats per surfel (point xyz, rMax, unit normal xyz, 0).  options: { samples (16), seed (0), bias (1e-4),
   // indexBase (0), simple }.  Resolves to { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }: of `samples`

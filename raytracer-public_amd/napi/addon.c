@@ -398,6 +398,43 @@ static napi_value fn_closest_points(napi_env env, napi_callback_info info) {    
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- k-nearest queries (an extension beyond the reference; include/mi355pt.h pt_nearest_k_host) ------------------------------------- */
+
+/* points: Float32Array of 4 floats per point (PtPoint: x, y, z, rMax), k: 1 .. PT_NEAREST_MAX_K -> { k, dist: Float32Array of n * k, prim:
+ * Uint32Array, u, v }: row i at [i * k, i * k + k), ascending by dist, padded with dist = Infinity and prim = 0xFFFFFFFF; flags: PT_NEAREST_* */
+static napi_value nearest_k_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value k_v, napi_value flags_v) {
+    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 4) { napi_throw_range_error(env, NULL, "nearestK: 4 floats per point"); return NULL; }
+    const uint32_t k = get_u32(env, k_v), flags = get_u32(env, flags_v);
+    if (k == 0 || k > PT_NEAREST_MAX_K) { napi_throw_range_error(env, NULL, "nearestK: k must be 1 .. 64"); return NULL; }
+    const size_t n = len / 4, m = n * k;
+    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
+    PtClosest* res = (PtClosest*)aligned_alloc(16, (m ? m : 1) * sizeof(PtClosest));
+    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(pts, d, n * sizeof(PtPoint));
+    int rc = pt_nearest_k_host(ctx, pts, n, k, flags, res);
+    free(pts);
+    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_nearest_k_host"); }
+    napi_value o, kv, dist, prim, u, v; void *pd, *pp, *pu, *pv;
+    if (!(dist = make_typed(env, napi_float32_array, 4, m, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) ||
+        !(u = make_typed(env, napi_float32_array, 4, m, &pu)) || !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(res); return NULL; }
+    for (size_t i = 0; i < m; ++i) {
+        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
+    }
+    free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_uint32(env, k, &kv));
+    napi_set_named_property(env, o, "k", kv);
+    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_nearest_k(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array points, k, flags) */
+    napi_value argv[4]; if (!get_args(env, info, 4, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return nearest_k_on(env, ctx, argv[1], argv[2], argv[3]);
+}
+
 /* ---- radius queries (an extension beyond the reference; include/mi355pt.h pt_radius_count_host, pt_radius_search_host) ---------------- */
 
 static PtPoint* radius_points(napi_env env, napi_value points_v, const char* what, size_t* n) {
@@ -857,6 +894,12 @@ static napi_value fn_group_signed_distance(napi_env env, napi_callback_info info
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return signed_distance_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_nearest_k(napi_env env, napi_callback_info info) {     /* (group, points, k, flags): on member 0 */
+    napi_value argv[4]; if (!get_args(env, info, 4, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return nearest_k_on(env, ctx, argv[1], argv[2], argv[3]);
+}
 static napi_value fn_group_radius_count(napi_env env, napi_callback_info info) {   /* (group, points, flags): on member 0 */
     napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -935,6 +978,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
         {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
         {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
+        {"nearestK", fn_nearest_k}, {"groupNearestK", fn_group_nearest_k},
         {"radiusCount", fn_radius_count}, {"groupRadiusCount", fn_group_radius_count}, {"radiusSearch", fn_radius_search}, {"groupRadiusSearch", fn_group_radius_search},
         {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
