@@ -208,6 +208,22 @@ def shrink_case(tris, bvh4, rays, bounded, steps=16):
     raise AssertionError("no node to damage")
 
 
+def point_passes(tris, rays):
+    """[(points, k, the rays count_hits takes or None)] of treeaudit.audit_points"""
+    return [(ta.near_points(rays, tris), ta.K_NEAR, rays), (ta.far_points(tris), ta.K_FAR, None)]
+
+
+def judged_points(ctx, tris, passes, kernels):
+    """Every pass through every kernel: yields (points, rays, simple, results, {query: judgement}); a damaged tree may lose triangles, but
+    it reports nothing the reference cannot accept and no malformed list."""
+    for pts, k, rr in passes:
+        for simple in kernels:
+            res = ta.point_queries(ctx, pts, rr, simple, k)
+            js = ta.judge_points(tris, pts, rr, res, k)
+            assert all(len(j.phantom) == 0 and len(j.malformed) == 0 for j in js.values())
+            yield pts, rr, simple, res, js
+
+
 def check_detection(ctx, tris, good, kernels):
     """Three damaged copies of the correct tree `good`, each installed with ctx.set_bvh4."""
     rays = ta.aimed_rays(tris)
@@ -232,6 +248,33 @@ def check_detection(ctx, tris, good, kernels):
             assert set(j.lost_tris.tolist()) <= set(r.outside["tri"].tolist())       # every loss is attributed
             with pytest.raises(AssertionError, match="lost triangles.*%d" % node):
                 ta.assert_judged(j, "shrunk box", r)
+    #    The point queries prune by bound2, restated in float64 with its slack: a point whose bound2 to the shrunk box
+    #    exceeds r_max^2 cannot reach its triangle (radius: lost, no exception; closest and k-nearest: its own triangle is not reported; the
+    #    judge excuses it only where a nearer triangle answers), one whose bound2 is below r_max^2 still finds it in its radius list.
+    passes = point_passes(tris, rays)
+    outside, seen = set(r.outside["tri"].tolist()), {}
+    for pts, rr, simple, res, js in judged_points(ctx, tris, passes, kernels):
+        pidx = idx if pts.what == "near" else below
+        b2 = ta.bound2_f64(pts.P[pidx], box[:3], box[3:])
+        r2 = pts.r_max[pidx].astype(np.float64) ** 2
+        must = pidx[pts.auditable[pidx] & (b2 > r2 * (1 + 1e-3))]
+        keep = set(pidx[b2 < r2 * (1 - 1e-3)].tolist())
+        for j in js.values():
+            assert set(j.lost_tris.tolist()) <= outside <= set(below.tolist()), (pts.what, simple, j.query)     # every lost triangle lies below the damaged node
+        lost = set(js["radius"].lost.tolist())
+        assert set(must.tolist()) <= lost and not lost & keep and lost <= set(pidx.tolist()), (pts.what, simple, len(must), len(lost))
+        assert np.all(res["closest"][1][must] != pts.tri[must]) and not (res["knn"][1][must] == pts.tri[must, None]).any()
+        assert set(must.tolist()) <= set(js["closest"].lost.tolist()) | set(np.flatnonzero(js["closest"].excused).tolist())
+        if rr is not None:                                                            # count_hits prunes at t_max, on the host as on the device
+            meets_c, misses_c = ta.segment_meets_box(rays, idx, box[:3], box[3:], True)
+            lost_c = set(js["hits"].lost.tolist())
+            assert set(idx[misses_c & js["hits"].auditable[idx]].tolist()) <= lost_c and not lost_c & set(idx[meets_c].tolist()) and lost_c <= set(idx.tolist())
+        seen[pts.what] = (len(must), len(keep), len(lost))
+        if lost:
+            with pytest.raises(AssertionError, match="lost triangles.*%d" % node):
+                ta.assert_point_judged(js["radius"], "shrunk box", r)
+    print("shrunk box %d: points that must be lost / must be kept / lost by radius_search -- %s" % (node, seen))
+    assert seen["near"][0] > 0 and seen["near"][1] > 0 and seen["near"][2] > 0     # without the damage nothing is lost: the audit sees this box
     # 2. two leaves' triangle indices swapped, boxes left: both leaves flagged, and only they
     rec = good[1:].reshape(-1, 8)
     leaves = np.flatnonzero(rec[:, 7] & 0x80000000)
@@ -245,6 +288,22 @@ def check_detection(ctx, tris, good, kernels):
     ctx.set_bvh4(bad)
     j = ta.judge(tris, rays, ctx.trace_rays(rays.O, rays.D, t_max=rays.t_max, simple=kernels[0]))
     assert set(j.lost_tris.tolist()) == {ta_, tb_}
+    #    Points: the walk meets each triangle in the other's leaf, so a point finds its own triangle only if that leaf's box lies within
+    #    r_max (and the slack) of it.  Which of the two applies is computed from the boxes and printed: apart (as in the scenes of these
+    #    tests, where the two leaves are a third of the tree apart), the radius lists must name both triangles and no other; within reach,
+    #    the audit may name either, neither or both, and nothing but them.
+    box_of = {ta_: ta.decode(good[1 + 8 * b: 4 + 8 * b]), tb_: ta.decode(good[1 + 8 * a: 4 + 8 * a])}           # the box each triangle now sits in
+    for pts, rr, simple, res, js in judged_points(ctx, tris, passes, kernels):
+        apart = True
+        for t, bx in box_of.items():
+            pi = np.flatnonzero(pts.tri == t)
+            apart &= bool(np.all(pts.auditable[pi] & (ta.bound2_f64(pts.P[pi], bx[:3], bx[3:]) > pts.r_max[pi].astype(np.float64) ** 2 * (1 + 1e-3))))
+        print("swapped leaves, %s pass, simple %d: %s" % (pts.what, simple, "the boxes are apart: both triangles must be named" if apart else
+              "the boxes lie within r_max + s of each other's points: the audit need not name the triangles"))
+        assert all(set(j.lost_tris.tolist()) <= {ta_, tb_} for j in js.values())
+        if apart:
+            assert set(js["radius"].lost_tris.tolist()) == {ta_, tb_}
+            assert {ta_, tb_} <= set(js["closest"].lost_tris.tolist()) | set(pts.tri[js["closest"].excused].tolist())
     # 3. one box enlarged: no ray can see it, the no-loose-boxes check does
     bad = good.copy()
     o = ord16(halves(bad[1 + 8 * node: 4 + 8 * node]))
@@ -255,6 +314,8 @@ def check_detection(ctx, tris, good, kernels):
     ctx.set_bvh4(bad)
     j = ta.judge(tris, rays, ctx.trace_rays(rays.O, rays.D, t_max=rays.t_max, simple=kernels[0]))
     assert len(j.lost) == 0
+    for pts, rr, simple, res, js in judged_points(ctx, tris, passes, kernels):
+        assert all(len(j.lost) == 0 for j in js.values())                             # invisible to the points as to the rays
     with pytest.raises(AssertionError, match="not the rule's"):
         ta.assert_tree(r, "enlarged box")
 

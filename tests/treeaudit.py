@@ -1,6 +1,6 @@
 """An exhaustive audit of a BVH as the traversal sees it: every triangle of every tree, not the rays a test happens to sample.
 
-Two checks, both O(N) on the reference side, numpy and float64 only -- no oracle, no product code:
+Three checks, all O(N) on the reference side, numpy and float64 only -- no oracle, no product code:
 
 1. verify_bvh4 / verify_bvh2: a proof on the words read back from the device (read_bvh4 / read_bvh2).  Topology (every reachable node
    reached once, every triangle in exactly one reachable leaf, child counts, pre-order for trees this library builds); transitive
@@ -9,6 +9,9 @@ Two checks, both O(N) on the reference side, numpy and float64 only -- no oracle
    DESIGN.md sections 3 and 14 give, stated in the ordered-integer form of f16).  Vectorised level by level.
 2. aimed_rays / judge: four rays aimed at every triangle, traced by the code under test and judged by float64 Moeller-Trumbore
    (pathref.pair) against that triangle alone, and against the triangle the code reported.
+3. near_points / far_points / judge_closest, judge_radius, judge_knn, judge_counts / audit_points: the origins of those rays, and one point
+   farther above every centroid, through the closest-point, radius, k-nearest and crossing-count queries, judged by float64 point-triangle
+   distances (closestref) against that triangle and the reported ones alone: O(points + listed entries).
 
 The megakernel's own traversal (pt_megakernel_loop.inc) cannot be reached by caller rays, so check 2 does not cover it; it stays covered by
 the sampled pathref renders and by bit equality with the other kernels over the same arena, which check 1 does cover.
@@ -18,6 +21,8 @@ import time
 
 import numpy as np
 
+import closest_cases as clc
+import closestref
 import pathref
 from refit_cases import INVALID, LEAF, halves, ord16, unord16
 
@@ -490,6 +495,314 @@ class HostContext:
             _, uu, vv, _ = pathref.pair(self.tris, O[hit], D[hit], prim[hit], np.float32)
             u[hit], v[hit] = uu, vv
         return t, prim, u, v
+
+    # ---- the point and crossing-count queries: the host twins, their counters kept for stats() as a device context keeps them ----
+    def stats(self):
+        return self._stats
+
+    def _twin(self, fn, *a, **kw):
+        res = fn(self.tris, self.b4, *a, stats=True, **{k: v for k, v in kw.items() if k != "stats"})
+        self._stats = res[-1]
+        return res[:-1]
+
+    def closest_points(self, points, r_max=None, **kw):
+        return self._twin(self.rt.closest_points_bvh4, points, r_max, **kw)
+
+    def radius_search(self, points, r_max=None, **kw):
+        return self._twin(self.rt.radius_search_bvh4, points, r_max, **kw)
+
+    def radius_count(self, points, r_max=None, **kw):
+        return np.diff(self._twin(self.rt.radius_search_bvh4, points, r_max, capacity=0, **kw)[0].astype(np.int64)).astype(np.uint32)
+
+    def nearest_k(self, points, k, r_max=None, **kw):
+        return self._twin(self.rt.nearest_k_bvh4, points, k, r_max, **kw)
+
+    def count_hits(self, origins, directions=None, t_max=None, **kw):
+        return self._twin(self.rt.count_hits_bvh4, origins, directions, t_max, **kw)[0]
+
+
+# ---- aimed points: the point and crossing-count queries ---------------------------------------------------------------------------------
+H2_REL = 16 * 2.0 ** -12             # the far pass: sixteen times the slack s = 2^-12 of bound2
+K_NEAR, K_FAR = 8, 64                # nearest_k's k in the two passes
+
+
+class Points:
+    """P (R, 3) and r_max (R,) in f32; tri (R,): the triangle point i is aimed at; what: "near" or "far".  The float64 side, filled in by
+    the first judge: tol, d_own, auditable, and a memo of every (point, triangle) distance a judge has asked for."""
+
+    def __init__(self, tris, P, r_max, tri, what):
+        self.tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+        self.P, self.r_max, self.tri, self.what = np.ascontiguousarray(P, np.float32), np.ascontiguousarray(r_max, np.float32), np.asarray(tri, np.int64), what
+        self.n, self.R = self.tris.size // 9, len(self.tri)
+        self.tol = clc.tolerance(self.P, self.tris) if self.R else 0.0
+        self._keys, self._d = np.zeros(0, np.int64), np.zeros(0)
+        self.d_own = self.distance(np.arange(self.R), self.tri)
+        r = self.r_max.astype(np.float64)
+        self.auditable = (self.d_own >= 4 * self.tol) & (self.d_own <= r - 4 * self.tol)
+
+    def records(self):
+        return np.concatenate([self.P, self.r_max[:, None]], 1)
+
+    def distance(self, idx, prim):
+        """closestref.distance_to(P[idx], triangle prim), each pair evaluated once however many kernels report it."""
+        keys = (np.asarray(idx, np.int64) << 32) | np.asarray(prim, np.int64)
+        pos = np.minimum(np.searchsorted(self._keys, keys), max(len(self._keys) - 1, 0))
+        known = self._keys[pos] == keys if len(self._keys) else np.zeros(len(keys), bool)
+        out = np.empty(len(keys))
+        out[known] = self._d[pos[known]]
+        new, inv = np.unique(keys[~known], return_inverse=True)
+        if len(new):
+            d = closestref.distance_to(self.P[new >> 32], self.tris, new & 0xFFFFFFFF)
+            out[~known] = d[inv]
+            k = np.concatenate([self._keys, new]); order = np.argsort(k, kind="stable")
+            self._keys, self._d = k[order], np.concatenate([self._d, d])[order]
+        return out
+
+    def uv_distance(self, idx, prim, u, v):
+        """float64 distance from P[idx] to the point (u, v) of triangle prim."""
+        return np.linalg.norm(self.P[idx].astype(np.float64) - clc.closest_point_of(self.tris, prim, u, v), axis=1)
+
+
+def near_points(rays, tris):
+    """The near pass: the origins of aimed_rays -- P + s h' n at the four barycentric positions, h' = H_REL max(1, |P|inf) with the sliver
+    rule as it is -- with r_max = 2 h', the ray's t_max."""
+    return Points(tris, rays.O, rays.t_max, rays.tri, "near")
+
+
+def far_points(tris):
+    """The far pass: one point per triangle, H2 = 16 * 2^-12 * max(1, |c|inf) above (even triangles) or below (odd) the centroid c, with
+    r_max = 2 H2.  bound2 carries a slack of s = 2^-12, more than the near pass's r_max of about 2e-4: there every box close to the point is
+    entered and pruning at the leaves' level never decides anything.  Sixteen times s makes it decide."""
+    T = np.asarray(tris, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    n = len(T)
+    c = np.cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+    ln = np.sqrt((c * c).sum(1))
+    with np.errstate(all="ignore"):
+        nrm = np.where((ln > 0)[:, None] & np.isfinite(ln)[:, None], c / ln[:, None], np.array([0.0, 0.0, 1.0]))
+    cen = T.mean(1)
+    s = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    h2 = H2_REL * np.maximum(1.0, np.abs(cen).max(-1))
+    return Points(tris, cen + (s * h2)[:, None] * nrm, 2 * h2, np.arange(n), "far")
+
+
+class PointJudgement:
+    """Per point and query.  lost: points whose own triangle the query must have reported and did not; phantom: points with an entry the
+    reference cannot accept (a triangle beyond the count, a dist or (u, v) point more than tol from the float64 distance of the reported
+    triangle, a triangle beyond r_max + tol), malformed: points whose list or row breaks the form (a triangle twice, a row out of order or
+    badly padded, a count that is not the list's length).  excused: auditable points that say nothing about their own triangle --
+    answered by a nearer triangle (closest), a full row of certain neighbours (k-nearest); never used by the radius and count judges."""
+
+    def summary(self):
+        return "%s pass, %d triangles, %d points: not auditable %.3f %%, %s %.3f %% (%d points), lost %d (triangles %d), phantom %d, malformed %d, %d entries; reference %.2f s" % (
+            self.what, self.n, self.R, 100 * self.share_not_auditable, self.excuse, 100 * self.share_excused, int(self.excused.sum()),
+            len(self.lost), len(self.lost_tris), len(self.phantom), len(self.malformed), self.entries, self.seconds)
+
+    def counts(self):
+        """the figures two runs over the same bits must share"""
+        return (self.R, int((~self.auditable).sum()), int(self.excused.sum()), len(self.lost), len(self.lost_tris), len(self.phantom), len(self.malformed), self.entries)
+
+
+def _point_judgement(pts, query, excuse, t0, lost, phantom, malformed, excused, entries):
+    j = PointJudgement()
+    j.query, j.what, j.excuse, j.n, j.R, j.tri, j.auditable = query, pts.what, excuse, pts.n, pts.R, pts.tri, pts.auditable
+    j.lost, j.phantom, j.malformed = np.flatnonzero(lost), np.flatnonzero(phantom), np.flatnonzero(malformed)
+    j.excused = excused & pts.auditable
+    j.lost_tris = np.unique(pts.tri[j.lost])
+    j.share_not_auditable = float((~pts.auditable).mean()) if pts.R else 0.0
+    j.share_excused = float(j.excused.mean()) if pts.R else 0.0
+    j.entries = int(entries)
+    j.seconds = time.time() - t0
+    return j
+
+
+def _entries_off(pts, idx, dist, prim, u, v):
+    """The value rules of a reported entry (point idx[i], triangle prim[i] < n): -> (float64 distance of prim, bool: the entry is a phantom).
+    |dist - d_f64| <= tol, the (u, v) point within tol of that distance (closest_cases.deviations' rule), and d_f64 <= r_max + tol."""
+    d = pts.distance(idx, prim)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(dist.astype(np.float64) - d) <= pts.tol) & (np.abs(pts.uv_distance(idx, prim, u, v) - d) <= pts.tol) & (d <= pts.r_max[idx].astype(np.float64) + pts.tol)
+    return d, ~ok
+
+
+def judge_closest(tris, pts, got):
+    """got = (dist, prim, u, v) of closest_points over pts.records().  Lost: an auditable point reports nothing, or a triangle whose float64
+    distance exceeds d_own + tol.  Answered by another triangle (excused, capped): prim != own and d_f64(prim) < d_own - tol."""
+    t0 = time.time()
+    dist, prim, u, v = [np.asarray(a) for a in got]
+    found = prim != MISS
+    inr = found & (prim < pts.n)
+    idx = np.flatnonzero(inr)
+    d, off = _entries_off(pts, idx, dist[idx], prim[idx], u[idx], v[idx])
+    phantom = found & ~inr
+    phantom[idx[off]] = True
+    drep = np.full(pts.R, np.inf); drep[idx] = d
+    lost = pts.auditable & (drep > pts.d_own + pts.tol)
+    other = inr & (prim.astype(np.int64) != pts.tri) & (drep < pts.d_own - pts.tol)
+    return _point_judgement(pts, "closest_points", "answered by another triangle", t0, lost, phantom, np.zeros(pts.R, bool), other, len(idx))
+
+
+def judge_radius(tris, pts, offsets, entries, counts=None):
+    """offsets and entries = (dist, prim, u, v) of radius_search, counts of radius_count.  No point is excused: a nearer neighbour does not
+    excuse a missing triangle.  Lost: the own triangle of an auditable point is not in its list."""
+    t0 = time.time()
+    off = np.asarray(offsets).astype(np.int64)
+    dist, prim, u, v = [np.asarray(a) for a in entries]
+    assert len(off) == pts.R + 1 and off[0] == 0 and off[-1] == len(prim) and np.all(np.diff(off) >= 0), "offsets are no offsets into the entries"
+    owner = np.repeat(np.arange(pts.R), np.diff(off))
+    phantom = np.zeros(pts.R, bool); malformed = np.zeros(pts.R, bool)
+    inr = prim < pts.n
+    phantom[owner[~inr]] = True
+    d, bad = _entries_off(pts, owner[inr], dist[inr], prim[inr], u[inr], v[inr])
+    phantom[owner[inr][bad]] = True
+    keys = np.sort((owner << 32) | prim.astype(np.int64))
+    malformed[keys[1:][keys[1:] == keys[:-1]] >> 32] = True                    # a triangle twice in one list
+    if counts is not None:
+        malformed |= np.asarray(counts).astype(np.int64) != np.diff(off)
+    lost = pts.auditable & ~np.isin((np.arange(pts.R) << 32) | pts.tri, keys)
+    return _point_judgement(pts, "radius_search", "excused", t0, lost, phantom, malformed, np.zeros(pts.R, bool), len(prim))
+
+
+def judge_knn(tris, pts, rows, k):
+    """rows = (dist, prim, u, v), each (R, k), of nearest_k.  Form: the listed entries first, in ascending order of
+    dist, distinct triangles, then padding of dist = +inf, prim = 0xFFFFFFFF, u = v = 0.  Lost: own is absent from the row of an auditable
+    point -- unless all k entries have d_f64 <= d_own + tol, a full row of certain neighbours (excused, capped)."""
+    t0 = time.time()
+    dist, prim, u, v = [np.ascontiguousarray(a).reshape(pts.R, k) for a in rows]
+    listed = prim != MISS
+    pad_ok = listed | ((dist.view(np.uint32) == 0x7F800000) & (u.view(np.uint32) == 0) & (v.view(np.uint32) == 0))
+    with np.errstate(invalid="ignore"):
+        malformed = ~pad_ok.all(1) | (listed[:, :-1] < listed[:, 1:]).any(1) | (listed[:, 1:] & ~(dist[:, :-1] <= dist[:, 1:])).any(1)
+    p64 = np.where(listed, prim.astype(np.int64), (1 << 40) + np.arange(k)[None, :])
+    srt = np.sort(p64, 1)
+    malformed |= (srt[:, 1:] == srt[:, :-1]).any(1)
+    inr = listed & (prim < pts.n)
+    pi, col = np.nonzero(inr)
+    d, bad = _entries_off(pts, pi, dist[pi, col], prim[pi, col], u[pi, col], v[pi, col])
+    phantom = (listed & ~inr).any(1)
+    phantom[pi[bad]] = True
+    drow = np.full((pts.R, k), np.inf); drow[pi, col] = d
+    has_own = (p64 == pts.tri[:, None]).any(1)
+    crowded = ~has_own & (drow <= (pts.d_own + pts.tol)[:, None]).all(1)
+    lost = pts.auditable & ~has_own & ~crowded
+    return _point_judgement(pts, "nearest_k %d" % k, "a full row of certain neighbours", t0, lost, phantom, malformed, crowded, len(pi))
+
+
+def judge_counts(rays, counts, tris=None):
+    """counts of count_hits over the aimed rays (t_max = 2 h').  Lost: a count of 0 on a ray whose own triangle margins() accepts with every
+    margin to spare (rays.own, computed once per ray set)."""
+    t0 = time.time()
+    if rays.own is None:
+        rays.own = margins(tris, rays.O, rays.D, rays.tri, rays.t_max)
+    counts = np.asarray(counts)
+    j = PointJudgement()
+    j.query, j.what, j.excuse, j.n, j.R, j.tri, j.auditable = "count_hits", "near", "excused", rays.n, len(rays.tri), rays.tri, rays.own["tight"]
+    j.lost = np.flatnonzero(j.auditable & (counts == 0))
+    j.phantom = j.malformed = np.zeros(0, np.int64)
+    j.excused = np.zeros(j.R, bool)
+    j.lost_tris = np.unique(rays.tri[j.lost])
+    j.share_not_auditable = float((~j.auditable).mean()) if j.R else 0.0
+    j.share_excused, j.entries, j.seconds = 0.0, int(counts.sum()), time.time() - t0
+    return j
+
+
+def assert_point_judged(j, name, tree=None, capped=True):
+    """No lost triangle, no phantom, no malformed list; and (capped) the points this audit cannot use -- not auditable, answered by another
+    triangle, a full row of certain neighbours -- each at most pathref.FRAGILE_CAP of the case.  `tree`: a TreeReport, or a function that
+    makes one, asked only when a triangle is lost."""
+    print("%s %s %s" % (name, j.query, j.summary()))
+    if len(j.lost_tris):
+        if callable(tree):
+            tree = tree()
+        why = "" if tree is None else "; boxes they leave (tri -> nodes): %s" % {int(t): tree.leaves_box_of(t).tolist() for t in j.lost_tris[:10]}
+        raise AssertionError("%s %s, %s pass: %d lost triangles, first %s%s" % (name, j.query, j.what, len(j.lost_tris), j.lost_tris[:20].tolist(), why))
+    assert len(j.phantom) == 0, "%s %s, %s pass: %d points report an entry the reference cannot accept, first points %s" % (name, j.query, j.what, len(j.phantom), j.phantom[:10].tolist())
+    assert len(j.malformed) == 0, "%s %s, %s pass: %d points with a malformed list, row or count, first points %s" % (name, j.query, j.what, len(j.malformed), j.malformed[:10].tolist())
+    if capped:
+        cap = pathref.FRAGILE_CAP
+        assert j.share_not_auditable <= cap, "%s %s, %s pass: %.2f %% of the points are not auditable (cap 2 %%): change the scene or the distance" % (name, j.query, j.what, 100 * j.share_not_auditable)
+        assert j.share_excused <= cap, "%s %s, %s pass: %.2f %% of the points are %s (cap 2 %%): change the scene or the distance" % (name, j.query, j.what, 100 * j.share_excused, j.excuse)
+
+
+def bound2_f64(p, lo, hi, s=2.0 ** -12):
+    """bound2 of DESIGN.md section 15 restated in float64, slack included: per axis g = max(mn - (p + s), (p - s) - mx, 0), the sum of the squares."""
+    p = np.asarray(p, np.float64)
+    g = np.maximum(np.maximum(lo - (p + s), (p - s) - hi), 0.0)
+    return (g * g).sum(-1)
+
+
+def point_queries(ctx, pts, rays, simple, k, stats=False, closest=True):
+    """The five calls over one pass, as their judges take them: -> dict(closest, count, search, knn[, hits]; drops: stack_drops per call with stats)."""
+    rec = pts.records()
+    out, drops = {}, []
+
+    def run(key, call, *a, **kw):
+        out[key] = call(*a, simple=simple, stats=stats, **kw)
+        if stats:
+            drops.append(int(ctx.stats()["stack_drops"]))
+    if closest:
+        run("closest", ctx.closest_points, rec)
+    run("count", ctx.radius_count, rec)
+    run("search", ctx.radius_search, rec)
+    run("knn", ctx.nearest_k, rec, k)
+    if rays is not None:
+        run("hits", ctx.count_hits, rays.O, rays.D, t_max=rays.t_max)
+    out["drops"] = drops
+    return out
+
+
+def judge_points(tris, pts, rays, res, k):
+    """-> {query: judgement} for one point_queries result."""
+    out = dict(radius=judge_radius(tris, pts, res["search"][0], res["search"][1:], res["count"]), knn=judge_knn(tris, pts, res["knn"], k))
+    if "closest" in res:
+        out["closest"] = judge_closest(tris, pts, res["closest"])
+    if "hits" in res:
+        out["hits"] = judge_counts(rays, res["hits"], tris)
+    return out
+
+
+def audit_points(ctx, tris, name, rays=None, kernels=KERNELS, capped=True, tree=None, far_closest=True, passes=None):
+    """Every triangle through the point and crossing-count queries of `ctx` (a device context or HostContext): the near pass (the origins of
+    the aimed rays, r_max = 2 h', k = 8; the same records as rays through count_hits) and the far pass (far_points, k = 64), each through
+    closest_points, radius_count + radius_search and nearest_k of every kernel in `kernels`, each result through its judge.  The counting
+    variant of every query runs once per pass and must drop nothing at the 64-entry cap: everything the judges hold is what a walk without
+    drops owes.  -> {(pass, simple): {query: judgement}}.
+
+    Measured on the CPU over the host twins, all points, built and refitted after `wave` and `deform`, accel 0, 1 and 2 (tests/test_point_audit.py
+    prints them) -- points not auditable / answered by another triangle (closest) / a full row of certain neighbours (k-nearest):
+      (no point of any scene below was not auditable, no k-nearest row was full of certain neighbours: 0 % / . / 0 % throughout; the figures
+      are the closest-point shares, built / after wave / after deform, the largest of the three accel levels)
+                                        near pass                      far pass
+      soups 1, 2, 3, 4, 5, 64, 65       0 / 0 / 0 %                    0 / 0 / 0 %
+      soup 777                          0 / 0.03 / 0.03 %              0.39 / 0.64 / 0.77 %
+      soup 30,000 (size 0.2)            0.41 / 0.46 / 0.32 %           17.8 / 19.3 / 10.2 %      no far closest; deform is of the same soup at size 0.1
+                                                                                                 (at size 0.2 it gives 1.01 % in the near pass)
+      soup 30,000, size 0.02            0.002 / 0.002 / 0.015 %        0.58 / 0.64 / 1.13 %      no far closest after deform
+      soup 120,000, size 0.02           0.016 / 0.020 / 0.061 %        2.41 / 2.58 / 4.47 %      no far closest
+      dragon-class 20,000               0 / 0 / 0.04 %                 0.17 / 0.35 / 3.62 %      no far closest after deform
+      sponza-class 12,000               0 / 0 / (2.98 %)               10.6 / 10.7 / (16.6 %)    no far closest; deform is outside the capped audit:
+                                                                                                 test_point_audit.test_deformed_sponza_slivers
+      f16 grid                          0 / 0 / 0 %                    0 / 0 / 0.52 %
+    A scene or a pass above 1 % is changed, never the cap, which is asserted wherever closest_points is judged.  far_closest=False: the far
+    pass of this case has another triangle within 16 * 2^-12 of more than 1 % of its centroids -- the scene's density, which no distance of
+    this pass can avoid -- so closest_points is not part of its far pass (not called, not judged); radius_search and nearest_k, which excuse
+    nothing there, and everything of the near pass still are.  The far pass of closest_points is carried by the cases under 1 %: the small soups,
+    soup 30,000 at size 0.02 (built, wave), the dragon-class scene (built, wave), the f16 grid.
+    passes: (near, far) Points made before, whose float64 side is then shared."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    rays = aimed_rays(tris) if rays is None else rays
+    if tree is None:
+        tree = lambda: verify_bvh4(tris, ctx.read_bvh4(), built=False)
+    out = {}
+    near, far = passes if passes is not None else (near_points(rays, tris), far_points(tris))
+    for pts, k, rr in ((near, K_NEAR, rays), (far, K_FAR, None)):
+        closest = far_closest or pts.what == "near"
+        drops = point_queries(ctx, pts, rr, True, k, stats=True, closest=closest)["drops"]
+        assert not any(drops), "%s, %s pass: the walk drops pushes at the 64-entry cap (%s): not a case for this audit, pick another" % (name, pts.what, drops)
+        for simple in kernels:
+            out[pts.what, simple] = js = judge_points(tris, pts, rr, point_queries(ctx, pts, rr, simple, k, closest=closest), k)
+            for j in js.values():
+                assert_point_judged(j, "%s simple %d" % (name, simple), tree, capped)
+    return out
 
 
 # ---- scenes both audit files use ------------------------------------------------------------------------------------------------------
