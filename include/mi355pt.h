@@ -724,7 +724,7 @@ PT_API int  pt_group_read_tonemapped(PtGroup* group, int from_rgba8, uint8_t* ds
  * Exported for this repository's own tests and tools (tests/test_gpu_parity.py, tools/ab/sweep.sh, tools/wave_timeline.py); a binding
  * for the reference has no use for them and they may change between builds of the library. */
 /* Override one launch heuristic of this context ("GRIDDIV", "ROWS", "CHUNK", "XCD", "SHADE", "FILL", "SLOTS", "CULL",
- * "STATSBATCH", "QUAD", "FORK", "BOUNDED", "TIMELINE"); value 0xFFFFFFFF restores the measured default.  Launches the open batch first.  The same knobs are read
+ * "STATSBATCH", "QUAD", "FORK", "BOUNDED", "TIMELINE", "EXPOSE", "EXBUDGET"); value 0xFFFFFFFF restores the measured default.  Launches the open batch first.  The same knobs are read
  * from PT_TUNE_<NAME> once, when a context is created.  "TIMELINE" = 1: ordinary (non-STATS) megakernel launches run the TIMELINE variant of the kernel --
  * the production kernel plus wave-uniform bookkeeping in scalar registers, same registers / occupancy, no scratch -- and leave the record pt_debug_wave_times reads. */
 PT_API int pt_debug_set_tune(PtContext* ctx, const char* name, uint32_t value);
@@ -752,6 +752,20 @@ PT_API int pt_debug_wave_times(PtContext* ctx, unsigned long long* dst, uint32_t
  * host wait -- when the view repeats; this call computes the cover at once and leaves it for the launches that follow.  The frames pt_set_batch holds
  * are not touched. */
 PT_API int pt_debug_traced_tiles(PtContext* ctx, const PtRenderParams* params, uint32_t* bitmask_out, uint32_t words, uint32_t* rect_tiles, uint32_t* traced_tiles);
+/* Exposed triangles: PT_MODE_PATH's light is directional and fixed, so a triangle on which no shadow ray can be occluded
+ * is known from the scene alone; a megakernel launch adds the light term of a hit on such a triangle without tracing the ray.  The mask (one bit
+ * per triangle, 2 * ceil(num_tris / 64) words) is computed on the device in front of the first launch of at least 2^24 ray segments that sees a tree
+ * version -- after pt_update_triangles the second such launch.  Knob "EXPOSE": 0 every shadow ray is traced, 1 = default, 2 instrumented launches
+ * skip as well and count what they skip; knob "EXBUDGET": the leaves a query may test before it gives up and leaves its triangle unflagged.
+ * pt_debug_exposure: params != NULL computes the mask now, for the current tree and that camera's distance, and waits for it; NULL reports the mask
+ * there is.  info_out[7] = {1 when the mask holds for the current tree version, flagged triangles, queries that gave up, triangles too ill-conditioned
+ * as occluders to be left to the walk, shadow rays the last "EXPOSE" = 2 PT_FLAG_STATS launch did not trace, words of the mask, 1 when the last megakernel launch -- of any variant -- read the mask}; *kernel_ms = duration
+ * of the two kernels; bounds_out[3] = {s_max, d_max of pt_exposure_flags_host, the camera distance} the mask holds for; mask_out (optional,
+ * `words` >= info_out[5]). */
+PT_API int pt_debug_exposure(PtContext* ctx, const PtRenderParams* params, uint32_t info_out[7], double bounds_out[3], float* kernel_ms, uint32_t* mask_out, uint32_t words);
+/* The same flags on the CPU from the triangles alone (every pair tested, the arithmetic of the device route; no GPU, no context) for ray
+ * origins within s_max of every scene point and hit coordinates up to d_max; mask: 2 * ceil(num_tris / 64) words. */
+PT_API int pt_exposure_flags_host(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask_out, uint32_t words, uint32_t* flagged);
 
 #ifdef __cplusplus
 }

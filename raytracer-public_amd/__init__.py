@@ -144,7 +144,7 @@ EXPORTS = [
     "pt_group_build_bvh_accel",
     "pt_group_set_bvh2", "pt_group_set_bvh4", "pt_group_set_batch", "pt_group_render", "pt_group_flush", "pt_group_synchronize", "pt_group_read_radiance",
     "pt_group_read_rgba8", "pt_group_read_tonemapped",
-    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_traced_tiles",     # diagnostics section of the header
+    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_traced_tiles", "pt_debug_exposure", "pt_exposure_flags_host",     # diagnostics section of the header
 ]
 
 
@@ -192,6 +192,16 @@ def _torch_route():
     if not _TORCH_FIRST:
         raise RuntimeError("the torch route of the ray queries needs `import torch` before this package is imported: both must use "
                            "the same HIP runtime (torch ships its own)")
+
+
+def exposure_flags_host(tris, s_max, d_max):
+    """CPU twin of the exposure mask: bool per triangle (every pair tested; no GPU)."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    n = tris.size // 9
+    words = ((n + 63) // 64) * 2
+    bits = np.zeros(max(words, 1), np.uint32); cnt = C.c_uint32()
+    _check(lib.pt_exposure_flags_host(_p(tris, C.c_float), C.c_uint32(n), C.c_double(s_max), C.c_double(d_max), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(cnt)))
+    return np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)[:n]
 
 
 def pack_rays(origins, directions, t_max=None):
@@ -715,6 +725,19 @@ class Context:
         self._ck(lib.pt_debug_traced_tiles(self.h, C.byref(params), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(nr), C.byref(nt)))
         mask = np.unpackbits(bits.view(np.uint8), bitorder="little")[: tx * ty].astype(bool).reshape(ty, tx)
         return mask, nr.value, nt.value
+
+    def debug_exposure(self, params=None, want_mask=True):
+        """Diagnostics: the exposure mask.  params: compute it now for the current tree and that camera; None: the mask
+        there is.  Returns a dict: valid, flagged, gave_up, listed, skipped, kernel_ms, mask (bool per triangle, or None), s_max, d_max, cam_max, used (the last megakernel launch read the mask)."""
+        info = (C.c_uint32 * 7)(); ms = C.c_float(); bd = (C.c_double * 3)()
+        self._ck(lib.pt_debug_exposure(self.h, C.byref(params) if params is not None else None, info, bd, C.byref(ms), None, C.c_uint32(0)))
+        mask = None
+        if want_mask and info[5]:
+            bits = np.zeros(info[5], np.uint32)
+            self._ck(lib.pt_debug_exposure(self.h, None, info, bd, C.byref(ms), _p(bits, C.c_uint32), C.c_uint32(info[5])))
+            mask = np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)
+        return {"valid": bool(info[0]), "flagged": info[1], "gave_up": info[2], "listed": info[3], "skipped": info[4], "kernel_ms": ms.value, "mask": mask,
+                "s_max": bd[0], "d_max": bd[1], "cam_max": bd[2], "used": bool(info[6])}
 
     def timing_collect_spans(self, capacity):
         """(start_ms, dur_ms) of the launches recorded since timing_begin; starts are relative to the first launch."""

@@ -5,10 +5,12 @@
 #include "mi355pt.h"
 #include "pt_host.h"
 #include "pt_kernels.h"
+#include "pt_expose.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,16 +43,16 @@ struct DevBuf {
 struct PtTune {
     static constexpr uint32_t kAuto = 0xFFFFFFFFu;
     uint32_t grid_div = kAuto, rows = kAuto, chunk = kAuto, xcd = kAuto, shade = kAuto, fill = kAuto,
-             slots = kAuto, cull = kAuto, stats_batch = kAuto, quad = kAuto, fork = kAuto, bounded = kAuto, timeline = kAuto;
+             slots = kAuto, cull = kAuto, stats_batch = kAuto, quad = kAuto, fork = kAuto, bounded = kAuto, timeline = kAuto, expose = kAuto, expose_budget = kAuto;
     uint32_t* find(const char* name) {
         static const struct { const char* n; uint32_t PtTune::* m; } tab[] = {
             {"GRIDDIV", &PtTune::grid_div}, {"ROWS", &PtTune::rows}, {"CHUNK", &PtTune::chunk}, {"XCD", &PtTune::xcd}, {"SHADE", &PtTune::shade},
-            {"FILL", &PtTune::fill}, {"SLOTS", &PtTune::slots}, {"CULL", &PtTune::cull}, {"STATSBATCH", &PtTune::stats_batch}, {"QUAD", &PtTune::quad}, {"FORK", &PtTune::fork}, {"BOUNDED", &PtTune::bounded}, {"TIMELINE", &PtTune::timeline}};
+            {"FILL", &PtTune::fill}, {"SLOTS", &PtTune::slots}, {"CULL", &PtTune::cull}, {"STATSBATCH", &PtTune::stats_batch}, {"QUAD", &PtTune::quad}, {"FORK", &PtTune::fork}, {"BOUNDED", &PtTune::bounded}, {"TIMELINE", &PtTune::timeline}, {"EXPOSE", &PtTune::expose}, {"EXBUDGET", &PtTune::expose_budget}};
         for (const auto& t : tab) if (std::strcmp(name, t.n) == 0) return &(this->*(t.m));
         return nullptr;
     }
     void from_environment() {
-        static const char* names[] = {"GRIDDIV", "ROWS", "CHUNK", "XCD", "SHADE", "FILL", "SLOTS", "CULL", "STATSBATCH", "QUAD", "FORK", "BOUNDED", "TIMELINE"};
+        static const char* names[] = {"GRIDDIV", "ROWS", "CHUNK", "XCD", "SHADE", "FILL", "SLOTS", "CULL", "STATSBATCH", "QUAD", "FORK", "BOUNDED", "TIMELINE", "EXPOSE", "EXBUDGET"};
         for (const char* n : names) {
             const std::string key = std::string("PT_TUNE_") + n;
             const char* v = std::getenv(key.c_str());
@@ -118,6 +120,19 @@ struct PtContext {
     Cover covers[kCovers]; uint64_t cover_clock = 0;
     std::vector<ptk::CoverCam> cover_cams;                 // the distinct cameras of the launch being planned
     uint32_t cover_ids = 0;
+    // Exposed triangles (pt_expose.hip): one bit per triangle that no shadow ray of the fixed light can be occluded on, computed in front of
+    // the first large PT_MODE_PATH launch of a tree version (after pt_update_triangles: of the second, so geometry that moves every frame never
+    // pays for it), on that launch's side stream, with no host wait.  expose_version: the tree version the mask holds for (0: none);
+    // expose_cam / expose_s / expose_d: the camera distance and the operand bounds (ptex::Bounds) it was computed for.
+    // The mask lives in the scene arena, behind the wide nodes (expose_off: its byte offset there), so that the megakernel reaches it from the
+    // arena's base like every record.
+    DevBuf<uint32_t> d_expose_info, d_expose_bad, d_expose_skipped; uint64_t expose_off = 0;      // (d_expose_skipped: the COUNTERS variant's one word, nobody else's)
+    uint32_t* expose_mask() const { return (uint32_t*)((char*)d_scene.ptr + expose_off); }
+    // expose_gen counts the masks computed, whatever the tree version: a recompute for a farther camera keeps the version, and every stream that
+    // is to read the new mask has to wait for it (FrameSlot::expose_waited is compared with this, not with the version).
+    uint32_t expose_version = 0, expose_gen = 0, expose_noted = 0, expose_tris = 0; bool tree_updated = false, expose_last_used = false;
+    double expose_cam = 0.0, expose_s = 0.0, expose_d = 0.0;
+    hipEvent_t ev_expose = nullptr, ev_expose_t0 = nullptr, ev_expose_t1 = nullptr;
     // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
     DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
     DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
@@ -134,6 +149,7 @@ struct PtContext {
     // dense start of the next; the resolve passes stay in call order on the main stream.
     struct FrameSlot {
         hipStream_t side = nullptr; hipEvent_t resolved = nullptr, done = nullptr; bool used = false;
+        uint32_t expose_waited = 0;                                     // the mask generation (PtContext::expose_gen) this slot's stream has waited for (PtContext::ev_expose)
         uint64_t resolved_seq = 0;                                      // launch sequence number of the latest record of `resolved` (pt_buffer_busy)
         DevBuf<uint32_t> queue; DevBuf<float4> samples; DevBuf<uint2> spill; DevBuf<uint4> rays;
         // owned-tile slots that the launch in this slot traces (the others are culled: every camera ray misses the root box, or every box
@@ -251,8 +267,9 @@ uint64_t tri_region_bytes(uint32_t num_tris) { return (uint64_t(num_tris) + 1u) 
 // Room for `num_tris` triangle records and `nodes` wide nodes; triangle records that are already there survive a regrowth.
 int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
     const uint64_t tri_bytes = tri_region_bytes(num_tris);
-    const uint64_t need = tri_bytes + (nodes + 1u) * 64u;
-    if (need >= 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "scene too large: triangle records and BVH nodes are addressed by 32-bit byte offsets (4 GiB)");
+    const uint64_t mask_bytes = ((uint64_t(ptk::expose_mask_words(num_tris)) * 4u + 63u) / 64u) * 64u;          // the exposure mask, behind the nodes
+    const uint64_t need = tri_bytes + (nodes + 1u) * 64u + mask_bytes + (nodes / 8u + 16u) * 64u + 65536u;
+    if (need >= 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "scene too large: triangle records, BVH nodes (with their regrowth slack) and the exposure mask behind them are addressed by 32-bit byte offsets (4 GiB)");
     if (ctx->d_scene.ptr && ctx->node_off == tri_bytes && ctx->node_cap >= nodes) {
         if (ctx->scene_tris != num_tris)      // another triangle count in the same region: the never-hit record moves
             PT_HIP(ctx, hipMemset((char*)ctx->d_scene.ptr + uint64_t(num_tris) * 64u, 0, tri_bytes - uint64_t(num_tris) * 64u));
@@ -260,12 +277,14 @@ int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
     }
     const uint64_t cap_nodes = nodes + nodes / 8u + 16u;
     uint4* fresh = nullptr;
-    PT_HIP(ctx, hipMalloc((void**)&fresh, tri_bytes + (cap_nodes + 1u) * 64u));
+    const uint64_t mask_off = ((tri_bytes + (cap_nodes + 1u) * 64u + 65535u) / 65536u) * 65536u;      // a multiple of 64 KiB: RenderArgs::bounces_expose carries it in 16 bits
+    PT_HIP(ctx, hipMalloc((void**)&fresh, mask_off + mask_bytes));
     if (ctx->d_scene.ptr && ctx->scene_tris == num_tris && num_tris)          // the records of the current triangles move along
         PT_HIP(ctx, hipMemcpy(fresh, ctx->d_scene.ptr, uint64_t(num_tris) * 64u, hipMemcpyDeviceToDevice));
     if (ctx->d_scene.ptr) (void)hipFree(ctx->d_scene.ptr);
     PT_HIP(ctx, hipMemset((char*)fresh + uint64_t(num_tris) * 64u, 0, tri_bytes - uint64_t(num_tris) * 64u));      // the never-hit record
-    ctx->d_scene.ptr = fresh; ctx->d_scene.cap = size_t((tri_bytes + (cap_nodes + 1u) * 64u) / 16u);
+    ctx->d_scene.ptr = fresh; ctx->d_scene.cap = size_t((mask_off + mask_bytes) / 16u);
+    ctx->expose_off = mask_off; ctx->expose_version = 0;
     ctx->node_off = tri_bytes; ctx->node_cap = cap_nodes; ctx->scene_tris = num_tris;
     return PT_OK;
 }
@@ -274,7 +293,7 @@ int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
 // cut (cut_count 0: launches cull by the root box's rectangle alone) when the root is a leaf or the tree is empty.  Waits for the
 // stream, as every call that installs a tree does anyway.
 int install_cut(PtContext* ctx) {
-    ++ctx->tree_version; ctx->cut_count = 0;
+    ++ctx->tree_version; ctx->cut_count = 0; ctx->tree_updated = false;
     const uint32_t base16 = uint32_t(ctx->node_off / 16u), root = ctx->wide_meta.root_ref;
     if (root == pt::kInvalid || (root & pt::kLeafFlag) || ctx->num_wide == 0u || root < base16) return PT_OK;
     PT_HIP(ctx, ctx->d_cut.ensure(ptk::kCutMax + 1u));
@@ -604,6 +623,59 @@ int stage_traced_tiles(PtContext* ctx, PtContext::FrameSlot& sl, const uint32_t 
     return PT_OK;
 }
 
+// ---- exposed triangles (pt_expose.hip) ----
+// The largest camera distance of the frames, or -1 when a launch of them may not skip shadow rays: the proof bounds |d| by 1.001, so every
+// quaternion has to be a unit one to 1e-4, and everything has to be finite.
+double expose_cam_norm(const ptk::FrameParams* frames, uint32_t nf) {
+    double c = 0.0;
+    for (uint32_t i = 0; i < nf; ++i) {
+        const float* q = frames[i].quat; const float* p = frames[i].cam;
+        const double n2 = double(q[0]) * q[0] + double(q[1]) * q[1] + double(q[2]) * q[2] + double(q[3]) * q[3];
+        if (!(n2 >= 1.0 - 1e-4 && n2 <= 1.0 + 1e-4)) return -1.0;
+        const double d = std::sqrt(double(p[0]) * p[0] + double(p[1]) * p[1] + double(p[2]) * p[2]);
+        if (!(d < 1e30)) return -1.0;
+        c = std::max(c, d);
+    }
+    return c;
+}
+// the largest distance of a corner of the root box (grown as pt_expose.h grows a box) from the origin, or -1 when it is not finite
+double expose_scene_norm(const PtContext* ctx) {
+    const uint32_t* b = ctx->wide_meta.root_box;
+    const double mn[3] = {pt::half_to_float(b[0] & 0xffffu), pt::half_to_float(b[0] >> 16), pt::half_to_float(b[1] & 0xffffu)};
+    const double mx[3] = {pt::half_to_float(b[1] >> 16), pt::half_to_float(b[2] & 0xffffu), pt::half_to_float(b[2] >> 16)};
+    double r2 = 0.0;
+    for (int a = 0; a < 3; ++a) { const double m = std::max(std::fabs(mn[a]), std::fabs(mx[a])) + ptex::kBoxGrow; r2 += m * m; }
+    const double r = std::sqrt(r2);
+    return r < 1e30 ? r : -1.0;
+}
+bool expose_possible(const PtContext* ctx) {
+    return ctx->have_bvh && ctx->num_tris != 0u && ctx->wide_meta.root_ref != pt::kInvalid && !ctx->wide_meta.root_degenerate;
+}
+// the mask of the current tree version for cameras up to `cam` from the origin, on `stream` (ev_expose follows it there)
+int compute_exposure(PtContext* ctx, double cam, hipStream_t stream) {
+    const double r = expose_scene_norm(ctx);
+    if (r < 0.0) return PT_OK;
+    // (a mask of this tree version that a farther camera replaces keeps the larger of the two distances: near and far views do not take turns)
+    const double cb = std::max(std::max(cam * 1.25, r), ctx->expose_version == ctx->tree_version ? ctx->expose_cam : 0.0);
+    PT_HIP(ctx, ctx->d_expose_info.ensure(ptk::kExposeInfoWords)); PT_HIP(ctx, ctx->d_expose_bad.ensure(ptk::kExposeBadMax));
+    if (!ctx->d_expose_skipped.ptr) { PT_HIP(ctx, ctx->d_expose_skipped.ensure(1)); PT_HIP(ctx, hipMemset(ctx->d_expose_skipped.ptr, 0, sizeof(uint32_t))); }
+    if (!ctx->ev_expose) {
+        PT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_expose, hipEventDisableTiming));
+        PT_HIP(ctx, hipEventCreate(&ctx->ev_expose_t0)); PT_HIP(ctx, hipEventCreate(&ctx->ev_expose_t1));
+    }
+    // one pass at a time: the info block, the list and the mask are shared, so this pass starts behind the one before it, on whatever stream that ran
+    if (ctx->expose_gen != 0u) PT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_expose, 0));
+    ctx->expose_cam = cb; ctx->expose_s = cb + r + 1e-3; ctx->expose_d = r + 1e-3;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_expose_t0, stream));
+    PT_HIP(ctx, ptk::launch_expose(ctx->d_scene.ptr, uint32_t(ctx->node_off / 16u), ctx->num_wide, ctx->wide_meta.root_ref, ctx->num_tris, ctx->expose_s, ctx->expose_d,
+                                   ptk::kExposeNodeBudget, PtTune::pick(ctx->tune.expose_budget, ptk::kExposeLeafBudget), ctx->d_expose_info.ptr, ctx->d_expose_bad.ptr,
+                                   ctx->expose_mask(), stream));
+    PT_HIP(ctx, hipEventRecord(ctx->ev_expose_t1, stream));
+    PT_HIP(ctx, hipEventRecord(ctx->ev_expose, stream));
+    ctx->expose_version = ctx->tree_version; ctx->expose_tris = ctx->num_tris; ++ctx->expose_gen;
+    return PT_OK;
+}
+
 // Launch the queued frames as one persistent launch (trace on a side stream, resolve on the main stream).
 int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count) {
     if (!ctx->pending) return PT_OK;
@@ -661,6 +733,24 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     A.shade_threshold = P.shade_threshold; A.fill_threshold = P.fill_threshold; A.quad_live = P.quad_live; A.fork_shadow = P.fork_shadow;
     A.rcp_short = (PtTune::pick(ctx->tune.bounded, 1u) != 0u && arith_is_bounded(ctx, ctx->pending_frames, nf)) ? 1u : 0u;      // knob BOUNDED = 0: always the general forms (tests)
 
+    // exposed triangles: knob EXPOSE 0 = every shadow ray is traced, 1 (default) = production launches skip those of exposed triangles, 2 = instrumented
+    // launches as well (the oracle counts the rays, and TIMELINE is compared with COUNTERS: by default both trace everything).  The mask is
+    // taken by a launch of at least 2^24 ray segments that finds none for the tree version -- after an update by the second such launch.
+    bool expose_use = false, expose_compute = false; double expose_cam = -1.0;
+    {
+        const uint32_t knob = PtTune::pick(ctx->tune.expose, 1u);
+        const bool instr = stats || PtTune::pick(ctx->tune.timeline, 0u) != 0u;
+        if (knob != 0u && (!instr || knob >= 2u) && A.ref_mode == 0u && expose_possible(ctx) && (expose_cam = expose_cam_norm(ctx->pending_frames.data(), nf)) >= 0.0) {
+            const bool current = ctx->expose_version == ctx->tree_version && ctx->expose_version != 0u;
+            const bool fits = current && expose_cam <= ctx->expose_cam && expose_scene_norm(ctx) + 1e-3 <= ctx->expose_d;
+            if (!current && cover_now) {
+                if (!ctx->tree_updated || ctx->expose_noted == ctx->tree_version) expose_compute = true;
+                else ctx->expose_noted = ctx->tree_version;
+            } else if (current && !fits && cover_now) expose_compute = true;      // a camera beyond the mask's bounds: a large launch takes the mask again, for the wider bounds
+            expose_use = expose_compute || fits;
+        }
+    }
+
     // ---- prepare: frame slots (instrumented launches always use slot 0 and are not overlapped), traced-tile list ------------------------
     ctx->num_slots = P.slots;
     if (int rc = prepare_slots(ctx, P, A, nf, stats)) return rc;
@@ -685,6 +775,19 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     // for the previous frame's resolve -- that is what lets consecutive frames overlap); the resolve on the main stream waits for the trace.
     if (!ring) PT_HIP(ctx, hipEventRecord(e0, ctx->stream));
     if (sl.used) PT_HIP(ctx, hipStreamWaitEvent(sl.side, sl.resolved, 0));
+    A.bounces_expose = std::min(A.max_bounces, 0xffffu);      // (the bounce count of a path is a 16-bit field of its state)
+    if (expose_compute) {
+        if (int rc = compute_exposure(ctx, expose_cam, sl.side)) return rc;
+        sl.expose_waited = ctx->expose_gen;
+        expose_use = ctx->expose_version == ctx->tree_version;
+    }
+    if (expose_use) {
+        if (sl.expose_waited != ctx->expose_gen) { PT_HIP(ctx, hipStreamWaitEvent(sl.side, ctx->ev_expose, 0)); sl.expose_waited = ctx->expose_gen; }
+        A.bounces_expose |= uint32_t(ctx->expose_off) & 0xffff0000u;
+        if (stats) A.expose_skipped = ctx->d_expose_skipped.ptr;
+    }
+    ctx->expose_last_used = (A.bounces_expose >> 16) != 0u;
+    if (stats && ctx->d_expose_skipped.ptr) PT_HIP(ctx, hipMemsetAsync(ctx->d_expose_skipped.ptr, 0, sizeof(uint32_t), sl.side));      // (an instrumented launch that skips nothing says so)
     if (cull) {
         if (!sl.cull_valid) {
             PT_HIP(ctx, hipMemcpyAsync(sl.trace_slots.ptr, sl.h_trace, (traced.size() + cover_words) * sizeof(uint32_t), hipMemcpyHostToDevice, sl.side));
@@ -785,6 +888,8 @@ void pt_destroy(PtContext* ctx) {
     ctx->d_morton.release(); ctx->d_triidx.release(); ctx->d_parent.release(); ctx->d_flags.release();
     ctx->d_out.release(); ctx->d_accum.release(); ctx->d_compact.release(); ctx->d_compact_accum.release();
     ctx->d_tiles.release(); ctx->d_u32tmp.release(); ctx->d_stats.release();
+    ctx->d_expose_info.release(); ctx->d_expose_bad.release(); ctx->d_expose_skipped.release();
+    if (ctx->ev_expose) { (void)hipEventDestroy(ctx->ev_expose); (void)hipEventDestroy(ctx->ev_expose_t0); (void)hipEventDestroy(ctx->ev_expose_t1); }
     ctx->d_wave_times.release();
     ctx->d_bounds.release(); ctx->d_counters.release(); ctx->d_code_tmp.release(); ctx->d_index_tmp.release(); ctx->d_node2.release();
     ctx->d_subtree.release(); ctx->d_ids.release(); ctx->d_bnd.release(); ctx->d_child_pos.release(); ctx->d_build_temp.release();
@@ -1046,6 +1151,7 @@ int update_triangles(PtContext* ctx, const char* fn, const void* tris, uint32_t 
         PT_HIP(ctx, ptk::launch_refit4(ctx->d_tris9.ptr, num_tris, ctx->d_bvh4.ptr, ctx->num_nodes4, refit_buffers(ctx), ctx->wide(), ctx->stream));
         PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit, ctx->d_bvh4.ptr + 1, 12, hipMemcpyDeviceToHost, ctx->stream));
         ++ctx->tree_version;        // new boxes at the places the cut names: the next launch takes a new tile cover
+        ctx->tree_updated = true;   // and the exposure mask is void: taken again when a second large launch sees this version
     }
     PT_HIP(ctx, hipMemcpyAsync(ctx->h_refit + 3, ctx->d_edge_max.ptr, 4, hipMemcpyDeviceToHost, ctx->stream));
     PT_HIP(ctx, hipEventRecord(ctx->ev_refit, ctx->stream));
@@ -2185,6 +2291,51 @@ int pt_debug_wave_times(PtContext* ctx, unsigned long long* dst, uint32_t max_wa
     const uint32_t n = ctx->wave_times_n < max_waves ? ctx->wave_times_n : max_waves;
     if (n) PT_HIP(ctx, hipMemcpy(dst, ctx->d_wave_times.ptr, size_t(n) * ptk::kWaveTimeWords * 8u, hipMemcpyDeviceToHost));
     if (n_waves) *n_waves = n;
+    return PT_OK;
+}
+
+/* diagnostics: the exposure mask (pt_expose.hip).  params != NULL: the mask is computed now, for the current tree and that camera, and
+ * waited for; NULL: whatever mask there is.  info_out[7]: 1 when the mask holds for the current tree version, flagged triangles, queries that
+ * ran out of their budget, listed ill-conditioned triangles, shadow rays the last EXPOSE = 2 instrumented launch skipped, words of the mask, 1 when the last megakernel launch read the mask. */
+int pt_debug_exposure(PtContext* ctx, const PtRenderParams* p, uint32_t info_out[7], double bounds_out[3], float* kernel_ms, uint32_t* mask_out, uint32_t words) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto& sl : ctx->slots) if (sl.side && sl.used) PT_HIP(ctx, hipStreamSynchronize(sl.side));
+    if (p) {
+        if (!expose_possible(ctx)) return fail(ctx, PT_ERR_NO_SCENE, "pt_debug_exposure: no tree to walk");
+        ptk::FrameParams f; std::memset(&f, 0, sizeof(f));
+        std::memcpy(f.cam, p->cam_pos, 12); std::memcpy(f.quat, p->cam_quat, 16);
+        const double cam = expose_cam_norm(&f, 1u);
+        if (cam < 0.0) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_exposure: the camera allows no skipping (quaternion not of unit length, or not finite)");
+        if (int rc = compute_exposure(ctx, cam, ctx->stream)) return rc;
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const bool have = ctx->expose_version != 0u && ctx->d_expose_info.ptr != nullptr;
+    uint32_t h[ptk::kExposeInfoWords] = {0};
+    if (have) PT_HIP(ctx, hipMemcpy(h, ctx->d_expose_info.ptr, sizeof h, hipMemcpyDeviceToHost));
+    if (have) PT_HIP(ctx, hipMemcpy(h + ptk::kExposeSkipped, ctx->d_expose_skipped.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t need = have ? ptk::expose_mask_words(ctx->expose_tris) : 0u;
+    if (info_out) {
+        info_out[0] = have && ctx->expose_version == ctx->tree_version ? 1u : 0u; info_out[1] = h[ptk::kExposeFlagged]; info_out[2] = h[ptk::kExposeBudget];
+        info_out[3] = h[ptk::kExposeBad]; info_out[4] = h[ptk::kExposeSkipped]; info_out[5] = need; info_out[6] = ctx->expose_last_used ? 1u : 0u;
+    }
+    if (bounds_out) { bounds_out[0] = have ? ctx->expose_s : 0.0; bounds_out[1] = have ? ctx->expose_d : 0.0; bounds_out[2] = have ? ctx->expose_cam : 0.0; }
+    if (kernel_ms) { *kernel_ms = 0.0f; if (have) PT_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev_expose_t0, ctx->ev_expose_t1)); }
+    if (mask_out) {
+        if (words < need) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_exposure: the mask needs one bit per triangle, in an even number of words per 64");
+        if (need) PT_HIP(ctx, hipMemcpy(mask_out, ctx->expose_mask(), size_t(need) * 4u, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+
+int pt_exposure_flags_host(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask_out, uint32_t words, uint32_t* flagged) {
+    if ((!tris && num_tris) || !mask_out) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: null pointer");
+    if (words < ((num_tris + 63u) / 64u) * 2u) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: the mask needs 2 * ceil(num_tris / 64) words");
+    if (!(s_max >= 0.0 && d_max >= 0.0)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: bad bounds");
+    const uint32_t n = pt::exposure_flags(tris, num_tris, s_max, d_max, mask_out);
+    if (flagged) *flagged = n;
     return PT_OK;
 }
 

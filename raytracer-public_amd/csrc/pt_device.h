@@ -224,6 +224,7 @@ __device__ __forceinline__ ItemInfo decode_item(const RenderArgs& A, uint32_t lo
 }
 
 constexpr float kEpsOrigin = 1e-4f;
+constexpr float kExposeGate = 0.1002f;   // |n . d| below which the shadow ray of a hit on an exposed triangle is traced all the same (pt_expose.h::kGate)
 constexpr float kBgPrimary = 0.01f;    // renderer.wgsl:410
 constexpr float kSkyAmbient = 0.15f;   // renderer.wgsl:352
 constexpr uint32_t kRRStart = 2;

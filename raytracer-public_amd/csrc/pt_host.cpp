@@ -3,6 +3,7 @@
 // (BVH4_wide), plus the re-layout of the reference's buffers into the device formats the
 // HIP kernels read.  Strict f32/f64 (-ffp-contract=off); no HIP calls.
 #include "pt_host.h"
+#include "pt_expose.h"
 #include "pt_closest.h"
 
 #include <cmath>
@@ -1384,6 +1385,34 @@ bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64
         o[0] = 2u * odd > samples ? 1u : 0u; o[1] = odd; o[2] = samples; o[3] = 0u;
     }
     return true;
+}
+
+// ---- exposed triangles: every pair, with the arithmetic of pt_expose.h (pt_expose.hip walks the tree instead) ----
+uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask) {
+    const uint32_t words = ((num_tris + 63u) / 64u) * 2u;
+    std::memset(mask, 0, size_t(words) * sizeof(uint32_t));
+    std::vector<TriRecord> rec(num_tris);
+    if (num_tris) build_tri_records(tris, num_tris, rec.data());
+    // the light direction as the kernels hold it (pt_device.h::light_dir: normalize3 in f32)
+    const float inv = 1.0f / std::sqrt((1.0f * 1.0f + 1.5f * 1.5f) + 1.0f * 1.0f);
+    const ptex::Light g = ptex::make_light(1.0f * inv, 1.5f * inv, 1.0f * inv);
+    const ptex::Bounds b = {s_max, d_max};
+    auto load = [&](uint32_t t) {
+        ptex::Tri r;
+        for (int a = 0; a < 3; ++a) { r.v0[a] = rec[t].axis[a][0]; r.e1[a] = rec[t].axis[a][1]; r.e2[a] = rec[t].axis[a][2]; }
+        return r;
+    };
+    std::vector<ptex::Tri> all(num_tris);
+    for (uint32_t t = 0; t < num_tris; ++t) all[t] = load(t);
+    uint32_t flagged = 0;
+    for (uint32_t t = 0; t < num_tris; ++t) {
+        const float n32[3] = {rec[t].n[0], rec[t].n[1], rec[t].n[2]};
+        const ptex::Query q = ptex::make_query(all[t], n32, g, b);
+        bool blocked = !q.ok;
+        for (uint32_t n = 0; n < num_tris && !blocked; ++n) blocked = ptex::blocks(q, all[n], g);
+        if (!blocked) { mask[t >> 5] |= 1u << (t & 31u); ++flagged; }
+    }
+    return flagged;
 }
 
 } // namespace pt

@@ -65,17 +65,23 @@
                         finish = true;
                     } else {
                         const F3 n = tri_normal_ref(A, S.best_tri);
+                        // exposed triangles (pt_expose.hip): the word of the hit triangle's bit, asked for next to the normal (an independent load)
+                        uint32_t ex_word = 0u;
+                        uint32_t bx = A.bounces_expose;                // the bounce limit and the mask's place in one launch constant (pt_kernels.h)
+                        asm volatile("" : "+s"(bx));                   // (opaque: what is derived from it is computed here, not hoisted out of the launch loops and held through them)
+                        if ((bx >> 16) != 0u) ex_word = *(const uint32_t*)((const char*)A.scene + ((bx & 0xffff0000u) + (((S.best_tri & 0x7fffffffu) >> 7) << 2)));
                         // what does not depend on the normal is computed while it is on its way from memory (a dependent fetch the pass would otherwise sit out):
                         // the hit point, this bounce's random numbers, the direction sample in its local frame
                         const F3 hp = S.o + S.d * S.best_t;
                         const float u_rr = rnd(S.key, bounce, 4);
                         F3 l_next = cosine_local<BOUNDED>(rnd(S.key, bounce, 2), rnd(S.key, bounce, 3));
                         asm volatile("" : "+v"(l_next.x), "+v"(l_next.y), "+v"(l_next.z));       // (done HERE: before the first use of the normal)
-                        const F3 nf = (dot3(n, S.d) < 0.0f) ? n : f3(-n.x, -n.y, -n.z);
+                        const float nd = dot3(n, S.d);
+                        const F3 nf = (nd < 0.0f) ? n : f3(-n.x, -n.y, -n.z);
                         const F3 so = hp + nf * kEpsOrigin;
                         const float ndl = dot3(nf, L);
                         S.contrib = (S.T * base) * ndl;
-                        bool cont = bounce < A.max_bounces;
+                        bool cont = bounce < (bx & 0xffffu);
                         if (cont) {
                             F3 Tn = S.T * base;
                             if (bounce >= kRRStart) {
@@ -86,7 +92,20 @@
                             if (cont) { S.T = Tn; S.d_next = cosine_world<BOUNDED>(nf, l_next); }
                         }
                         S.o = so;
-                        if (ndl > 0.0f) {
+                        // The shadow ray of a hit on an exposed triangle finds nothing (DESIGN.md section 6.2: no triangle reaches into the prism its origin
+                        // lies in, for hits at |n . d| >= kExposeGate, which bounds the origin's error inside the plane): its term is added here -- where
+                        // the traced ray's end would add it, nothing having been added in between -- and the path goes on as without a light term.
+                        // (the three conditions are folded into one lane value and tested once: held as lane masks they cost spilled scalar registers)
+                        uint32_t lit = (ex_word >> ((S.best_tri >> 2) & 31u)) & 1u;
+                        lit = (fabsf(nd) >= kExposeGate) ? lit : 0u;
+                        lit = (ndl > 0.0f) ? lit : 0u;
+                        asm volatile("" : "+v"(lit));
+                        {   // (a select in front of the branch the pass had before, not a branch of its own: no further definition of the pass's lane masks)
+                            const F3 r1 = S.rad + S.contrib;
+                            S.rad = f3(lit != 0u ? r1.x : S.rad.x, lit != 0u ? r1.y : S.rad.y, lit != 0u ? r1.z : S.rad.z);
+                            if (STATS && lit != 0u && count_lane()) ++c_lit;
+                        }
+                        if (ndl > 0.0f && lit == 0u) {
                             if (cont && fork_on) want_fork = true;          // settled below, with the other seats
                             else {
                             S.d = L; S.inv = invL;

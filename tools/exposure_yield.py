@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""What the exposure mask takes away from a frame, counted on the device by the COUNTERS variant of the megakernel.
+
+  python tools/exposure_yield.py [--scene dragon|sponza] [--tris N] [--width W --height H] [--spp S] [--bounces B] [--cam x y z] [--host]
+
+One instrumented frame with knob EXPOSE at 1 (every shadow ray traced: the oracle's counters) and one at 2 (the rays of exposed triangles
+skipped and counted); the difference of the node records and triangle tests is what the skipped rays cost.  Prints one JSON line: triangles
+flagged / listed / out of budget, the two kernels' duration, closest and shadow rays, skipped rays and their share, node records and triangle
+tests saved and their share of the frame's.  --host adds the host twin's flagged count (every pair of triangles: small scenes only).
+The shares by ray kind of a CPU walk (camera / bounce / shadow, occluded or not) are not reported: the oracle counts rays, not steps per kind."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+rt = importlib.import_module("raytracer-public_amd")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="dragon", choices=("dragon", "sponza"))
+    ap.add_argument("--tris", type=int, default=None)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--bounces", type=int, default=8)
+    ap.add_argument("--cam", type=float, nargs=3, default=None)
+    ap.add_argument("--host", action="store_true")
+    a = ap.parse_args()
+    dragon = a.scene == "dragon"
+    n = a.tris or (871414 if dragon else 262144)
+    cam = tuple(a.cam) if a.cam else ((0.0, 0.0, 2.5) if dragon else (0.55, -0.05, 0.05))
+    quat = (0.0, 0.0, 0.0, 1.0) if dragon else (0.0, 0.6630, 0.0, 0.7486)
+    tris = rt.procedural_scene(rt.SCENE_DRAGON_CLASS if dragon else rt.SCENE_SPONZA_CLASS, n)
+    ctx = rt.Context(0)
+    ctx.set_triangles(tris); ctx.build_bvh()
+    p = ctx.make_params(a.width, a.height, cam, quat, mode=rt.PT_MODE_PATH, spp=a.spp, max_bounces=a.bounces, seed=1, stats=True)
+    info = ctx.debug_exposure(p, want_mask=False)
+    ctx.render(p); full = ctx.stats()
+    ctx.debug_set_tune("EXPOSE", 2)
+    ctx.render(p); cut = ctx.stats()
+    skipped = ctx.debug_exposure(None, want_mask=False)["skipped"]
+    out = {"scene": a.scene, "triangles": n, "frame": [a.width, a.height, a.spp, a.bounces], "flagged": info["flagged"], "listed": info["listed"],
+           "gave_up": info["gave_up"], "kernels_ms": round(info["kernel_ms"], 3), "s_max": info["s_max"], "rays_closest": full["rays_closest"],
+           "rays_shadow": full["rays_shadow"], "skipped": skipped, "skipped_share_of_shadow_rays": round(skipped / max(1, full["rays_shadow"]), 4),
+           "nodes_examined": full["nodes_examined"], "nodes_saved": full["nodes_examined"] - cut["nodes_examined"],
+           "nodes_saved_share": round((full["nodes_examined"] - cut["nodes_examined"]) / max(1, full["nodes_examined"]), 4),
+           "tris_tested": full["tris_tested"], "tris_saved": full["tris_tested"] - cut["tris_tested"]}
+    assert cut["rays_shadow"] == full["rays_shadow"] - skipped
+    if a.host:
+        out["host_twin_flagged"] = int(rt.exposure_flags_host(tris, info["s_max"], info["d_max"]).sum())
+    print(json.dumps(out), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
