@@ -514,6 +514,54 @@ PT_API int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t
 PT_API int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
                                  uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats);
 
+/* ---- hit lists: which triangles does a ray cross, and where -- all of them, each with t and u, v? (an extension beyond the reference;
+ * DESIGN.md section 20) -----------------------------------------------------------------------------------------------------------
+ * Records: PtRay in, one PtHit (t, prim, u, v) per crossing out; offsets is uint64_t[n + 1].  Every result is an integer or a bit pattern.
+ * Which crossings: exactly the records pt_count_hits counts for the same ray and flags -- the same walk over the context's CURRENT tree in
+ *   the same visit order, best = min(t_max, 1e30) constant, a record accepted iff the Moller-Trumbore test of the ray queries holds and
+ *   t < best, 64 stack entries with a push at the cap dropped (and counted), a leaf with t >= num_tris skipped, a degenerate root box: no
+ *   crossing.  Rays with no walk (a NaN in org or dir, or t_max <= 0 or NaN) have an empty list.  So offsets[i + 1] - offsets[i] equals
+ *   pt_count_hits' count of ray i, always, with stack drops too, and a list is non-empty exactly when pt_trace_rays(PT_TRACE_ANY_HIT)
+ *   reports a hit.  Misses are never stored.
+ * Entries: t is the t of the accepted test; u, v come from the arithmetic of pt_trace_rays' result on the same triangle record -- the bits
+ *   pt_trace_rays gives for that ray if that triangle is the only one.
+ * Order: without PT_HITS_SORTED the list of a ray is in VISIT ORDER, which is a property of the ray and the tree, not of the scheduling:
+ *   every kernel variant and the host twin give the same order.  With PT_HITS_BRUTE_FORCE it is triangle index order.  With
+ *   PT_HITS_SORTED every fully stored list is in ascending order of the 64-bit key (bits(t) << 32) | prim; every stored t is positive and
+ *   finite, so bit order is value order, and the sorted list depends on neither the tree, the kernel variant nor the scheduling (equal keys
+ *   can only be one triangle held by two leaves, whose entries are identical).
+ * pt_list_hits: offsets[0] = 0 and offsets[i + 1] - offsets[i] = count[i] in uint64_t (no wrap); offsets[n] = the total.  The entry
+ *   with global index g = offsets[i] + k is written iff g < capacity; entries at and beyond min(total, capacity) are not touched.  The
+ *   offsets are always complete: offsets[n] > capacity says that the list was truncated and how large the retry must be.
+ *   hits_device = NULL is allowed with capacity = 0 (offsets only).  With PT_HITS_SORTED only the lists with offsets[i + 1] <= capacity are
+ *   sorted: the one list that straddles the capacity stays in visit order.  Three launches on the context's stream (four with
+ *   PT_HITS_SORTED), no host wait: pt_count_hits' walk into a buffer of the context, an exclusive scan, a second walk of the same steps
+ *   that stores entry k of ray i at offsets[i] + k, the in-place sort.  No atomic appends anything.
+ * PT_HITS_BRUTE_FORCE, PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL: what PT_COUNT_BRUTE_FORCE, PT_COUNT_STATS and PT_COUNT_SIMPLE_KERNEL mean for
+ *   pt_count_hits; the counters are counted over the count walk only.
+ * Completeness: the list is a subset of the PT_HITS_BRUTE_FORCE list on a tree whose leaves hold each triangle once; the two are equal (as
+ *   sets, and bit for bit when sorted) wherever nothing is dropped at the cap and no crossing is lost to an f16 box.
+ *   STACK DROPS LOSE ENTRIES, as they lose counts in pt_count_hits: a dropped subtree is missing from the list without a mark on the item;
+ *   the only report is stack_drops of PT_HITS_STATS.  A caller that needs every crossing checks that counter, or uses PT_HITS_BRUTE_FORCE.
+ * Ordering, errors and alignment: as pt_radius_search.  Rays and hits 16-byte aligned, offsets 8-byte; a NULL or misaligned pointer (hits:
+ *   unless capacity = 0), unknown flags or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the scene).  No triangles + tree:
+ *   PT_ERR_NO_SCENE.  n = 0: PT_OK, no kernel is launched, offsets[0] = 0.  A scene change after a call does not change its results. */
+enum { PT_HITS_STATS = 1u, PT_HITS_SIMPLE_KERNEL = 2u, PT_HITS_BRUTE_FORCE = 4u, PT_HITS_SORTED = 8u };
+/* n rays from device memory (PtRay[n], 16-byte aligned) -> offsets_device: uint64_t[n + 1] (8-byte aligned); hits_device: PtHit[capacity]
+ * (16-byte aligned).  Asynchronous on the context's stream (pt_get_stream), no host wait. */
+PT_API int pt_list_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags,
+                        void* offsets_device, void* hits_device, uint64_t capacity);
+/* The same from host arrays: staged; the host reads the total between the scan and the second walk; returns when everything is written. */
+PT_API int pt_list_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags,
+                             uint64_t* offsets, PtHit* hits, uint64_t capacity);
+/* Host twin (no context, no GPU): the same offsets, entry bits and order (and the same truncation at `capacity`; it sorts by the same key)
+ * and, with PT_HITS_STATS and stats != NULL, the same counters as the device gives for the tree pt_set_bvh4(bvh4) installs over
+ * pt_set_triangles(tris).  bvh4 = NULL (words = 0) only with PT_HITS_BRUTE_FORCE; a malformed bvh4: PT_ERR_BAD_BVH; a NULL rays pointer
+ * with n > 0, NULL offsets, NULL hits with capacity > 0, offsets not 8-byte aligned, or unknown flags: PT_ERR_INVALID_ARG.  rays and hits
+ * need only the alignment of their types here. */
+PT_API int pt_list_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtRay* rays, uint64_t n,
+                             uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity, PtStats* stats);
+
 /* ---- k-nearest queries: which k triangles are closest to a point, each with its contact point? (an extension beyond the reference;
  * DESIGN.md section 19) -----------------------------------------------------------------------------------------------------------
  * Records: PtPoint in, PtClosest out.  out holds n * k PtClosest, row i at out[i*k .. i*k + k-1].  Every result is an integer or a bit

@@ -38,6 +38,8 @@ PT_COUNT_STATS, PT_COUNT_SIMPLE_KERNEL, PT_COUNT_BRUTE_FORCE = 1, 2, 4
 PT_CONTAIN_STATS, PT_CONTAIN_SIMPLE_KERNEL = 1, 2
 # radius queries (include/mi355pt.h pt_radius_search)
 PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
+# hit lists (include/mi355pt.h pt_list_hits)
+PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL, PT_HITS_BRUTE_FORCE, PT_HITS_SORTED = 1, 2, 4, 8
 # k-nearest queries (include/mi355pt.h pt_nearest_k)
 PT_NEAREST_STATS, PT_NEAREST_SIMPLE_KERNEL, PT_NEAREST_BRUTE_FORCE = 1, 2, 4
 PT_NEAREST_MAX_K = 64
@@ -137,6 +139,7 @@ EXPORTS = [
     "pt_count_hits", "pt_count_hits_host", "pt_count_hits_bvh4", "pt_contains", "pt_contains_host", "pt_contains_bvh4",
     "pt_signed_distance", "pt_signed_distance_host",
     "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
+    "pt_list_hits", "pt_list_hits_host", "pt_list_hits_bvh4",
     "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
@@ -281,6 +284,10 @@ def _count_flags(stats, simple, brute_force):
 
 def _radius_flags(stats, simple, brute_force):
     return (PT_RADIUS_STATS if stats else 0) | (PT_RADIUS_SIMPLE_KERNEL if simple else 0) | (PT_RADIUS_BRUTE_FORCE if brute_force else 0)
+
+
+def _hits_flags(stats, simple, brute_force, sort):
+    return (PT_HITS_STATS if stats else 0) | (PT_HITS_SIMPLE_KERNEL if simple else 0) | (PT_HITS_BRUTE_FORCE if brute_force else 0) | (PT_HITS_SORTED if sort else 0)
 
 
 def _nearest_flags(stats, simple, brute_force):
@@ -459,6 +466,34 @@ def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=Fals
                                          pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
                                          entries.ctypes.data_as(C.POINTER(PtClosest)) if cap else None, C.c_uint64(cap),
                                          C.byref(st) if stats else None))
+    if capacity is None:
+        call(None, 0)
+        capacity = int(offsets[n])
+    entries = _aligned_zeros((int(capacity), 4), np.uint32)
+    call(entries, int(capacity))
+    res = (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+    return res + (st.as_dict(),) if stats else res
+
+
+def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.list_hits (no GPU): every triangle of `tris` each ray crosses over the tree set_bvh4(bvh4) installs, with the
+    device's bits and order.  bvh4 None needs brute_force=True.  Returns (offsets, t, prim, u, v): offsets (n + 1,) uint64, the list of ray i
+    at offsets[i]:offsets[i + 1], in visit order (index order with brute_force; ascending (t, prim) with sort=True).  capacity None: every
+    entry (the twin runs twice, once for the total); else the first min(offsets[-1], capacity) entries, offsets complete.  The counters as
+    a dict in sixth place with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    rays = _ray_records(origins, directions, t_max)
+    n = rays.shape[0]
+    offsets = np.zeros(n + 1, np.uint64)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    flags = _hits_flags(stats, simple, brute_force, sort)
+
+    def call(entries, cap):
+        _check(lib.pt_list_hits_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                     rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                     entries.ctypes.data_as(C.POINTER(PtHit)) if cap else None, C.c_uint64(cap),
+                                     C.byref(st) if stats else None))
     if capacity is None:
         call(None, 0)
         capacity = int(offsets[n])
@@ -1237,6 +1272,64 @@ class Context:
         stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_radius_search(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
                                       C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    # ---- hit lists (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 20) ----
+    def list_hits(self, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):
+        """Which triangles does each ray cross (up to t_max), and where?  Returns (offsets, t, prim, u, v): the list of ray i is entries
+        offsets[i]:offsets[i + 1] -- exactly the crossings count_hits counts -- in the walk's visit order (index order with brute_force), or
+        with sort=True in ascending order of (t, prim); the point of an entry is org + t * dir = v0 + u * (v1 - v0) + v * (v2 - v0) of
+        triangle prim.  offsets has n + 1 elements and is always complete: offsets[-1] is the total, and offsets[-1] > capacity says that
+        only the first `capacity` entries were written (the one list that straddles the capacity is then left in visit order).
+
+        origins, directions, t_max: as count_hits.  numpy arrays take the host route (staged, returns when done): offsets is uint64 and the
+        entry arrays hold min(offsets[-1], capacity) elements; capacity=None starts with room for 4 entries per ray and runs the query again
+        when offsets[-1] says that this was too little.
+        torch tensors on the context's device stay there, on the context's stream: offsets is int64, prim torch.uint32.  With `capacity` given
+        the torch route waits for nothing on the host and the entry tensors hold `capacity` elements, of which those from offsets[-1] on are
+        not written.  With capacity=None it reads offsets[-1] once to size the entries: that is the one host wait of this call (the rays
+        are then counted a second time); pass a capacity to avoid it.
+        stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that crossings were lost at the 64-entry stack cap;
+        brute_force lists every crossing regardless."""
+        flags = _hits_flags(stats, simple, brute_force, sort)
+        if _is_torch(origins):
+            _torch_route()
+            import torch
+            rays = self._ray_tensor(origins, directions, t_max, "list_hits")
+            n = rays.shape[0]
+            dev = rays.device
+            offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+            if capacity is None:
+                self._on_context_stream(dev, lambda: self.list_hits_device(rays.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
+                capacity = int(offsets[-1].item())          # the one host wait
+            cap = int(capacity)
+            entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            self._on_context_stream(dev, lambda: self.list_hits_device(rays.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
+            ef = entries.view(torch.float32)
+            return offsets, ef[:, 0], entries.view(torch.uint32)[:, 1], ef[:, 2], ef[:, 3]
+        rays = _ray_records(origins, directions, t_max)
+        n = rays.shape[0]
+        offsets = np.zeros(n + 1, np.uint64)
+
+        def call(entries, cap):
+            self._ck(lib.pt_list_hits_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                           entries.ctypes.data_as(C.POINTER(PtHit)) if cap else None, C.c_uint64(cap)))
+        retry = capacity is None
+        if retry:
+            capacity = 4 * n + 64                   # a first guess; offsets[n] says how large the retry must be
+        entries = _aligned_zeros((int(capacity), 4), np.uint32)
+        call(entries, int(capacity))
+        if retry and int(offsets[n]) > capacity:
+            capacity = int(offsets[n])
+            entries = _aligned_zeros((capacity, 4), np.uint32)
+            call(entries, capacity)
+        return (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+
+    def list_hits_device(self, rays_ptr, n, offsets_ptr, hits_ptr, capacity, flags=0):
+        """Raw device route: n PtRay records at rays_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
+        `capacity` PtHit records at hits_ptr (16-byte aligned; 0 with capacity 0: offsets only).  Three launches on the context's stream
+        (get_stream), four with PT_HITS_SORTED, no host wait; the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_list_hits(self.h, C.c_void_p(rays_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
+                                  C.c_void_p(hits_ptr) if hits_ptr else None, C.c_uint64(capacity)))
 
     # ---- k-nearest queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 19) ----
     def nearest_k(self, points, k, r_max=None, stats=False, simple=False, brute_force=False):

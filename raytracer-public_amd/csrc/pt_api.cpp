@@ -2107,6 +2107,98 @@ int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* 
     return PT_OK;
 }
 
+// ---- hit lists (include/mi355pt.h; pt_hitlist.hip) ------------------------------------------------------------------------------
+// The counts, the scan's scratch and the staging buffers are radius search's (d_rd_*): both queries use them between launches of one
+// call on the context's stream, which orders them, and the host forms wait for the stream before they return.
+
+namespace {
+constexpr uint32_t kHitsFlags = PT_HITS_STATS | PT_HITS_SIMPLE_KERNEL | PT_HITS_BRUTE_FORCE | PT_HITS_SORTED;
+static_assert(PT_HITS_STATS == PT_COUNT_STATS && PT_HITS_SIMPLE_KERNEL == PT_COUNT_SIMPLE_KERNEL && PT_HITS_BRUTE_FORCE == PT_COUNT_BRUTE_FORCE,
+              "the count walk of pt_list_hits is pt_count_hits' with the same flags");
+
+// flags, batch size and the pointers; the scene behind them (check_radius_scene)
+int check_hits(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* offsets, const void* hits, uint64_t capacity) {
+    if (flags & ~kHitsFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
+    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
+    if (!aligned16(rays)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays must be non-null and 16-byte aligned");
+    if (!aligned8(offsets)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": offsets must be non-null and 8-byte aligned");
+    if (capacity ? !aligned16(hits) : (hits && !aligned16(hits)))
+        return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": hits must be 16-byte aligned, and non-null unless capacity is 0");
+    return PT_OK;
+}
+// the count walk (pt_count_hits' own launch, counters included) into the context's buffer and the scan into `offsets`: two launches, no host wait
+int hits_offsets_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, unsigned long long* offsets) {
+    const size_t temp_bytes = ptk::radius_scan_temp_bytes(n);
+    PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_temp.ensure(temp_bytes));
+    if (int rc = count_on_stream(ctx, rays, n, flags & kCountFlags, ctx->d_rd_counts.ptr)) return rc;
+    PT_HIP(ctx, ptk::launch_radius_scan(ctx->d_rd_counts.ptr, n, offsets, ctx->d_rd_temp.ptr, temp_bytes, ctx->stream));
+    return PT_OK;
+}
+// the fill walk from `offsets` into `hits` and, with PT_HITS_SORTED, the sort: one or two launches, no host wait.  PT_HITS_STATS counted
+// over the count walk; its fill walk is the one-ray-per-thread kernel.
+int hits_fill_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* hits, uint64_t capacity) {
+    if (int rc = sync_refit_meta(ctx)) return rc;
+    ptk::RenderArgs A; scene_args(ctx, A);
+    const bool brute = (flags & PT_HITS_BRUTE_FORCE) != 0, simple = (flags & (PT_HITS_SIMPLE_KERNEL | PT_HITS_STATS)) != 0;
+    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_HL_WAVES_PER_SIMD);
+    if (!simple && !brute) PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_HL_SHORT_STACK));
+    PT_HIP(ctx, ptk::launch_hit_fill(A, rays, n, offsets, hits, capacity, simple, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
+    if (flags & PT_HITS_SORTED) PT_HIP(ctx, ptk::launch_hit_sort(offsets, hits, capacity, n, ctx->stream));
+    return PT_OK;
+}
+} // namespace
+
+// three or four launches, no host wait: the counts into the context's buffer, their scan into offsets, the entries, their sort
+int pt_list_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* offsets_device, void* hits_device, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_hits(ctx, "pt_list_hits", rays_device, n, flags, offsets_device, hits_device, capacity)) return rc;
+    if (int rc = check_radius_scene(ctx, "pt_list_hits")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    unsigned long long* offsets = static_cast<unsigned long long*>(offsets_device);
+    if (n == 0) { PT_HIP(ctx, hipMemsetAsync(offsets, 0, sizeof(unsigned long long), ctx->stream)); return PT_OK; }
+    if (int rc = hits_offsets_on_stream(ctx, rays_device, uint32_t(n), flags, offsets)) return rc;
+    if (capacity == 0) return PT_OK;
+    return hits_fill_on_stream(ctx, rays_device, uint32_t(n), flags, offsets, hits_device, capacity);
+}
+
+// staged: the host reads the total between the scan and the fill walk, so the staging buffer holds min(total, capacity) entries
+int pt_list_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_hits(ctx, "pt_list_hits_host", rays, n, flags, offsets, hits, capacity)) return rc;
+    if (int rc = check_radius_scene(ctx, "pt_list_hits_host")) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    if (n == 0) { offsets[0] = 0; return PT_OK; }
+    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rd_offsets.ensure(size_t(n) + 1));
+    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = hits_offsets_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_rd_offsets.ptr, (size_t(n) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t held = std::min<uint64_t>(offsets[n], capacity);
+    if (held == 0) return PT_OK;
+    PT_HIP(ctx, ctx->d_rd_entries.ensure(size_t(held)));
+    if (int rc = hits_fill_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr, ctx->d_rd_entries.ptr, held)) return rc;
+    PT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_rd_entries.ptr, size_t(held) * sizeof(PtHit), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+int pt_list_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtRay* rays, uint64_t n,
+                      uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity, PtStats* stats) {
+    if (flags & ~kHitsFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: unknown flags");
+    const bool brute = (flags & PT_HITS_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && !rays) || !offsets || (capacity && !hits) || (!bvh4 && !brute))
+        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: null pointer");
+    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: offsets must be 8-byte aligned");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: more than 2^32 - 1 rays");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::list_hits(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(rays), n, offsets,
+                       reinterpret_cast<uint32_t*>(hits), capacity, (flags & PT_HITS_SORTED) != 0, (flags & PT_HITS_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
 // ---- k-nearest queries (include/mi355pt.h; pt_knn.hip) --------------------------------------------------------------------------
 
 static_assert(PT_NEAREST_MAX_K == ptk::kNearestMaxK && PT_NEAREST_MAX_K == pt::kNearestMaxK, "one PT_NEAREST_MAX_K for the header, the kernels and the twin");

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <limits>
 #include <thread>
 
@@ -1257,7 +1258,9 @@ inline bool tri_hit_h(const RayH& r, const TriRecord& rec, float& t) {
     return ok_det && ok_u && ok_v && (t > kTriEps_h);
 }
 
-uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt) {
+// the counting walk; every crossing is handed to accept(t, triangle)
+template <class Accept>
+uint32_t walk_cross_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt, Accept accept) {
     const WideBvh& wb = *W.wide;
     uint32_t count = 0;
     if (wb.root_ref == kInvalid || W.num_tris == 0u) return 0u;
@@ -1275,7 +1278,7 @@ uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounter
             if (ti4 < 4u * W.num_tris) {
                 cnt.tris += 1;
                 float t;
-                if (tri_hit_h(r, W.rec[ti4 >> 2], t) && t < best) ++count;
+                if (tri_hit_h(r, W.rec[ti4 >> 2], t) && t < best) { accept(t, ti4 >> 2); ++count; }
             }
             need_pop = true;
         } else {
@@ -1312,6 +1315,26 @@ uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounter
         }
     }
     return count;
+}
+uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt) {
+    return walk_cross_h(W, r, best, cnt, [](float, uint32_t) {});
+}
+// pt_rayquery.hip::hit_record on a triangle record, operation by operation: the u, v of the accepted test
+inline void hit_uv_h(const RayH& r, const TriRecord& rec, float& u, float& v) {
+    const float v0[3] = {rec.axis[0][0], rec.axis[1][0], rec.axis[2][0]};
+    const float e1[3] = {rec.axis[0][1], rec.axis[1][1], rec.axis[2][1]};
+    const float e2[3] = {rec.axis[0][2], rec.axis[1][2], rec.axis[2][2]};
+    auto dot = [](const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    auto cross = [](const float a[3], const float b[3], float c[3]) {
+        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    float pv[3]; cross(r.d, e2, pv);
+    const float det = dot(e1, pv);
+    const float inv_det = 1.0f / det;
+    const float sv[3] = {r.o[0] - v0[0], r.o[1] - v0[1], r.o[2] - v0[2]};
+    u = inv_det * dot(sv, pv);
+    float q[3]; cross(sv, e1, q);
+    v = inv_det * dot(r.d, q);
 }
 } // namespace
 
@@ -1383,6 +1406,84 @@ bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64
         uint32_t odd = 0;
         for (uint32_t s = 0; s < samples; ++s) odd += counts[i * samples + s] & 1u;
         o[0] = 2u * odd > samples ? 1u : 0u; o[1] = odd; o[2] = samples; o[3] = 0u;
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Hit lists (host twin of pt_hitlist.hip): count_hits' walk twice around a scan, the second time storing entry k of ray i at
+// offsets[i] + k, then each fully stored list sorted by (t bits << 32 | prim)
+// ------------------------------------------------------------------------------------
+bool list_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
+               uint64_t* offsets, uint32_t* entries, uint64_t capacity, bool sorted, uint64_t* counters, std::string& err) {
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers), unused(workers);
+    // one ray: the walk (or every triangle in index order), each crossing handed to accept(ray, t, triangle)
+    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
+        RayH r;
+        for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
+        const float tmax = q[3];
+        const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
+        if (nan || !(tmax > 0.0f)) return;
+        const float best = wmin_h(tmax, kInfT_h);
+        if (bvh4) { walk_cross_h(W, r, best, cnt, [&](float t, uint32_t tri) { accept(r, t, tri); }); return; }
+        for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, rec[t], th) && th < best) accept(r, th, t); }
+        cnt.tris += num_tris;
+    };
+    auto parallel = [&](auto run) {
+        if (workers == 1) { run(uint64_t(0)); return; }
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    };
+    // the count walk: offsets[i + 1] holds the count of ray i until the scan
+    offsets[0] = 0;
+    parallel([&](uint64_t w) {
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            uint64_t count = 0;
+            query(rays + i * 8, per[w], [&](const RayH&, float, uint32_t) { ++count; });
+            offsets[i + 1] = count;
+        }
+    });
+    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
+    // the fill walk: the same steps, entry k of ray i at offsets[i] + k where that is below the capacity; then the sort of a list that
+    // was stored in full
+    if (entries && capacity) {
+        parallel([&](uint64_t w) {
+            std::vector<std::array<uint32_t, 4>> list;
+            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+                uint64_t g = offsets[i];
+                if (g >= capacity) break;                       // the offsets only grow
+                query(rays + i * 8, unused[w], [&](const RayH& r, float t, uint32_t tri) {
+                    if (g < capacity) {
+                        float u, v; hit_uv_h(r, rec[tri], u, v);
+                        uint32_t* o = entries + g * 4; o[0] = bits_of(t); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
+                    }
+                    ++g;
+                });
+                if (sorted && offsets[i + 1] <= capacity && offsets[i + 1] - offsets[i] > 1u) {
+                    auto* first = reinterpret_cast<std::array<uint32_t, 4>*>(entries + offsets[i] * 4);
+                    list.assign(first, first + (offsets[i + 1] - offsets[i]));
+                    std::stable_sort(list.begin(), list.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) {
+                        return ((uint64_t(a[0]) << 32) | a[1]) < ((uint64_t(b[0]) << 32) | b[1]);
+                    });
+                    std::memcpy(first, list.data(), list.size() * sizeof(list[0]));
+                }
+            }
+        });
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
     }
     return true;
 }

@@ -130,6 +130,14 @@ bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
 bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
               uint32_t samples, uint32_t seed, uint32_t index_base, uint32_t* out, uint64_t* counters, std::string& err);
 
+// ---- hit lists (pt_list_hits; host twin of pt_hitlist.hip, bit for bit) -----------------------------------------------------------------
+// rays: as count_hits; offsets: n + 1 words, the exclusive prefix sums of count_hits' counts (offsets[n] = the total); entries: (t bits,
+// prim, u bits, v bits) per crossing, the list of ray i in visit order (index order without a tree) from offsets[i] on, written only below
+// `capacity` (entries = nullptr with capacity 0: offsets only).  sorted: every list with offsets[i + 1] <= capacity in ascending order of
+// (t bits << 32 | prim).  counters (optional): as count_hits, over the count walk.
+bool list_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
+               uint64_t* offsets, uint32_t* entries, uint64_t capacity, bool sorted, uint64_t* counters, std::string& err);
+
 // ---- procedural stand-in scenes ---------------------------------------------------
 bool procedural_scene(uint32_t kind, uint32_t seed, uint32_t num_tris, float* out, std::string& err);
 

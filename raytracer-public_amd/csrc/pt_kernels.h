@@ -85,6 +85,22 @@
 #ifndef PT_RD_FILL
 #define PT_RD_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
 #endif
+// hit lists (pt_hitlist.hip): the crossing counts' values taken over for the fill walk, unmeasured for it until tools/hitlist_bench.py has run
+#ifndef PT_HL_SHORT_STACK
+#define PT_HL_SHORT_STACK 12        // LDS stack entries per lane of hit_fill_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_HL_WAVES_PER_SIMD
+#define PT_HL_WAVES_PER_SIMD 6      // wavefronts of hit_fill_kernel per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_HL_FILL
+#define PT_HL_FILL 8                // idle lanes of a wavefront at which they take the next rays of its chunk
+#endif
+#ifndef PT_HL_LANE_MAX
+#define PT_HL_LANE_MAX 16           // hit_sort_kernel: a list of at most this many entries is sorted by one lane, a longer one by its wavefront
+#endif
+#ifndef PT_HL_LDS_MAX
+#define PT_HL_LDS_MAX 512           // hit_sort_kernel: a list of at most this many entries is sorted in LDS (16 bytes each), a longer one on global memory
+#endif
 // k-nearest queries (pt_knn.hip).  The short stack and the fill are the point queries' values taken over: tools/knn_bench.py ran with them
 // (profiles/knn_ab.json), no other value has been tried, so as choices they are unmeasured.  The waves per SIMD follow from the LDS of a one-wavefront workgroup, 8 * 64 * (PT_NK_SHORT_STACK + KCAP)
 // bytes: floor(floor(163,840 / LDS) / 4), capped at the point queries' 6 -- 8,192 B, 14,336 B and 38,912 B for the tiers 4, 16 and 64.
@@ -302,6 +318,15 @@ hipError_t launch_radius(const RenderArgs& A, const void* points, uint32_t n, vo
 // item n read as 0); temp: at least radius_scan_temp_bytes(n) bytes
 size_t radius_scan_temp_bytes(uint32_t n);
 hipError_t launch_radius_scan(const void* counts, uint32_t n, unsigned long long* offsets, void* temp, size_t temp_bytes, hipStream_t stream);
+// ---- hit lists (pt_hitlist.hip): every crossing along a ray, with t, triangle and u, v -------------------------------------------
+// The fill walk behind launch_count_hits and launch_radius_scan: rays: PtRay[n]; entry k of ray i (a PtHit record, in visit order) goes to
+// entries[offsets[i] + k] where that index is below `capacity`.  brute: every triangle in index order; simple: one ray per thread; else the
+// persistent kernel with `grid` wavefronts at most (walk_grid(.., PT_HL_WAVES_PER_SIMD)), the queue block and
+// walk_spill_entries(grid, PT_HL_SHORT_STACK) spill entries.
+hipError_t launch_hit_fill(const RenderArgs& A, const void* rays, uint32_t n, const unsigned long long* offsets, void* entries, unsigned long long capacity,
+                           bool simple, bool brute, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// every list with offsets[i + 1] <= capacity in place into ascending (t bits << 32 | prim)
+hipError_t launch_hit_sort(const unsigned long long* offsets, void* entries, unsigned long long capacity, uint32_t n, hipStream_t stream);
 // ---- k-nearest queries (pt_knn.hip): the k closest triangles to each point ----------------------------------------------------------
 // points: PtPoint[n] (float4 each, 16-byte aligned); out: PtClosest[n * k] (uint4 each), row i at out[i * k], sorted by distance and padded
 // with (+inf, 0xFFFFFFFF, 0, 0); 1 <= k <= kNearestMaxK.  One launch, the closest-point walk with best2 replaced by the k-th best squared

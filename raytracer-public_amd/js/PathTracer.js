@@ -232,6 +232,36 @@ class PathTracer {
     return { count: s.prim.length, dist: s.dist, prim: s.prim, u: s.u, v: s.v };
   }
 
+  // ---- hit lists: an extension beyond the reference (include/mi355pt.h pt_list_hits, DESIGN.md section 20) ----
+  // rays: Float32Array, 8 floats per ray (origin xyz, tMax, direction xyz, 0).  Resolves to { offsets, t, prim, u, v }: the triangles ray i
+  // crosses before tMax -- the ones countHits counts -- are entries offsets[i] .. offsets[i + 1] - 1 (offsets: Float64Array of n + 1 exact
+  // integers), each with its distance t and its barycentrics u, v, in the order the walk meets them (triangle order with
+  // options.bruteForce), or with options.sort in ascending order of t (equal t: ascending prim).  A ray with a NaN or tMax <= 0 has an
+  // empty list.  options.simple: the one-ray-per-thread kernels.  A ray through a very deep tree can lose crossings at the 64-entry stack
+  // cap (the header says when); bruteForce never does.  Triangles only.  On a group: member 0, which holds the whole scene.
+  async listHits(rays, options) {
+    const o = options || {}, flags = (o.simple ? 2 : 0) | (o.bruteForce ? 4 : 0) | (o.sort ? 8 : 0);
+    return this.group ? native().groupListHits(this.group, rays, flags) : native().listHits(this.device, rays, flags);
+  }
+  // Every crossing of the ray from (ox, oy, oz) along (dx, dy, dz), nearest first: resolves to { count, t, prim, u, v }.  options.tMax
+  // (default: no limit), options.simple, options.bruteForce.
+  async hitsAlong(ox, oy, oz, dx, dy, dz, options) {
+    const o = options || {}, tMax = o.tMax === undefined ? Infinity : o.tMax;
+    const s = await this.listHits(Float32Array.of(ox, oy, oz, tMax, dx, dy, dz, 0), Object.assign({}, o, { sort: true }));
+    return { count: s.prim.length, t: s.t, prim: s.prim, u: s.u, v: s.v };
+  }
+  // A thickness frame of the current camera: camera rays -> listHits(sort) -> t[1] - t[0].  Resolves to a Float32Array of width * height
+  // distances between the first and the second crossing, row-major like the radiance; 0 where the camera ray has fewer than two crossings.
+  async thickness(options) {
+    const w = this.canvas.width, h = this.canvas.height, ubo = this._ubo();
+    const rays = new Float32Array(w * h * 8);
+    for (let y = 0; y < h; y++) for (let x = 0; x < w; x++) rays.set(native().cameraRay(ubo, x, y), (y * w + x) * 8);
+    const s = await this.listHits(rays, Object.assign({}, options || {}, { sort: true }));
+    const out = new Float32Array(w * h);
+    for (let i = 0; i < w * h; i++) { const a = s.offsets[i]; if (s.offsets[i + 1] - a >= 2) out[i] = Math.fround(s.t[a + 1] - s.t[a]); }
+    return out;
+  }
+
   // ---- k-nearest queries: an extension beyond the reference (include/mi355pt.h pt_nearest_k, DESIGN.md section 19) ----
   // points: Float32Array, 4 floats per point (x, y, z, rMax; rMax = Infinity for no limit); k: 1 .. 64.  Resolves to { k, dist, prim, u, v }
   // (Float32Array / Uint32Array of n * k): row i at [i * k, i * k + k) holds the at most k triangles within rMax in ascending order of

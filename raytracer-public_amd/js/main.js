@@ -21,6 +21,8 @@
 //        [--nearest X,Y,Z]                                   after the frames: the point of the scene nearest to (X, Y, Z), as one JSON line (closest-point query, an extension)
 //        [--ao S [--ao-radius R]]                            after the frames: an ambient-occlusion frame of the camera, S samples per pixel within R (default: no limit), grey
 //                                                            (v, v, v, 1) with v = visibility, 0 where the camera ray misses; --out writes it (linear, v * 255 rounded), --radiance the floats
+//        [--thickness]                                       after the frames: a thickness frame of the camera, grey (d, d, d, 1) with d = t[1] - t[0] of the camera ray's sorted hit list
+//                                                            (hit lists, an extension), black where the ray has fewer than two crossings; --out writes it (linear, min(d, 1) * 255 rounded), --radiance the floats
 //        [--pick X,Y]                                        after the frames: what is under pixel (X, Y), as one JSON line (ray query, an extension)
 "use strict";
 const fs = require("fs");
@@ -117,6 +119,15 @@ async function main() {
     for (let i = 0; i < vis.length; i++) { aoFrame[4 * i] = aoFrame[4 * i + 1] = aoFrame[4 * i + 2] = vis[i]; aoFrame[4 * i + 3] = 1; sum += vis[i]; }
     console.log(JSON.stringify({ ao: aoSamples, radius: radius === null ? null : Number(radius), width: canvas.width, height: canvas.height, meanVisibility: sum / vis.length }));
   }
+  if (flag("thickness")) {       // camera rays -> listHits(sort) -> t[1] - t[0] (an extension)
+    pathTracer.setCameraPosition(camera.position[0], camera.position[1], camera.position[2]);
+    pathTracer.setCameraQuaternion(camera.rotation[0], camera.rotation[1], camera.rotation[2], camera.rotation[3]);
+    const d = await pathTracer.thickness();
+    aoFrame = new Float32Array(d.length * 4);
+    let sum = 0, walls = 0;
+    for (let i = 0; i < d.length; i++) { aoFrame[4 * i] = aoFrame[4 * i + 1] = aoFrame[4 * i + 2] = d[i]; aoFrame[4 * i + 3] = 1; if (d[i] > 0) { sum += d[i]; walls++; } }
+    console.log(JSON.stringify({ thickness: true, width: canvas.width, height: canvas.height, pixelsWithTwoHits: walls, meanThickness: walls ? sum / walls : null }));
+  }
   const radiance = arg("radiance", null), trisOut = arg("triangles", null);      // what a test compares with the oracle: the last frame (f32 RGBA) and the triangles it was traced over
   if (radiance) { const img = aoFrame || pathTracer.readRadiance(); fs.writeFileSync(radiance, Buffer.from(img.buffer, img.byteOffset, img.byteLength)); }
   if (trisOut) { const t = pathTracer.trianglesData; fs.writeFileSync(trisOut, Buffer.from(t.buffer, t.byteOffset, t.byteLength)); }
@@ -135,7 +146,7 @@ async function main() {
   const out = arg("out", null);
   if (out) {      // what the tonemapper pass would have put on the canvas (tonemapper.wgsl)
     let rgba = null;
-    if (aoFrame) { rgba = new Uint8Array(aoFrame.length); for (let i = 0; i < aoFrame.length; i++) rgba[i] = Math.round(aoFrame[i] * 255); }
+    if (aoFrame) { rgba = new Uint8Array(aoFrame.length); for (let i = 0; i < aoFrame.length; i++) rgba[i] = Math.round(Math.min(aoFrame[i], 1) * 255); }
     else rgba = pathTracer.readTonemapped(true);
     const header = Buffer.from("P6\n" + canvas.width + " " + canvas.height + "\n255\n");
     const rgb = Buffer.alloc(canvas.width * canvas.height * 3);

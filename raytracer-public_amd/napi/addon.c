@@ -503,6 +503,53 @@ static napi_value fn_radius_search(napi_env env, napi_callback_info info) {     
     return radius_search_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- hit lists (an extension beyond the reference; include/mi355pt.h pt_list_hits_host) ------------------------------------------------ */
+
+/* rays: Float32Array of 8 floats per ray; flags: PT_HITS_* -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), t, prim,
+ * u, v }: every entry.  The first call has room for 4 entries per ray; when offsets[n] says that this was too little, the query runs again
+ * with room for all. */
+static napi_value list_hits_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value flags_v) {
+    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, "listHits: 8 floats per ray"); return NULL; }
+    const uint32_t flags = get_u32(env, flags_v);
+    const size_t n = len / 8;
+    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
+    uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
+    uint64_t cap = 4 * (uint64_t)n + 64;
+    PtHit* res = (PtHit*)aligned_alloc(16, (size_t)cap * sizeof(PtHit));
+    if (!rays || !off || !res) { free(rays); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(rays, d, n * sizeof(PtRay));
+    int rc = pt_list_hits_host(ctx, rays, n, flags, off, res, cap);
+    if (rc == 0 && off[n] > cap) {
+        cap = off[n];
+        free(res);
+        res = (PtHit*)aligned_alloc(16, (size_t)cap * sizeof(PtHit));
+        if (!res) { free(rays); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        rc = pt_list_hits_host(ctx, rays, n, flags, off, res, cap);
+    }
+    free(rays);
+    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_list_hits_host"); }
+    const size_t m = (size_t)off[n];
+    napi_value o, offs, t, prim, u, v; void *po, *pt_, *pp, *pu, *pv;
+    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(t = make_typed(env, napi_float32_array, 4, m, &pt_)) ||
+        !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) || !(u = make_typed(env, napi_float32_array, 4, m, &pu)) ||
+        !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(off); free(res); return NULL; }
+    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
+    for (size_t i = 0; i < m; ++i) {
+        ((float*)pt_)[i] = res[i].t; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
+    }
+    free(off); free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_list_hits(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array rays, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return list_hits_on(env, ctx, argv[1], argv[2]);
+}
+
 /* ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h pt_occlusion_host, pt_hit_surfels_host) ---- */
 
 /* surfels: Float32Array of 8 floats per surfel (PtSurfel: p xyz, rMax, n xyz, reserved); opt: { samples, seed, bias, indexBase, simple }
@@ -912,6 +959,12 @@ static napi_value fn_group_radius_search(napi_env env, napi_callback_info info) 
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return radius_search_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_list_hits(napi_env env, napi_callback_info info) {      /* (group, rays, flags): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return list_hits_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_hit_surfels(napi_env env, napi_callback_info info) {     /* (group, rays, t, prim, u, v, rMax): on member 0 */
     napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -979,6 +1032,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
         {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
         {"nearestK", fn_nearest_k}, {"groupNearestK", fn_group_nearest_k},
+        {"listHits", fn_list_hits}, {"groupListHits", fn_group_list_hits},
         {"radiusCount", fn_radius_count}, {"groupRadiusCount", fn_group_radius_count}, {"radiusSearch", fn_radius_search}, {"groupRadiusSearch", fn_group_radius_search},
         {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
