@@ -1,6 +1,6 @@
 """An exhaustive audit of a BVH as the traversal sees it: every triangle of every tree, not the rays a test happens to sample.
 
-Three checks, all O(N) on the reference side, numpy and float64 only -- no oracle, no product code:
+Four checks, all O(N) on the reference side, numpy and float64 only -- no oracle, no product code:
 
 1. verify_bvh4 / verify_bvh2: a proof on the words read back from the device (read_bvh4 / read_bvh2).  Topology (every reachable node
    reached once, every triangle in exactly one reachable leaf, child counts, pre-order for trees this library builds); transitive
@@ -12,6 +12,12 @@ Three checks, all O(N) on the reference side, numpy and float64 only -- no oracl
 3. near_points / far_points / judge_closest, judge_radius, judge_knn, judge_counts / audit_points: the origins of those rays, and one point
    farther above every centroid, through the closest-point, radius, k-nearest and crossing-count queries, judged by float64 point-triangle
    distances (closestref) against that triangle and the reported ones alone: O(points + listed entries).
+
+4. through_rays / aimed_surfels / judge_hits, judge_occlusion / audit_lists: the aimed rays made long (from outside the scene's box, t_max =
+   +inf) through list_hits, sorted and unsorted, and the counting walk behind count_hits and contains; the aimed rays as surfels through
+   occlusion (the sample rays are the product's occlusion_rays_host, the one piece of product code on the reference side: it is pinned to
+   numpy bit for bit and is no part of any walk); contains, signed_distance and occlusion against their compositions.  Judged by float64 Moeller-Trumbore against the own
+   triangle and the listed ones alone: O(rays + listed entries).
 
 The megakernel's own traversal (pt_megakernel_loop.inc) cannot be reached by caller rays, so check 2 does not cover it; it stays covered by
 the sampled pathref renders and by bit equality with the other kernels over the same arena, which check 1 does cover.
@@ -294,7 +300,7 @@ def aimed_rays(tris, k=4, h=H_REL):
 
 
 def margins(tris, O, D, prim, t_max):
-    """pathref._candidates for the pair (ray i, triangle prim[i]) alone, elementwise: -> dict(acc, loose, tight, t, u, v, mt)."""
+    """pathref._candidates for the pair (ray i, triangle prim[i]) alone, elementwise: -> dict(acc, loose, tight, t, u, v, mt, mb, det)."""
     det, u, v, t = pathref.pair(tris, O, D, prim)
     T = np.asarray(tris, np.float32).reshape(-1, 3, 3)[np.asarray(prim, np.int64)].astype(np.float64)
     o = np.asarray(O, np.float32).astype(np.float64); d = np.asarray(D, np.float32).astype(np.float64)
@@ -312,7 +318,7 @@ def margins(tris, O, D, prim, t_max):
         acc = (adet >= eps) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t > eps) & (t < b0)
         loose = (adet >= eps - pathref.D_DET) & (bary > -mb) & (t > eps - mt) & (t < b0 + mt)
         tight = (adet >= eps + pathref.D_DET) & (bary >= mb) & (t >= eps + mt) & (t <= b0 - mt)
-    return dict(acc=acc, loose=loose | acc, tight=tight, t=t, u=u, v=v, mt=mt, det=det)
+    return dict(acc=acc, loose=loose | acc, tight=tight, t=t, u=u, v=v, mt=mt, mb=mb, det=det)
 
 
 class Judgement:
@@ -520,6 +526,12 @@ class HostContext:
     def count_hits(self, origins, directions=None, t_max=None, **kw):
         return self._twin(self.rt.count_hits_bvh4, origins, directions, t_max, **kw)[0]
 
+    def list_hits(self, origins, directions=None, t_max=None, **kw):
+        return self._twin(self.rt.list_hits_bvh4, origins, directions, t_max, **kw)
+
+    def contains(self, points, samples=3, **kw):
+        return self._twin(self.rt.contains_bvh4, points, samples, **kw)
+
 
 # ---- aimed points: the point and crossing-count queries ---------------------------------------------------------------------------------
 H2_REL = 16 * 2.0 ** -12             # the far pass: sixteen times the slack s = 2^-12 of bound2
@@ -599,7 +611,8 @@ class PointJudgement:
 
     def counts(self):
         """the figures two runs over the same bits must share"""
-        return (self.R, int((~self.auditable).sum()), int(self.excused.sum()), len(self.lost), len(self.lost_tris), len(self.phantom), len(self.malformed), self.entries)
+        return (self.R, int((~self.auditable).sum()), int(self.excused.sum()), len(self.lost), len(self.lost_tris), len(self.phantom), len(self.malformed), self.entries,
+                len(getattr(self, "values_off", ())))
 
 
 def _point_judgement(pts, query, excuse, t0, lost, phantom, malformed, excused, entries):
@@ -717,7 +730,11 @@ def assert_point_judged(j, name, tree=None, capped=True):
         raise AssertionError("%s %s, %s pass: %d lost triangles, first %s%s" % (name, j.query, j.what, len(j.lost_tris), j.lost_tris[:20].tolist(), why))
     assert len(j.phantom) == 0, "%s %s, %s pass: %d points report an entry the reference cannot accept, first points %s" % (name, j.query, j.what, len(j.phantom), j.phantom[:10].tolist())
     assert len(j.malformed) == 0, "%s %s, %s pass: %d points with a malformed list, row or count, first points %s" % (name, j.query, j.what, len(j.malformed), j.malformed[:10].tolist())
+    off = getattr(j, "values_off", ())                                          # judge_hits only: t, u or v of a certain entry beyond the pair's own margin
+    assert len(off) == 0, "%s %s: t, u or v beyond the pair's margin on %d rays (worst %.3f of it), first %s" % (name, j.query, len(off), j.worst, off[:10].tolist())
     if capped:
+        blind = getattr(j, "share_blind_tris", 0.0)                             # judge_occlusion only
+        assert blind <= pathref.FRAGILE_CAP, "%s %s: %.2f %% of the triangles have no auditable surfel (cap 2 %%)" % (name, j.query, 100 * blind)
         cap = pathref.FRAGILE_CAP
         assert j.share_not_auditable <= cap, "%s %s, %s pass: %.2f %% of the points are not auditable (cap 2 %%): change the scene or the distance" % (name, j.query, j.what, 100 * j.share_not_auditable)
         assert j.share_excused <= cap, "%s %s, %s pass: %.2f %% of the points are %s (cap 2 %%): change the scene or the distance" % (name, j.query, j.what, 100 * j.share_excused, j.excuse)
@@ -805,6 +822,272 @@ def audit_points(ctx, tris, name, rays=None, kernels=KERNELS, capped=True, tree=
     return out
 
 
+# ---- through rays and aimed surfels: hit lists, occlusion, containment and signed distance -----------------------------------------------
+OCC_SAMPLES, OCC_SEED = 8, 7         # occlusion over the aimed surfels: samples per surfel, a fixed seed; bias 0
+CONTAIN_SAMPLES = 3
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _product():
+    import importlib
+    return importlib.import_module("raytracer-public_amd")
+
+
+def through_rays(tris, k=None):
+    """The aimed rays made long: each keeps its direction, its origin is moved back along the ray to where the line leaves the scene's
+    bounding box grown by 5 % of its diagonal (float64, rounded to f32 before anybody sees it), t_max = +inf.  Such a ray crosses its own
+    triangle at the aimed point and whatever else lies on the line.  k: rays per triangle, 4 for scenes below 1,000 triangles and 1 above.
+    .aimed: the aimed rays they were made from (the surfels and near-pass points of the same audit)."""
+    n = np.asarray(tris).size // 9
+    k = (4 if n < 1000 else 1) if k is None else k
+    a = aimed_rays(tris, k)
+    V = np.asarray(tris, np.float32).reshape(-1, 3).astype(np.float64)
+    lo, hi = V.min(0), V.max(0)
+    pad = 0.05 * np.sqrt(((hi - lo) ** 2).sum())
+    lo, hi = lo - pad, hi + pad
+    o, d = a.O.astype(np.float64), a.D.astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = np.where(d > 0, (o - lo) / d, np.where(d < 0, (o - hi) / d, np.inf)).min(1)      # o - s d reaches a face of the box
+    s = np.maximum(s, 0.0)
+    r = Rays()
+    r.O = (o - s[:, None] * d).astype(np.float32)
+    r.D = a.D
+    r.t_max = np.full(len(o), np.inf, np.float32)
+    r.tri, r.P, r.k, r.n, r.own, r.aimed = a.tri, a.P, k, a.n, None, a
+    return r
+
+
+def aimed_surfels(rays):
+    """One PtSurfel record per aimed ray: p = the ray's origin, n = its direction, r_max = its t_max -- the normal points at the triangle,
+    h' above it, and the sample rays end 2 h' away."""
+    sf = np.zeros((len(rays.tri), 8), np.float32)
+    sf[:, 0:3], sf[:, 3], sf[:, 4:7] = rays.O, rays.t_max, rays.D
+    return sf
+
+
+def containment_rays(points, samples=CONTAIN_SAMPLES):
+    """The rays contains() counts along: the occlusion rays of the surfels {p, +inf, (0, 0, 1)}, bias 0, seed 0."""
+    sf = np.zeros((len(points), 8), np.float32)
+    sf[:, 0:3], sf[:, 3], sf[:, 6] = np.asarray(points, np.float32)[:, :3], np.inf, 1.0
+    return _product().occlusion_rays_host(sf, samples, seed=0, bias=0.0)
+
+
+PAIR_FIELDS = ("loose", "tight", "t", "u", "v", "mt", "mb")
+
+
+def pair_margins(tris, rays, owner, prim):
+    """margins() of the pairs (ray owner[i], triangle prim[i]), each pair evaluated once per ray set however many kernels list it."""
+    keys = (np.asarray(owner, np.int64) << 32) | np.asarray(prim, np.int64)
+    if getattr(rays, "pairs", None) is None:
+        rays.pairs = (np.zeros(0, np.int64), {f: np.zeros(0, bool if f in ("loose", "tight") else np.float64) for f in PAIR_FIELDS})
+    known_keys, memo = rays.pairs
+    pos = np.minimum(np.searchsorted(known_keys, keys), max(len(known_keys) - 1, 0))
+    known = known_keys[pos] == keys if len(known_keys) else np.zeros(len(keys), bool)
+    new = np.unique(keys[~known])
+    if len(new):
+        ri = new >> 32
+        m = margins(tris, rays.O[ri], rays.D[ri], new & 0xFFFFFFFF, rays.t_max[ri])
+        k = np.concatenate([known_keys, new]); order = np.argsort(k, kind="stable")
+        rays.pairs = known_keys, memo = k[order], {f: np.concatenate([memo[f], m[f]])[order] for f in PAIR_FIELDS}
+        pos = np.searchsorted(known_keys, keys)
+    return {f: memo[f][pos] for f in PAIR_FIELDS}
+
+
+def judge_hits(tris, rays, lists, sorted_lists, counts):
+    """lists, sorted_lists = (offsets, t, prim, u, v) of list_hits without and with sort, counts of count_hits, over the same rays (through_rays).
+    O(rays + listed entries): float64 Moeller-Trumbore of each ray against its own triangle and against each listed one, nothing else.
+    Lost: the own triangle is accepted with every margin to spare and is not in the list, or the count of such a ray is 0.  Phantom: an entry
+    whose triangle is out of range or not even loosely accepted.  Malformed: a triangle twice; a list whose length is not the count, or not
+    the sorted list's; a sorted list out of ascending (bits(t) << 32) | prim; one that is no permutation of the unsorted list (multisets of
+    the four words); a t that is not positive and finite.  values_off: an entry the reference accepts for certain whose u or v is more than
+    the pair's own mb, or whose t more than its mt, from float64 -- margins()' rule, 16 ulp x kappa, no new constant; .worst is the largest
+    such ratio (measured over every case of tests/test_list_audit.py and tests/test_gpu_list_audit.py: at most 0.148; above 1 it is a finding
+    to explain, not a margin to widen).  Nothing is excused: a list reports every crossing, so no occluder can answer in place of the own triangle."""
+    t0 = time.time()
+    if rays.own is None:
+        rays.own = margins(tris, rays.O, rays.D, rays.tri, rays.t_max)
+    aud = rays.own["tight"]
+    n, R = rays.n, len(rays.tri)
+    off, t, prim, u, v = [np.asarray(a) for a in lists]
+    soff, st, sprim, su, sv = [np.asarray(a) for a in sorted_lists]
+    off, soff = off.astype(np.int64), soff.astype(np.int64)
+    for o_, p_ in ((off, prim), (soff, sprim)):
+        assert len(o_) == R + 1 and o_[0] == 0 and o_[-1] == len(p_) and np.all(np.diff(o_) >= 0), "offsets are no offsets into the entries"
+    lens, slens = np.diff(off), np.diff(soff)
+    owner, sowner = np.repeat(np.arange(R), lens), np.repeat(np.arange(R), slens)
+    phantom = np.zeros(R, bool); malformed = np.zeros(R, bool)
+    # every listed entry against float64
+    inr = prim < n
+    phantom[owner[~inr]] = True
+    ei = np.flatnonzero(inr)
+    oe = owner[ei]
+    m = pair_margins(tris, rays, oe, prim[ei])
+    phantom[oe[~m["loose"]]] = True
+    sure = m["tight"]
+    with np.errstate(all="ignore"):
+        ratio = np.maximum(np.maximum(np.abs(u[ei] - m["u"]), np.abs(v[ei] - m["v"])) / m["mb"], np.abs(t[ei] - m["t"]) / m["mt"])
+        ratio = np.where(sure, ratio, 0.0)
+        badt = ~(np.isfinite(t) & (t > 0)); sbadt = ~(np.isfinite(st) & (st > 0))
+    values_off = np.unique(oe[~(ratio <= 1)])
+    # form
+    key = np.sort((owner << 32) | prim.astype(np.int64))
+    malformed[key[1:][key[1:] == key[:-1]] >> 32] = True                       # a triangle twice in one list
+    malformed |= (np.asarray(counts).astype(np.int64) != lens) | (lens != slens)
+    malformed[owner[badt]] = True; malformed[sowner[sbadt]] = True
+    skey = (_bits(st).astype(np.uint64) << np.uint64(32)) | sprim.astype(np.uint64)
+    down = (sowner[1:] == sowner[:-1]) & (skey[1:] < skey[:-1])
+    malformed[sowner[1:][down]] = True                                         # not in ascending order of (bits(t) << 32) | prim
+    same = lens == slens                                                       # a permutation: the lists of equal length, as multisets of the four words
+    rows = []
+    for ow, (a, b, c, d_) in ((owner, (t, prim, u, v)), (sowner, (st, sprim, su, sv))):
+        pick = np.flatnonzero(same[ow])
+        k1 = (ow[pick] << 32) | b[pick].astype(np.int64)
+        k2 = (_bits(a)[pick].astype(np.int64) << 32) | _bits(c)[pick].astype(np.int64)
+        k3 = _bits(d_)[pick].astype(np.int64)
+        order = np.lexsort((k3, k2, k1))
+        rows.append((k1[order], k2[order], k3[order]))
+    differ = (rows[0][0] != rows[1][0]) | (rows[0][1] != rows[1][1]) | (rows[0][2] != rows[1][2])
+    malformed[np.unique(np.concatenate([rows[0][0][differ], rows[1][0][differ]]) >> 32)] = True
+    has_own = np.isin((np.arange(R) << 32) | rays.tri, key)
+    lost = aud & (~has_own | (np.asarray(counts) == 0))
+    j = PointJudgement()
+    j.query, j.what, j.excuse, j.n, j.R, j.tri, j.auditable = "list_hits", "through", "excused", n, R, rays.tri, aud
+    j.lost, j.phantom, j.malformed, j.values_off = np.flatnonzero(lost), np.flatnonzero(phantom), np.flatnonzero(malformed), values_off
+    j.excused = np.zeros(R, bool)
+    j.lost_tris = np.unique(rays.tri[j.lost])
+    j.share_not_auditable = float((~aud).mean()) if R else 0.0
+    j.share_excused, j.entries = 0.0, len(prim)
+    j.worst = float(ratio.max(initial=0.0))
+    j.share_margin = float((m["loose"] & ~sure).mean()) if len(ei) else 0.0
+    j.longest = int(lens.max(initial=0))
+    j.sorted = (soff, st, sprim, su, sv)
+    j.certain = (oe[sure], prim[ei][sure])                                      # (ray, triangle) of every entry the reference accepts for certain
+    j.seconds = time.time() - t0
+    return j
+
+
+def occlusion_floor(tris, rays, samples=OCC_SAMPLES, seed=OCC_SEED):
+    """Per aimed surfel: how many of its sample rays (occlusion_rays_host: pinned to numpy bit for bit, no part of any walk; bias 0) accept
+    the surfel's own triangle with every margin to spare, in float64, against that triangle alone.  Computed once per ray set."""
+    memo = getattr(rays, "occ", None)
+    if memo is None or memo[0] != (samples, seed):
+        sr = _product().occlusion_rays_host(aimed_surfels(rays), samples, seed=seed, bias=0.0)
+        m = margins(tris, sr[:, 0:3], sr[:, 4:7], np.repeat(rays.tri, samples), sr[:, 3])
+        rays.occ = memo = ((samples, seed), m["tight"].reshape(-1, samples).sum(1))
+    return memo[1]
+
+
+def judge_occlusion(tris, rays, result, samples=OCC_SAMPLES, seed=OCC_SEED):
+    """result = (visibility, unoccluded, samples) of occlusion over aimed_surfels(rays), bias 0.  A lower bound: samples - unoccluded must
+    be at least occlusion_floor -- any-hit may be answered by any triangle, but a sample ray that certainly crosses the own triangle within
+    r_max is occluded.  A shortfall is a lost triangle.  Malformed: a samples field that is not `samples`, a visibility that is not the
+    correctly rounded unoccluded / samples.  Not auditable: a surfel none of whose sample rays certainly crosses its triangle;
+    share_blind_tris: triangles without an auditable surfel."""
+    t0 = time.time()
+    floor = occlusion_floor(tris, rays, samples, seed)
+    vis, unocc, smp = [np.asarray(a) for a in result]
+    n, R = rays.n, len(rays.tri)
+    want = (unocc.astype(np.float64) / samples).astype(np.float32)
+    j = PointJudgement()
+    j.query, j.what, j.excuse, j.n, j.R, j.tri, j.auditable = "occlusion", "surfel", "excused", n, R, rays.tri, floor > 0
+    j.lost = np.flatnonzero(samples - unocc.astype(np.int64) < floor)
+    j.phantom = np.zeros(0, np.int64)
+    j.malformed = np.flatnonzero((smp != samples) | (unocc > samples) | (_bits(vis) != _bits(want)))
+    j.excused = np.zeros(R, bool)
+    j.lost_tris = np.unique(rays.tri[j.lost])
+    j.share_not_auditable = float((floor == 0).mean()) if R else 0.0
+    j.share_blind_tris = float((np.bincount(rays.tri[floor > 0], minlength=n) == 0).mean()) if n else 0.0
+    j.share_sure = float(floor.sum()) / max(R * samples, 1)
+    j.share_excused, j.entries, j.seconds = 0.0, int(floor.sum()), time.time() - t0
+    return j
+
+
+def audit_lists(ctx, tris, name, kernels=KERNELS, capped=True, rays=None, brute=True, tree=None):
+    """Every triangle through the hit lists, the long counting walk, containment, and (on a device context) occlusion and signed distance of
+    `ctx`: one through ray per triangle (four below 1,000 triangles) through list_hits, list_hits(sort) and count_hits of every kernel in
+    `kernels` and through judge_hits; OCC_SAMPLES occlusion samples per aimed surfel through judge_occlusion; and the compositions as
+    equalities -- occlusion with occlusion_rays -> trace_rays(any_hit), contains(samples 3) over the near-pass points with the parity
+    majority of count_hits over containment_rays, signed_distance with closest_points under contains' sign.  The counting variant of every
+    query runs first and must drop nothing at the 64-entry cap.  Last, list_hits(brute_force=True) goes through judge_hits: with no tree
+    nothing can be lost, so that call validates the judge (`brute`: the brute-force lists do not depend on the tree, so a caller that
+    audits several trees over the same triangles may ask for them once).  -> {(query, simple or "brute"): judgement}.
+
+    Measured on the CPU over the host twins, built and refitted after `wave` and `deform`, accel 0, 1 and 2 (tests/test_list_audit.py prints
+    them; the lists of a scene are the same at every level, only the stack differs).  No ray of any case was not auditable, nothing was lost,
+    unexplained or malformed, no walk dropped a push.  Listed entries, built / wave / deform; the longest list; the deepest stack of the three
+    levels and states (of 64; persistent_walk's short stack is 12); entries at a margin of the reference; the largest deviation of a listed
+    t, u or v from float64 as a share of that pair's own margin (mt, mb):
+      soups 1, 2, 3, 4, 5 (4 rays each)   4 .. 20 / = / =                 1     2    0 %              0.050
+      soups 64, 65                        267, 265 / 264, 273 / 265, 266  3     7    0 %              0.067
+      soup 777                            4,719 / 4,916 / 5,016           6     14   0.040 - 0.042 %  0.101
+      soup 30,000 (size 0.2)              632,993 / 676,057 / 201,318     57    31   0.035 - 0.063 %  0.148     deform is of the same soup at size 0.1
+      soup 30,000, size 0.02              36,174 / 36,601 / 36,953        6     21   0.064 - 0.079 %  0.123
+      dragon-class 20,000                 68,114 / 69,718 / 72,262        18    25   0.046 - 0.094 %  0.114
+      sponza-class 12,000                 54,860 / 61,302 / .             32    21   0.68 - 0.73 %    0.117     wave only (test_point_audit.MOVES)
+      f16 grid                            1,536 / 1,952 / 3,353           9     16   0 - 0.060 %      0.091
+      coincident deck (12 triangles)      288                             6     7    0 %              0.003
+    A ratio above 1 would be a finding to explain, not a margin to widen; the largest anywhere is 0.148.
+    Occlusion's reference side (no tree: occlusion_floor) over the same states -- sample rays that certainly cross the own triangle / surfels
+    without such a ray = triangles without such a surfel above 1,000 triangles, where each has one surfel:
+      small soups 69.5 - 78.1 % / 0 %;  soup 30,000 70.2 - 71.1 % / 0.023 - 0.040 %;  size 0.02 70.2 - 71.2 % / 0.050 - 0.097 %;
+      dragon-class 71.8 - 72.2 % / 0 %;  sponza-class 61.0 - 61.1 % / 0.367 %;  f16 grid 71.4 - 71.6 % / 0 %.
+    On the MI355X (tests/test_gpu_list_audit.py) every case above gave the twin's figures in every category through both kernels and the
+    brute-force kernel, nothing lost below the occlusion bound, and every composition held."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    thr = through_rays(tris) if rays is None else rays
+    aim = thr.aimed
+    device = hasattr(ctx, "occlusion")
+    if tree is None:
+        tree = lambda: verify_bvh4(tris, ctx.read_bvh4(), built=False)
+    pts = np.concatenate([aim.O, aim.t_max[:, None]], 1)
+    sf = aimed_surfels(aim)
+    crays = containment_rays(pts)
+    # the counting variants: nothing dropped at the cap
+    seen = {}
+    ctx.list_hits(thr.O, thr.D, stats=True); seen["list_hits"] = dict(ctx.stats())
+    ctx.count_hits(thr.O, thr.D, stats=True); seen["count_hits"] = dict(ctx.stats())
+    ctx.contains(pts, samples=CONTAIN_SAMPLES, stats=True); seen["contains"] = dict(ctx.stats())
+    if device:
+        ctx.occlusion(sf, OCC_SAMPLES, seed=OCC_SEED, bias=0.0, stats=True); seen["occlusion"] = dict(ctx.stats())
+    drops = {q: int(s["stack_drops"]) for q, s in seen.items()}
+    print("%s: deepest stack %s" % (name, {q: int(s["max_stack"]) for q, s in seen.items()}))
+    assert not any(drops.values()), "%s: the walk drops pushes at the 64-entry cap (%s): not a case for this audit, pick another" % (name, drops)
+    out = {}
+
+    def hits(key, **kw):
+        counts = ctx.count_hits(thr.O, thr.D, **kw)
+        kw["capacity"] = int(np.asarray(counts).astype(np.int64).sum()) + 1     # room for what was counted and one more: no second pass for the total
+        lists = ctx.list_hits(thr.O, thr.D, **kw)
+        out["hits", key] = j = judge_hits(tris, thr, lists[:5], ctx.list_hits(thr.O, thr.D, sort=True, **kw)[:5], counts)
+        what = "%s %s" % (name, "brute force" if key == "brute" else "simple %d" % key)
+        print("%s list_hits: longest list %d, entries at a margin of the reference %.3f %%, worst value deviation %.3f of its margin" % (what, j.longest, 100 * j.share_margin, j.worst))
+        assert_point_judged(j, what, tree, capped)
+    for simple in kernels:
+        hits(simple, simple=simple)
+        inside = ctx.contains(pts, samples=CONTAIN_SAMPLES, simple=simple)[:3]
+        odd = (np.asarray(ctx.count_hits(crays, simple=simple)).reshape(len(pts), CONTAIN_SAMPLES) & 1).sum(1).astype(np.uint32)
+        assert np.array_equal(inside[1], odd) and np.array_equal(inside[0], (2 * odd > CONTAIN_SAMPLES).astype(np.uint32)) and np.all(inside[2] == CONTAIN_SAMPLES), \
+            "%s simple %d: contains is not the parity majority of count_hits over its rays, first points %s" % (name, simple, np.flatnonzero(inside[1] != odd)[:10].tolist())
+        if not device:
+            continue
+        res = ctx.occlusion(sf, OCC_SAMPLES, seed=OCC_SEED, bias=0.0, simple=simple)
+        out["occlusion", simple] = j = judge_occlusion(tris, aim, res)
+        print("%s simple %d occlusion: %.1f %% of the sample rays certainly cross the own triangle, triangles without such a surfel %.3f %%" % (name, simple, 100 * j.share_sure, 100 * j.share_blind_tris))
+        assert_point_judged(j, "%s simple %d" % (name, simple), tree, capped)
+        prim = ctx.trace_rays(ctx.occlusion_rays(sf, OCC_SAMPLES, seed=OCC_SEED, bias=0.0), any_hit=True, simple=simple)[1]
+        assert np.array_equal(res[1], (np.asarray(prim) == MISS).reshape(len(sf), OCC_SAMPLES).sum(1)), "%s simple %d: occlusion is not the count over its rays through trace_rays" % (name, simple)
+        sd = ctx.signed_distance(pts, samples=CONTAIN_SAMPLES, simple=simple)
+        cp = ctx.closest_points(pts, simple=simple)[:4]
+        assert np.array_equal(_bits(np.abs(sd[0])), _bits(cp[0])) and np.array_equal(np.signbit(sd[0]), inside[0].astype(bool)) and np.array_equal(sd[1], cp[1]) \
+            and np.array_equal(_bits(sd[2]), _bits(cp[2])) and np.array_equal(_bits(sd[3]), _bits(cp[3])), "%s simple %d: signed_distance is not closest_points under contains' sign" % (name, simple)
+    if brute:
+        hits("brute", brute_force=True)
+    return out
+
+
 # ---- scenes both audit files use ------------------------------------------------------------------------------------------------------
 def f16_grid(cells=16):
     """Three axis-aligned planes of cells x cells quads whose vertices are multiples of 1 / 8: exactly representable in f16, every leaf box
@@ -832,6 +1115,17 @@ def soup(n, seed, size=0.2):
     rng = np.random.default_rng(seed)
     c = rng.random((n, 1, 3), dtype=np.float32) * 2 - 1
     return (c + (rng.random((n, 3, 3), dtype=np.float32) - 0.5) * size).astype(np.float32).reshape(-1)
+
+
+def coincident_deck(layers=3, seed=0):
+    """`layers` parallel unit quads at distinct z (hitlist_cases.deck), every one of them twice, the triangles in shuffled order: a ray
+    through the deck crosses two triangles at every layer with the same bits of t, so in a sorted list only `prim` orders them.  The
+    smallest scene of this audit in which a sort key without `prim` shows: with one or two doubled layers the visit order of some build
+    level happens to ascend in `prim` at every tie; with three (seed 0) every level has ties visited the other way round."""
+    import hitlist_cases as hc
+    T = hc.deck(layers, seed)[0].reshape(-1, 9)
+    both = np.concatenate([T, T])
+    return both[np.random.default_rng(seed).permutation(len(both))].reshape(-1)
 
 
 def collapse_cluster(tris, centre, count):
