@@ -294,16 +294,17 @@ def _nearest_flags(stats, simple, brute_force):
     return (PT_NEAREST_STATS if stats else 0) | (PT_NEAREST_SIMPLE_KERNEL if simple else 0) | (PT_NEAREST_BRUTE_FORCE if brute_force else 0)
 
 
-def _row_columns(rows, n, k):
-    """(n * k, 4) uint32 PtClosest records -> (dist, prim, u, v), each (n, k)"""
-    f = rows.view(np.float32)
-    return tuple(a.reshape(n, k).copy() for a in (f[:, 0], rows[:, 1], f[:, 2], f[:, 3]))
+def _columns(rec):
+    """(..., 4) uint32 result records (PtHit, PtClosest: f32, u32, f32, f32) -> their four columns, (t | dist, prim, u, v), as copies"""
+    f = rec.view(np.float32)
+    return f[..., 0].copy(), rec[..., 1].copy(), f[..., 2].copy(), f[..., 3].copy()
 
 
-def _entry_columns(entries):
-    """(m, 4) uint32 PtClosest records -> (dist, prim, u, v)"""
-    f = entries.view(np.float32)
-    return f[:, 0].copy(), entries[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+def _torch_columns(rec):
+    """the same of a torch (..., 4) int32 tensor, as views of it (prim as torch.uint32)"""
+    import torch
+    f = rec.view(torch.float32)
+    return f[..., 0], rec.view(torch.uint32)[..., 1], f[..., 2], f[..., 3]
 
 
 def _contain_params(samples, seed, index_base, stats=False, simple=False):
@@ -411,16 +412,11 @@ def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=Fals
     n = pts.shape[0]
     out = _aligned_zeros((n, 4), np.uint32)
     st = PtStats()
-    if bvh4 is None:
-        bp, words = None, 0
-    else:
-        bvh4 = np.ascontiguousarray(bvh4, np.uint32).reshape(-1)
-        bp, words = _p(bvh4, C.c_uint32), bvh4.size
+    keep, bp, words = _bvh4_arg(bvh4)
     _check(lib.pt_closest_points_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
                                       pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(_closest_flags(stats, simple, brute_force)),
                                       out.ctypes.data_as(C.POINTER(PtClosest)), C.byref(st) if stats else None))
-    f = out.view(np.float32)
-    res = (f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy())
+    res = _columns(out)
     return res + (st.as_dict(),) if stats else res
 
 
@@ -471,7 +467,7 @@ def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=Fals
         capacity = int(offsets[n])
     entries = _aligned_zeros((int(capacity), 4), np.uint32)
     call(entries, int(capacity))
-    res = (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+    res = (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
     return res + (st.as_dict(),) if stats else res
 
 
@@ -499,7 +495,7 @@ def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=No
         capacity = int(offsets[n])
     entries = _aligned_zeros((int(capacity), 4), np.uint32)
     call(entries, int(capacity))
-    res = (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+    res = (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
     return res + (st.as_dict(),) if stats else res
 
 
@@ -517,7 +513,7 @@ def nearest_k_bvh4(tris, bvh4, points, k, r_max=None, stats=False, simple=False,
                                  pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF),
                                  C.c_uint32(_nearest_flags(stats, simple, brute_force)), rows.ctypes.data_as(C.POINTER(PtClosest)),
                                  C.byref(st) if stats else None))
-    res = _row_columns(rows, n, k)
+    res = _columns(rows.reshape(n, k, 4))
     return res + (st.as_dict(),) if stats else res
 
 
@@ -868,21 +864,14 @@ class Context:
         results are torch tensors (prim as torch.uint32).  stats: the counting kernel, counters in stats() afterwards."""
         flags = (PT_TRACE_ANY_HIT if any_hit else 0) | (PT_TRACE_STATS if stats else 0) | (PT_TRACE_SIMPLE_KERNEL if simple else 0)
         if _is_torch(origins):
-            return self._trace_rays_torch(origins, directions, t_max, flags)
-        if directions is None:
-            rays = np.asarray(origins, np.float32).reshape(-1, 8)
-            if rays.ctypes.data % 16 or not rays.flags.c_contiguous or t_max is not None:
-                r2 = _aligned_zeros(rays.shape, np.float32); r2[...] = rays; rays = r2     # (the caller's records are never written)
-                if t_max is not None:
-                    rays[:, 3] = t_max
-        else:
-            rays = pack_rays(origins, directions, t_max)
+            rays = self._ray_tensor(origins, directions, t_max, "trace_rays")
+            return _torch_columns(self._torch_launch(rays, (4,), lambda r, n, o: self.trace_rays_device(r, n, o, flags)))
+        rays = _ray_records(origins, directions, t_max)
         n = rays.shape[0]
         hits = _aligned_zeros((n, 4), np.uint32)
         self._ck(lib.pt_trace_rays_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags),
                                         hits.ctypes.data_as(C.POINTER(PtHit))))
-        f = hits.view(np.float32)
-        return f[:, 0].copy(), hits[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+        return _columns(hits)
 
     def trace_rays_device(self, rays_ptr, n, hits_ptr, flags=0):
         """Raw device route: n PtRay records at rays_ptr -> n PtHit records at hits_ptr (16-byte aligned device pointers).  Asynchronous on
@@ -906,29 +895,14 @@ class Context:
         launch()
         after = torch.cuda.Event(); after.record(ext); cur.wait_event(after)
 
-    def _trace_rays_torch(self, origins, directions, t_max, flags):
-        _torch_route()
+    def _torch_launch(self, rec, tail, launch):
+        """The torch route of a query that is one call: an int32 result tensor of shape (n,) + tail next to the n records `rec`, and
+        launch(records pointer, n, results pointer) on the context's stream, ordered with torch's current stream both ways."""
         import torch
-        dev = origins.device
-        if dev.type != "cuda":
-            raise ValueError("trace_rays: torch tensors must be on the context's GPU (got %s)" % dev)
-        if directions is None:
-            rays = origins.reshape(-1, 8)
-            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.data_ptr() % 16:
-                rays = rays.to(torch.float32).contiguous().clone()
-            if t_max is not None:
-                rays = rays.clone(); rays[:, 3] = t_max
-        else:
-            o = origins.reshape(-1, 3).to(torch.float32); d = directions.reshape(-1, 3).to(device=dev, dtype=torch.float32)
-            n = o.shape[0]
-            tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if t_max is None else \
-                torch.as_tensor(t_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
-            rays = torch.cat([o, tm, d, torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
-        n = rays.shape[0]
-        hits = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        self._on_context_stream(dev, lambda: self.trace_rays_device(rays.data_ptr(), n, hits.data_ptr(), flags))
-        hf = hits.view(torch.float32)
-        return hf[:, 0], hits.view(torch.uint32)[:, 1], hf[:, 2], hf[:, 3]
+        n = rec.shape[0]
+        out = torch.empty((n,) + tail, dtype=torch.int32, device=rec.device)
+        self._on_context_stream(rec.device, lambda: launch(rec.data_ptr(), n, out.data_ptr()))
+        return out
 
     def camera_rays(self, params, device=None):
         """The rays PT_MODE_REFERENCE traces through each pixel centre of `params` (make_params): a torch (height * width, 8) float32 tensor of
@@ -951,43 +925,19 @@ class Context:
         stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle in index order, no tree."""
         flags = _closest_flags(stats, simple, brute_force)
         if _is_torch(points):
-            return self._closest_points_torch(points, r_max, flags)
+            pts = self._point_tensor(points, r_max, "closest_points")
+            return _torch_columns(self._torch_launch(pts, (4,), lambda p, n, o: self.closest_points_device(p, n, o, flags)))
         pts = _point_records(points, r_max)
         n = pts.shape[0]
         out = _aligned_zeros((n, 4), np.uint32)
         self._ck(lib.pt_closest_points_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags),
                                             out.ctypes.data_as(C.POINTER(PtClosest))))
-        f = out.view(np.float32)
-        return f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+        return _columns(out)
 
     def closest_points_device(self, ptr, n, out_ptr, flags=0):
         """Raw device route: n PtPoint records at ptr -> n PtClosest records at out_ptr (16-byte aligned device pointers).  Asynchronous on
         the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_closest_points(self.h, C.c_void_p(ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(out_ptr)))
-
-    def _closest_points_torch(self, points, r_max, flags):
-        _torch_route()
-        import torch
-        dev = points.device
-        if dev.type != "cuda":
-            raise ValueError("closest_points: torch tensors must be on the context's GPU (got %s)" % dev)
-        if points.dim() == 2 and points.shape[1] == 4:
-            pts = points
-            if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.data_ptr() % 16:
-                pts = pts.to(torch.float32).contiguous().clone()
-            if r_max is not None:
-                pts = pts.clone(); pts[:, 3] = r_max
-        else:
-            p = points.reshape(-1, 3).to(torch.float32)
-            n = p.shape[0]
-            rm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if r_max is None else \
-                torch.as_tensor(r_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
-            pts = torch.cat([p, rm], dim=1).contiguous()
-        n = pts.shape[0]
-        out = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        self._on_context_stream(dev, lambda: self.closest_points_device(pts.data_ptr(), n, out.data_ptr(), flags))
-        of = out.view(torch.float32)
-        return of[:, 0], out.view(torch.uint32)[:, 1], of[:, 2], of[:, 3]
 
     # ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 16) ----
     def occlusion(self, surfels, samples, seed=0, bias=1e-4, index_base=0, stats=False, simple=False):
@@ -1000,8 +950,9 @@ class Context:
         counters in stats() afterwards; simple: the one-ray-per-thread kernel."""
         p = _occlusion_params(samples, seed, bias, index_base, stats, simple)
         if _is_torch(surfels):
-            out = self._occlusion_torch(surfels, p)
             import torch
+            sf = self._surfel_tensor(surfels, "occlusion")
+            out = self._torch_launch(sf, (4,), lambda r, n, o: self.occlusion_device(r, n, p, o))
             return out.view(torch.float32)[:, 0], out.view(torch.uint32)[:, 1], out.view(torch.uint32)[:, 2]
         sf = _records8(surfels, "occlusion")
         n = sf.shape[0]
@@ -1018,15 +969,6 @@ class Context:
         if sf.dtype != torch.float32 or not sf.is_contiguous() or sf.data_ptr() % 16:
             sf = sf.to(torch.float32).contiguous().clone()
         return sf
-
-    def _occlusion_torch(self, surfels, p):
-        """a torch (n, 8) float32 tensor of PtSurfel records -> a torch (n, 4) int32 tensor of PtOcclusion records on the same device"""
-        import torch
-        sf = self._surfel_tensor(surfels, "occlusion")
-        n = sf.shape[0]
-        out = torch.empty((n, 4), dtype=torch.int32, device=sf.device)
-        self._on_context_stream(sf.device, lambda: self.occlusion_device(sf.data_ptr(), n, p, out.data_ptr()))
-        return out
 
     def occlusion_device(self, surfels_ptr, n, params, out_ptr):
         """Raw device route: n PtSurfel records at surfels_ptr -> n PtOcclusion records at out_ptr (16-byte aligned device pointers; params:
@@ -1107,13 +1049,9 @@ class Context:
         result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle, no tree."""
         flags = _count_flags(stats, simple, brute_force)
         if _is_torch(origins):
-            _torch_route()
             import torch
             rays = self._ray_tensor(origins, directions, t_max, "count_hits")
-            n = rays.shape[0]
-            counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
-            self._on_context_stream(rays.device, lambda: self.count_hits_device(rays.data_ptr(), n, counts.data_ptr(), flags))
-            return counts.view(torch.uint32)
+            return self._torch_launch(rays, (), lambda r, n, o: self.count_hits_device(r, n, o, flags)).view(torch.uint32)
         rays = _ray_records(origins, directions, t_max)
         n = rays.shape[0]
         counts = np.zeros(n, np.uint32)
@@ -1126,6 +1064,7 @@ class Context:
         self._ck(lib.pt_count_hits(self.h, C.c_void_p(rays_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
 
     def _ray_tensor(self, origins, directions, t_max, what):
+        _torch_route()
         import torch
         dev = origins.device
         if dev.type != "cuda":
@@ -1144,6 +1083,7 @@ class Context:
         return torch.cat([o, tm, d, torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
 
     def _point_tensor(self, points, r_max, what):
+        _torch_route()
         import torch
         dev = points.device
         if dev.type != "cuda":
@@ -1170,13 +1110,9 @@ class Context:
         device stay there, on the context's stream, with no host synchronisation."""
         p = _contain_params(samples, seed, index_base, stats, simple)
         if _is_torch(points):
-            _torch_route()
             import torch
             pts = self._point_tensor(points, None, "contains")
-            n = pts.shape[0]
-            out = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
-            self._on_context_stream(pts.device, lambda: self.contains_device(pts.data_ptr(), n, p, out.data_ptr()))
-            o = out.view(torch.uint32)
+            o = self._torch_launch(pts, (4,), lambda r, n, o: self.contains_device(r, n, p, o)).view(torch.uint32)
             return o[:, 0], o[:, 1], o[:, 2]
         pts = _point_records(points, None)
         n = pts.shape[0]
@@ -1199,13 +1135,9 @@ class Context:
         were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
         flags = _radius_flags(stats, simple, brute_force)
         if _is_torch(points):
-            _torch_route()
             import torch
             pts = self._point_tensor(points, r_max, "radius_count")
-            n = pts.shape[0]
-            counts = torch.empty((n,), dtype=torch.int32, device=pts.device)
-            self._on_context_stream(pts.device, lambda: self.radius_count_device(pts.data_ptr(), n, counts.data_ptr(), flags))
-            return counts.view(torch.uint32)
+            return self._torch_launch(pts, (), lambda r, n, o: self.radius_count_device(r, n, o, flags)).view(torch.uint32)
         pts = _point_records(points, r_max)
         n = pts.shape[0]
         counts = np.zeros(n, np.uint32)
@@ -1234,37 +1166,43 @@ class Context:
         which large radii over deep trees reach sooner than any other query; brute_force lists every triangle within r_max regardless."""
         flags = _radius_flags(stats, simple, brute_force)
         if _is_torch(points):
-            _torch_route()
-            import torch
-            pts = self._point_tensor(points, r_max, "radius_search")
-            n = pts.shape[0]
-            dev = pts.device
-            offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-            if capacity is None:
-                self._on_context_stream(dev, lambda: self.radius_search_device(pts.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
-                capacity = int(offsets[-1].item())          # the one host wait
-            cap = int(capacity)
-            entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-            self._on_context_stream(dev, lambda: self.radius_search_device(pts.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
-            ef = entries.view(torch.float32)
-            return offsets, ef[:, 0], entries.view(torch.uint32)[:, 1], ef[:, 2], ef[:, 3]
-        pts = _point_records(points, r_max)
-        n = pts.shape[0]
+            return self._list_torch(self._point_tensor(points, r_max, "radius_search"), self.radius_search_device, flags, capacity)
+        return self._list_host(_point_records(points, r_max), PtPoint, lib.pt_radius_search_host, PtClosest, flags, capacity, 16)
+
+    def _list_torch(self, rec, search_device, flags, capacity):
+        """The torch route of a list query over the n records `rec`: with a capacity one call of `search_device` (radius_search_device,
+        list_hits_device) and no host wait; without, one for the offsets, the read of offsets[-1], and one for the entries."""
+        import torch
+        n, dev = rec.shape[0], rec.device
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        if capacity is None:
+            self._on_context_stream(dev, lambda: search_device(rec.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
+            capacity = int(offsets[-1].item())          # the one host wait
+        cap = int(capacity)
+        entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        self._on_context_stream(dev, lambda: search_device(rec.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
+        return (offsets,) + _torch_columns(entries)
+
+    def _list_host(self, rec, record, search_host, entry, flags, capacity, guess):
+        """The host route of a list query over the n numpy records `rec` (of ctypes type `record`; entries of type `entry`) through
+        `search_host` (pt_radius_search_host, pt_list_hits_host).  capacity None: room for `guess` entries per record at first, and a second
+        run when offsets[n] says that this was too little."""
+        n = rec.shape[0]
         offsets = np.zeros(n + 1, np.uint64)
 
         def call(entries, cap):
-            self._ck(lib.pt_radius_search_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                               entries.ctypes.data_as(C.POINTER(PtClosest)) if cap else None, C.c_uint64(cap)))
+            self._ck(search_host(self.h, rec.ctypes.data_as(C.POINTER(record)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                 entries.ctypes.data_as(C.POINTER(entry)) if cap else None, C.c_uint64(cap)))
         retry = capacity is None
         if retry:
-            capacity = 16 * n + 64                  # a first guess; offsets[n] says how large the retry must be
+            capacity = guess * n + 64               # a first guess; offsets[n] says how large the retry must be
         entries = _aligned_zeros((int(capacity), 4), np.uint32)
         call(entries, int(capacity))
         if retry and int(offsets[n]) > capacity:
             capacity = int(offsets[n])
             entries = _aligned_zeros((capacity, 4), np.uint32)
             call(entries, capacity)
-        return (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+        return (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
 
     def radius_search_device(self, points_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
         """Raw device route: n PtPoint records at points_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
@@ -1292,37 +1230,8 @@ class Context:
         brute_force lists every crossing regardless."""
         flags = _hits_flags(stats, simple, brute_force, sort)
         if _is_torch(origins):
-            _torch_route()
-            import torch
-            rays = self._ray_tensor(origins, directions, t_max, "list_hits")
-            n = rays.shape[0]
-            dev = rays.device
-            offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-            if capacity is None:
-                self._on_context_stream(dev, lambda: self.list_hits_device(rays.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
-                capacity = int(offsets[-1].item())          # the one host wait
-            cap = int(capacity)
-            entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-            self._on_context_stream(dev, lambda: self.list_hits_device(rays.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
-            ef = entries.view(torch.float32)
-            return offsets, ef[:, 0], entries.view(torch.uint32)[:, 1], ef[:, 2], ef[:, 3]
-        rays = _ray_records(origins, directions, t_max)
-        n = rays.shape[0]
-        offsets = np.zeros(n + 1, np.uint64)
-
-        def call(entries, cap):
-            self._ck(lib.pt_list_hits_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                           entries.ctypes.data_as(C.POINTER(PtHit)) if cap else None, C.c_uint64(cap)))
-        retry = capacity is None
-        if retry:
-            capacity = 4 * n + 64                   # a first guess; offsets[n] says how large the retry must be
-        entries = _aligned_zeros((int(capacity), 4), np.uint32)
-        call(entries, int(capacity))
-        if retry and int(offsets[n]) > capacity:
-            capacity = int(offsets[n])
-            entries = _aligned_zeros((capacity, 4), np.uint32)
-            call(entries, capacity)
-        return (offsets,) + _entry_columns(entries[: min(int(offsets[n]), int(capacity))])
+            return self._list_torch(self._ray_tensor(origins, directions, t_max, "list_hits"), self.list_hits_device, flags, capacity)
+        return self._list_host(_ray_records(origins, directions, t_max), PtRay, lib.pt_list_hits_host, PtHit, flags, capacity, 4)
 
     def list_hits_device(self, rays_ptr, n, offsets_ptr, hits_ptr, capacity, flags=0):
         """Raw device route: n PtRay records at rays_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
@@ -1346,20 +1255,14 @@ class Context:
         flags = _nearest_flags(stats, simple, brute_force)
         k = int(k)
         if _is_torch(points):
-            _torch_route()
-            import torch
             pts = self._point_tensor(points, r_max, "nearest_k")
-            n = pts.shape[0]
-            rows = torch.empty((n, min(max(k, 1), PT_NEAREST_MAX_K), 4), dtype=torch.int32, device=pts.device)
-            self._on_context_stream(pts.device, lambda: self.nearest_k_device(pts.data_ptr(), n, k, rows.data_ptr(), flags))
-            rf = rows.view(torch.float32)
-            return rf[:, :, 0], rows.view(torch.uint32)[:, :, 1], rf[:, :, 2], rf[:, :, 3]
+            return _torch_columns(self._torch_launch(pts, (min(max(k, 1), PT_NEAREST_MAX_K), 4), lambda p, n, o: self.nearest_k_device(p, n, k, o, flags)))
         pts = _point_records(points, r_max)
         n = pts.shape[0]
         rows = _aligned_zeros((n * min(max(k, 0), PT_NEAREST_MAX_K), 4), np.uint32)
         self._ck(lib.pt_nearest_k_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(flags),
                                        rows.ctypes.data_as(C.POINTER(PtClosest))))
-        return _row_columns(rows, n, k)
+        return _columns(rows.reshape(n, k, 4))
 
     def nearest_k_device(self, ptr, n, k, out_ptr, flags=0):
         """Raw device route: n PtPoint records at ptr -> n * k PtClosest records at out_ptr, row i at record i * k (16-byte aligned device
@@ -1371,20 +1274,13 @@ class Context:
         nothing within r_max).  Arguments as closest_points and contains; three launches on the context's stream, no host wait."""
         p = _contain_params(samples, seed, index_base, False, simple)
         if _is_torch(points):
-            _torch_route()
-            import torch
             pts = self._point_tensor(points, r_max, "signed_distance")
-            n = pts.shape[0]
-            out = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
-            self._on_context_stream(pts.device, lambda: self.signed_distance_device(pts.data_ptr(), n, p, out.data_ptr()))
-            of = out.view(torch.float32)
-            return of[:, 0], out.view(torch.uint32)[:, 1], of[:, 2], of[:, 3]
+            return _torch_columns(self._torch_launch(pts, (4,), lambda r, n, o: self.signed_distance_device(r, n, p, o)))
         pts = _point_records(points, r_max)
         n = pts.shape[0]
         out = _aligned_zeros((n, 4), np.uint32)
         self._ck(lib.pt_signed_distance_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtClosest))))
-        f = out.view(np.float32)
-        return f[:, 0].copy(), out[:, 1].copy(), f[:, 2].copy(), f[:, 3].copy()
+        return _columns(out)
 
     def signed_distance_device(self, points_ptr, n, params, out_ptr):
         """Raw device route: n PtPoint records at points_ptr -> n PtClosest records at out_ptr (16-byte aligned; params: PtContainParams)."""

@@ -2,12 +2,10 @@
 // upload / build, render dispatch, readback.  Mirrors the host side of the reference's
 // PathTracer class (src/libs/PathTracer.js); each entry point cites what it replaces in the
 // header.  No CPU fallback for device work: without a usable HIP device pt_create fails.
-#include "mi355pt.h"
-#include "pt_host.h"
-#include "pt_kernels.h"
+// The batched queries over the context's tree (pt_trace_rays .. pt_nearest_k) live in pt_api_queries.cpp;
+// pt_context.h holds the context and the helpers both files share.
+#include "pt_context.h"
 #include "pt_expose.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
@@ -17,181 +15,9 @@
 #include <string>
 #include <vector>
 
-namespace {
+namespace pti {
 
 thread_local std::string g_global_error;
-
-template <typename T>
-struct DevBuf {
-    T* ptr = nullptr; size_t cap = 0;   // capacity in elements
-    hipError_t ensure(size_t n) {
-        if (n <= cap && ptr) return hipSuccess;
-        if (ptr) { (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-        if (n == 0) n = 1;
-        hipError_t e = hipMalloc((void**)&ptr, n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-};
-
-} // namespace
-
-// Development overrides of the megakernel's launch heuristics.  kAuto = use the measured default for the launch at hand.
-// Read from PT_TUNE_* ONCE, when the context is created (a shipped library does not consult the environment per launch);
-// tests and tools/ab/sweep.sh change them through pt_debug_set_tune.
-struct PtTune {
-    static constexpr uint32_t kAuto = 0xFFFFFFFFu;
-    uint32_t grid_div = kAuto, rows = kAuto, chunk = kAuto, xcd = kAuto, shade = kAuto, fill = kAuto,
-             slots = kAuto, cull = kAuto, stats_batch = kAuto, quad = kAuto, fork = kAuto, bounded = kAuto, timeline = kAuto, expose = kAuto, expose_budget = kAuto;
-    uint32_t* find(const char* name) {
-        static const struct { const char* n; uint32_t PtTune::* m; } tab[] = {
-            {"GRIDDIV", &PtTune::grid_div}, {"ROWS", &PtTune::rows}, {"CHUNK", &PtTune::chunk}, {"XCD", &PtTune::xcd}, {"SHADE", &PtTune::shade},
-            {"FILL", &PtTune::fill}, {"SLOTS", &PtTune::slots}, {"CULL", &PtTune::cull}, {"STATSBATCH", &PtTune::stats_batch}, {"QUAD", &PtTune::quad}, {"FORK", &PtTune::fork}, {"BOUNDED", &PtTune::bounded}, {"TIMELINE", &PtTune::timeline}, {"EXPOSE", &PtTune::expose}, {"EXBUDGET", &PtTune::expose_budget}};
-        for (const auto& t : tab) if (std::strcmp(name, t.n) == 0) return &(this->*(t.m));
-        return nullptr;
-    }
-    void from_environment() {
-        static const char* names[] = {"GRIDDIV", "ROWS", "CHUNK", "XCD", "SHADE", "FILL", "SLOTS", "CULL", "STATSBATCH", "QUAD", "FORK", "BOUNDED", "TIMELINE", "EXPOSE", "EXBUDGET"};
-        for (const char* n : names) {
-            const std::string key = std::string("PT_TUNE_") + n;
-            const char* v = std::getenv(key.c_str());
-            if (v && *v) *find(n) = uint32_t(std::strtoul(v, nullptr, 10));
-        }
-    }
-    static uint32_t pick(uint32_t knob, uint32_t dflt) { return knob == kAuto ? dflt : knob; }
-};
-
-struct PtContext {
-    int device = 0;
-    PtTune tune;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool timed = false;
-    std::string err;
-
-    // scene (host mirrors kept for rebuilds / readback of small metadata only)
-    uint32_t num_tris = 0, num_nodes2 = 0, num_nodes4 = 0;
-    bool edges_small = false;        // every |edge component| of the uploaded triangles is below 2^20 (pt_set_triangles; see arith_is_bounded)
-    DevBuf<uint32_t> d_edge_max;
-    bool have_tris = false, have_bvh = false, have_bvh2 = false;
-    bool bvh2_refit_pending = false;  // pt_build_bvh leaves the internal BVH2 bounds to the first pt_read_bvh2 (nothing on the render path reads them)
-    pt::WideBvh wide_meta;           // root info; nodes vector emptied after upload
-
-    DevBuf<float> d_tris9;           // reference layout
-    // One arena for the two record arrays the traversal gathers from: [triangle records, 64 B each, padded to a multiple of
-    // 64 B | wide nodes, 64 B each]: one allocation, one base address, 32-bit byte offsets reach both kinds.
-    DevBuf<uint4> d_scene; uint64_t node_off = 0, node_cap = 0; uint32_t scene_tris = 0;
-    float4* trirec() const { return (float4*)d_scene.ptr; }
-    uint4* wide() const { return d_scene.ptr + node_off / 16; }
-    DevBuf<uint32_t> d_bvh2, d_bvh4; // reference layouts
-    DevBuf<uint32_t> d_morton, d_triidx, d_parent, d_flags;
-    // device-side scene build (pt_build.hip): scratch kept for rebuilds
-    DevBuf<unsigned long long> d_bounds; DevBuf<uint32_t> d_counters, d_code_tmp, d_index_tmp, d_node2, d_subtree, d_ids, d_bnd;
-    DevBuf<uint4> d_child_pos; DevBuf<unsigned char> d_build_temp; uint32_t* h_word = nullptr;
-    DevBuf<uint32_t> d_ploc;         // PT_ACCEL_PLOC cluster buffers (ptk::ploc_words), allocated on first use
-    DevBuf<float4> d_spheres; uint32_t num_spheres = 0;
-    // refit in place (pt_update_triangles, pt_refit.hip).  The plan (ptk::RefitBuffers) is derived at the first update or pt_bvh_cost after
-    // a tree was installed; every call that installs a tree drops it.  tree_built: the BVH4 is this library's own build (every node
-    // reachable, d_ids still holds the wide indices of launch_internal_scan), so the plan is derived on the device.
-    bool tree_built = false, refit_ready = false, refit2_ready = false;
-    uint32_t num_wide = 0;            // wide nodes in the arena
-    DevBuf<uint2> d_refit_up, d_refit_self; DevBuf<uint4> d_refit_ref; DevBuf<uint32_t> d_refit_arrive, d_refit_parent2, d_refit_arrive2;
-    DevBuf<double> d_cost;
-    bool bvh2_stale = false;          // the BVH2 still holds the boxes of earlier triangles: refitted by the next pt_read_bvh2
-    // the host's copies after an update (root box, edge maximum) come back through a pinned block behind the refit; whoever reads them
-    // next waits for that copy (sync_refit_meta)
-    uint32_t* h_refit = nullptr; hipEvent_t ev_refit = nullptr; bool meta_pending = false, meta_has_root = false;
-    // Tile cover (pt_cover.hip).  The cut of the wide tree is taken whenever a tree is installed (install_cut); tree_version counts
-    // everything that changes a box (install, refit).  A cover -- the tiles the cut's live boxes reach from a set of cameras -- is
-    // computed on a stream of its own that waits for nothing, read back through a pinned block, and kept until the cameras, the
-    // resolution or the tree change: with an unchanged camera a launch adds no kernel, no copy and no host wait.  The last kCovers results
-    // are kept (least recently used goes first), so a few alternating views -- stereo eyes, a diagnostics call between launches -- do
-    // not evict each other.
-    DevBuf<uint32_t> d_cut; uint32_t cut_count = 0, tree_version = 0;
-    hipStream_t cover_stream = nullptr; DevBuf<uint32_t> d_cover; uint32_t* h_cover = nullptr; size_t h_cover_cap = 0;
-    struct Cover {
-        bool valid = false, computed = false, usable = false;      // valid: the view has been seen; computed: its mask is there; usable: every box could be projected (else the launch keeps the rectangle)
-        uint32_t tree_version = 0, width = 0, height = 0, id = 0; uint64_t used = 0;
-        std::vector<ptk::CoverCam> cams; std::vector<uint32_t> mask;
-    };
-    static constexpr int kCovers = 4;
-    Cover covers[kCovers]; uint64_t cover_clock = 0;
-    std::vector<ptk::CoverCam> cover_cams;                 // the distinct cameras of the launch being planned
-    uint32_t cover_ids = 0;
-    // Exposed triangles (pt_expose.hip): one bit per triangle that no shadow ray of the fixed light can be occluded on, computed in front of
-    // the first large PT_MODE_PATH launch of a tree version (after pt_update_triangles: of the second, so geometry that moves every frame never
-    // pays for it), on that launch's side stream, with no host wait.  expose_version: the tree version the mask holds for (0: none);
-    // expose_cam / expose_s / expose_d: the camera distance and the operand bounds (ptex::Bounds) it was computed for.
-    // The mask lives in the scene arena, behind the wide nodes (expose_off: its byte offset there), so that the megakernel reaches it from the
-    // arena's base like every record.
-    DevBuf<uint32_t> d_expose_info, d_expose_bad, d_expose_skipped; uint64_t expose_off = 0;      // (d_expose_skipped: the COUNTERS variant's one word, nobody else's)
-    uint32_t* expose_mask() const { return (uint32_t*)((char*)d_scene.ptr + expose_off); }
-    // expose_gen counts the masks computed, whatever the tree version: a recompute for a farther camera keeps the version, and every stream that
-    // is to read the new mask has to wait for it (FrameSlot::expose_waited is compared with this, not with the version).
-    uint32_t expose_version = 0, expose_gen = 0, expose_noted = 0, expose_tris = 0; bool tree_updated = false, expose_last_used = false;
-    double expose_cam = 0.0, expose_s = 0.0, expose_d = 0.0;
-    hipEvent_t ev_expose = nullptr, ev_expose_t0 = nullptr, ev_expose_t1 = nullptr;
-    // batched ray queries (pt_trace_rays): queue word and deep-stack spill area of the persistent kernel, staging of pt_trace_rays_host
-    DevBuf<unsigned long long> d_rq_queue, d_rq_spill; DevBuf<uint4> d_rq_rays, d_rq_hits;
-    DevBuf<uint4> d_oc_surfels;         // staging of pt_hit_surfels_host's result (its rays and hits use the two above)
-    DevBuf<uint4> d_cr_contain;         // pt_signed_distance: the PtContainment records between its containment launch and the sign kernel
-    // radius queries (pt_radius_search): the counts between the count walk and the scan, the scan's scratch (grown like the staging buffers),
-    // and the staging of pt_radius_search_host's offsets and entries
-    DevBuf<uint32_t> d_rd_counts; DevBuf<unsigned char> d_rd_temp; DevBuf<unsigned long long> d_rd_offsets; DevBuf<uint4> d_rd_entries;
-
-    // frame
-    DevBuf<float4> d_out, d_accum, d_compact, d_compact_accum;
-    DevBuf<uint32_t> d_tiles, d_u32tmp;
-    // Frame slots: the trace phase of consecutive pt_render calls runs on alternating side streams
-    // (own sample / control / scratch buffers each), so the sparse tail of one frame overlaps the
-    // dense start of the next; the resolve passes stay in call order on the main stream.
-    struct FrameSlot {
-        hipStream_t side = nullptr; hipEvent_t resolved = nullptr, done = nullptr; bool used = false;
-        uint32_t expose_waited = 0;                                     // the mask generation (PtContext::expose_gen) this slot's stream has waited for (PtContext::ev_expose)
-        uint64_t resolved_seq = 0;                                      // launch sequence number of the latest record of `resolved` (pt_buffer_busy)
-        DevBuf<uint32_t> queue; DevBuf<float4> samples; DevBuf<uint2> spill; DevBuf<uint4> rays;
-        // owned-tile slots that the launch in this slot traces (the others are culled: every camera ray misses the root box, or every box
-        // of the tree's cut), followed by the tile cover's bitmask (RenderArgs::trace_slots); key word 8 = the cover's id (0: rectangle only)
-        DevBuf<uint32_t> trace_slots; uint32_t* h_trace = nullptr; size_t h_trace_cap = 0; hipEvent_t trace_copied = nullptr;
-        uint32_t cull_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; uint32_t num_trace_tiles = 0; bool cull_valid = false;
-        DevBuf<ptk::FrameParams> frame_params; DevBuf<float4*> frame_outs;      // per-frame parameters / targets of the launch in this slot
-        const void* primed_ptr = nullptr; size_t primed_samples = 0;   // what the resident prefill covers
-    };
-    static constexpr int kMaxSlots = 16;
-    FrameSlot slots[kMaxSlots]; int num_slots = 0; uint32_t next_slot = 0;
-    // frames queued for one batched launch (pt_set_batch): launched when full or when anything needs their result
-    uint32_t batch_size = 1; uint32_t pending = 0; ptk::RenderArgs pendingA; bool pending_ring = false; uint32_t pending_rank = 0, pending_count = 1;
-    std::vector<ptk::FrameParams> pending_frames; std::vector<float4*> pending_outs;
-    DevBuf<unsigned long long> d_wave_times; uint32_t wave_times_n = 0;
-    int num_cus = 0;
-    DevBuf<unsigned long long> d_stats;
-    std::vector<uint32_t> tiles_host; uint32_t tiles_w = 0, tiles_h = 0, tiles_rank = 0, tiles_count = 0;
-    uint32_t out_w = 0, out_h = 0;   // dimensions of the last full-frame result in d_out
-    uint32_t accum_w = 0, accum_h = 0, accum_count = 0, accum_rank = 0;
-    uint64_t compact_floats = 0;
-    uint32_t share_w = 0, share_h = 0, share_count = 0, share_max_tiles = 0;      // cached: largest tile share of a (W, H, count) split (pt_deinterleave*)
-    float4* ext_compact = nullptr; uint64_t ext_compact_floats = 0;
-    float4* ext_out = nullptr; uint64_t ext_out_floats = 0;      // caller-owned whole-frame target (pt_set_output_buffer)
-    const float4* last_full = nullptr;                          // where the last whole-frame result lives (d_out or a caller's buffer)
-    bool last_stats = false;
-    uint64_t stats_culled = 0;          // pixel-samples of the last instrumented launch that were culled (counted as one root-box miss each)
-    std::vector<hipEvent_t> ring;    // start/stop pairs recorded by pt_render while timing is on
-    uint32_t ring_used = 0;
-    // pt_buffer_busy: the byte ranges that launches not yet known to be delivered write into.  Every launch appends its targets with its
-    // sequence number.  The context's stream is in order and every launch's last write is followed there by an event that exists anyway
-    // (the frame slot's `resolved`, re-recorded by the slot's next launch; `misc_fence` behind the kernels that do not use a slot), each
-    // remembering the sequence number of its LATEST record: once such an event has completed, every launch up to that number has been
-    // delivered -- whatever frame slot it ran in and however many launches were submitted after it.  (No event of its own per launch:
-    // one more marker on the stream cost the reference's 0.16 ms frame 18 % with one render() per launch.)
-    struct InFlight { const char* lo; const char* hi; uint64_t seq; };
-    std::vector<InFlight> inflight;
-    uint64_t launch_seq = 0, delivered_seq = 0;
-    hipEvent_t misc_fence = nullptr; uint64_t misc_fence_seq = 0;
-};
-
-namespace {
 
 int fail(PtContext* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg; else g_global_error = msg;
@@ -200,7 +26,6 @@ int fail(PtContext* ctx, int code, const std::string& msg) {
 int fail_hip(PtContext* ctx, hipError_t e, const char* what) {
     return fail(ctx, PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define PT_HIP(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail_hip((ctx), e__, #call); } while (0)
 
 int bind(PtContext* ctx) {
     if (!ctx) return fail(nullptr, PT_ERR_INVALID_ARG, "null context");
@@ -224,6 +49,12 @@ int sync_refit_meta(PtContext* ctx) {
     }
     return PT_OK;
 }
+
+} // namespace pti
+
+using namespace pti;
+
+namespace {
 
 // which pixels a running accumulation covers: tile rank (bits 0..11), tile count (12..23), compact tile-major layout (bit 31)
 uint32_t accum_share_key(uint32_t rank, uint32_t count, bool compact) { return (rank & 0xfffu) | ((count & 0xfffu) << 12) | (compact ? 0x80000000u : 0u); }
@@ -828,15 +659,15 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     ctx->timed = !ring;
     return PT_OK;
 }
+} // namespace
 
-int flush_pending(PtContext* ctx) {
+int pti::flush_pending(PtContext* ctx) {
     if (!ctx->pending) return PT_OK;
     const uint32_t count = ctx->tiles_count ? ctx->tiles_count : 1u;
     const bool sharded = ctx->pendingA.compact != 0u;
     return flush_pending_stats(ctx, ctx->pendingA.stats != nullptr, sharded, sharded ? count : 1u);
 }
 
-} // namespace
 
 extern "C" {
 
@@ -1522,753 +1353,6 @@ int pt_render(PtContext* ctx, const PtRenderParams* p) {
     }
     if (ring) ctx->ring_used += 2;
     ctx->timed = !ring;
-    return PT_OK;
-}
-
-// ---- batched ray queries (include/mi355pt.h; pt_rayquery.hip) ----------------------------------------------------------------
-
-static_assert(sizeof(PtRay) == 32 && sizeof(PtHit) == 16, "PtRay / PtHit are read and written as 2 x 16 B and 16 B records");
-
-namespace {
-constexpr uint32_t kTraceFlags = PT_TRACE_ANY_HIT | PT_TRACE_STATS | PT_TRACE_SIMPLE_KERNEL;
-bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
-
-// arguments, then the scene; *proceed = false when there is nothing to launch (n = 0)
-int check_trace(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* hits) {
-    if (flags & ~kTraceFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
-    if (!aligned16(rays) || !aligned16(hits)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays and hits must be non-null and 16-byte aligned");
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-
-// The queue block and the spill area of the persistent query kernels (pt_walk.h), shared by the ray, closest-point and occlusion queries:
-// their launches are ordered by the stream, and DevBuf::ensure only ever grows a buffer, so the area fits whichever kernel asked for most.
-hipError_t ensure_walk_buffers(PtContext* ctx, uint32_t grid, int short_stack) {
-    const hipError_t e = ctx->d_rq_queue.ensure(ptk::kRqQueueWords);
-    return e != hipSuccess ? e : ctx->d_rq_spill.ensure(ptk::walk_spill_entries(grid, short_stack));
-}
-
-// the launch itself: rays / hits in device memory, on the context's stream, behind whatever pt_set_batch still holds
-int trace_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* hits) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
-    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
-    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
-    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
-    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
-    const bool anyhit = (flags & PT_TRACE_ANY_HIT) != 0, stats = (flags & PT_TRACE_STATS) != 0, simple = (flags & PT_TRACE_SIMPLE_KERNEL) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_RQ_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_RQ_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_trace_rays(A, rays, hits, n, anyhit, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-} // namespace
-
-int pt_trace_rays(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* hits_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_trace(ctx, "pt_trace_rays", rays_device, n, flags, hits_device)) return rc;
-    return trace_on_stream(ctx, rays_device, uint32_t(n), flags, hits_device);
-}
-
-int pt_trace_rays_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, PtHit* hits) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_trace(ctx, "pt_trace_rays_host", rays, n, flags, hits)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = trace_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtHit), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_camera_rays(PtContext* ctx, const PtRenderParams* p, void* rays_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: null params");
-    if (!aligned16(rays_device)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: rays must be non-null and 16-byte aligned");
-    if (p->width == 0 || p->height == 0 || p->width > 32768 || p->height > 32768) return fail(ctx, PT_ERR_INVALID_ARG, "pt_camera_rays: bad resolution");
-    if (int rc = flush_pending(ctx)) return rc;
-    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
-    A.width = p->width; A.height = p->height; A.focal = p->focal; A.aspect = p->aspect;
-    std::memcpy(A.cam, p->cam_pos, 12); std::memcpy(A.quat, p->cam_quat, 16);
-    PT_HIP(ctx, ptk::launch_camera_rays(A, rays_device, ctx->stream));
-    return PT_OK;
-}
-
-// ---- batched closest-point queries (include/mi355pt.h; pt_pointquery.hip) -----------------------------------------------------
-
-static_assert(sizeof(PtPoint) == 16 && sizeof(PtClosest) == 16, "PtPoint / PtClosest are read and written as 16 B records");
-
-namespace {
-constexpr uint32_t kClosestFlags = PT_CLOSEST_STATS | PT_CLOSEST_SIMPLE_KERNEL | PT_CLOSEST_BRUTE_FORCE;
-
-int check_closest(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t flags, const void* out) {
-    if (flags & ~kClosestFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
-    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-
-// the launch itself: points / results in device memory, on the context's stream, behind whatever pt_set_batch still holds
-int closest_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* out) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
-    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
-    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
-    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
-    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
-    const bool stats = (flags & PT_CLOSEST_STATS) != 0, simple = (flags & PT_CLOSEST_SIMPLE_KERNEL) != 0, brute = (flags & PT_CLOSEST_BRUTE_FORCE) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_PQ_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple && !brute) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_PQ_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_closest_points(A, points, out, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-} // namespace
-
-int pt_closest_points(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* out_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_closest(ctx, "pt_closest_points", points_device, n, flags, out_device)) return rc;
-    return closest_on_stream(ctx, points_device, uint32_t(n), flags, out_device);
-}
-
-int pt_closest_points_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_closest(ctx, "pt_closest_points_host", points, n, flags, out)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = closest_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
-                           const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out, PtStats* stats) {
-    if (flags & ~kClosestFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: unknown flags");
-    const bool brute = (flags & PT_CLOSEST_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && (!points || !out)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: null pointer");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_closest_points_bvh4: more than 2^32 - 1 points");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::closest_points(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n,
-                            reinterpret_cast<uint32_t*>(out), (flags & PT_CLOSEST_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->rays_closest = counters[0]; stats->nodes_examined = counters[1]; stats->tris_tested = counters[2];
-        stats->stack_drops = counters[3]; stats->max_stack = counters[4];
-    }
-    return PT_OK;
-}
-
-// ---- batched ambient-occlusion queries (include/mi355pt.h; pt_occlusion.hip) --------------------------------------------------
-
-static_assert(sizeof(PtSurfel) == 32 && sizeof(PtOcclusion) == 16, "PtSurfel / PtOcclusion are read and written as 2 x 16 B and 16 B records");
-
-namespace {
-constexpr uint32_t kOcclusionFlags = PT_OCCLUSION_STATS | PT_OCCLUSION_SIMPLE_KERNEL;
-
-// the parameter block and the batch size; the pointers and the scene are checked by the callers (pointers before the scene)
-int check_occlusion_params(PtContext* ctx, const char* fn, uint64_t n, const PtOcclusionParams* p) {
-    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": null params");
-    if (p->flags & ~kOcclusionFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 surfels");
-    if (p->samples < 1u || p->samples > 65536u) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": samples must be 1..65536");
-    if (n * uint64_t(p->samples) > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 sample rays (n * samples)");
-    if (!(p->bias >= 0.0f)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": bias must be >= 0");
-    return PT_OK;
-}
-int check_occlusion(PtContext* ctx, const char* fn, const void* surfels, uint64_t n, const PtOcclusionParams* p, const void* out, bool need_scene) {
-    if (int rc = check_occlusion_params(ctx, fn, n, p)) return rc;
-    if (!aligned16(surfels) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": surfels and results must be non-null and 16-byte aligned");
-    if (need_scene && (!ctx->have_tris || !ctx->have_bvh)) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-void scene_args(PtContext* ctx, ptk::RenderArgs& A) {
-    std::memset(&A, 0, sizeof(A));
-    A.nodes = ctx->wide(); A.tris = ctx->trirec(); A.scene = ctx->d_scene.ptr; A.node_off = uint32_t(ctx->node_off);
-    A.num_tris = ctx->num_tris; A.tri_gate = 0xFFFFFFFFu;
-    A.root_ref = ctx->wide_meta.root_ref; std::memcpy(A.root_box, ctx->wide_meta.root_box, 12);
-    A.root_degenerate = ctx->wide_meta.root_degenerate ? 1u : 0u;
-}
-
-// the launch itself: surfels / results in device memory, on the context's stream, behind whatever pt_set_batch still holds
-int occlusion_on_stream(PtContext* ctx, const void* surfels, uint32_t n, const PtOcclusionParams& p, void* out) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool stats = (p.flags & PT_OCCLUSION_STATS) != 0, simple = (p.flags & PT_OCCLUSION_SIMPLE_KERNEL) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_OC_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_OC_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_occlusion(A, surfels, out, n, p.samples, p.seed, p.index_base, p.bias, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-} // namespace
-
-int pt_occlusion(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* out_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_occlusion(ctx, "pt_occlusion", surfels_device, n, params, out_device, true)) return rc;
-    return occlusion_on_stream(ctx, surfels_device, uint32_t(n), *params, out_device);
-}
-
-int pt_occlusion_host(PtContext* ctx, const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtOcclusion* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_occlusion(ctx, "pt_occlusion_host", surfels, n, params, out, true)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, surfels, size_t(n) * sizeof(PtSurfel), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = occlusion_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtOcclusion), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_occlusion_rays(PtContext* ctx, const void* surfels_device, uint64_t n, const PtOcclusionParams* params, void* rays_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_occlusion(ctx, "pt_occlusion_rays", surfels_device, n, params, rays_device, false)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    PT_HIP(ctx, ptk::launch_occlusion_rays(surfels_device, rays_device, uint32_t(n), params->samples, params->seed, params->index_base, params->bias, ctx->stream));
-    return PT_OK;
-}
-
-int pt_occlusion_rays_host(const PtSurfel* surfels, uint64_t n, const PtOcclusionParams* params, PtRay* rays) {
-    if (int rc = check_occlusion_params(nullptr, "pt_occlusion_rays_host", n, params)) return rc;
-    if (n && (!surfels || !rays)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_occlusion_rays_host: null pointer");
-    pt::occlusion_rays(reinterpret_cast<const float*>(surfels), n, params->samples, params->seed, params->index_base, params->bias, reinterpret_cast<float*>(rays));
-    return PT_OK;
-}
-
-int pt_hit_surfels(PtContext* ctx, const void* rays_device, const void* hits_device, uint64_t n, float r_max, void* surfels_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels: more than 2^32 - 1 rays");
-    if (!aligned16(rays_device) || !aligned16(hits_device) || !aligned16(surfels_device))
-        return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels: rays, hits and surfels must be non-null and 16-byte aligned");
-    if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_hit_surfels: no triangles set");
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
-    A.tris = ctx->trirec(); A.num_tris = ctx->num_tris;
-    PT_HIP(ctx, ptk::launch_hit_surfels(A, rays_device, hits_device, uint32_t(n), r_max, surfels_device, ctx->stream));
-    return PT_OK;
-}
-
-int pt_hit_surfels_host(PtContext* ctx, const PtRay* rays, const PtHit* hits, uint64_t n, float r_max, PtSurfel* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels_host: more than 2^32 - 1 rays");
-    if (!aligned16(rays) || !aligned16(hits) || !aligned16(out))
-        return fail(ctx, PT_ERR_INVALID_ARG, "pt_hit_surfels_host: rays, hits and surfels must be non-null and 16-byte aligned");
-    if (!ctx->have_tris) return fail(ctx, PT_ERR_NO_SCENE, "pt_hit_surfels_host: no triangles set");
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n))); PT_HIP(ctx, ctx->d_oc_surfels.ensure(size_t(n) * 2));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_hits.ptr, hits, size_t(n) * sizeof(PtHit), hipMemcpyHostToDevice, ctx->stream));
-    ptk::RenderArgs A; std::memset(&A, 0, sizeof(A));
-    A.tris = ctx->trirec(); A.num_tris = ctx->num_tris;
-    PT_HIP(ctx, ptk::launch_hit_surfels(A, ctx->d_rq_rays.ptr, ctx->d_rq_hits.ptr, uint32_t(n), r_max, ctx->d_oc_surfels.ptr, ctx->stream));
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_oc_surfels.ptr, size_t(n) * sizeof(PtSurfel), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-// ---- crossing counts, containment, signed distance (include/mi355pt.h; pt_crossings.hip) ---------------------------------------
-
-static_assert(sizeof(PtContainment) == 16 && sizeof(PtContainParams) == 16, "PtContainment is written as one 16 B record");
-
-namespace {
-constexpr uint32_t kCountFlags = PT_COUNT_STATS | PT_COUNT_SIMPLE_KERNEL | PT_COUNT_BRUTE_FORCE;
-constexpr uint32_t kContainFlags = PT_CONTAIN_STATS | PT_CONTAIN_SIMPLE_KERNEL;
-bool aligned4(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3u) == 0u; }
-
-int check_count(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* counts) {
-    if (flags & ~kCountFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
-    if (!aligned16(rays) || !aligned4(counts)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays must be non-null and 16-byte aligned, counts non-null and 4-byte aligned");
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-// the parameter block and the batch size; the pointers and the scene are checked by the callers (pointers before the scene)
-int check_contain_params(PtContext* ctx, const char* fn, uint64_t n, const PtContainParams* p) {
-    if (!p) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": null params");
-    if (p->flags & ~kContainFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
-    if (p->samples < 1u || p->samples > 255u || (p->samples & 1u) == 0u) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": samples must be odd and in 1..255");
-    if (n * uint64_t(p->samples) > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 sample rays (n * samples)");
-    return PT_OK;
-}
-int check_contain(PtContext* ctx, const char* fn, const void* points, uint64_t n, const PtContainParams* p, const void* out) {
-    if (int rc = check_contain_params(ctx, fn, n, p)) return rc;
-    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-
-// the launches themselves: device memory, on the context's stream, behind whatever pt_set_batch still holds
-int count_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, void* counts) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool stats = (flags & PT_COUNT_STATS) != 0, simple = (flags & PT_COUNT_SIMPLE_KERNEL) != 0, brute = (flags & PT_COUNT_BRUTE_FORCE) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_CR_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple && !brute) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_CR_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_count_hits(A, rays, counts, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-int contains_on_stream(PtContext* ctx, const void* points, uint32_t n, const PtContainParams& p, void* out) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool stats = (p.flags & PT_CONTAIN_STATS) != 0, simple = (p.flags & PT_CONTAIN_SIMPLE_KERNEL) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_CR_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_CR_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_contains(A, points, out, n, p.samples, p.seed, p.index_base, simple, stats, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-// three launches, no host wait: the closest points into `out`, the containment into the context's buffer, the sign
-int signed_on_stream(PtContext* ctx, const void* points, uint32_t n, const PtContainParams& p, void* out) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    PT_HIP(ctx, ctx->d_cr_contain.ensure(size_t(n)));
-    if (int rc = closest_on_stream(ctx, points, n, 0u, out)) return rc;
-    if (int rc = contains_on_stream(ctx, points, n, p, ctx->d_cr_contain.ptr)) return rc;
-    PT_HIP(ctx, ptk::launch_apply_sign(ctx->d_cr_contain.ptr, out, n, ctx->stream));
-    return PT_OK;
-}
-void stats_from(PtStats* stats, const uint64_t counters[5]) {
-    std::memset(stats, 0, sizeof(*stats));
-    stats->rays_closest = counters[0]; stats->nodes_examined = counters[1]; stats->tris_tested = counters[2];
-    stats->stack_drops = counters[3]; stats->max_stack = counters[4];
-}
-} // namespace
-
-int pt_count_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* counts_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_count(ctx, "pt_count_hits", rays_device, n, flags, counts_device)) return rc;
-    return count_on_stream(ctx, rays_device, uint32_t(n), flags, counts_device);
-}
-
-int pt_count_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_count(ctx, "pt_count_hits_host", rays, n, flags, counts)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rq_hits.ensure((size_t(n) + 3) / 4));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = count_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(counts, ctx->d_rq_hits.ptr, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_count_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
-                       const PtRay* rays, uint64_t n, uint32_t flags, uint32_t* counts, PtStats* stats) {
-    if (flags & ~kCountFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: unknown flags");
-    const bool brute = (flags & PT_COUNT_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && (!rays || !counts)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: null pointer");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_count_hits_bvh4: more than 2^32 - 1 rays");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::count_hits(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(rays), n, counts,
-                        (flags & PT_COUNT_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) stats_from(stats, counters);
-    return PT_OK;
-}
-
-int pt_contains(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_contain(ctx, "pt_contains", points_device, n, params, out_device)) return rc;
-    return contains_on_stream(ctx, points_device, uint32_t(n), *params, out_device);
-}
-
-int pt_contains_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_contain(ctx, "pt_contains_host", points, n, params, out)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = contains_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtContainment), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_contains_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
-                     const PtPoint* points, uint64_t n, const PtContainParams* params, PtContainment* out, PtStats* stats) {
-    if (int rc = check_contain_params(nullptr, "pt_contains_bvh4", n, params)) return rc;
-    if ((!tris && num_tris) || (n && (!points || !out)) || !bvh4) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_contains_bvh4: null pointer");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::contains(tris, num_tris, bvh4, words, reinterpret_cast<const float*>(points), n, params->samples, params->seed, params->index_base,
-                      reinterpret_cast<uint32_t*>(out), (params->flags & PT_CONTAIN_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) stats_from(stats, counters);
-    return PT_OK;
-}
-
-int pt_signed_distance(PtContext* ctx, const void* points_device, uint64_t n, const PtContainParams* params, void* out_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_contain(ctx, "pt_signed_distance", points_device, n, params, out_device)) return rc;
-    return signed_on_stream(ctx, points_device, uint32_t(n), *params, out_device);
-}
-
-int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, const PtContainParams* params, PtClosest* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_contain(ctx, "pt_signed_distance_host", points, n, params, out)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = signed_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), *params, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-// ---- radius queries (include/mi355pt.h; pt_radius.hip) -------------------------------------------------------------------------
-
-namespace {
-constexpr uint32_t kRadiusFlags = PT_RADIUS_STATS | PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_BRUTE_FORCE;
-bool aligned8(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 7u) == 0u; }
-
-// flags, batch size and the points; the other pointers are checked by the callers, and the scene behind them (check_radius_scene)
-int check_radius(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t flags) {
-    if (flags & ~kRadiusFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
-    if (!aligned16(points)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points must be non-null and 16-byte aligned");
-    return PT_OK;
-}
-int check_radius_search(PtContext* ctx, const char* fn, const void* offsets, const void* entries, uint64_t capacity) {
-    if (!aligned8(offsets)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": offsets must be non-null and 8-byte aligned");
-    if (capacity ? !aligned16(entries) : (entries && !aligned16(entries)))
-        return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": entries must be 16-byte aligned, and non-null unless capacity is 0");
-    return PT_OK;
-}
-int check_radius_scene(PtContext* ctx, const char* fn) {
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-
-// One walk on the context's stream, behind whatever pt_set_batch still holds: the count walk into `counts` (offsets = nullptr), or the fill
-// walk from `offsets` into `entries`.  PT_RADIUS_STATS counts over the count walk only; its fill walk is the one-point-per-thread kernel.
-int radius_walk_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* counts, const unsigned long long* offsets,
-                          void* entries, uint64_t capacity) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool fill = offsets != nullptr, brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
-    const bool stats = (flags & PT_RADIUS_STATS) != 0 && !fill, simple = (flags & (PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_STATS)) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_RD_WAVES_PER_SIMD);
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple && !brute) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_RD_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_radius(A, points, n, counts, offsets, entries, capacity, simple, stats, brute,
-                                   ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-// the count walk into the context's buffer and the scan into `offsets`: two launches, no host wait
-int radius_offsets_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, unsigned long long* offsets) {
-    const size_t temp_bytes = ptk::radius_scan_temp_bytes(n);
-    PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_temp.ensure(temp_bytes));
-    if (int rc = radius_walk_on_stream(ctx, points, n, flags, ctx->d_rd_counts.ptr, nullptr, nullptr, 0)) return rc;
-    PT_HIP(ctx, ptk::launch_radius_scan(ctx->d_rd_counts.ptr, n, offsets, ctx->d_rd_temp.ptr, temp_bytes, ctx->stream));
-    return PT_OK;
-}
-} // namespace
-
-int pt_radius_count(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* counts_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_count", points_device, n, flags)) return rc;
-    if (!aligned4(counts_device)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_radius_count: counts must be non-null and 4-byte aligned");
-    if (int rc = check_radius_scene(ctx, "pt_radius_count")) return rc;
-    return radius_walk_on_stream(ctx, points_device, uint32_t(n), flags, counts_device, nullptr, nullptr, 0);
-}
-
-int pt_radius_count_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint32_t* counts) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_count_host", points, n, flags)) return rc;
-    if (!aligned4(counts)) return fail(ctx, PT_ERR_INVALID_ARG, "pt_radius_count_host: counts must be non-null and 4-byte aligned");
-    if (int rc = check_radius_scene(ctx, "pt_radius_count_host")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n)));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = radius_walk_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_counts.ptr, nullptr, nullptr, 0)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(counts, ctx->d_rd_counts.ptr, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-// three launches, no host wait: the counts into the context's buffer, their scan into offsets, the entries
-int pt_radius_search(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_search", points_device, n, flags)) return rc;
-    if (int rc = check_radius_search(ctx, "pt_radius_search", offsets_device, entries_device, capacity)) return rc;
-    if (int rc = check_radius_scene(ctx, "pt_radius_search")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    unsigned long long* offsets = static_cast<unsigned long long*>(offsets_device);
-    if (n == 0) { PT_HIP(ctx, hipMemsetAsync(offsets, 0, sizeof(unsigned long long), ctx->stream)); return PT_OK; }
-    if (int rc = radius_offsets_on_stream(ctx, points_device, uint32_t(n), flags, offsets)) return rc;
-    if (capacity == 0) return PT_OK;
-    return radius_walk_on_stream(ctx, points_device, uint32_t(n), flags, nullptr, offsets, entries_device, capacity);
-}
-
-// staged: the host reads the total between the scan and the fill walk, so the staging buffer holds min(total, capacity) entries
-int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_search_host", points, n, flags)) return rc;
-    if (int rc = check_radius_search(ctx, "pt_radius_search_host", offsets, entries, capacity)) return rc;
-    if (int rc = check_radius_scene(ctx, "pt_radius_search_host")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) { offsets[0] = 0; return PT_OK; }
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_offsets.ensure(size_t(n) + 1));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = radius_offsets_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_rd_offsets.ptr, (size_t(n) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t held = std::min<uint64_t>(offsets[n], capacity);
-    if (held == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rd_entries.ensure(size_t(held)));
-    if (int rc = radius_walk_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, nullptr, ctx->d_rd_offsets.ptr, ctx->d_rd_entries.ptr, held)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(entries, ctx->d_rd_entries.ptr, size_t(held) * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
-                          uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats) {
-    if (flags & ~kRadiusFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: unknown flags");
-    const bool brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && !points) || !offsets || (capacity && !entries) || (!bvh4 && !brute))
-        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: null pointer");
-    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: offsets must be 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: more than 2^32 - 1 points");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::radius_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, offsets,
-                           reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_RADIUS_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) stats_from(stats, counters);
-    return PT_OK;
-}
-
-// ---- hit lists (include/mi355pt.h; pt_hitlist.hip) ------------------------------------------------------------------------------
-// The counts, the scan's scratch and the staging buffers are radius search's (d_rd_*): both queries use them between launches of one
-// call on the context's stream, which orders them, and the host forms wait for the stream before they return.
-
-namespace {
-constexpr uint32_t kHitsFlags = PT_HITS_STATS | PT_HITS_SIMPLE_KERNEL | PT_HITS_BRUTE_FORCE | PT_HITS_SORTED;
-static_assert(PT_HITS_STATS == PT_COUNT_STATS && PT_HITS_SIMPLE_KERNEL == PT_COUNT_SIMPLE_KERNEL && PT_HITS_BRUTE_FORCE == PT_COUNT_BRUTE_FORCE,
-              "the count walk of pt_list_hits is pt_count_hits' with the same flags");
-
-// flags, batch size and the pointers; the scene behind them (check_radius_scene)
-int check_hits(PtContext* ctx, const char* fn, const void* rays, uint64_t n, uint32_t flags, const void* offsets, const void* hits, uint64_t capacity) {
-    if (flags & ~kHitsFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 rays");
-    if (!aligned16(rays)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": rays must be non-null and 16-byte aligned");
-    if (!aligned8(offsets)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": offsets must be non-null and 8-byte aligned");
-    if (capacity ? !aligned16(hits) : (hits && !aligned16(hits)))
-        return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": hits must be 16-byte aligned, and non-null unless capacity is 0");
-    return PT_OK;
-}
-// the count walk (pt_count_hits' own launch, counters included) into the context's buffer and the scan into `offsets`: two launches, no host wait
-int hits_offsets_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, unsigned long long* offsets) {
-    const size_t temp_bytes = ptk::radius_scan_temp_bytes(n);
-    PT_HIP(ctx, ctx->d_rd_counts.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rd_temp.ensure(temp_bytes));
-    if (int rc = count_on_stream(ctx, rays, n, flags & kCountFlags, ctx->d_rd_counts.ptr)) return rc;
-    PT_HIP(ctx, ptk::launch_radius_scan(ctx->d_rd_counts.ptr, n, offsets, ctx->d_rd_temp.ptr, temp_bytes, ctx->stream));
-    return PT_OK;
-}
-// the fill walk from `offsets` into `hits` and, with PT_HITS_SORTED, the sort: one or two launches, no host wait.  PT_HITS_STATS counted
-// over the count walk; its fill walk is the one-ray-per-thread kernel.
-int hits_fill_on_stream(PtContext* ctx, const void* rays, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* hits, uint64_t capacity) {
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool brute = (flags & PT_HITS_BRUTE_FORCE) != 0, simple = (flags & (PT_HITS_SIMPLE_KERNEL | PT_HITS_STATS)) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, PT_HL_WAVES_PER_SIMD);
-    if (!simple && !brute) PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_HL_SHORT_STACK));
-    PT_HIP(ctx, ptk::launch_hit_fill(A, rays, n, offsets, hits, capacity, simple, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (flags & PT_HITS_SORTED) PT_HIP(ctx, ptk::launch_hit_sort(offsets, hits, capacity, n, ctx->stream));
-    return PT_OK;
-}
-} // namespace
-
-// three or four launches, no host wait: the counts into the context's buffer, their scan into offsets, the entries, their sort
-int pt_list_hits(PtContext* ctx, const void* rays_device, uint64_t n, uint32_t flags, void* offsets_device, void* hits_device, uint64_t capacity) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_hits(ctx, "pt_list_hits", rays_device, n, flags, offsets_device, hits_device, capacity)) return rc;
-    if (int rc = check_radius_scene(ctx, "pt_list_hits")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    unsigned long long* offsets = static_cast<unsigned long long*>(offsets_device);
-    if (n == 0) { PT_HIP(ctx, hipMemsetAsync(offsets, 0, sizeof(unsigned long long), ctx->stream)); return PT_OK; }
-    if (int rc = hits_offsets_on_stream(ctx, rays_device, uint32_t(n), flags, offsets)) return rc;
-    if (capacity == 0) return PT_OK;
-    return hits_fill_on_stream(ctx, rays_device, uint32_t(n), flags, offsets, hits_device, capacity);
-}
-
-// staged: the host reads the total between the scan and the fill walk, so the staging buffer holds min(total, capacity) entries
-int pt_list_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_hits(ctx, "pt_list_hits_host", rays, n, flags, offsets, hits, capacity)) return rc;
-    if (int rc = check_radius_scene(ctx, "pt_list_hits_host")) return rc;
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0) { offsets[0] = 0; return PT_OK; }
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n) * 2)); PT_HIP(ctx, ctx->d_rd_offsets.ensure(size_t(n) + 1));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, rays, size_t(n) * sizeof(PtRay), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = hits_offsets_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(offsets, ctx->d_rd_offsets.ptr, (size_t(n) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t held = std::min<uint64_t>(offsets[n], capacity);
-    if (held == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rd_entries.ensure(size_t(held)));
-    if (int rc = hits_fill_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), flags, ctx->d_rd_offsets.ptr, ctx->d_rd_entries.ptr, held)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_rd_entries.ptr, size_t(held) * sizeof(PtHit), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_list_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtRay* rays, uint64_t n,
-                      uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity, PtStats* stats) {
-    if (flags & ~kHitsFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: unknown flags");
-    const bool brute = (flags & PT_HITS_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && !rays) || !offsets || (capacity && !hits) || (!bvh4 && !brute))
-        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: null pointer");
-    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: offsets must be 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: more than 2^32 - 1 rays");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::list_hits(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(rays), n, offsets,
-                       reinterpret_cast<uint32_t*>(hits), capacity, (flags & PT_HITS_SORTED) != 0, (flags & PT_HITS_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) stats_from(stats, counters);
-    return PT_OK;
-}
-
-// ---- k-nearest queries (include/mi355pt.h; pt_knn.hip) --------------------------------------------------------------------------
-
-static_assert(PT_NEAREST_MAX_K == ptk::kNearestMaxK && PT_NEAREST_MAX_K == pt::kNearestMaxK, "one PT_NEAREST_MAX_K for the header, the kernels and the twin");
-
-namespace {
-constexpr uint32_t kNearestFlags = PT_NEAREST_STATS | PT_NEAREST_SIMPLE_KERNEL | PT_NEAREST_BRUTE_FORCE;
-
-int check_nearest(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t k, uint32_t flags, const void* out) {
-    if (flags & ~kNearestFlags) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": unknown flags");
-    if (k == 0u || k > PT_NEAREST_MAX_K) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": k must be 1 .. PT_NEAREST_MAX_K");
-    if (n > 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^32 - 1 points");
-    if (!aligned16(points) || !aligned16(out)) return fail(ctx, PT_ERR_INVALID_ARG, std::string(fn) + ": points and results must be non-null and 16-byte aligned");
-    if (!ctx->have_tris || !ctx->have_bvh) return fail(ctx, PT_ERR_NO_SCENE, std::string(fn) + ": scene not set (triangles + BVH)");
-    return PT_OK;
-}
-
-// the launch itself: points / rows in device memory, on the context's stream, behind whatever pt_set_batch still holds
-int nearest_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t k, uint32_t flags, void* out) {
-    if (int rc = flush_pending(ctx)) return rc;
-    if (n == 0u) return PT_OK;
-    if (int rc = sync_refit_meta(ctx)) return rc;
-    ptk::RenderArgs A; scene_args(ctx, A);
-    const bool stats = (flags & PT_NEAREST_STATS) != 0, simple = (flags & PT_NEAREST_SIMPLE_KERNEL) != 0, brute = (flags & PT_NEAREST_BRUTE_FORCE) != 0;
-    const uint32_t grid = ptk::walk_grid(ctx->num_cus, ptk::nearest_k_waves_per_simd(k));
-    if (stats) {
-        ctx->stats_culled = 0;
-        PT_HIP(ctx, hipMemsetAsync(ctx->d_stats.ptr, 0, 24 * sizeof(unsigned long long), ctx->stream));
-        A.stats = ctx->d_stats.ptr;
-    } else if (!simple && !brute) {
-        PT_HIP(ctx, ensure_walk_buffers(ctx, grid, PT_NK_SHORT_STACK));
-    }
-    PT_HIP(ctx, ptk::launch_nearest_k(A, points, out, n, k, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, grid, ctx->stream));
-    if (stats) ctx->last_stats = true;
-    return PT_OK;
-}
-} // namespace
-
-int pt_nearest_k(PtContext* ctx, const void* points_device, uint64_t n, uint32_t k, uint32_t flags, void* out_device) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_nearest(ctx, "pt_nearest_k", points_device, n, k, flags, out_device)) return rc;
-    return nearest_on_stream(ctx, points_device, uint32_t(n), k, flags, out_device);
-}
-
-// staged through the buffers of the ray and closest-point queries: n points in, n * k records out
-int pt_nearest_k_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t k, uint32_t flags, PtClosest* out) {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_nearest(ctx, "pt_nearest_k_host", points, n, k, flags, out)) return rc;
-    if (int rc = flush_pending(ctx)) return rc;           // as pt_closest_points_host: before the staging; nearest_on_stream then finds nothing queued
-    if (n == 0) return PT_OK;
-    PT_HIP(ctx, ctx->d_rq_rays.ensure(size_t(n))); PT_HIP(ctx, ctx->d_rq_hits.ensure(size_t(n) * k));
-    PT_HIP(ctx, hipMemcpyAsync(ctx->d_rq_rays.ptr, points, size_t(n) * sizeof(PtPoint), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = nearest_on_stream(ctx, ctx->d_rq_rays.ptr, uint32_t(n), k, flags, ctx->d_rq_hits.ptr)) return rc;
-    PT_HIP(ctx, hipMemcpyAsync(out, ctx->d_rq_hits.ptr, size_t(n) * k * sizeof(PtClosest), hipMemcpyDeviceToHost, ctx->stream));
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-int pt_nearest_k_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
-                      uint32_t k, uint32_t flags, PtClosest* out, PtStats* stats) {
-    if (flags & ~kNearestFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: unknown flags");
-    if (k == 0u || k > PT_NEAREST_MAX_K) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: k must be 1 .. PT_NEAREST_MAX_K");
-    const bool brute = (flags & PT_NEAREST_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && (!points || !out)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: null pointer");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_nearest_k_bvh4: more than 2^32 - 1 points");
-    std::string err;
-    uint64_t counters[5] = {0, 0, 0, 0, 0};
-    if (!pt::nearest_k(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, k,
-                       reinterpret_cast<uint32_t*>(out), (flags & PT_NEAREST_STATS) && stats ? counters : nullptr, err))
-        return fail(nullptr, PT_ERR_BAD_BVH, err);
-    if (stats) stats_from(stats, counters);
     return PT_OK;
 }
 
