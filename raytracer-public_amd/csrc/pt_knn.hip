@@ -13,6 +13,7 @@
 // goes behind every pair with d2' <= d2, so equal distances keep visit order, and the pair behind the k-th falls off.  The visit order
 // depends on the point and the tree alone, so the three kernels' walks and the host twin (pt_host.cpp::nearest_k) give the same rows, ties
 // included.  The point-triangle arithmetic is pt_closest.h, shared with the twin.
+// The point record, the slack, box_bound2 and tri_d2 are pt_points.h's, shared with pt_pointquery.hip and pt_radius.hip.
 // Records: PtPoint = one float4 (p.xyz, r_max), an entry = PtClosest = one uint4 (dist bits, prim, u bits, v bits); row i is
 // out[i * k .. i * k + k - 1], padded with (+inf, 0xFFFFFFFF, 0, 0).  Plain vector stores only; the one atomic is the walk's queue claim.
 #include <hip/hip_runtime.h>
@@ -21,41 +22,10 @@
 #include "pt_kernels.h"
 #include "pt_device.h"
 #include "pt_closest.h"
+#include "pt_points.h"
 #include "pt_walk.h"
 
 namespace ptk {
-
-constexpr uint32_t kNkInfBits = 0x7F800000u;
-
-// pt_pointquery.hip::point_slack, box_bound2 and their two helpers, restated: the same instructions on the same operands
-struct NkSlack { F3 hi, lo; };
-__device__ __forceinline__ NkSlack nk_slack(F3 p) {
-    NkSlack s;
-    s.hi = f3(p.x + ptcp::kSlack, p.y + ptcp::kSlack, p.z + ptcp::kSlack);
-    s.lo = f3(p.x - ptcp::kSlack, p.y - ptcp::kSlack, p.z - ptcp::kSlack);
-    return s;
-}
-__device__ __forceinline__ float nk_minus_half_lo(float o, uint32_t w) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
-__device__ __forceinline__ float nk_minus_half_hi(float o, uint32_t w) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
-__device__ __forceinline__ float nk_box_bound2(const NkSlack& s, uint32_t w0, uint32_t w1, uint32_t w2) {
-    const float gx = wmax(wmax(half_lo_minus(w0, s.hi.x), nk_minus_half_hi(s.lo.x, w1)), 0.0f);
-    const float gy = wmax(wmax(half_hi_minus(w0, s.hi.y), nk_minus_half_lo(s.lo.y, w2)), 0.0f);
-    const float gz = wmax(wmax(half_lo_minus(w1, s.hi.z), nk_minus_half_hi(s.lo.z, w2)), 0.0f);
-    return (gx * gx + gy * gy) + gz * gz;
-}
-
-__device__ __forceinline__ void nk_load_point(const float4* __restrict__ pts, uint32_t i, F3& p, float& rmax) {
-    const float4 a = pts[i];
-    p = f3(a.x, a.y, a.z); rmax = a.w;
-}
-// d2 of one triangle record (three axis-major pieces: v0[a], e1[a], e2[a])
-__device__ __forceinline__ float nk_tri_d2(F3 p, const float4 a, const float4 b, const float4 c) {
-    const float ax = p.x - a.x, ay = p.y - b.x, az = p.z - c.x;
-    float u, v;
-    ptcp::closest_uv(ax, ay, az, a.y, b.y, c.y, a.z, b.z, c.z, u, v);
-    return ptcp::closest_d2(ax, ay, az, a.y, b.y, c.y, a.z, b.z, c.z, u, v);
-}
-__device__ __forceinline__ float4 nk_as_float4(const uint4 u) { return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)); }
 
 // ------------------------------------------------------------------------------------
 // the list: at most k pairs (d2 bits << 32 | tag), ascending by d2, entry j at lst[j * STRIDE].  STRIDE = 64 is a lane's column of LDS
@@ -96,7 +66,7 @@ __device__ __forceinline__ void nk_write_row(uint4* __restrict__ out, const floa
         ptcp::closest_uv(p.x - a.x, p.y - b.x, p.z - c.x, a.y, b.y, c.y, a.z, b.z, c.z, u, v);
         o[j] = make_uint4(__float_as_uint(sqrtf(nk_pair_d2(e))), tri, __float_as_uint(u), __float_as_uint(v));
     }
-    for (uint32_t j = count; j < k; ++j) o[j] = make_uint4(kNkInfBits, kInvalidRef, 0u, 0u);
+    for (uint32_t j = count; j < k; ++j) o[j] = make_uint4(kInfBits, kInvalidRef, 0u, 0u);
 }
 
 // ------------------------------------------------------------------------------------
@@ -109,8 +79,8 @@ __device__ __forceinline__ void nearest_walk_point(const RenderArgs& A, F3 p, fl
     if (A.root_ref == kInvalidRef || A.num_tris == 0u) return;
     if (STATS) { cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u; }      // the root record is fetched before its degenerate check
     if (A.root_degenerate) return;
-    const NkSlack s = nk_slack(p);
-    if (!(nk_box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < worst2)) return;
+    const PointSlack s = point_slack(p);
+    if (!(box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < worst2)) return;
     uint32_t cur = A.root_ref;
     int sp = 0;
     for (;;) {
@@ -120,7 +90,7 @@ __device__ __forceinline__ void nearest_walk_point(const RenderArgs& A, F3 p, fl
             if (ti4 < 4u * A.num_tris) {                          // an out-of-range leaf points at the record behind the last triangle: skipped
                 const float4* tp = (const float4*)arena_record(A, cur);
                 if (STATS) cnt.tris += 1;
-                const float d2 = nk_tri_d2(p, tp[0], tp[1], tp[2]);
+                const float d2 = tri_d2(p, tp[0], tp[1], tp[2]);
                 if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, cur);
             }
             need_pop = true;
@@ -128,8 +98,8 @@ __device__ __forceinline__ void nearest_walk_point(const RenderArgs& A, F3 p, fl
             const uint4* np = arena_record(A, cur);
             const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
             const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
-            const float t0 = nk_box_bound2(s, n0.x, n0.y, n0.z), t1 = nk_box_bound2(s, n1.x, n1.y, n1.z);
-            const float t2 = nk_box_bound2(s, n2.x, n2.y, n2.z), t3 = nk_box_bound2(s, n3.x, n3.y, n3.z);
+            const float t0 = box_bound2(s, n0.x, n0.y, n0.z), t1 = box_bound2(s, n1.x, n1.y, n1.z);
+            const float t2 = box_bound2(s, n2.x, n2.y, n2.z), t3 = box_bound2(s, n3.x, n3.y, n3.z);
             const bool h0 = t0 < worst2, h1 = t1 < worst2, h2 = t2 < worst2, h3 = t3 < worst2;
             if (STATS) cnt.nodes += (r0 != kInvalidRef) + (r1 != kInvalidRef) + (r2 != kInvalidRef) + (r3 != kInvalidRef);
             uint32_t enter;
@@ -166,7 +136,7 @@ __global__ __launch_bounds__(256) void nearest_k_simple_kernel(const RenderArgs 
     Counters cnt; cnt.nodes = cnt.tris = cnt.drops = cnt.maxstack = 0;
     if (i < n) {
         F3 p; float rmax;
-        nk_load_point(pts, i, p, rmax);
+        load_point(pts, i, p, rmax);
         unsigned long long lst[kNearestMaxK];
         uint32_t count = 0;
         if (ptcp::point_walked(p.x, p.y, p.z, rmax)) {
@@ -190,21 +160,21 @@ struct NearestWalk {
     const float4* __restrict__ pts; uint4* __restrict__ out; const float4* __restrict__ tris; uint32_t leaf_end, k;
     unsigned long long* lst;
     uint32_t rid = 0, count = 0; float worst2 = 0.0f;
-    F3 p = f3(0, 0, 0); NkSlack s = nk_slack(p);
+    F3 p = f3(0, 0, 0); PointSlack s = point_slack(p);
 
     __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
         rid = item;
         float rmax;
-        nk_load_point(pts, rid, p, rmax);
+        load_point(pts, rid, p, rmax);
         worst2 = rmax * rmax; count = 0u;
-        s = nk_slack(p);
-        if (scene_ok && ptcp::point_walked(p.x, p.y, p.z, rmax) && nk_box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < worst2) return true;
+        s = point_slack(p);
+        if (scene_ok && ptcp::point_walked(p.x, p.y, p.z, rmax) && box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < worst2) return true;
         nk_write_row<64, 2>(out, tris, p, lst, 0u, k, rid);
         return false;
     }
-    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& bound2) const { bound2 = nk_box_bound2(s, w0, w1, w2); return bound2 < worst2; }
+    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& bound2) const { bound2 = box_bound2(s, w0, w1, w2); return bound2 < worst2; }
     __device__ __forceinline__ bool leaf(uint32_t cur, const uint4 n0, const uint4 n1, const uint4 n2) {
-        const float d2 = nk_tri_d2(p, nk_as_float4(n0), nk_as_float4(n1), nk_as_float4(n2));
+        const float d2 = tri_d2(p, as_float4(n0), as_float4(n1), as_float4(n2));
         if (((cur & 0x7fffffffu) < leaf_end) & (d2 < worst2)) worst2 = nk_insert<64>(lst, count, k, worst2, d2, cur);
         return false;                                                     // no leaf ends the point
     }
@@ -233,7 +203,7 @@ __global__ __launch_bounds__(256) void nearest_k_brute_kernel(const RenderArgs A
     __shared__ float4 rec[kNkBruteTile][3];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     F3 p = f3(0, 0, 0); float rmax = 0.0f;
-    if (i < n) nk_load_point(pts, i, p, rmax);
+    if (i < n) load_point(pts, i, p, rmax);
     const bool walked = (i < n) && ptcp::point_walked(p.x, p.y, p.z, rmax);
     float worst2 = rmax * rmax;
     unsigned long long lst[kNearestMaxK];
@@ -249,7 +219,7 @@ __global__ __launch_bounds__(256) void nearest_k_brute_kernel(const RenderArgs A
         __syncthreads();
         if (walked) {
             for (uint32_t t = 0; t < tile; ++t) {
-                const float d2 = nk_tri_d2(p, rec[t][0], rec[t][1], rec[t][2]);
+                const float d2 = tri_d2(p, rec[t][0], rec[t][1], rec[t][2]);
                 if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, base + t);
             }
             if (STATS) cnt.tris += tile;

@@ -9,56 +9,21 @@
 //   * hit_surfels_kernel              PtRay + PtHit -> PtSurfel
 //
 // Item i * samples + s is sample ray s of surfel i.  Its ray is a pure function of the surfel record and (seed, index_base + i, s)
-// (sample_ray below), so the persistent kernel, the simple kernel and occlusion_rays_kernel produce the same bits, and a sample is occluded
+// (pt_rays.h::sample_ray), so the persistent kernel, the simple kernel and occlusion_rays_kernel produce the same bits, and a sample is occluded
 // exactly when pt_trace_rays(PT_TRACE_ANY_HIT) reports a hit for the record occlusion_rays_kernel writes: occlusion_kernel and
 // pt_rayquery.hip::trace_rays_kernel<true> are the same walk (pt_walk.h::persistent_walk) and the same tests (pt_device.h).
+// The surfel record, the sample ray, the lane state of the walk and the per-id counting are pt_rays.h's, shared with pt_crossings.hip.
 // Records: PtSurfel = two float4 (p.xyz, r_max | n.xyz, reserved), PtOcclusion = one uint4 (visibility bits, unoccluded, samples, 0).
 // The counter of surfel i is word 1 of its output record: zeroed by the launch, incremented by vector atomics, completed by the finish kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <algorithm>
 
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_rays.h"
 #include "pt_walk.h"
 
 namespace ptk {
-
-struct Surfel { F3 p, n; float r_max; };
-__device__ __forceinline__ Surfel load_surfel(const float4* __restrict__ surfels, uint32_t i) {
-    const float4 a = surfels[(size_t)i * 2], b = surfels[(size_t)i * 2 + 1];
-    Surfel s; s.p = f3(a.x, a.y, a.z); s.r_max = a.w; s.n = f3(b.x, b.y, b.z);
-    return s;
-}
-// a surfel with a NaN in p, n or r_max, or with r_max <= 0, is not traced (a NaN r_max fails the comparison as well)
-__device__ __forceinline__ bool surfel_traced(const Surfel& s) {
-    const bool nan = __builtin_isnan(s.p.x) | __builtin_isnan(s.p.y) | __builtin_isnan(s.p.z) | __builtin_isnan(s.n.x) | __builtin_isnan(s.n.y) | __builtin_isnan(s.n.z);
-    return !nan & (s.r_max > 0.0f);
-}
-// sample ray s of the surfel with sample index `pixel` = index_base + i (mod 2^32): DESIGN.md section 4's cosine sampling around n as given
-__device__ __forceinline__ void sample_ray(const Surfel& sf, uint32_t seed, uint32_t pixel, uint32_t s, float bias, F3& o, F3& d) {
-    const uint32_t key = sample_key(seed, pixel, s);
-    const float u1 = rnd(key, 0u, 2u), u2 = rnd(key, 0u, 3u);
-    d = cosine_dir(sf.n, u1, u2);
-    o = sf.p + sf.n * bias;
-}
-// pt_rayquery.hip::ray_traced: a ray with a NaN in org or dir is a miss and is not traversed (t_max = r_max > 0 holds for a traced surfel)
-__device__ __forceinline__ bool ray_walks(F3 o, F3 d) {
-    return !(__builtin_isnan(o.x) | __builtin_isnan(o.y) | __builtin_isnan(o.z) | __builtin_isnan(d.x) | __builtin_isnan(d.y) | __builtin_isnan(d.z));
-}
-// The lanes of `miss` that hold the same surfel add their number to its counter with ONE atomic (the first of them issues it): with 64
-// samples per surfel the lanes of a chunk share a surfel, and one same-address atomic per ray would serialise in the L2.  Wave-uniform loop
-// over the distinct surfels among the finishing lanes (one or two in practice).  Integer sums: any order gives the same bits.
-__device__ __forceinline__ void count_misses(uint4* __restrict__ out, bool miss, uint32_t sid, uint32_t lane) {
-    unsigned long long m = __ballot(miss);
-    while (m != 0ull) {
-        const int leader = __builtin_ctzll(m);
-        const uint32_t s0 = (uint32_t)__shfl((int)sid, leader, 64);
-        const unsigned long long same = __ballot(miss && sid == s0);
-        if (lane == (uint32_t)leader) atomicAdd(&((uint32_t*)(out + s0))[1], (uint32_t)__popcll(same));
-        m &= ~same;
-    }
-}
 
 // ------------------------------------------------------------------------------------
 // simple kernel: one sample ray per thread, the renderer's traversal with its 64-entry private stack
@@ -76,7 +41,7 @@ __global__ __launch_bounds__(256) void occlusion_simple_kernel(const RenderArgs 
         if (surfel_traced(sf)) {
             F3 o, d; sample_ray(sf, seed, index_base + sid, s, bias, o, d);
             n_rays = 1; miss = true;
-            if (ray_walks(o, d)) {
+            if (ray_traced(o, d, sf.r_max)) {
                 Ray r; r.o = o; r.d = d; r.inv = safe_inv(d);
                 uint2 stk[kStackMax];
                 float bt; uint32_t bi;
@@ -84,26 +49,25 @@ __global__ __launch_bounds__(256) void occlusion_simple_kernel(const RenderArgs 
             }
         }
     }
-    count_misses(out, miss, sid, threadIdx.x & 63u);
+    count_same(out, miss, sid, threadIdx.x & 63u);
     if (STATS) add_stats(A, 1, n_rays, cnt);
 }
 
 // ------------------------------------------------------------------------------------
 // persistent kernel: one wavefront per workgroup, one sample ray per lane, lanes refilled from the wavefront's chunk
 // ------------------------------------------------------------------------------------
-// persistent_walk's Q (pt_walk.h) of a sample ray: RayWalk<true> of pt_rayquery.hip, except where a ray comes from (32 bytes of surfel
-// instead of 32 bytes of ray: no ray record is ever written) and where it goes (a count instead of a 16-byte hit record).  A lane keeps
-// neither the hit triangle nor the ray's number: only the surfel id it counts for.  The counting is wave-wide (count_misses), so it sits
-// in the two hooks: behind a hand-out for the rays that end where they start, behind a step for those that ended in it without a hit.
-struct OcclusionWalk {
+// persistent_walk's Q (pt_walk.h) of a sample ray: RayState (pt_rays.h) as RayWalk<true> of pt_rayquery.hip has it, except where a ray
+// comes from (32 bytes of surfel instead of 32 bytes of ray: no ray record is ever written) and where it goes (a count instead of a
+// 16-byte hit record).  A lane keeps neither the hit triangle nor the ray's number: only the surfel id it counts for.  `best` never
+// moves (the first hit ends the ray).  The counting is wave-wide (count_same), so it sits in the two hooks: behind a hand-out for the
+// rays that end where they start, behind a step for those that ended in it without a hit.
+struct OcclusionWalk : RayState {
     static constexpr bool kWaveHooks = true;
-    static constexpr float kKeyInit = kInfT;      // pt_device.h::order_children
     const float4* __restrict__ surfels; uint4* __restrict__ out;
     uint32_t samples, samples_magic, seed, index_base; float bias;
-    uint32_t sid = 0; float best = 0.0f;
+    uint32_t sid = 0;
     bool miss = false;          // this lane's new ray ends where it starts: it is not walked, or it misses the root box
     bool occluded = false;      // this lane's ray ended in this step at a hit
-    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
 
     __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
         uint32_t s; divmod_magic(item, samples, samples_magic, sid, s);
@@ -111,32 +75,26 @@ struct OcclusionWalk {
         if (!surfel_traced(sf)) return false;
         sample_ray(sf, seed, index_base + sid, s, bias, o, d);
         best = wmin(sf.r_max, kInfT);
-        inv = safe_inv(d); sel = ray_selectors(inv);
-        Ray r; r.o = o; r.d = d; r.inv = inv;
-        float troot;
-        if (scene_ok && ray_walks(o, d) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) return true;
+        if (enter_root(A, scene_ok, ray_traced(o, d, sf.r_max))) return true;
         miss = true;
         return false;
     }
-    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& tmin) const { return lane_of(slab_sel(o, inv, sel, w0, w1, w2, best, tmin)); }
     __device__ __forceinline__ bool leaf(uint32_t, const uint4 n0, const uint4 n1, const uint4 n2) {
         float t;
         if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) occluded = true;      // any hit ends the ray
         return occluded;
     }
-    __device__ __forceinline__ float bound() const { return best; }      // `best` never moves (the first hit ends the ray)
-    __device__ __forceinline__ void finish(const RenderArgs&) {}
-    __device__ __forceinline__ void after_refill(uint32_t lane) { count_misses(out, miss, sid, lane); miss = false; }
+    __device__ __forceinline__ void after_refill(uint32_t lane) { count_same(out, miss, sid, lane); miss = false; }
     // the lanes whose ray ended in this step without a hit, combined per surfel
     __device__ __forceinline__ void after_step(bool done, uint32_t lane) {
-        if (__ballot(done) != 0ull) count_misses(out, done && !occluded, sid, lane);
+        if (__ballot(done) != 0ull) count_same(out, done && !occluded, sid, lane);
         occluded = false;
     }
 };
 __global__ __launch_bounds__(64) void occlusion_kernel(const RenderArgs A, const float4* __restrict__ surfels, uint4* __restrict__ out, uint32_t items,
                                                        uint32_t samples, uint32_t samples_magic, uint32_t seed, uint32_t index_base, float bias,
                                                        unsigned long long* __restrict__ queue, unsigned long long* __restrict__ spill, uint32_t fill) {
-    OcclusionWalk q{surfels, out, samples, samples_magic, seed, index_base, bias};
+    OcclusionWalk q; q.surfels = surfels; q.out = out; q.samples = samples; q.samples_magic = samples_magic; q.seed = seed; q.index_base = index_base; q.bias = bias;
     persistent_walk<PT_OC_SHORT_STACK>(A, items, queue, spill, fill, q);
 }
 
@@ -182,9 +140,6 @@ __global__ __launch_bounds__(256) void hit_surfels_kernel(const RenderArgs A, co
     surfels[(size_t)i * 2] = make_float4(p.x, p.y, p.z, r);
     surfels[(size_t)i * 2 + 1] = make_float4(nf.x, nf.y, nf.z, 0.0f);
 }
-
-// floor(2^32 / d), saturated for d = 1 (divmod_magic's one correction covers the difference)
-static uint32_t magic_of(uint32_t d) { return (uint32_t)std::min<unsigned long long>((1ull << 32) / d, 0xFFFFFFFFull); }
 
 hipError_t launch_occlusion(const RenderArgs& A, const void* surfels, void* out, uint32_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias,
                             bool simple, bool stats, unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream) {

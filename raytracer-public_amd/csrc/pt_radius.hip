@@ -12,6 +12,7 @@
 // a point is its accepted leaves in visit order, which depends on the point and the tree alone: the count walk and the fill walk of a
 // point take the same steps whichever lane, wavefront or kernel runs them, so entry k lands at offsets[i] + k without an atomic.
 // The point-triangle arithmetic is pt_closest.h, shared with the host twin (pt_host.cpp::radius_search), which gives the same bits.
+// The point record, the slack, box_bound2 and tri_d2 are pt_points.h's, shared with pt_pointquery.hip and pt_knn.hip.
 // Records: PtPoint = one float4 (p.xyz, r_max), an entry = PtClosest = one uint4 (dist bits, prim, u bits, v bits).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,38 +21,10 @@
 #include "pt_kernels.h"
 #include "pt_device.h"
 #include "pt_closest.h"
+#include "pt_points.h"
 #include "pt_walk.h"
 
 namespace ptk {
-
-// pt_pointquery.hip::point_slack, box_bound2 and their two helpers, restated: the same instructions on the same operands
-struct RdSlack { F3 hi, lo; };
-__device__ __forceinline__ RdSlack rd_slack(F3 p) {
-    RdSlack s;
-    s.hi = f3(p.x + ptcp::kSlack, p.y + ptcp::kSlack, p.z + ptcp::kSlack);
-    s.lo = f3(p.x - ptcp::kSlack, p.y - ptcp::kSlack, p.z - ptcp::kSlack);
-    return s;
-}
-__device__ __forceinline__ float rd_minus_half_lo(float o, uint32_t w) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
-__device__ __forceinline__ float rd_minus_half_hi(float o, uint32_t w) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
-__device__ __forceinline__ float rd_box_bound2(const RdSlack& s, uint32_t w0, uint32_t w1, uint32_t w2) {
-    const float gx = wmax(wmax(half_lo_minus(w0, s.hi.x), rd_minus_half_hi(s.lo.x, w1)), 0.0f);
-    const float gy = wmax(wmax(half_hi_minus(w0, s.hi.y), rd_minus_half_lo(s.lo.y, w2)), 0.0f);
-    const float gz = wmax(wmax(half_lo_minus(w1, s.hi.z), rd_minus_half_hi(s.lo.z, w2)), 0.0f);
-    return (gx * gx + gy * gy) + gz * gz;
-}
-
-__device__ __forceinline__ void rd_load_point(const float4* __restrict__ pts, uint32_t i, F3& p, float& rmax) {
-    const float4 a = pts[i];
-    p = f3(a.x, a.y, a.z); rmax = a.w;
-}
-// d2 of one triangle record (three axis-major pieces: v0[a], e1[a], e2[a]) with the u, v it was computed from
-__device__ __forceinline__ float rd_tri_d2(F3 p, const float4 a, const float4 b, const float4 c, float& u, float& v) {
-    const float ax = p.x - a.x, ay = p.y - b.x, az = p.z - c.x;
-    ptcp::closest_uv(ax, ay, az, a.y, b.y, c.y, a.z, b.z, c.z, u, v);
-    return ptcp::closest_d2(ax, ay, az, a.y, b.y, c.y, a.z, b.z, c.z, u, v);
-}
-__device__ __forceinline__ float4 rd_as_float4(const uint4 u) { return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)); }
 
 // What the three kernels do with an accepted leaf: count it, and with FILL store its entry (one plain 16-byte vector store) when its
 // global index is below the capacity.  base + k is 64-bit: the total of a batch may pass 2^32.
@@ -77,8 +50,8 @@ __device__ __forceinline__ void radius_walk_point(const RenderArgs& A, F3 p, flo
     if (A.root_ref == kInvalidRef || A.num_tris == 0u) return;
     if (STATS) { cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u; }      // the root record is fetched before its degenerate check
     if (A.root_degenerate) return;
-    const RdSlack s = rd_slack(p);
-    if (!(rd_box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < r2)) return;
+    const PointSlack s = point_slack(p);
+    if (!(box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < r2)) return;
     uint32_t cur = A.root_ref;
     int sp = 0;
     for (;;) {
@@ -89,7 +62,7 @@ __device__ __forceinline__ void radius_walk_point(const RenderArgs& A, F3 p, flo
                 const float4* tp = (const float4*)arena_record(A, cur);
                 if (STATS) cnt.tris += 1;
                 float u, v;
-                const float d2 = rd_tri_d2(p, tp[0], tp[1], tp[2], u, v);
+                const float d2 = tri_d2(p, tp[0], tp[1], tp[2], u, v);
                 if (d2 < r2) sink.accept(d2, ti4 >> 2, u, v);
             }
             need_pop = true;
@@ -97,8 +70,8 @@ __device__ __forceinline__ void radius_walk_point(const RenderArgs& A, F3 p, flo
             const uint4* np = arena_record(A, cur);
             const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
             const uint32_t r0 = n0.w, r1 = n1.w, r2r = n2.w, r3 = n3.w;
-            const float t0 = rd_box_bound2(s, n0.x, n0.y, n0.z), t1 = rd_box_bound2(s, n1.x, n1.y, n1.z);
-            const float t2 = rd_box_bound2(s, n2.x, n2.y, n2.z), t3 = rd_box_bound2(s, n3.x, n3.y, n3.z);
+            const float t0 = box_bound2(s, n0.x, n0.y, n0.z), t1 = box_bound2(s, n1.x, n1.y, n1.z);
+            const float t2 = box_bound2(s, n2.x, n2.y, n2.z), t3 = box_bound2(s, n3.x, n3.y, n3.z);
             const bool h0 = t0 < r2, h1 = t1 < r2, h2 = t2 < r2, h3 = t3 < r2;
             if (STATS) cnt.nodes += (r0 != kInvalidRef) + (r1 != kInvalidRef) + (r2r != kInvalidRef) + (r3 != kInvalidRef);
             uint32_t enter;
@@ -136,7 +109,7 @@ __global__ __launch_bounds__(256) void radius_simple_kernel(const RenderArgs A, 
     Counters cnt; cnt.nodes = cnt.tris = cnt.drops = cnt.maxstack = 0;
     if (i < n) {
         F3 p; float rmax;
-        rd_load_point(pts, i, p, rmax);
+        load_point(pts, i, p, rmax);
         RdSink<FILL> sink{entries, capacity};
         if (FILL) sink.base = offsets[i];
         if (ptcp::point_walked(p.x, p.y, p.z, rmax)) {
@@ -160,25 +133,25 @@ struct RadiusWalk {
     const float4* __restrict__ pts; uint32_t* __restrict__ counts; const unsigned long long* __restrict__ offsets; uint32_t leaf_end;
     RdSink<FILL> sink;
     uint32_t rid = 0; float r2 = 0.0f;
-    F3 p = f3(0, 0, 0); RdSlack s = rd_slack(p);
+    F3 p = f3(0, 0, 0); PointSlack s = point_slack(p);
 
     __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
         rid = item;
         float rmax;
-        rd_load_point(pts, rid, p, rmax);
+        load_point(pts, rid, p, rmax);
         r2 = rmax * rmax; sink.count = 0u;
-        s = rd_slack(p);
-        if (scene_ok && ptcp::point_walked(p.x, p.y, p.z, rmax) && rd_box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < r2) {
+        s = point_slack(p);
+        if (scene_ok && ptcp::point_walked(p.x, p.y, p.z, rmax) && box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < r2) {
             if (FILL) sink.base = offsets[rid];
             return true;
         }
         if (!FILL) counts[rid] = 0u;
         return false;
     }
-    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& bound2) const { bound2 = rd_box_bound2(s, w0, w1, w2); return bound2 < r2; }
+    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& bound2) const { bound2 = box_bound2(s, w0, w1, w2); return bound2 < r2; }
     __device__ __forceinline__ bool leaf(uint32_t cur, const uint4 n0, const uint4 n1, const uint4 n2) {
         float u, v;
-        const float d2 = rd_tri_d2(p, rd_as_float4(n0), rd_as_float4(n1), rd_as_float4(n2), u, v);
+        const float d2 = tri_d2(p, as_float4(n0), as_float4(n1), as_float4(n2), u, v);
         if (((cur & 0x7fffffffu) < leaf_end) & (d2 < r2)) sink.accept(d2, (cur & 0x7fffffffu) >> 2, u, v);
         return false;                                                     // no leaf ends the point
     }
@@ -206,7 +179,7 @@ __global__ __launch_bounds__(256) void radius_brute_kernel(const RenderArgs A, c
     __shared__ float4 rec[kRdBruteTile][3];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     F3 p = f3(0, 0, 0); float rmax = 0.0f;
-    if (i < n) rd_load_point(pts, i, p, rmax);
+    if (i < n) load_point(pts, i, p, rmax);
     const bool walked = (i < n) && ptcp::point_walked(p.x, p.y, p.z, rmax);
     const float r2 = rmax * rmax;
     RdSink<FILL> sink{entries, capacity};
@@ -223,7 +196,7 @@ __global__ __launch_bounds__(256) void radius_brute_kernel(const RenderArgs A, c
         if (walked) {
             for (uint32_t k = 0; k < tile; ++k) {
                 float u, v;
-                const float d2 = rd_tri_d2(p, rec[k][0], rec[k][1], rec[k][2], u, v);
+                const float d2 = tri_d2(p, rec[k][0], rec[k][1], rec[k][2], u, v);
                 if (d2 < r2) sink.accept(d2, base + k, u, v);
             }
             if (STATS) cnt.tris += tile;

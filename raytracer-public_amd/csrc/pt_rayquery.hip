@@ -7,40 +7,22 @@
 // Both trace kernels walk the tree exactly as render_rays_kernel does (visit order, first-minimum ties, pushes far -> near, the silent drop at
 // 64 entries, re-validation at pop) with `best` starting at min(t_max, kInfT), so with t_max = +inf a result is the oracle's orc_trace_ray, bit for bit.
 // Records: PtRay = two float4 (org.xyz, t_max | dir.xyz, reserved), PtHit = one uint4 (t bits, prim, u bits, v bits).
+// The ray record, the hit record and the lane state of the walk are pt_rays.h's, shared with the occlusion, crossing and hit-list queries.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pt_kernels.h"
 #include "pt_device.h"
+#include "pt_rays.h"
 #include "pt_walk.h"
 
 namespace ptk {
 
-__device__ __forceinline__ void load_ray(const float4* __restrict__ rays, uint32_t i, F3& o, F3& d, float& tmax) {
-    const float4 a = rays[(size_t)i * 2], b = rays[(size_t)i * 2 + 1];
-    o = f3(a.x, a.y, a.z); tmax = a.w; d = f3(b.x, b.y, b.z);
-}
-// a ray with a NaN anywhere, or with t_max <= 0, is a miss and is not traversed (a NaN t_max fails the comparison as well)
-__device__ __forceinline__ bool ray_traced(F3 o, F3 d, float tmax) {
-    const bool nan = __builtin_isnan(o.x) | __builtin_isnan(o.y) | __builtin_isnan(o.z) | __builtin_isnan(d.x) | __builtin_isnan(d.y) | __builtin_isnan(d.z);
-    return !nan & (tmax > 0.0f);
-}
-// The 16-byte result.  u, v are recomputed from the winning triangle's record with the arithmetic of the accepted test
-// (renderer.wgsl:185-205, pt_device.h::traverse): the same operations on the same operands, so the same bits, and the traversal
-// step keeps no registers for them.
+// The 16-byte result: pt_rays.h::hit_entry on the winning triangle's record, or the miss
 __device__ __forceinline__ uint4 hit_record(const RenderArgs& A, F3 o, F3 d, float t, uint32_t tri) {
     if (tri == kInvalidRef) return make_uint4(0x7F800000u, kInvalidRef, 0u, 0u);      // +inf, no triangle, u = v = 0
-    const float4* tp = A.tris + (size_t)tri * 4;
-    const float4 a = tp[0], b = tp[1], c = tp[2];
-    const F3 v0 = f3(a.x, b.x, c.x), e1 = f3(a.y, b.y, c.y), e2 = f3(a.z, b.z, c.z);   // axis-major record (pt_host.h::TriRecord)
-    const F3 p = cross3(d, e2);
-    const float det = dot3(e1, p);
-    const float inv_det = 1.0f / det;
-    const F3 s = o - v0;
-    const float u = inv_det * dot3(s, p);
-    const F3 q = cross3(s, e1);
-    const float v = inv_det * dot3(d, q);
-    return make_uint4(__float_as_uint(t), tri, __float_as_uint(u), __float_as_uint(v));
+    const uint4* tp = (const uint4*)A.tris + (size_t)tri * 4;
+    return hit_entry(o, d, t, tri, tp[0], tp[1], tp[2]);
 }
 
 // ------------------------------------------------------------------------------------
@@ -70,43 +52,34 @@ __global__ __launch_bounds__(256) void trace_rays_simple_kernel(const RenderArgs
 // ------------------------------------------------------------------------------------
 // persistent kernel: one wavefront per workgroup, one ray per lane, lanes refilled from the wavefront's chunk
 // ------------------------------------------------------------------------------------
-// persistent_walk's Q (pt_walk.h) of a ray: the key of a child is tmin of its slab test, `best` starts at min(t_max, kInfT).  A leaf whose
-// triangle index is out of range points at the all-zero record behind the last triangle, which tri_hit rejects.
+// persistent_walk's Q (pt_walk.h) of a traced ray: RayState (pt_rays.h) with the closest triangle so far; `best` starts at
+// min(t_max, kInfT) and shrinks to each accepted hit.
 template <bool ANYHIT>
-struct RayWalk {
+struct RayWalk : RayState {
     static constexpr bool kWaveHooks = false;
-    static constexpr float kKeyInit = kInfT;      // pt_device.h::order_children
     const float4* __restrict__ rays; uint4* __restrict__ hits;
-    uint32_t rid = 0, btri = kInvalidRef; float best = 0.0f;
-    F3 o = f3(0, 0, 0), d = o, inv = o; RaySel sel = ray_selectors(inv);
+    uint32_t rid = 0, btri = kInvalidRef;
 
     __device__ __forceinline__ bool start(const RenderArgs& A, uint32_t item, bool scene_ok) {
         rid = item;
         float tmax;
         load_ray(rays, rid, o, d, tmax);
         best = wmin(tmax, kInfT); btri = kInvalidRef;
-        inv = safe_inv(d); sel = ray_selectors(inv);
-        Ray r; r.o = o; r.d = d; r.inv = inv;
-        float troot;
-        if (scene_ok && ray_traced(o, d, tmax) && slab(r, A.root_box[0], A.root_box[1], A.root_box[2], best, troot)) return true;
+        if (enter_root(A, scene_ok, ray_traced(o, d, tmax))) return true;
         hits[rid] = hit_record(A, o, d, 0.0f, kInvalidRef);
         return false;
     }
-    __device__ __forceinline__ bool child(uint32_t w0, uint32_t w1, uint32_t w2, float& tmin) const { return lane_of(slab_sel(o, inv, sel, w0, w1, w2, best, tmin)); }
     __device__ __forceinline__ bool leaf(uint32_t cur, const uint4 n0, const uint4 n1, const uint4 n2) {
         float t;
         if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) { best = t; btri = cur; return ANYHIT; }
         return false;
     }
-    __device__ __forceinline__ float bound() const { return best; }      // entries whose box the ray no longer reaches (tmin >= best) are skipped
     __device__ __forceinline__ void finish(const RenderArgs& A) { hits[rid] = hit_record(A, o, d, best, btri == kInvalidRef ? kInvalidRef : (btri & 0x7fffffffu) >> 2); }
-    __device__ __forceinline__ void after_refill(uint32_t) {}
-    __device__ __forceinline__ void after_step(bool, uint32_t) {}
 };
 template <bool ANYHIT>
 __global__ __launch_bounds__(64) void trace_rays_kernel(const RenderArgs A, const float4* __restrict__ rays, uint4* __restrict__ hits, uint32_t n,
                                                         unsigned long long* __restrict__ queue, unsigned long long* __restrict__ spill, uint32_t fill) {
-    RayWalk<ANYHIT> q{rays, hits};
+    RayWalk<ANYHIT> q; q.rays = rays; q.hits = hits;
     persistent_walk<PT_RQ_SHORT_STACK>(A, n, queue, spill, fill, q);
 }
 

@@ -1,7 +1,11 @@
-// pt_walk.h -- the one persistent walk of the batched queries: trace_rays_kernel<ANYHIT> (pt_rayquery.hip),
-// closest_points_kernel (pt_pointquery.hip) and occlusion_kernel (pt_occlusion.hip) fill a Q -- the per-lane state of one item and what
-// differs between the queries -- and call persistent_walk, which owns the chunk queue, the refill, the 64 B step, the child ordering,
-// the stack with its cap and the end of the wavefront.
+// pt_walk.h -- the one persistent walk of the batched queries.  A kernel fills a Q -- the per-lane state of one
+// item and what differs between the queries -- and calls persistent_walk, which owns the chunk queue, the refill, the 64 B step, the
+// child ordering, the stack with its cap and the end of the wavefront.  The Qs:
+//   rays (they derive from pt_rays.h::RayState)   RayWalk<ANYHIT> (pt_rayquery.hip: trace_rays_kernel), OcclusionWalk (pt_occlusion.hip:
+//                                                 occlusion_kernel), CountWalk and ContainsWalk (pt_crossings.hip: count_hits_kernel,
+//                                                 contains_kernel), HitWalk (pt_hitlist.hip: hit_fill_kernel)
+//   points (helpers in pt_points.h)               PointWalk (pt_pointquery.hip: closest_points_kernel), RadiusWalk<FILL> (pt_radius.hip:
+//                                                 radius_kernel), NearestWalk (pt_knn.hip: nearest_k_kernel<KCAP>)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -13,6 +13,8 @@ contains: --points points uniform in the scene's box, samples per point S in (1,
 Per variant: the median over --reps runs (after one warm-up) by events on the context's stream, in Mrays/s.  The variants must give the
 same results; the tool stops if they do not.  There is no gate: the queries have no predecessor to be measured against.
 
+PB_BASE=1 in the environment runs the library of an earlier commit instead (tools/ab/README); the JSON records "build": "base" | "tree".
+
     python tools/crossings_bench.py [--reps 5] [--points 2000000] [--out profiles/crossings_ab.json]
 """
 import argparse
@@ -50,9 +52,13 @@ def main():
     ap.add_argument("--configs", default=",".join(rq.CONFIGS))
     args = ap.parse_args()
     import torch
-    rt = importlib.import_module("raytracer-public_amd")
+    # PB_BASE=1: the library of an earlier commit (tools/ab/raytracer_base, built by tools/ab/README) for an A/B within one session
+    base = bool(os.environ.get("PB_BASE"))
+    if base:
+        sys.path.insert(0, os.path.join(ROOT, "tools", "ab"))
+    rt = importlib.import_module("raytracer_base" if base else "raytracer-public_amd")
     stream = torch.cuda.current_stream()
-    result = {"tool": "tools/crossings_bench.py", "reps": args.reps, "device": torch.cuda.get_device_name(0),
+    result = {"tool": "tools/crossings_bench.py", "build": "base" if base else "tree", "reps": args.reps, "device": torch.cuda.get_device_name(0),
               "GPU_MAX_HW_QUEUES": os.environ["GPU_MAX_HW_QUEUES"], "configs": {}}
     for name in args.configs.split(","):
         c = rq.CONFIGS[name]

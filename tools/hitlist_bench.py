@@ -11,6 +11,8 @@ sort.  Next to it the count alone (pt_count_hits), so that list_over_two_counts 
 maximum, the share of lists above PT_HL_LANE_MAX = 16) and stack_drops / max_stack from one PT_HITS_STATS pass.  The variants must give
 the same sorted lists; the tool stops if they do not.  There is no gate: the query has no predecessor.
 
+PB_BASE=1 in the environment runs the library of an earlier commit instead (tools/ab/README); the JSON records "build": "base" | "tree".
+
     python tools/hitlist_bench.py [--reps 5] [--out profiles/hitlist_ab.json]      (--out defaults to that file)
 """
 import argparse
@@ -48,9 +50,13 @@ def main():
     ap.add_argument("--configs", default=",".join(rq.CONFIGS))
     args = ap.parse_args()
     import torch
-    rt = importlib.import_module("raytracer-public_amd")
+    # PB_BASE=1: the library of an earlier commit (tools/ab/raytracer_base, built by tools/ab/README) for an A/B within one session
+    base = bool(os.environ.get("PB_BASE"))
+    if base:
+        sys.path.insert(0, os.path.join(ROOT, "tools", "ab"))
+    rt = importlib.import_module("raytracer_base" if base else "raytracer-public_amd")
     stream = torch.cuda.current_stream()
-    result = {"tool": "tools/hitlist_bench.py", "reps": args.reps, "device": torch.cuda.get_device_name(0),
+    result = {"tool": "tools/hitlist_bench.py", "build": "base" if base else "tree", "reps": args.reps, "device": torch.cuda.get_device_name(0),
               "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "configs": {}}
     for name in args.configs.split(","):
         c = rq.CONFIGS[name]

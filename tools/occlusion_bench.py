@@ -12,6 +12,8 @@ Per scene, tree, samples per surfel S in (16, 64) and r_max in (+inf, 0.25), fou
 Per variant: the median over --reps runs (after one warm-up) by events on the context's stream, in Mrays/s (rays = surfels * S), and the
 ratios F/C, F/S, F/T of those rates.  F, S and C must give the same counts; the tool stops if they do not.
 
+PB_BASE=1 in the environment runs the library of an earlier commit instead (tools/ab/README); the JSON records "build": "base" | "tree".
+
     python tools/occlusion_bench.py [--reps 5] [--out profiles/occlusion_ab.json]
 """
 import argparse
@@ -43,9 +45,13 @@ def main():
     ap.add_argument("--configs", default=",".join(CONFIGS))
     args = ap.parse_args()
     import torch
-    rt = importlib.import_module("raytracer-public_amd")
+    # PB_BASE=1: the library of an earlier commit (tools/ab/raytracer_base, built by tools/ab/README) for an A/B within one session
+    base = bool(os.environ.get("PB_BASE"))
+    if base:
+        sys.path.insert(0, os.path.join(ROOT, "tools", "ab"))
+    rt = importlib.import_module("raytracer_base" if base else "raytracer-public_amd")
     stream = torch.cuda.current_stream()
-    result = {"tool": "tools/occlusion_bench.py", "reps": args.reps, "device": torch.cuda.get_device_name(0),
+    result = {"tool": "tools/occlusion_bench.py", "build": "base" if base else "tree", "reps": args.reps, "device": torch.cuda.get_device_name(0),
               "GPU_MAX_HW_QUEUES": os.environ["GPU_MAX_HW_QUEUES"], "resolution": [W, H], "rows": []}
     for name in args.configs.split(","):
         c = CONFIGS[name]

@@ -12,6 +12,8 @@ Per set and kernel: the median over --reps launches (after one warm-up) of the l
 Per set: node records examined in one PT_TRACE_STATS pass, and those per second at the persistent kernel's time -- next to the
 megakernel's rate on C2 (BENCH_r06: about 410 M records per 0.69 ms frame).
 
+PB_BASE=1 in the environment runs the library of an earlier commit instead (tools/ab/README); the JSON records "build": "base" | "tree".
+
     python tools/rayquery_bench.py [--reps 5] [--out profiles/rayquery_ab.json]
 """
 import argparse
@@ -78,9 +80,13 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
-    rt = importlib.import_module("raytracer-public_amd")
+    # PB_BASE=1: the library of an earlier commit (tools/ab/raytracer_base, built by tools/ab/README) for an A/B within one session
+    base = bool(os.environ.get("PB_BASE"))
+    if base:
+        sys.path.insert(0, os.path.join(ROOT, "tools", "ab"))
+    rt = importlib.import_module("raytracer_base" if base else "raytracer-public_amd")
     stream = torch.cuda.current_stream()
-    result = {"tool": "tools/rayquery_bench.py", "reps": args.reps, "device": torch.cuda.get_device_name(0), "configs": {},
+    result = {"tool": "tools/rayquery_bench.py", "build": "base" if base else "tree", "reps": args.reps, "device": torch.cuda.get_device_name(0), "configs": {},
               "megakernel_c2_reference": dict(MEGAKERNEL_C2, node_records_per_s=MEGAKERNEL_C2["node_records_per_frame"] / (MEGAKERNEL_C2["ms_per_frame"] * 1e-3))}
     for name, c in CONFIGS.items():
         rng = np.random.default_rng(RNG_SEED)
