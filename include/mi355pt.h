@@ -514,6 +514,75 @@ PT_API int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t
 PT_API int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
                                  uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats);
 
+/* ---- box-overlap queries: which triangles overlap an axis-aligned box -- all of them? (an extension beyond the reference; DESIGN.md
+ * section 21) --------------------------------------------------------------------------------------------------------------------
+ * Records: PtBox in (32 B, read as 2 x 16 B like PtRay; the pads are ignored), one PtOverlap per accepted triangle out (16 B, written as
+ *   one record; both reserved words are written as 0); offsets is uint64_t[n + 1].  Every result is an integer.
+ *   verts_inside: bit i is set when vertex i lies in the closed box; 7 means that the whole triangle is inside.
+ * Walked boxes: a box is walked iff its six coordinates are finite and lo[k] <= hi[k] on every axis.  Zero-extent boxes (a point, a
+ *   segment, a rectangle) are valid.  Any other box has count 0 and an empty list.
+ * The triangle test (csrc/pt_overlap.h, one text for the kernels and the host twin; plain f32, each operation rounded once) on a triangle
+ *   record as stored (v0, e1 = v1 - v0, e2 = v2 - v0):
+ *   vertices: v1 = v0 + e1, v2 = v0 + e2, per component.
+ *   (a) the box axes, compared directly with the corners as given, no centre involved: on each axis k, min(v0k, v1k, v2k) <= hi[k] and
+ *       max(v0k, v1k, v2k) >= lo[k], and no v_ik is a NaN.  The same comparisons give verts_inside.
+ *   (b) the plane, relative to the centre: c = (lo + hi) * 0.5f, h = (hi - lo) * 0.5f, a_i = v_i - c, n = e1 x e2 (each product rounded,
+ *       then the difference): |(n.x a0.x + n.y a0.y) + n.z a0.z| <= (|n.x| h.x + |n.y| h.y) + |n.z| h.z.
+ *   (c) nine edge axes: for f = e1, e2 - e1, e2 in that order, crossed with x, y, z in that order, the projections p_i of a_0..a_2 and the
+ *       box radius r, every product rounded, then the difference or the sum:
+ *         x: p_i = a_i.z f.y - a_i.y f.z, r = h.y |f.z| + h.z |f.y|;   y: p_i = a_i.x f.z - a_i.z f.x, r = h.x |f.z| + h.z |f.x|;
+ *         z: p_i = a_i.y f.x - a_i.x f.y, r = h.x |f.y| + h.y |f.x|;   the axis passes iff min p <= r and max p >= -r.
+ *   A triangle is ACCEPTED iff (a) passes and either verts_inside != 0 or (b) and all of (c) pass: a vertex in the closed box is an overlap
+ *   with no rounding involved.  Every comparison is written so that a NaN operand fails it: a NaN triangle is never accepted.  Touching
+ *   counts as overlap.  The result is a pure boolean, so early exits change nothing.
+ * The node test, on a packed f16 child box (mn, mx): a child is entered iff mn[k] <= hi[k] + s and mx[k] >= lo[k] - s on every axis, with
+ *   s = 2^-12 (the slack of pt_closest_points); hi + s and lo - s are computed once per box.  The inverted box of an empty slot fails.
+ * The walk: the shared walk of the point queries with every key equal -- passing children are walked depth first in slot order; the stack
+ *   holds 64 entries and a push at the cap is dropped (and counted); a degenerate root box gives 0 for every box; a leaf with
+ *   tri >= num_tris is skipped.  Spheres (pt_set_spheres) take no part.
+ * The list: count[i] = the number of accepted leaves of box i; its list is those leaves IN VISIT ORDER, which is a property of the box and
+ *   the tree, not of the scheduling: every kernel variant and the host twin give the same order.
+ * pt_box_search: offsets[0] = 0 and offsets[i + 1] - offsets[i] = count[i] in uint64_t (no wrap); offsets[n] = the total.  The entry with
+ *   global index g = offsets[i] + k is written iff g < capacity; entries at and beyond min(total, capacity) are not touched.  The offsets
+ *   are always complete: offsets[n] > capacity says that the list was truncated and how large the retry must be.  entries_device = NULL is
+ *   allowed with capacity = 0 (offsets only).  Three launches on the context's stream, no host wait: the count walk into a buffer of the
+ *   context, an exclusive scan, a second walk of the same steps that stores entry k of box i at offsets[i] + k.  No atomic appends anything.
+ * PT_BOX_BRUTE_FORCE: every triangle in index order through the same triangle test, no tree; the list is then in index order.
+ * PT_BOX_STATS: the counting variant (one box per thread) fills pt_get_stats: rays_closest = n, nodes_examined, tris_tested, stack_drops
+ *   and max_stack by the rules of PT_RADIUS_STATS, counted over the count walk only.  With PT_BOX_BRUTE_FORCE only rays_closest and
+ *   tris_tested are counted.
+ * PT_BOX_SIMPLE_KERNEL: the one-box-per-thread kernels instead of the persistent one (A/B checks); the results are the same.
+ * Completeness: for vertex coordinates within [-4, 4] and box coordinates within [-32, 32], wherever every triangle is reachable from the
+ *   root and the walk drops nothing at the cap (stack_drops = 0), the walk lists exactly the set PT_BOX_BRUTE_FORCE lists (DESIGN.md
+ *   section 21 has the proof).  STACK DROPS LOSE ENTRIES: nothing is ever pruned behind a large box, so it reaches the 64-entry cap as a
+ *   large radius does; the only report is stack_drops of PT_BOX_STATS.  With drops the walk's list is a subset of the brute-force list.
+ * Ordering, errors and alignment: as pt_radius_search.  Boxes and entries 16-byte aligned, offsets 8-byte, counts 4-byte; a NULL or
+ *   misaligned pointer (entries: unless capacity = 0), unknown flags or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the scene).
+ *   No triangles + tree: PT_ERR_NO_SCENE.  n = 0: PT_OK, no kernel is launched (pt_box_search still sets offsets[0] = 0).  A scene change
+ *   after a call does not change its results. */
+typedef struct PtBox     { float lo[3]; float pad0; float hi[3]; float pad1; } PtBox;             /* 32 B, 16-byte aligned arrays */
+typedef struct PtOverlap { uint32_t prim; uint32_t verts_inside; uint32_t reserved[2]; } PtOverlap; /* 16 B */
+enum { PT_BOX_STATS = 1u, PT_BOX_SIMPLE_KERNEL = 2u, PT_BOX_BRUTE_FORCE = 4u };
+/* n boxes from device memory (PtBox[n], 16-byte aligned), n counts into device memory (uint32_t[n], 4-byte aligned).  Asynchronous on
+ * the context's stream (pt_get_stream). */
+PT_API int pt_box_count(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags, void* counts_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the counts are written. */
+PT_API int pt_box_count_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags, uint32_t* counts);
+/* n boxes from device memory -> offsets_device: uint64_t[n + 1] (8-byte aligned); entries_device: PtOverlap[capacity] (16-byte aligned).
+ * Asynchronous on the context's stream, no host wait. */
+PT_API int pt_box_search(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags,
+                         void* offsets_device, void* entries_device, uint64_t capacity);
+/* The same from host arrays: staged; the host reads the total between the scan and the second walk; returns when everything is written. */
+PT_API int pt_box_search_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags,
+                              uint64_t* offsets, PtOverlap* entries, uint64_t capacity);
+/* Host twin (no context, no GPU): the same offsets, entry words and order (and the same truncation at `capacity`) and, with PT_BOX_STATS
+ * and stats != NULL, the same counters as the device gives for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).
+ * bvh4 = NULL (words = 0) only with PT_BOX_BRUTE_FORCE; a malformed bvh4: PT_ERR_BAD_BVH; a NULL boxes pointer with n > 0, NULL offsets,
+ * NULL entries with capacity > 0, offsets not 8-byte aligned, or unknown flags: PT_ERR_INVALID_ARG.  boxes and entries need only the
+ * alignment of their types here. */
+PT_API int pt_box_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtBox* boxes, uint64_t n,
+                              uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity, PtStats* stats);
+
 /* ---- hit lists: which triangles does a ray cross, and where -- all of them, each with t and u, v? (an extension beyond the reference;
  * DESIGN.md section 20) -----------------------------------------------------------------------------------------------------------
  * Records: PtRay in, one PtHit (t, prim, u, v) per crossing out; offsets is uint64_t[n + 1].  Every result is an integer or a bit pattern.

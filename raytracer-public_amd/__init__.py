@@ -40,6 +40,8 @@ PT_CONTAIN_STATS, PT_CONTAIN_SIMPLE_KERNEL = 1, 2
 PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
 # hit lists (include/mi355pt.h pt_list_hits)
 PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL, PT_HITS_BRUTE_FORCE, PT_HITS_SORTED = 1, 2, 4, 8
+# box-overlap queries (include/mi355pt.h pt_box_search)
+PT_BOX_STATS, PT_BOX_SIMPLE_KERNEL, PT_BOX_BRUTE_FORCE = 1, 2, 4
 # k-nearest queries (include/mi355pt.h pt_nearest_k)
 PT_NEAREST_STATS, PT_NEAREST_SIMPLE_KERNEL, PT_NEAREST_BRUTE_FORCE = 1, 2, 4
 PT_NEAREST_MAX_K = 64
@@ -94,6 +96,16 @@ class PtClosest(C.Structure):
     _fields_ = [("dist", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
 
 
+class PtBox(C.Structure):
+    """include/mi355pt.h PtBox (32 B); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per box (lo xyz, pad, hi xyz, pad)."""
+    _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
+
+
+class PtOverlap(C.Structure):
+    """include/mi355pt.h PtOverlap (16 B): prim, verts_inside (bit i: vertex i lies in the closed box; 7: the whole triangle), two zero words."""
+    _fields_ = [("prim", C.c_uint32), ("verts_inside", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class PtSurfel(C.Structure):
     """include/mi355pt.h PtSurfel (32 B, the shape of PtRay); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per surfel
     (p xyz, r_max, n xyz, 0)."""
@@ -139,6 +151,7 @@ EXPORTS = [
     "pt_count_hits", "pt_count_hits_host", "pt_count_hits_bvh4", "pt_contains", "pt_contains_host", "pt_contains_bvh4",
     "pt_signed_distance", "pt_signed_distance_host",
     "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
+    "pt_box_count", "pt_box_count_host", "pt_box_search", "pt_box_search_host", "pt_box_search_bvh4",
     "pt_list_hits", "pt_list_hits_host", "pt_list_hits_bvh4",
     "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
@@ -241,6 +254,23 @@ def _point_records(points, r_max):
     return pack_points(a, r_max)
 
 
+def pack_boxes(lo, hi):
+    """numpy: (n, 8) float32 PtBox records (lo xyz, 0, hi xyz, 0) in a 16-byte aligned buffer."""
+    a = np.asarray(lo, np.float32).reshape(-1, 3)
+    b = np.asarray(hi, np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError("lo and hi differ in shape: %s vs %s" % (a.shape, b.shape))
+    out = _aligned_zeros((a.shape[0], 8), np.float32)
+    out[:, 0:3] = a
+    out[:, 4:7] = b
+    return out
+
+
+def _box_records(lo, hi):
+    """(n, 3) lo + hi, or (n, 8) PtBox records (hi None) -> aligned (n, 8) float32 records."""
+    return pack_boxes(lo, hi) if hi is not None else _records8(lo, "box records")
+
+
 def pack_surfels(points, normals, r_max=None):
     """numpy: (n, 8) float32 PtSurfel records (p xyz, r_max, n xyz, 0) in a 16-byte aligned buffer; r_max None = +inf, a scalar or (n,)."""
     return pack_rays(points, normals, r_max)
@@ -284,6 +314,10 @@ def _count_flags(stats, simple, brute_force):
 
 def _radius_flags(stats, simple, brute_force):
     return (PT_RADIUS_STATS if stats else 0) | (PT_RADIUS_SIMPLE_KERNEL if simple else 0) | (PT_RADIUS_BRUTE_FORCE if brute_force else 0)
+
+
+def _box_flags(stats, simple, brute_force):
+    return (PT_BOX_STATS if stats else 0) | (PT_BOX_SIMPLE_KERNEL if simple else 0) | (PT_BOX_BRUTE_FORCE if brute_force else 0)
 
 
 def _hits_flags(stats, simple, brute_force, sort):
@@ -468,6 +502,35 @@ def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=Fals
     entries = _aligned_zeros((int(capacity), 4), np.uint32)
     call(entries, int(capacity))
     res = (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
+    return res + (st.as_dict(),) if stats else res
+
+
+def box_search_bvh4(tris, bvh4, lo, hi=None, capacity=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.box_search (no GPU): every triangle of `tris` that overlaps each box over the tree set_bvh4(bvh4) installs, with
+    the device's words and order.  bvh4 None needs brute_force=True.  lo, hi: (n, 3) corners, or lo alone as (n, 8) PtBox records.  Returns
+    (offsets, prim, verts_inside): offsets (n + 1,) uint64, the list of box i at offsets[i]:offsets[i + 1], in visit order (index order with
+    brute_force).  capacity None: every entry (the twin runs twice, once for the total); else the first min(offsets[-1], capacity) entries,
+    offsets complete.  The counters as a dict in fourth place with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    boxes = _box_records(lo, hi)
+    n = boxes.shape[0]
+    offsets = np.zeros(n + 1, np.uint64)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    flags = _box_flags(stats, simple, brute_force)
+
+    def call(entries, cap):
+        _check(lib.pt_box_search_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                      boxes.ctypes.data_as(C.POINTER(PtBox)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                                      entries.ctypes.data_as(C.POINTER(PtOverlap)) if cap else None, C.c_uint64(cap),
+                                      C.byref(st) if stats else None))
+    if capacity is None:
+        call(None, 0)
+        capacity = int(offsets[n])
+    entries = _aligned_zeros((int(capacity), 4), np.uint32)
+    call(entries, int(capacity))
+    held = entries[: min(int(offsets[n]), int(capacity))]
+    res = (offsets, held[:, 0].copy(), held[:, 1].copy())
     return res + (st.as_dict(),) if stats else res
 
 
@@ -1210,6 +1273,79 @@ class Context:
         stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_radius_search(self.h, C.c_void_p(points_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
                                       C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    # ---- box-overlap queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 21) ----
+    def _box_tensor(self, lo, hi, what):
+        _torch_route()
+        import torch
+        dev = lo.device
+        if dev.type != "cuda":
+            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
+        if hi is None:
+            if lo.dim() != 2 or lo.shape[1] != 8:
+                raise ValueError("%s: expected (n, 8) PtBox records or lo and hi of shape (n, 3), got shape %s" % (what, tuple(lo.shape)))
+            boxes = lo
+            if boxes.dtype != torch.float32 or not boxes.is_contiguous() or boxes.data_ptr() % 16:
+                boxes = boxes.to(torch.float32).contiguous().clone()
+            return boxes
+        a = lo.reshape(-1, 3).to(torch.float32); b = hi.reshape(-1, 3).to(device=dev, dtype=torch.float32)
+        if a.shape != b.shape:
+            raise ValueError("%s: lo and hi differ in shape: %s vs %s" % (what, tuple(a.shape), tuple(b.shape)))
+        z = torch.zeros((a.shape[0], 1), dtype=torch.float32, device=dev)
+        return torch.cat([a, z, b, z], dim=1).contiguous()
+
+    def box_count(self, lo, hi=None, stats=False, simple=False, brute_force=False):
+        """How many triangles overlap each axis-aligned box?  Returns the (n,) uint32 counts (0 for a box with a NaN, an infinity or lo > hi).
+
+        lo, hi: (n, 3) float32 corners, or lo alone as (n, 8) PtBox records (lo xyz, pad, hi xyz, pad).  numpy arrays take the host route
+        (staged, returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host
+        synchronisation; the result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0
+        means that triangles were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
+        flags = _box_flags(stats, simple, brute_force)
+        if _is_torch(lo):
+            import torch
+            boxes = self._box_tensor(lo, hi, "box_count")
+            return self._torch_launch(boxes, (), lambda r, n, o: self.box_count_device(r, n, o, flags)).view(torch.uint32)
+        boxes = _box_records(lo, hi)
+        n = boxes.shape[0]
+        counts = np.zeros(n, np.uint32)
+        self._ck(lib.pt_box_count_host(self.h, boxes.ctypes.data_as(C.POINTER(PtBox)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
+        return counts
+
+    def box_count_device(self, boxes_ptr, n, counts_ptr, flags=0):
+        """Raw device route: n PtBox records at boxes_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
+        context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_box_count(self.h, C.c_void_p(boxes_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
+
+    def box_search(self, lo, hi=None, capacity=None, stats=False, simple=False, brute_force=False):
+        """Which triangles overlap each axis-aligned box -- all of them?  Returns (offsets, prim, verts_inside): the list of box i is entries
+        offsets[i]:offsets[i + 1], in the walk's visit order (index order with brute_force); bit k of verts_inside says that vertex k of
+        triangle prim lies in the closed box (7: the whole triangle is inside).  offsets has n + 1 elements and is always complete:
+        offsets[-1] is the total, and offsets[-1] > capacity says that only the first `capacity` entries were written.  Touching counts.
+
+        lo, hi: as box_count.  numpy arrays take the host route (staged, returns when done): offsets is uint64 and the entry arrays hold
+        min(offsets[-1], capacity) elements; capacity=None starts with room for 16 entries per box and runs the query again when
+        offsets[-1] says that this was too little.
+        torch tensors on the context's device stay there, on the context's stream: offsets is int64, prim and verts_inside torch.uint32.
+        With `capacity` given the torch route waits for nothing on the host and the entry tensors hold `capacity` elements, of which those
+        from offsets[-1] on are not written.  With capacity=None it reads offsets[-1] once to size the entries: that is the one host wait
+        of this call (the boxes are then counted a second time); pass a capacity to avoid it.
+        stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack cap,
+        which large boxes over deep trees reach as large radii do; brute_force lists every overlapping triangle regardless."""
+        flags = _box_flags(stats, simple, brute_force)
+        if _is_torch(lo):
+            import torch
+            res = self._list_torch(self._box_tensor(lo, hi, "box_search"), self.box_search_device, flags, capacity)
+            return res[0], res[1].view(torch.uint32), res[2].view(torch.uint32)         # the four entry columns: prim, verts_inside, 0, 0
+        res = self._list_host(_box_records(lo, hi), PtBox, lib.pt_box_search_host, PtOverlap, flags, capacity, 16)
+        return res[0], res[1].view(np.uint32), res[2]
+
+    def box_search_device(self, boxes_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
+        """Raw device route: n PtBox records at boxes_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
+        `capacity` PtOverlap records at entries_ptr (16-byte aligned; 0 with capacity 0: offsets only).  Three launches on the context's
+        stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_box_search(self.h, C.c_void_p(boxes_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
+                                   C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
 
     # ---- hit lists (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 20) ----
     def list_hits(self, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):

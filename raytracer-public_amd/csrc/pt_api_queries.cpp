@@ -1,5 +1,5 @@
 // pt_api_queries.cpp -- the batched queries over the context's tree (include/mi355pt.h): closest hit / any hit, closest point,
-// occlusion, crossing counts, containment, signed distance, radius count / search, hit lists and k-nearest, with the host twins
+// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, hit lists and k-nearest, with the host twins
 // (*_bvh4) next to them.
 #include "pt_context.h"
 
@@ -448,8 +448,8 @@ int radius_fill_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32
     return radius_walk_on_stream(ctx, points, n, flags, nullptr, offsets, entries, capacity);
 }
 
-// A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, hit lists over rays.  The
-// counts, the scan's scratch and the staging buffers (d_rd_*) are shared: both queries use them between launches of one call on the
+// A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, box search over boxes, hit
+// lists over rays.  The counts, the scan's scratch and the staging buffers (d_rd_*) are shared: the queries use them between launches of one call on the
 // context's stream, which orders them, and the host forms wait for the stream before they return.
 struct ListQuery {
     size_t in_bytes;             // one input record
@@ -540,6 +540,94 @@ int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* 
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::radius_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, offsets,
                            reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_RADIUS_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
+// ---- box-overlap queries (include/mi355pt.h; pt_overlap.hip) --------------------------------------------------------------------
+
+static_assert(sizeof(PtBox) == 32 && sizeof(PtOverlap) == sizeof(uint4), "PtBox / PtOverlap are read and written as 2 x 16 B and 16 B records");
+static_assert(PT_BOX_STATS == PT_RADIUS_STATS && PT_BOX_SIMPLE_KERNEL == PT_RADIUS_SIMPLE_KERNEL && PT_BOX_BRUTE_FORCE == PT_RADIUS_BRUTE_FORCE,
+              "the PT_BOX_* flags take the values of the PT_RADIUS_* flags");
+
+namespace {
+constexpr uint32_t kBoxFlags = PT_BOX_STATS | PT_BOX_SIMPLE_KERNEL | PT_BOX_BRUTE_FORCE;
+
+// flags, batch size and the boxes; the other pointers are checked by the callers, and the scene behind them
+int check_box(PtContext* ctx, const char* fn, const void* boxes, uint64_t n, uint32_t flags) {
+    if (int rc = check_flags(ctx, fn, flags, kBoxFlags)) return rc;
+    if (int rc = check_n(ctx, fn, n, "boxes")) return rc;
+    return check_records(ctx, fn, "boxes", {boxes});
+}
+
+// One walk: the count walk into `counts` (offsets = nullptr), or the fill walk from `offsets` into `entries`.  PT_BOX_STATS counts over
+// the count walk only; its fill walk is the one-box-per-thread kernel.
+int box_walk_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, void* counts, const unsigned long long* offsets,
+                       void* entries, uint64_t capacity) {
+    const bool fill = offsets != nullptr, brute = (flags & PT_BOX_BRUTE_FORCE) != 0;
+    const bool stats = (flags & PT_BOX_STATS) != 0 && !fill, simple = (flags & (PT_BOX_SIMPLE_KERNEL | PT_BOX_STATS)) != 0;
+    Walk W;
+    if (int rc = begin_walk(ctx, n, PT_BX_WAVES_PER_SIMD, PT_BX_SHORT_STACK, stats, !simple && !brute, W)) return rc;
+    if (W.launch) PT_HIP(ctx, ptk::launch_box(W.A, boxes, n, counts, offsets, entries, capacity, simple, stats, brute,
+                                              ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, W.grid, ctx->stream));
+    return end_walk(ctx, W);
+}
+int box_count_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, void* counts) {
+    return box_walk_on_stream(ctx, boxes, n, flags, counts, nullptr, nullptr, 0);
+}
+int box_fill_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* entries, uint64_t capacity) {
+    return box_walk_on_stream(ctx, boxes, n, flags, nullptr, offsets, entries, capacity);
+}
+constexpr ListQuery kBoxList = {sizeof(PtBox), box_count_on_stream, box_fill_on_stream};
+} // namespace
+
+int pt_box_count(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags, void* counts_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_box(ctx, "pt_box_count", boxes_device, n, flags)) return rc;
+    if (int rc = check_counts(ctx, "pt_box_count", counts_device)) return rc;
+    if (int rc = check_scene(ctx, "pt_box_count")) return rc;
+    return box_count_on_stream(ctx, boxes_device, uint32_t(n), flags, counts_device);
+}
+
+int pt_box_count_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags, uint32_t* counts) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_box(ctx, "pt_box_count_host", boxes, n, flags)) return rc;
+    if (int rc = check_counts(ctx, "pt_box_count_host", counts)) return rc;
+    if (int rc = check_scene(ctx, "pt_box_count_host")) return rc;
+    return staged(ctx, n, boxes, sizeof(PtBox), ctx->d_rd_counts, counts, sizeof(uint32_t),
+                  [&](const void* d_in, void* d_out) { return box_count_on_stream(ctx, d_in, uint32_t(n), flags, d_out); });
+}
+
+// three launches, no host wait (list_device)
+int pt_box_search(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_box(ctx, "pt_box_search", boxes_device, n, flags)) return rc;
+    if (int rc = check_list(ctx, "pt_box_search", offsets_device, entries_device, capacity, "entries")) return rc;
+    if (int rc = check_scene(ctx, "pt_box_search")) return rc;
+    return list_device(ctx, kBoxList, boxes_device, n, flags, offsets_device, entries_device, capacity);
+}
+
+int pt_box_search_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_box(ctx, "pt_box_search_host", boxes, n, flags)) return rc;
+    if (int rc = check_list(ctx, "pt_box_search_host", offsets, entries, capacity, "entries")) return rc;
+    if (int rc = check_scene(ctx, "pt_box_search_host")) return rc;
+    return list_host(ctx, kBoxList, boxes, n, flags, offsets, entries, capacity);
+}
+
+int pt_box_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtBox* boxes, uint64_t n,
+                       uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity, PtStats* stats) {
+    if (flags & ~kBoxFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: unknown flags");
+    const bool brute = (flags & PT_BOX_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && !boxes) || !offsets || (capacity && !entries) || (!bvh4 && !brute))
+        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: null pointer");
+    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: offsets must be 8-byte aligned");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: more than 2^32 - 1 boxes");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::box_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(boxes), n, offsets,
+                        reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_BOX_STATS) && stats ? counters : nullptr, err))
         return fail(nullptr, PT_ERR_BAD_BVH, err);
     if (stats) stats_from(stats, counters);
     return PT_OK;

@@ -5,6 +5,7 @@
 #include "pt_host.h"
 #include "pt_expose.h"
 #include "pt_closest.h"
+#include "pt_overlap.h"
 
 #include <cmath>
 #include <cstring>
@@ -622,15 +623,14 @@ inline float box_bound2_h(const float hi[3], const float lo[3], const uint32_t w
 
 // The walk of both point queries: `best2` is what child boxes and stacked entries are compared with, and `leaf(tri)` is called for every
 // reached leaf with tri < num_tris, in visit order -- the closest-point query lowers best2 there, the radius query leaves it alone.
-template <class Leaf>
-void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounters& cnt, Leaf leaf) {
+// `key(box words)` is what a child box is ordered and stacked by: bound2 of a point, or 0 / +inf of a box query (box_search).
+template <class Key, class Leaf>
+void walk_keys_h(const PointWalk& W, Key key, const float& best2, WalkCounters& cnt, Leaf leaf) {
     const WideBvh& wb = *W.wide;
     if (wb.root_ref == kInvalid || W.num_tris == 0u) return;
     cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
     if (wb.root_degenerate) return;
-    const float hi[3] = {p[0] + ptcp::kSlack, p[1] + ptcp::kSlack, p[2] + ptcp::kSlack};
-    const float lo[3] = {p[0] - ptcp::kSlack, p[1] - ptcp::kSlack, p[2] - ptcp::kSlack};
-    if (!(box_bound2_h(hi, lo, wb.root_box) < best2)) return;
+    if (!(key(wb.root_box) < best2)) return;
     struct Entry { uint32_t ref; float b2; } stk[kStackCap];
     uint32_t cur = wb.root_ref;
     int sp = 0;
@@ -647,7 +647,7 @@ void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounte
             const WideNode& nd = wb.nodes[(cur - W.node_base16) >> 2];
             float t[4]; bool h[4]; uint32_t r[4];
             for (int k = 0; k < 4; ++k) {
-                r[k] = nd.child[k].ref; t[k] = box_bound2_h(hi, lo, nd.child[k].box); h[k] = t[k] < best2;
+                r[k] = nd.child[k].ref; t[k] = key(nd.child[k].box); h[k] = t[k] < best2;
                 cnt.nodes += (r[k] != kInvalid);
             }
             int nslot = -1, fslot = -1;
@@ -676,6 +676,12 @@ void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounte
             if (!found) break;
         }
     }
+}
+template <class Leaf>
+void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounters& cnt, Leaf leaf) {
+    const float hi[3] = {p[0] + ptcp::kSlack, p[1] + ptcp::kSlack, p[2] + ptcp::kSlack};
+    const float lo[3] = {p[0] - ptcp::kSlack, p[1] - ptcp::kSlack, p[2] - ptcp::kSlack};
+    walk_keys_h(W, [&](const uint32_t* w) { return box_bound2_h(hi, lo, w); }, best2, cnt, leaf);
 }
 void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& best_tri, WalkCounters& cnt) {
     best_tri = kInvalid;
@@ -794,6 +800,82 @@ bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
                 if (g >= capacity) break;                       // the offsets only grow
                 query(points + i * 4, unused[w], [&](float d2, uint32_t tri, float u, float v) {
                     if (g < capacity) { uint32_t* o = entries + g * 4; o[0] = bits_of(std::sqrt(d2)); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v); }
+                    ++g;
+                });
+            }
+        });
+    }
+    if (counters) {
+        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Box-overlap queries (host twin of pt_overlap.hip): the walk with every key equal -- 0 for a child whose box meets the query box moved out
+// by the slack, +inf for any other, against a bound of 1 -- every accepted leaf counted and, in a second walk of the same steps, listed at
+// offsets[i] + k.  The arithmetic is pt_overlap.h, the text the kernels compile.
+// ------------------------------------------------------------------------------------
+bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* boxes, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
+    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+    WideBvh wide;
+    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+    std::vector<TriRecord> rec(num_tris);
+    build_tri_records(tris, num_tris, rec.data());
+    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+    std::vector<WalkCounters> per(workers), unused(workers);
+    // one box: the walk (or every triangle in index order), each accepted leaf handed to `accept`
+    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
+        if (!ptov::box_walked(q[0], q[1], q[2], q[4], q[5], q[6])) return;
+        const ptov::Box b = ptov::make_box(q[0], q[1], q[2], q[4], q[5], q[6]);
+        auto leaf = [&](uint32_t t) {
+            const TriRecord& r = rec[t];
+            uint32_t in;
+            if (ptov::tri_overlaps(b, r.axis[0][0], r.axis[1][0], r.axis[2][0], r.axis[0][1], r.axis[1][1], r.axis[2][1],
+                                   r.axis[0][2], r.axis[1][2], r.axis[2][2], in)) accept(t, in);
+        };
+        if (bvh4) {
+            const float bound = 1.0f;
+            walk_keys_h(W, [&](const uint32_t* w) {
+                const bool meets = ptov::node_overlaps(b, half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu),
+                                                       half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16));
+                return meets ? 0.0f : std::numeric_limits<float>::infinity();
+            }, bound, cnt, leaf);
+            return;
+        }
+        for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+        cnt.tris += num_tris;
+    };
+    auto parallel = [&](auto run) {
+        if (workers == 1) { run(uint64_t(0)); return; }
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
+        for (std::thread& t : pool) t.join();
+    };
+    // the count walk: offsets[i + 1] holds the count of box i until the scan
+    offsets[0] = 0;
+    parallel([&](uint64_t w) {
+        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+            uint64_t count = 0;
+            query(boxes + i * 8, per[w], [&](uint32_t, uint32_t) { ++count; });
+            offsets[i + 1] = count;
+        }
+    });
+    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
+    // the fill walk: the same steps, entry k of box i at offsets[i] + k where that is below the capacity
+    if (entries && capacity) {
+        parallel([&](uint64_t w) {
+            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+                uint64_t g = offsets[i];
+                if (g >= capacity) break;                       // the offsets only grow
+                query(boxes + i * 8, unused[w], [&](uint32_t tri, uint32_t in) {
+                    if (g < capacity) { uint32_t* o = entries + g * 4; o[0] = tri; o[1] = in; o[2] = 0u; o[3] = 0u; }
                     ++g;
                 });
             }

@@ -110,6 +110,15 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
 bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                    uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
 
+// ---- box-overlap queries (pt_box_count, pt_box_search; host twin of pt_overlap.hip, word for word) -----------------------------------
+// boxes: n x (lo.xyz, pad, hi.xyz, pad); offsets: n + 1 words, the exclusive prefix sums of the counts (offsets[n] = the total); entries:
+// (prim, verts_inside, 0, 0) per accepted leaf, the list of box i in visit order from offsets[i] on, written only below `capacity` (entries =
+// nullptr with capacity 0: offsets only).  bvh4 = nullptr: every triangle in index order; else closest_points' walk with every key equal
+// (a child is entered iff pt_overlap.h::node_overlaps) and the triangle test of pt_overlap.h.  counters (optional): boxes, nodes examined,
+// triangles tested, stack drops, max stack of the count walk -- as the device's PT_BOX_STATS counts them.
+bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* boxes, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
+
 // ---- k-nearest queries (pt_nearest_k; host twin of pt_knn.hip, bit for bit) -----------------------------------------------------------
 // points: n x (x, y, z, r_max); out: n * k records of four words (dist bits, prim, u bits, v bits), row i at out + i * k * 4: the at most k
 // triangles nearest to point i within r_max in ascending order of distance, equal distances in visit order (index order without a tree),

@@ -85,6 +85,17 @@
 #ifndef PT_RD_FILL
 #define PT_RD_FILL 8                // idle lanes of a wavefront at which they take the next points of its chunk
 #endif
+// box-overlap queries (pt_overlap.hip): the radius queries' values taken over.  tools/box_bench.py ran with them (profiles/box_ab.json); no
+// other value has been tried, so as choices they are unmeasured.  box_kernel<FILL> compiles to 78 / 79 VGPRs: 80 is the most that holds 6 waves per SIMD
+#ifndef PT_BX_SHORT_STACK
+#define PT_BX_SHORT_STACK 12        // LDS stack entries per lane of box_kernel<FILL>; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_BX_WAVES_PER_SIMD
+#define PT_BX_WAVES_PER_SIMD 6      // wavefronts of box_kernel<FILL> per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_BX_FILL
+#define PT_BX_FILL 8                // idle lanes of a wavefront at which they take the next boxes of its chunk
+#endif
 // hit lists (pt_hitlist.hip): the crossing counts' values taken over for the fill walk, unmeasured for it until tools/hitlist_bench.py has run
 #ifndef PT_HL_SHORT_STACK
 #define PT_HL_SHORT_STACK 12        // LDS stack entries per lane of hit_fill_kernel; deeper entries spill to the context's spill area
@@ -318,6 +329,14 @@ hipError_t launch_radius(const RenderArgs& A, const void* points, uint32_t n, vo
 // item n read as 0); temp: at least radius_scan_temp_bytes(n) bytes
 size_t radius_scan_temp_bytes(uint32_t n);
 hipError_t launch_radius_scan(const void* counts, uint32_t n, unsigned long long* offsets, void* temp, size_t temp_bytes, hipStream_t stream);
+// ---- box-overlap queries (pt_overlap.hip): every triangle that overlaps an axis-aligned box ------------------------------------
+// boxes: PtBox[n] (two float4 each, 16-byte aligned).  One walk per launch, launch_radius' two forms: offsets = nullptr counts the accepted
+// leaves of box i into counts[i]; offsets != nullptr stores entry k of box i (a PtOverlap record, in visit order) at
+// entries[offsets[i] + k] where that index is below `capacity`.  brute, simple, stats, grid, queue and spill as launch_radius, with
+// PT_BX_WAVES_PER_SIMD and PT_BX_SHORT_STACK.  The scan between the two is launch_radius_scan.
+hipError_t launch_box(const RenderArgs& A, const void* boxes, uint32_t n, void* counts, const unsigned long long* offsets, void* entries,
+                      unsigned long long capacity, bool simple, bool stats, bool brute,
+                      unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- hit lists (pt_hitlist.hip): every crossing along a ray, with t, triangle and u, v -------------------------------------------
 // The fill walk behind launch_count_hits and launch_radius_scan: rays: PtRay[n]; entry k of ray i (a PtHit record, in visit order) goes to
 // entries[offsets[i] + k] where that index is below `capacity`.  brute: every triangle in index order; simple: one ray per thread; else the

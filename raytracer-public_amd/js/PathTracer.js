@@ -232,6 +232,28 @@ class PathTracer {
     return { count: s.prim.length, dist: s.dist, prim: s.prim, u: s.u, v: s.v };
   }
 
+  // ---- box-overlap queries: an extension beyond the reference (include/mi355pt.h pt_box_search, DESIGN.md section 21) ----
+  // boxes: Float32Array, 8 floats per box (lo xyz, 0, hi xyz, 0).  boxSearch resolves to { offsets, prim, vertsInside }: the triangles that
+  // overlap box i (touching counts) are entries offsets[i] .. offsets[i + 1] - 1 (offsets: Float64Array of n + 1 exact integers), in the
+  // order the walk meets them (triangle order with options.bruteForce); bit k of vertsInside says that vertex k lies in the closed box
+  // (7: the whole triangle is inside).  boxCount resolves to a Uint32Array of the list lengths alone.  A box with a NaN, an infinity or
+  // lo > hi on an axis has an empty list.  options.bruteForce: every triangle, no tree; options.simple: the one-box-per-thread kernels.
+  // A box that covers much of a deep tree can lose triangles at the 64-entry stack cap (the header says when); bruteForce never does.
+  // Triangles only.  On a group: member 0, which holds the whole scene.
+  async boxSearch(boxes, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
+    return this.group ? native().groupBoxSearch(this.group, boxes, flags) : native().boxSearch(this.device, boxes, flags);
+  }
+  async boxCount(boxes, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
+    return this.group ? native().groupBoxCount(this.group, boxes, flags) : native().boxCount(this.device, boxes, flags);
+  }
+  // The triangles that overlap the box lo = [x, y, z] .. hi = [x, y, z]: resolves to { count, prim, vertsInside }.
+  async overlapping(lo, hi, options) {
+    const s = await this.boxSearch(Float32Array.of(lo[0], lo[1], lo[2], 0, hi[0], hi[1], hi[2], 0), options);
+    return { count: s.prim.length, prim: s.prim, vertsInside: s.vertsInside };
+  }
+
   // ---- hit lists: an extension beyond the reference (include/mi355pt.h pt_list_hits, DESIGN.md section 20) ----
   // rays: Float32Array, 8 floats per ray (origin xyz, tMax, direction xyz, 0).  Resolves to { offsets, t, prim, u, v }: the triangles ray i
   // crosses before tMax -- the ones countHits counts -- are entries offsets[i] .. offsets[i + 1] - 1 (offsets: Float64Array of n + 1 exact

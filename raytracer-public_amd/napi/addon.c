@@ -503,6 +503,70 @@ static napi_value fn_radius_search(napi_env env, napi_callback_info info) {     
     return radius_search_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- box-overlap queries (an extension beyond the reference; include/mi355pt.h pt_box_count_host, pt_box_search_host) ----------------- */
+
+static PtBox* box_records(napi_env env, napi_value boxes_v, const char* what, size_t* n) {
+    void* d; size_t len; if (!get_typed(env, boxes_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, what); return NULL; }
+    *n = len / 8;
+    PtBox* boxes = (PtBox*)aligned_alloc(16, (*n ? *n : 1) * sizeof(PtBox));
+    if (!boxes) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (*n) memcpy(boxes, d, *n * sizeof(PtBox));
+    return boxes;
+}
+/* boxes: Float32Array of 8 floats per box (lo xyz, pad, hi xyz, pad) -> Uint32Array: the triangles that overlap each box; flags: PT_BOX_* */
+static napi_value box_count_on(napi_env env, PtContext* ctx, napi_value boxes_v, napi_value flags_v) {
+    size_t n; PtBox* boxes = box_records(env, boxes_v, "boxCount: 8 floats per box", &n); if (!boxes) return NULL;
+    const uint32_t flags = get_u32(env, flags_v);
+    void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
+    if (!counts) { free(boxes); return NULL; }
+    uint32_t none = 0;
+    int rc = pt_box_count_host(ctx, boxes, n, flags, n ? (uint32_t*)pc : &none);
+    free(boxes);
+    if (rc != 0) return throw_pt(env, ctx, rc, "pt_box_count_host");
+    return counts;
+}
+/* boxes as above -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), prim, vertsInside }: every entry.  The first
+ * call has room for 16 entries per box; when offsets[n] says that this was too little, the query runs again with room for all. */
+static napi_value box_search_on(napi_env env, PtContext* ctx, napi_value boxes_v, napi_value flags_v) {
+    size_t n; PtBox* boxes = box_records(env, boxes_v, "boxSearch: 8 floats per box", &n); if (!boxes) return NULL;
+    const uint32_t flags = get_u32(env, flags_v);
+    uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
+    uint64_t cap = 16 * (uint64_t)n + 64;
+    PtOverlap* res = (PtOverlap*)aligned_alloc(16, (size_t)cap * sizeof(PtOverlap));
+    if (!off || !res) { free(boxes); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = pt_box_search_host(ctx, boxes, n, flags, off, res, cap);
+    if (rc == 0 && off[n] > cap) {
+        cap = off[n];
+        free(res);
+        res = (PtOverlap*)aligned_alloc(16, (size_t)cap * sizeof(PtOverlap));
+        if (!res) { free(boxes); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        rc = pt_box_search_host(ctx, boxes, n, flags, off, res, cap);
+    }
+    free(boxes);
+    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_box_search_host"); }
+    const size_t m = (size_t)off[n];
+    napi_value o, offs, prim, in; void *po, *pp, *pi;
+    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) ||
+        !(in = make_typed(env, napi_uint32_array, 4, m, &pi))) { free(off); free(res); return NULL; }
+    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
+    for (size_t i = 0; i < m; ++i) { ((uint32_t*)pp)[i] = res[i].prim; ((uint32_t*)pi)[i] = res[i].verts_inside; }
+    free(off); free(res);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "prim", prim); napi_set_named_property(env, o, "vertsInside", in);
+    return o;
+}
+static napi_value fn_box_count(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array boxes, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return box_count_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_box_search(napi_env env, napi_callback_info info) {          /* (ctx, Float32Array boxes, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return box_search_on(env, ctx, argv[1], argv[2]);
+}
+
 /* ---- hit lists (an extension beyond the reference; include/mi355pt.h pt_list_hits_host) ------------------------------------------------ */
 
 /* rays: Float32Array of 8 floats per ray; flags: PT_HITS_* -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), t, prim,
@@ -959,6 +1023,18 @@ static napi_value fn_group_radius_search(napi_env env, napi_callback_info info) 
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return radius_search_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_box_count(napi_env env, napi_callback_info info) {      /* (group, boxes, flags): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return box_count_on(env, ctx, argv[1], argv[2]);
+}
+static napi_value fn_group_box_search(napi_env env, napi_callback_info info) {     /* (group, boxes, flags): on member 0 */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return box_search_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_list_hits(napi_env env, napi_callback_info info) {      /* (group, rays, flags): on member 0 */
     napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -1033,6 +1109,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
         {"nearestK", fn_nearest_k}, {"groupNearestK", fn_group_nearest_k},
         {"listHits", fn_list_hits}, {"groupListHits", fn_group_list_hits},
+        {"boxCount", fn_box_count}, {"groupBoxCount", fn_group_box_count}, {"boxSearch", fn_box_search}, {"groupBoxSearch", fn_group_box_search},
         {"radiusCount", fn_radius_count}, {"groupRadiusCount", fn_group_radius_count}, {"radiusSearch", fn_radius_search}, {"groupRadiusSearch", fn_group_radius_search},
         {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
