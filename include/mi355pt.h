@@ -849,6 +849,10 @@ PT_API int pt_debug_set_tune(PtContext* ctx, const char* name, uint32_t value);
  * the queue's batch transposition, logical items, items per claim, items per XCD range (0: one queue), shade / fill thresholds, paths at which a
  * wavefront goes on with one ray per quad, shadow-ray forking, frame slots in rotation, frame slots set up.  (tests/test_launch_plan.py) */
 PT_API int pt_debug_launch_plan(uint32_t num_cus, uint32_t frames, uint32_t tile_count, uint32_t launches_in_flight, uint32_t traced_batches, uint32_t batch_size, uint32_t out[12]);
+/* The same pure function under overridden knobs: names[i] (pt_debug_set_tune's names) set to values[i], i < n, every other knob at its default -- the plan a
+ * context with those overrides would be given.  No GPU, no context, and the environment is not read.  (tests/test_queue_model.py) */
+PT_API int pt_debug_launch_plan_tuned(uint32_t num_cus, uint32_t frames, uint32_t tile_count, uint32_t launches_in_flight, uint32_t traced_batches, uint32_t batch_size,
+                                      const char* const* names, const uint32_t* values, uint32_t n, uint32_t out[12]);
 /* Raw counter block (24 words) of the last PT_FLAG_STATS launch: PtStats order in [0..6], then the instrumented megakernel's own
  * diagnostics (stack pushes by depth, longest path / ray in traversal steps, re-seated wavefronts, ...). */
 PT_API int pt_debug_counters(PtContext* ctx, unsigned long long* dst24);

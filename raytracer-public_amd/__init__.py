@@ -160,7 +160,7 @@ EXPORTS = [
     "pt_group_build_bvh_accel",
     "pt_group_set_bvh2", "pt_group_set_bvh4", "pt_group_set_batch", "pt_group_render", "pt_group_flush", "pt_group_synchronize", "pt_group_read_radiance",
     "pt_group_read_rgba8", "pt_group_read_tonemapped",
-    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_traced_tiles", "pt_debug_exposure", "pt_exposure_flags_host",     # diagnostics section of the header
+    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_launch_plan_tuned", "pt_debug_traced_tiles", "pt_debug_exposure", "pt_exposure_flags_host",     # diagnostics section of the header
 ]
 
 
@@ -629,6 +629,21 @@ def procedural_scene(kind, num_tris, seed=20260109):
     out = np.zeros(num_tris * 9, np.float32)
     _check(lib.pt_scene_procedural(C.c_uint32(kind), C.c_uint32(seed), C.c_uint32(num_tris), _p(out, C.c_float)))
     return out
+
+
+PLAN_FIELDS = ("grid", "perm_rows", "perm_cols", "total_items", "chunk_items", "xcd_span", "shade_threshold", "fill_threshold", "quad_live", "fork_shadow", "slots", "setup_slots")
+
+
+def debug_launch_plan_tuned(num_cus, frames, tile_count=1, launches_in_flight=0, traced_batches=1, batch_size=None, tune=None):
+    """Diagnostics: the megakernel's launch plan (a dict over PLAN_FIELDS) for a launch shape under the knob overrides of `tune` ({name: value}), as a
+    pure function: no GPU, no context.  Raises PtError where the host would refuse the launch."""
+    tune = dict(tune or {})
+    names = (C.c_char_p * max(len(tune), 1))(*[k.encode() for k in tune])
+    values = (C.c_uint32 * max(len(tune), 1))(*[int(v) & 0xFFFFFFFF for v in tune.values()])
+    out = (C.c_uint32 * 12)()
+    _check(lib.pt_debug_launch_plan_tuned(C.c_uint32(num_cus), C.c_uint32(frames), C.c_uint32(tile_count), C.c_uint32(launches_in_flight), C.c_uint32(traced_batches),
+                                          C.c_uint32(batch_size or frames), names, values, C.c_uint32(len(tune)), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
 
 def tile_layout(width, height, rank, count):

@@ -259,7 +259,8 @@ LaunchPlan plan_launch(const PtTune& tune, const PlanInput& in) {
         // grid: 2.9 ms, 3.8 ms on a quarter of it).  tools/ab/pipe_sweep.sh
         uint32_t div = PtTune::pick(tune.grid_div, count >= 8u ? 4u : (count >= 2u ? 2u : std::min(4u, 1u + in.launches_in_flight)));
         if (nf > 1u) div = div > nf ? div / nf : 1u;
-        if (div > 1u) P.grid = (P.grid + div - 1u) / div;
+        if (div > 1u) P.grid = uint32_t((uint64_t(P.grid) + div - 1u) / div);      // (in 64 bits: grid + div wrapped for a GRIDDIV near 2^32 and left a grid of 0)
+        if (P.grid < 1u) P.grid = 1u;
     }
     const uint32_t grid_lanes = P.grid * ptk::megakernel_block();
     // Rows of the batch transposition (the order in which the queue walks the (frame, tile, sample) batches).  Rows that are a multiple or a divisor
@@ -287,6 +288,9 @@ LaunchPlan plan_launch(const PtTune& tune, const PlanInput& in) {
         // XCD): 32-frame launches +2..3.5 %, HBM fetch traffic halved (L2 hit rate 85 -> 91 %); no gain at 8 frames of work, a loss for a single frame
         const uint32_t per = (P.total_items + 7u) / 8u;
         P.xcd_span = PtTune::pick(tune.xcd, work8 >= 64u ? 1u : 0u) ? ((per + P.chunk_items - 1u) / P.chunk_items) * P.chunk_items : 0u;
+        // the kernel computes a range's bounds (qi * span, that + span) in 32 bits.  A CHUNK override of 2^29 or more (the guard above lets it pass on a grid of
+        // one or two wavefronts) makes a span whose eighth range ends past 2^32: a range that wrapped to item 0 would hand the items out again.  One queue then
+        if (uint64_t(P.xcd_span) * 8ull > 0xFFFFFFFFull) P.xcd_span = 0u;
     }
     P.shade_threshold = PtTune::pick(tune.shade, PT_SHADE_THRESHOLD); P.fill_threshold = PtTune::pick(tune.fill, PT_FILL_THRESHOLD);
     P.quad_live = std::min(16u, PtTune::pick(tune.quad, PT_QUAD_LIVE));     // 16 quads per wavefront
@@ -1447,6 +1451,28 @@ int pt_debug_launch_plan(uint32_t num_cus, uint32_t frames, uint32_t tile_count,
     in.num_cus = num_cus; in.frames = frames; in.tile_count = tile_count ? tile_count : 1u; in.sharded = in.tile_count > 1u; in.stats = false;
     in.launches_in_flight = launches_in_flight; in.traced_batches = traced_batches; in.batch_size = batch_size ? batch_size : 1u;
     const LaunchPlan P = plan_launch(PtTune(), in);
+    if (P.error) return fail(nullptr, PT_ERR_INVALID_ARG, P.error);
+    const uint32_t v[12] = {P.grid, P.perm_rows, P.perm_cols, P.total_items, P.chunk_items, P.xcd_span, P.shade_threshold, P.fill_threshold, P.quad_live, P.fork_shadow,
+                            uint32_t(P.slots), uint32_t(P.setup_slots)};
+    std::memcpy(out, v, sizeof v);
+    return PT_OK;
+}
+
+/* diagnostics: the same pure function under overridden knobs -- what a context whose knobs names[i] were set to values[i] (pt_debug_set_tune's names;
+ * the others at their defaults) would be given for that launch.  No GPU, no context, no environment. */
+int pt_debug_launch_plan_tuned(uint32_t num_cus, uint32_t frames, uint32_t tile_count, uint32_t launches_in_flight, uint32_t traced_batches, uint32_t batch_size,
+                               const char* const* names, const uint32_t* values, uint32_t n, uint32_t out[12]) {
+    if (!out || frames == 0u || (n != 0u && (!names || !values))) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_debug_launch_plan_tuned: bad arguments");
+    PtTune tune;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t* knob = names[i] ? tune.find(names[i]) : nullptr;
+        if (!knob) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_debug_launch_plan_tuned: unknown knob");
+        *knob = values[i];
+    }
+    PlanInput in; std::memset(&in, 0, sizeof(in));
+    in.num_cus = num_cus; in.frames = frames; in.tile_count = tile_count ? tile_count : 1u; in.sharded = in.tile_count > 1u; in.stats = false;
+    in.launches_in_flight = launches_in_flight; in.traced_batches = traced_batches; in.batch_size = batch_size ? batch_size : 1u;
+    const LaunchPlan P = plan_launch(tune, in);
     if (P.error) return fail(nullptr, PT_ERR_INVALID_ARG, P.error);
     const uint32_t v[12] = {P.grid, P.perm_rows, P.perm_cols, P.total_items, P.chunk_items, P.xcd_span, P.shade_threshold, P.fill_threshold, P.quad_live, P.fork_shadow,
                             uint32_t(P.slots), uint32_t(P.setup_slots)};
