@@ -887,6 +887,15 @@ PT_API int pt_debug_exposure(PtContext* ctx, const PtRenderParams* params, uint3
 /* The same flags on the CPU from the triangles alone (every pair tested, the arithmetic of the device route; no GPU, no context) for ray
  * origins within s_max of every scene point and hit coordinates up to d_max; mask: 2 * ceil(num_tris / 64) words. */
 PT_API int pt_exposure_flags_host(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask_out, uint32_t words, uint32_t* flagged);
+/* Two tiers.  The mask above is the first tier's: it covers hits at |n . d| >= 0.1002.  The device computes a second mask in the same pass,
+ * for hits at |n . d| >= 0.3008 only: steeper hits need a third of the margin inside the triangle's plane, so the second tier flags a superset
+ * of the first.  A launch skips the shadow ray of a hit whose triangle the second tier flags when the hit passes the gate of the best tier
+ * that flags the triangle.  Knob "EXPOSE" + 4 (5, 6): launches use the first tier only (A/Bs, tests).
+ * pt_debug_exposure_tier2 reports the second tier of the mask there is: info_out[2] = {flagged triangles, walks that ran out of their budget
+ * after the first tier was settled as blocked}; mask_out (optional) as above.  pt_exposure_flags_host_gate: the CPU twin for any gate (the f64
+ * bound on |n . d| / |d|: 0.0999 for the first tier, what pt_exposure_flags_host uses, and 0.2999 for the second). */
+PT_API int pt_debug_exposure_tier2(PtContext* ctx, uint32_t info_out[2], uint32_t* mask_out, uint32_t words);
+PT_API int pt_exposure_flags_host_gate(const float* tris, uint32_t num_tris, double s_max, double d_max, double gate, uint32_t* mask_out, uint32_t words, uint32_t* flagged);
 
 #ifdef __cplusplus
 }

@@ -160,7 +160,7 @@ EXPORTS = [
     "pt_group_build_bvh_accel",
     "pt_group_set_bvh2", "pt_group_set_bvh4", "pt_group_set_batch", "pt_group_render", "pt_group_flush", "pt_group_synchronize", "pt_group_read_radiance",
     "pt_group_read_rgba8", "pt_group_read_tonemapped",
-    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_launch_plan_tuned", "pt_debug_traced_tiles", "pt_debug_exposure", "pt_exposure_flags_host",     # diagnostics section of the header
+    "pt_debug_set_tune", "pt_debug_counters", "pt_debug_wave_times", "pt_debug_launch_plan", "pt_debug_launch_plan_tuned", "pt_debug_traced_tiles", "pt_debug_exposure", "pt_exposure_flags_host", "pt_debug_exposure_tier2", "pt_exposure_flags_host_gate",     # diagnostics section of the header
 ]
 
 
@@ -210,13 +210,20 @@ def _torch_route():
                            "the same HIP runtime (torch ships its own)")
 
 
-def exposure_flags_host(tris, s_max, d_max):
-    """CPU twin of the exposure mask: bool per triangle (every pair tested; no GPU)."""
+EXPOSE_GATES = (0.0999, 0.2999)      # the two tiers' f64 gates (pt_expose.h: kGate, kGate2)
+
+
+def exposure_flags_host(tris, s_max, d_max, gate=None):
+    """CPU twin of the exposure mask: bool per triangle (every pair tested; no GPU).  gate: None = the first tier's, or the f64 bound on
+    |n . d| / |d| of the hits covered (EXPOSE_GATES)."""
     tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
     n = tris.size // 9
     words = ((n + 63) // 64) * 2
     bits = np.zeros(max(words, 1), np.uint32); cnt = C.c_uint32()
-    _check(lib.pt_exposure_flags_host(_p(tris, C.c_float), C.c_uint32(n), C.c_double(s_max), C.c_double(d_max), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(cnt)))
+    if gate is None:
+        _check(lib.pt_exposure_flags_host(_p(tris, C.c_float), C.c_uint32(n), C.c_double(s_max), C.c_double(d_max), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(cnt)))
+    else:
+        _check(lib.pt_exposure_flags_host_gate(_p(tris, C.c_float), C.c_uint32(n), C.c_double(s_max), C.c_double(d_max), C.c_double(gate), _p(bits, C.c_uint32), C.c_uint32(words), C.byref(cnt)))
     return np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)[:n]
 
 
@@ -837,16 +844,21 @@ class Context:
 
     def debug_exposure(self, params=None, want_mask=True):
         """Diagnostics: the exposure mask.  params: compute it now for the current tree and that camera; None: the mask
-        there is.  Returns a dict: valid, flagged, gave_up, listed, skipped, kernel_ms, mask (bool per triangle, or None), s_max, d_max, cam_max, used (the last megakernel launch read the mask)."""
-        info = (C.c_uint32 * 7)(); ms = C.c_float(); bd = (C.c_double * 3)()
+        there is.  Returns a dict: valid, flagged, gave_up, listed, skipped, kernel_ms, mask (bool per triangle, or None), s_max, d_max, cam_max, used (the last megakernel launch read the mask).
+        flagged, gave_up and mask are the first tier's; the second tier's (steeper hits only, a superset) are flagged2, gave_up2 (walks that ran
+        out of budget after the first tier was settled as blocked) and mask2.  skipped counts the rays either tier skipped."""
+        info = (C.c_uint32 * 7)(); ms = C.c_float(); bd = (C.c_double * 3)(); info2 = (C.c_uint32 * 2)()
         self._ck(lib.pt_debug_exposure(self.h, C.byref(params) if params is not None else None, info, bd, C.byref(ms), None, C.c_uint32(0)))
-        mask = None
+        self._ck(lib.pt_debug_exposure_tier2(self.h, info2, None, C.c_uint32(0)))
+        mask = mask2 = None
         if want_mask and info[5]:
             bits = np.zeros(info[5], np.uint32)
             self._ck(lib.pt_debug_exposure(self.h, None, info, bd, C.byref(ms), _p(bits, C.c_uint32), C.c_uint32(info[5])))
             mask = np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)
+            self._ck(lib.pt_debug_exposure_tier2(self.h, info2, _p(bits, C.c_uint32), C.c_uint32(info[5])))
+            mask2 = np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)
         return {"valid": bool(info[0]), "flagged": info[1], "gave_up": info[2], "listed": info[3], "skipped": info[4], "kernel_ms": ms.value, "mask": mask,
-                "s_max": bd[0], "d_max": bd[1], "cam_max": bd[2], "used": bool(info[6])}
+                "s_max": bd[0], "d_max": bd[1], "cam_max": bd[2], "used": bool(info[6]), "flagged2": info2[0], "gave_up2": info2[1], "mask2": mask2}
 
     def timing_collect_spans(self, capacity):
         """(start_ms, dur_ms) of the launches recorded since timing_begin; starts are relative to the first launch."""

@@ -98,7 +98,7 @@ uint64_t tri_region_bytes(uint32_t num_tris) { return (uint64_t(num_tris) + 1u) 
 // Room for `num_tris` triangle records and `nodes` wide nodes; triangle records that are already there survive a regrowth.
 int ensure_scene(PtContext* ctx, uint32_t num_tris, uint64_t nodes) {
     const uint64_t tri_bytes = tri_region_bytes(num_tris);
-    const uint64_t mask_bytes = ((uint64_t(ptk::expose_mask_words(num_tris)) * 4u + 63u) / 64u) * 64u;          // the exposure mask, behind the nodes
+    const uint64_t mask_bytes = ptk::expose_mask_bytes(num_tris);          // the exposure masks (both tiers, and the first tier alone 64 KiB-aligned behind them), behind the nodes
     const uint64_t need = tri_bytes + (nodes + 1u) * 64u + mask_bytes + (nodes / 8u + 16u) * 64u + 65536u;
     if (need >= 0xFFFFFFFFull) return fail(ctx, PT_ERR_INVALID_ARG, "scene too large: triangle records, BVH nodes (with their regrowth slack) and the exposure mask behind them are addressed by 32-bit byte offsets (4 GiB)");
     if (ctx->d_scene.ptr && ctx->node_off == tri_bytes && ctx->node_cap >= nodes) {
@@ -569,11 +569,13 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     A.rcp_short = (PtTune::pick(ctx->tune.bounded, 1u) != 0u && arith_is_bounded(ctx, ctx->pending_frames, nf)) ? 1u : 0u;      // knob BOUNDED = 0: always the general forms (tests)
 
     // exposed triangles: knob EXPOSE 0 = every shadow ray is traced, 1 (default) = production launches skip those of exposed triangles, 2 = instrumented
-    // launches as well (the oracle counts the rays, and TIMELINE is compared with COUNTERS: by default both trace everything).  The mask is
+    // launches as well (the oracle counts the rays, and TIMELINE is compared with COUNTERS: by default both trace everything); 4 added to either (5, 6):
+    // the first tier only (A/Bs and tests -- the launch is pointed at the copy of the mask whose two tiers are both the first).  The masks are
     // taken by a launch of at least 2^24 ray segments that finds none for the tree version -- after an update by the second such launch.
-    bool expose_use = false, expose_compute = false; double expose_cam = -1.0;
+    bool expose_use = false, expose_compute = false, expose_first_only = false; double expose_cam = -1.0;
     {
-        const uint32_t knob = PtTune::pick(ctx->tune.expose, 1u);
+        const uint32_t knob_all = PtTune::pick(ctx->tune.expose, 1u), knob = knob_all & 3u;
+        expose_first_only = (knob_all & 4u) != 0u;
         const bool instr = stats || PtTune::pick(ctx->tune.timeline, 0u) != 0u;
         if (knob != 0u && (!instr || knob >= 2u) && A.ref_mode == 0u && expose_possible(ctx) && (expose_cam = expose_cam_norm(ctx->pending_frames.data(), nf)) >= 0.0) {
             const bool current = ctx->expose_version == ctx->tree_version && ctx->expose_version != 0u;
@@ -618,7 +620,7 @@ int flush_pending_stats(PtContext* ctx, bool stats, bool sharded, uint32_t count
     }
     if (expose_use) {
         if (sl.expose_waited != ctx->expose_gen) { PT_HIP(ctx, hipStreamWaitEvent(sl.side, ctx->ev_expose, 0)); sl.expose_waited = ctx->expose_gen; }
-        A.bounces_expose |= uint32_t(ctx->expose_off) & 0xffff0000u;
+        A.bounces_expose |= uint32_t(ctx->expose_off + (expose_first_only ? ptk::expose_first_only_offset(ctx->expose_tris) : 0u)) & 0xffff0000u;
         if (stats) A.expose_skipped = ctx->d_expose_skipped.ptr;
     }
     ctx->expose_last_used = (A.bounces_expose >> 16) != 0u;
@@ -1496,6 +1498,15 @@ int pt_debug_wave_times(PtContext* ctx, unsigned long long* dst, uint32_t max_wa
     return PT_OK;
 }
 
+// one tier's words (0: the first, 1: the second) out of the arena's interleaved pair
+static int read_exposure_tier(PtContext* ctx, uint32_t tier, uint32_t words, uint32_t* out) {
+    if (!words) return PT_OK;
+    std::vector<uint32_t> both(size_t(words) * 2u);
+    PT_HIP(ctx, hipMemcpy(both.data(), ctx->expose_mask(), both.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t w = 0; w < words; ++w) out[w] = both[size_t(w) * 2u + tier];
+    return PT_OK;
+}
+
 /* diagnostics: the exposure mask (pt_expose.hip).  params != NULL: the mask is computed now, for the current tree and that camera, and
  * waited for; NULL: whatever mask there is.  info_out[7]: 1 when the mask holds for the current tree version, flagged triangles, queries that
  * ran out of their budget, listed ill-conditioned triangles, shadow rays the last EXPOSE = 2 instrumented launch skipped, words of the mask, 1 when the last megakernel launch read the mask. */
@@ -1527,7 +1538,27 @@ int pt_debug_exposure(PtContext* ctx, const PtRenderParams* p, uint32_t info_out
     if (kernel_ms) { *kernel_ms = 0.0f; if (have) PT_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev_expose_t0, ctx->ev_expose_t1)); }
     if (mask_out) {
         if (words < need) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_exposure: the mask needs one bit per triangle, in an even number of words per 64");
-        if (need) PT_HIP(ctx, hipMemcpy(mask_out, ctx->expose_mask(), size_t(need) * 4u, hipMemcpyDeviceToHost));
+        if (int rc = read_exposure_tier(ctx, 0u, need, mask_out)) return rc;
+    }
+    return PT_OK;
+}
+
+/* diagnostics: the second tier of whatever exposure mask there is (pt_debug_exposure computes both).  info_out[2]: its flagged triangles, walks
+ * that ran out of their budget after the first tier was settled as blocked (their triangles stay unflagged in the second tier); mask_out
+ * (optional): as pt_debug_exposure's, info_out[5] words of it. */
+int pt_debug_exposure_tier2(PtContext* ctx, uint32_t info_out[2], uint32_t* mask_out, uint32_t words) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = flush_pending(ctx)) return rc;
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto& sl : ctx->slots) if (sl.side && sl.used) PT_HIP(ctx, hipStreamSynchronize(sl.side));
+    const bool have = ctx->expose_version != 0u && ctx->d_expose_info.ptr != nullptr;
+    uint32_t h[ptk::kExposeInfoWords] = {0};
+    if (have) PT_HIP(ctx, hipMemcpy(h, ctx->d_expose_info.ptr, sizeof h, hipMemcpyDeviceToHost));
+    if (info_out) { info_out[0] = h[ptk::kExposeFlagged2]; info_out[1] = h[ptk::kExposeBudget2]; }
+    if (mask_out) {
+        const uint32_t need = have ? ptk::expose_mask_words(ctx->expose_tris) : 0u;
+        if (words < need) return fail(ctx, PT_ERR_INVALID_ARG, "pt_debug_exposure_tier2: the mask needs one bit per triangle, in an even number of words per 64");
+        if (int rc = read_exposure_tier(ctx, 1u, need, mask_out)) return rc;
     }
     return PT_OK;
 }
@@ -1536,7 +1567,17 @@ int pt_exposure_flags_host(const float* tris, uint32_t num_tris, double s_max, d
     if ((!tris && num_tris) || !mask_out) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: null pointer");
     if (words < ((num_tris + 63u) / 64u) * 2u) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: the mask needs 2 * ceil(num_tris / 64) words");
     if (!(s_max >= 0.0 && d_max >= 0.0)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host: bad bounds");
-    const uint32_t n = pt::exposure_flags(tris, num_tris, s_max, d_max, mask_out);
+    const uint32_t n = pt::exposure_flags(tris, num_tris, s_max, d_max, ptex::kGate, mask_out);
+    if (flagged) *flagged = n;
+    return PT_OK;
+}
+
+int pt_exposure_flags_host_gate(const float* tris, uint32_t num_tris, double s_max, double d_max, double gate, uint32_t* mask_out, uint32_t words, uint32_t* flagged) {
+    if ((!tris && num_tris) || !mask_out) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host_gate: null pointer");
+    if (words < ((num_tris + 63u) / 64u) * 2u) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host_gate: the mask needs 2 * ceil(num_tris / 64) words");
+    if (!(s_max >= 0.0 && d_max >= 0.0)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host_gate: bad bounds");
+    if (!(gate > 0.0 && gate <= 1.0)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_exposure_flags_host_gate: the gate is a cosine in (0, 1]");
+    const uint32_t n = pt::exposure_flags(tris, num_tris, s_max, d_max, gate, mask_out);
     if (flagged) *flagged = n;
     return PT_OK;
 }

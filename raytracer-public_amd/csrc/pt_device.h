@@ -225,6 +225,7 @@ __device__ __forceinline__ ItemInfo decode_item(const RenderArgs& A, uint32_t lo
 
 constexpr float kEpsOrigin = 1e-4f;
 constexpr float kExposeGate = 0.1002f;   // |n . d| below which the shadow ray of a hit on an exposed triangle is traced all the same (pt_expose.h::kGate)
+constexpr float kExposeGate2 = 0.3008f;  // the same for a triangle that only the second tier flags (pt_expose.h::kGate2: the same ratio 1.003)
 constexpr float kBgPrimary = 0.01f;    // renderer.wgsl:410
 constexpr float kSkyAmbient = 0.15f;   // renderer.wgsl:352
 constexpr uint32_t kRRStart = 2;

@@ -22,6 +22,7 @@ constexpr double kEps32 = 5.9604644775390625e-8;      // 2^-24: the relative err
 constexpr double kShift = 1e-4;                       // pt_device.h::kEpsOrigin
 constexpr double kCMin = 0.02;                        // smallest |n . L| of an exposed triangle
 constexpr double kGate = 0.0999;                      // smallest |n . d| / |d| of a hit whose shadow ray is skipped (the kernel asks 0.1002 in f32)
+constexpr double kGate2 = 0.2999;                     // the second tier's: steeper hits only, a third of the in-plane margin (the kernel asks 0.3008 in f32, the same ratio)
 constexpr double kNormalTol = 1e-5;                   // largest distance of the stored f32 normal from the f64 one
 constexpr double kDetMin = 9.99e-8;                   // below pt_device.h::kTriEps: a triangle whose |det| cannot reach it never accepts a shadow ray
 constexpr double kKappaCap = 36.0 * kEps32 / 1e-3;    // triangles with a larger error factor go to the list every query tests (pt_expose.hip)
@@ -56,7 +57,8 @@ struct Query {
     double c, nf[3], v0s[3];        // |n . Lh|, the unit normal on the light's side, v0 shifted by kShift along it
     double p[3][2];                 // the shifted triangle's corners across the light
     double en[3][3];                // its edges as inward half-planes a u + b v + d >= 0, (a, b) a unit vector
-    double rho_n, rho_xy;           // how far an origin can lie off the shifted plane, and off the shifted triangle within it
+    double rho_n, rho_xy;           // how far an origin can lie off the shifted plane, and off the shifted triangle within it (for hits at the query's gate or above)
+    double sinphi;                  // the sine of the angle between its edges e1, e2 (rho_xy_at)
     double cen[3], rad;             // centre and radius of the shifted triangle
     double lo[2], hi[2], wmin;      // its bounds across the light, its smallest depth along it
 };
@@ -72,7 +74,12 @@ PT_EX_HD double kappa_of(const Tri& n, const Light& g) {
     return 36.0 * kEps32 * l1 * l2 / det;          // det = |e1| |e2| sin(phi) |n . L|
 }
 
-PT_EX_HD Query make_query(const Tri& t, const float n32[3], const Light& g, const Bounds& b) {
+// rho_xy for another gate: the one term of a query that depends on the gate.  A larger gate gives a smaller margin, so what is exposed at
+// one gate is exposed at every larger one.
+PT_EX_HD double rho_xy_at(const Query& q, const Bounds& b, double gate) { return 36.0 * kEps32 * b.s_max / (q.sinphi * gate) + q.rho_n; }
+
+// gate: the smallest |n . d| / |d| of the hits whose shadow rays the flag is to cover (kGate, kGate2)
+PT_EX_HD Query make_query(const Tri& t, const float n32[3], const Light& g, const Bounds& b, double gate = kGate) {
     Query q; q.ok = false;
     double nn[3]; cross(t.e1, t.e2, nn);
     const double a2 = sqrt(dot(nn, nn)), l1 = sqrt(dot(t.e1, t.e1)), l2 = sqrt(dot(t.e2, t.e2));
@@ -88,7 +95,8 @@ PT_EX_HD Query make_query(const Tri& t, const float n32[3], const Light& g, cons
     // origin error: off the plane by the error of t along the ray's normal component (11.5 / sin phi + 2), the rounding
     // of the product d t (one more eps S_max: |d t| <= S_max), the rounding of the sum o + d t and of + nf 1e-4 (7 eps D_max); inside the plane by the errors of u, v and t over the cosine the kernel's gate leaves
     q.rho_n = kEps32 * (11.5 * b.s_max / sinphi + 3.0 * b.s_max + 7.0 * b.d_max) + 2e-9;
-    q.rho_xy = 36.0 * kEps32 * b.s_max / (sinphi * kGate) + q.rho_n;
+    q.sinphi = sinphi;
+    q.rho_xy = rho_xy_at(q, b, gate);
     if (!(q.rho_n < kShift)) return q;
     double vs[3][3];
     for (int a = 0; a < 3; ++a) {
@@ -122,18 +130,19 @@ PT_EX_HD Query make_query(const Tri& t, const float n32[3], const Light& g, cons
 }
 
 // the largest operand of a shadow-ray test of triangle n from an origin on T: |so - v0| plus the way along the ray to n's far corner
-PT_EX_HD double operand_of(const Query& q, const Tri& n) {
+PT_EX_HD double operand_of(const Query& q, double rho_xy, const Tri& n) {
     const double d[3] = {n.v0[0] - q.cen[0], n.v0[1] - q.cen[1], n.v0[2] - q.cen[2]};
-    return sqrt(dot(d, d)) + q.rad + q.rho_xy + sqrt(dot(n.e1, n.e1)) + sqrt(dot(n.e2, n.e2));
+    return sqrt(dot(d, d)) + q.rad + rho_xy + sqrt(dot(n.e1, n.e1)) + sqrt(dot(n.e2, n.e2));
 }
 
 // Does triangle n reach into T's prism?  n is clipped against the three planes through T's edges (pushed out by `grow`) that contain
 // the light direction; the height over T's shifted plane along the light is affine on the clipped polygon, so its maximum is at a corner.
-PT_EX_HD bool blocks(const Query& q, const Tri& n, const Light& g) {
+// rho_xy: the in-plane margin of the tier asked for (q.rho_xy, or rho_xy_at of another gate -- everything else of q is the same for every gate).
+PT_EX_HD bool blocks(const Query& q, double rho_xy, const Tri& n, const Light& g) {
     const double kap = kappa_of(n, g);
     if (kap < 0.0) return false;
-    const double rho_nb = kap * operand_of(q, n);
-    const double grow = q.rho_xy + q.rho_n + rho_nb, hthr = -(q.rho_n + rho_nb) / q.c;
+    const double rho_nb = kap * operand_of(q, rho_xy, n);
+    const double grow = rho_xy + q.rho_n + rho_nb, hthr = -(q.rho_n + rho_nb) / q.c;
     if (!(grow < 1e300)) return true;
     double pu[8], pv[8], ph[8], qu[8], qv[8], qh[8];
     for (int i = 0; i < 3; ++i) {
@@ -165,6 +174,7 @@ PT_EX_HD bool blocks(const Query& q, const Tri& n, const Light& g) {
     for (int i = 0; i < m; ++i) if (ph[i] > hthr) return true;
     return false;
 }
+PT_EX_HD bool blocks(const Query& q, const Tri& n, const Light& g) { return blocks(q, q.rho_xy, n, g); }
 
 // Can anything inside the box [mn, mx] (a live f16 box, grown here) block T?  No when the box lies beside T's grown footprint or
 // below the lowest point of its shifted plane over that footprint; the growth assumes the largest error factor a walked triangle has.

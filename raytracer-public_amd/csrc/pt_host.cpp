@@ -1571,7 +1571,7 @@ bool list_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
 }
 
 // ---- exposed triangles: every pair, with the arithmetic of pt_expose.h (pt_expose.hip walks the tree instead) ----
-uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask) {
+uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, double d_max, double gate, uint32_t* mask) {
     const uint32_t words = ((num_tris + 63u) / 64u) * 2u;
     std::memset(mask, 0, size_t(words) * sizeof(uint32_t));
     std::vector<TriRecord> rec(num_tris);
@@ -1590,7 +1590,7 @@ uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, doub
     uint32_t flagged = 0;
     for (uint32_t t = 0; t < num_tris; ++t) {
         const float n32[3] = {rec[t].n[0], rec[t].n[1], rec[t].n[2]};
-        const ptex::Query q = ptex::make_query(all[t], n32, g, b);
+        const ptex::Query q = ptex::make_query(all[t], n32, g, b, gate);
         bool blocked = !q.ok;
         for (uint32_t n = 0; n < num_tris && !blocked; ++n) blocked = ptex::blocks(q, all[n], g);
         if (!blocked) { mask[t >> 5] |= 1u << (t & 31u); ++flagged; }

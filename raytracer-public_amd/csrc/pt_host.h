@@ -91,8 +91,9 @@ void build_tri_records(const float* tris, uint32_t n, TriRecord* out);
 // ---- exposed triangles (host twin of pt_expose.hip, the arithmetic of pt_expose.h) ---------------------------
 // mask: 2 * ceil(num_tris / 64) words, bit t set when no shadow ray started on triangle t can be occluded, for ray origins within
 // s_max of every scene point and hit coordinates up to d_max.  Every pair of triangles is tested: no tree, no budget -- the device's
-// mask is this one without the queries that gave up.  Returns the number of flagged triangles.
-uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, double d_max, uint32_t* mask);
+// mask is this one without the queries that gave up.  gate: the smallest |n . d| / |d| of the hits covered (ptex::kGate for the first tier,
+// ptex::kGate2 for the second).  Returns the number of flagged triangles.
+uint32_t exposure_flags(const float* tris, uint32_t num_tris, double s_max, double d_max, double gate, uint32_t* mask);
 
 // ---- closest-point queries (pt_closest_points; host twin of pt_pointquery.hip, bit for bit) --------------------------------------
 // points: n x (x, y, z, r_max); out: n x (dist bits, prim, u bits, v bits).  bvh4 = nullptr: every triangle in index order; else the walk

@@ -211,7 +211,7 @@ struct RenderArgs {
     uint32_t  prime;            // 1: launch_trace must zero the control block itself
     uint32_t  ref_mode;         // 1: PT_MODE_REFERENCE on the megakernel -- one primary ray through each pixel centre, shade() of renderer.wgsl:348-353 (spp = 1, no bounces)
     // The megakernel's bounce limit (bits 0..15: min(max_bounces, 65535), the bounce count of a path being a 16-bit field) and, in bits 16..31, the
-    // byte offset in the arena, in units of 64 KiB, of the exposure mask (pt_expose.hip, DESIGN.md section 6.2: one bit per triangle), or 0 -- every
+    // byte offset in the arena, in units of 64 KiB, of the exposure mask (pt_expose.hip, DESIGN.md section 6.2: one bit per triangle and tier, the tiers' words interleaved), or 0 -- every
     // shadow ray is traced (no mask yet, a camera or the scene beyond the bounds it was computed for, an instrumented launch).  One word, because the
     // shade pass reads both at the same place: a second launch constant there costs spilled scalar registers.
     uint32_t bounces_expose;
@@ -390,11 +390,18 @@ hipError_t launch_tile_cover(const uint4* wide, const uint32_t* cut, uint32_t co
                              uint32_t* mask, uint32_t words, hipStream_t stream);
 // ---- exposed triangles (pt_expose.hip): which triangles no shadow ray of the fixed light can be occluded on ------------------------
 // info: kExposeInfoWords words, zeroed by the launch (flagged triangles, queries that ran out of their budget, listed ill-conditioned
-// triangles; the rest is spare); bad: kExposeBadMax words; mask: expose_mask_words(num_tris) words, every one written.
+// triangles, [a word the host fills in], the second tier's flagged triangles, walks that ran out of their budget with the first tier
+// already blocked; the rest is spare); bad: kExposeBadMax words.
+// mask: expose_mask_bytes(num_tris) bytes at a multiple of 64 KiB.  Two tiers (the gates of pt_expose.h: the second flags a superset of the
+// first) of expose_mask_words(num_tris) words each, interleaved word by word -- first tier, second tier -- and every word written; behind
+// them, expose_first_only_offset(num_tris) bytes (a multiple of 64 KiB) further on, the same layout with the first tier's words in both
+// places, so that a launch is told "first tier only" by where RenderArgs::bounces_expose points and by nothing else.
 // s_max, d_max: the operand bounds of ptex::Bounds (pt_expose.h) the flags hold for.
-constexpr uint32_t kExposeInfoWords = 8, kExposeFlagged = 0, kExposeBudget = 1, kExposeBad = 2, kExposeSkipped = 3, kExposeBadMax = 2048;
+constexpr uint32_t kExposeInfoWords = 8, kExposeFlagged = 0, kExposeBudget = 1, kExposeBad = 2, kExposeSkipped = 3, kExposeFlagged2 = 4, kExposeBudget2 = 5, kExposeBadMax = 2048;
 constexpr uint32_t kExposeNodeBudget = 2048, kExposeLeafBudget = 256;
 uint32_t expose_mask_words(uint32_t num_tris);
+uint64_t expose_first_only_offset(uint32_t num_tris);
+uint64_t expose_mask_bytes(uint32_t num_tris);
 hipError_t launch_expose(const uint4* scene, uint32_t node_base16, uint32_t num_wide, uint32_t root_ref, uint32_t num_tris, double s_max, double d_max,
                          uint32_t node_budget, uint32_t leaf_budget, uint32_t* info, uint32_t* bad, uint32_t* mask, hipStream_t stream);
 hipError_t launch_rgba8(const float4* src, uint32_t* dst, uint32_t n, hipStream_t stream);

@@ -66,10 +66,11 @@
                     } else {
                         const F3 n = tri_normal_ref(A, S.best_tri);
                         // exposed triangles (pt_expose.hip): the word of the hit triangle's bit, asked for next to the normal (an independent load)
-                        uint32_t ex_word = 0u;
+                        // (two tiers, their words interleaved: .x the first tier's, .y the second's -- one 8-byte load)
+                        uint2 ex_word = make_uint2(0u, 0u);
                         uint32_t bx = A.bounces_expose;                // the bounce limit and the mask's place in one launch constant (pt_kernels.h)
                         asm volatile("" : "+s"(bx));                   // (opaque: what is derived from it is computed here, not hoisted out of the launch loops and held through them)
-                        if ((bx >> 16) != 0u) ex_word = *(const uint32_t*)((const char*)A.scene + ((bx & 0xffff0000u) + (((S.best_tri & 0x7fffffffu) >> 7) << 2)));
+                        if ((bx >> 16) != 0u) ex_word = *(const uint2*)((const char*)A.scene + ((bx & 0xffff0000u) + (((S.best_tri & 0x7fffffffu) >> 7) << 3)));
                         // what does not depend on the normal is computed while it is on its way from memory (a dependent fetch the pass would otherwise sit out):
                         // the hit point, this bounce's random numbers, the direction sample in its local frame
                         const F3 hp = S.o + S.d * S.best_t;
@@ -93,11 +94,14 @@
                         }
                         S.o = so;
                         // The shadow ray of a hit on an exposed triangle finds nothing (DESIGN.md section 6.2: no triangle reaches into the prism its origin
-                        // lies in, for hits at |n . d| >= kExposeGate, which bounds the origin's error inside the plane): its term is added here -- where
+                        // lies in, for hits at |n . d| >= the gate, which bounds the origin's error inside the plane): its term is added here -- where
                         // the traced ray's end would add it, nothing having been added in between -- and the path goes on as without a light term.
-                        // (the three conditions are folded into one lane value and tested once: held as lane masks they cost spilled scalar registers)
-                        uint32_t lit = (ex_word >> ((S.best_tri >> 2) & 31u)) & 1u;
-                        lit = (fabsf(nd) >= kExposeGate) ? lit : 0u;
+                        // The second tier's bit (a superset of the first's) says that the hit may be skipped at all, the first tier's which gate it has to pass.
+                        // (the conditions are folded into one lane value and tested once: held as lane masks they cost spilled scalar registers)
+                        const uint32_t ex_bit = (S.best_tri >> 2) & 31u;
+                        uint32_t lit = (ex_word.y >> ex_bit) & 1u;
+                        const float ex_gate = ((ex_word.x >> ex_bit) & 1u) != 0u ? kExposeGate : kExposeGate2;
+                        lit = (fabsf(nd) >= ex_gate) ? lit : 0u;
                         lit = (ndl > 0.0f) ? lit : 0u;
                         asm volatile("" : "+v"(lit));
                         {   // (a select in front of the branch the pass had before, not a branch of its own: no further definition of the pass's lane masks)

@@ -3,10 +3,11 @@
 
   python tools/exposure_yield.py [--scene dragon|sponza] [--tris N] [--width W --height H] [--spp S] [--bounces B] [--cam x y z] [--host]
 
-One instrumented frame with knob EXPOSE at 1 (every shadow ray traced: the oracle's counters) and one at 2 (the rays of exposed triangles
-skipped and counted); the difference of the node records and triangle tests is what the skipped rays cost.  Prints one JSON line: triangles
-flagged / listed / out of budget, the two kernels' duration, closest and shadow rays, skipped rays and their share, node records and triangle
-tests saved and their share of the frame's.  --host adds the host twin's flagged count (every pair of triangles: small scenes only).
+One instrumented frame with knob EXPOSE at 1 (every shadow ray traced: the oracle's counters), one at 6 (the rays the first tier skips,
+counted) and one at 2 (both tiers); the difference of the node records and triangle tests is what the skipped rays cost.  Prints one JSON
+line: triangles flagged / out of budget per tier and listed, the two kernels' duration, closest and shadow rays, and under "tier1" and "both"
+the skipped rays and their share, node records and triangle tests saved and their share of the frame's.  --host adds the host twin's flagged
+counts (every pair of triangles: small scenes only).
 The shares by ray kind of a CPU walk (camera / bounce / shadow, occluded or not) are not reported: the oracle counts rays, not steps per kind."""
 import argparse
 import importlib
@@ -39,18 +40,22 @@ def main():
     p = ctx.make_params(a.width, a.height, cam, quat, mode=rt.PT_MODE_PATH, spp=a.spp, max_bounces=a.bounces, seed=1, stats=True)
     info = ctx.debug_exposure(p, want_mask=False)
     ctx.render(p); full = ctx.stats()
-    ctx.debug_set_tune("EXPOSE", 2)
-    ctx.render(p); cut = ctx.stats()
-    skipped = ctx.debug_exposure(None, want_mask=False)["skipped"]
-    out = {"scene": a.scene, "triangles": n, "frame": [a.width, a.height, a.spp, a.bounces], "flagged": info["flagged"], "listed": info["listed"],
-           "gave_up": info["gave_up"], "kernels_ms": round(info["kernel_ms"], 3), "s_max": info["s_max"], "rays_closest": full["rays_closest"],
-           "rays_shadow": full["rays_shadow"], "skipped": skipped, "skipped_share_of_shadow_rays": round(skipped / max(1, full["rays_shadow"]), 4),
-           "nodes_examined": full["nodes_examined"], "nodes_saved": full["nodes_examined"] - cut["nodes_examined"],
-           "nodes_saved_share": round((full["nodes_examined"] - cut["nodes_examined"]) / max(1, full["nodes_examined"]), 4),
-           "tris_tested": full["tris_tested"], "tris_saved": full["tris_tested"] - cut["tris_tested"]}
-    assert cut["rays_shadow"] == full["rays_shadow"] - skipped
+    out = {"scene": a.scene, "triangles": n, "frame": [a.width, a.height, a.spp, a.bounces], "flagged": info["flagged"], "flagged2": info["flagged2"],
+           "listed": info["listed"], "gave_up": info["gave_up"], "gave_up2": info["gave_up2"], "kernels_ms": round(info["kernel_ms"], 3), "s_max": info["s_max"],
+           "rays_closest": full["rays_closest"], "rays_shadow": full["rays_shadow"], "nodes_examined": full["nodes_examined"], "tris_tested": full["tris_tested"]}
+    # knob EXPOSE 6: instrumented launches skip with the first tier only; 2: with both tiers
+    for knob, tag in ((6, "tier1"), (2, "both")):
+        ctx.debug_set_tune("EXPOSE", knob)
+        ctx.render(p); cut = ctx.stats()
+        skipped = ctx.debug_exposure(None, want_mask=False)["skipped"]
+        assert cut["rays_shadow"] == full["rays_shadow"] - skipped
+        out[tag] = {"skipped": skipped, "skipped_share_of_shadow_rays": round(skipped / max(1, full["rays_shadow"]), 4),
+                    "nodes_saved": full["nodes_examined"] - cut["nodes_examined"],
+                    "nodes_saved_share": round((full["nodes_examined"] - cut["nodes_examined"]) / max(1, full["nodes_examined"]), 4),
+                    "tris_saved": full["tris_tested"] - cut["tris_tested"]}
     if a.host:
         out["host_twin_flagged"] = int(rt.exposure_flags_host(tris, info["s_max"], info["d_max"]).sum())
+        out["host_twin_flagged2"] = int(rt.exposure_flags_host(tris, info["s_max"], info["d_max"], gate=rt.EXPOSE_GATES[1]).sum())
     print(json.dumps(out), flush=True)
     ctx.close()
 
