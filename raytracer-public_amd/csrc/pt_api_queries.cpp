@@ -422,30 +422,35 @@ int pt_signed_distance_host(PtContext* ctx, const PtPoint* points, uint64_t n, c
 namespace {
 constexpr uint32_t kRadiusFlags = PT_RADIUS_STATS | PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_BRUTE_FORCE;
 
-// flags, batch size and the points; the other pointers are checked by the callers, and the scene behind them
-int check_radius(PtContext* ctx, const char* fn, const void* points, uint64_t n, uint32_t flags) {
+// The region queries (radius: points, box: boxes) share their flags' values, their check and their walk.
+static_assert(PT_BOX_STATS == PT_RADIUS_STATS && PT_BOX_SIMPLE_KERNEL == PT_RADIUS_SIMPLE_KERNEL && PT_BOX_BRUTE_FORCE == PT_RADIUS_BRUTE_FORCE,
+              "the PT_BOX_* flags take the values of the PT_RADIUS_* flags");
+constexpr uint32_t kBoxFlags = kRadiusFlags;
+
+// flags, batch size and the input records called `noun`; the other pointers are checked by the callers, and the scene behind them
+int check_region(PtContext* ctx, const char* fn, const void* in, uint64_t n, uint32_t flags, const char* noun) {
     if (int rc = check_flags(ctx, fn, flags, kRadiusFlags)) return rc;
-    if (int rc = check_n(ctx, fn, n, "points")) return rc;
-    return check_records(ctx, fn, "points", {points});
+    if (int rc = check_n(ctx, fn, n, noun)) return rc;
+    return check_records(ctx, fn, noun, {in});
 }
 
-// One walk: the count walk into `counts` (offsets = nullptr), or the fill walk from `offsets` into `entries`.  PT_RADIUS_STATS counts
-// over the count walk only; its fill walk is the one-point-per-thread kernel.
-int radius_walk_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* counts, const unsigned long long* offsets,
-                          void* entries, uint64_t capacity) {
+// One walk through `launch` (ptk::launch_radius, ptk::launch_box) with the grid and the stack of its two knobs: the count walk into
+// `counts` (offsets = nullptr), or the fill walk from `offsets` into `entries`.  The STATS flag counts over the count walk only; its fill
+// walk is the one-item-per-thread kernel.
+int region_walk_on_stream(PtContext* ctx, decltype(&ptk::launch_radius) launch, uint32_t waves_per_simd, int short_stack, const void* in, uint32_t n,
+                          uint32_t flags, void* counts, const unsigned long long* offsets, void* entries, uint64_t capacity) {
     const bool fill = offsets != nullptr, brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
     const bool stats = (flags & PT_RADIUS_STATS) != 0 && !fill, simple = (flags & (PT_RADIUS_SIMPLE_KERNEL | PT_RADIUS_STATS)) != 0;
     Walk W;
-    if (int rc = begin_walk(ctx, n, PT_RD_WAVES_PER_SIMD, PT_RD_SHORT_STACK, stats, !simple && !brute, W)) return rc;
-    if (W.launch) PT_HIP(ctx, ptk::launch_radius(W.A, points, n, counts, offsets, entries, capacity, simple, stats, brute,
-                                                 ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, W.grid, ctx->stream));
+    if (int rc = begin_walk(ctx, n, waves_per_simd, short_stack, stats, !simple && !brute, W)) return rc;
+    if (W.launch) PT_HIP(ctx, launch(W.A, in, n, counts, offsets, entries, capacity, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, W.grid, ctx->stream));
     return end_walk(ctx, W);
 }
 int radius_count_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, void* counts) {
-    return radius_walk_on_stream(ctx, points, n, flags, counts, nullptr, nullptr, 0);
+    return region_walk_on_stream(ctx, ptk::launch_radius, PT_RD_WAVES_PER_SIMD, PT_RD_SHORT_STACK, points, n, flags, counts, nullptr, nullptr, 0);
 }
 int radius_fill_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* entries, uint64_t capacity) {
-    return radius_walk_on_stream(ctx, points, n, flags, nullptr, offsets, entries, capacity);
+    return region_walk_on_stream(ctx, ptk::launch_radius, PT_RD_WAVES_PER_SIMD, PT_RD_SHORT_STACK, points, n, flags, nullptr, offsets, entries, capacity);
 }
 
 // A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, box search over boxes, hit
@@ -492,11 +497,23 @@ int list_host(PtContext* ctx, const ListQuery& q, const void* in, uint64_t n, ui
     return PT_OK;
 }
 constexpr ListQuery kRadiusList = {sizeof(PtPoint), radius_count_on_stream, radius_fill_on_stream};
+
+// The argument check of a list query's host twin (pt_radius_search_bvh4, pt_box_search_bvh4, pt_list_hits_bvh4): `in` holds n records
+// called `noun`, a NULL bvh4 goes with brute force only.
+int check_list_bvh4(const char* fn, uint32_t flags, uint32_t known, bool brute, const float* tris, uint32_t num_tris, const uint32_t* bvh4,
+                    const void* in, uint64_t n, const char* noun, const uint64_t* offsets, const void* entries, uint64_t capacity) {
+    const std::string f = std::string(fn) + ": ";
+    if (flags & ~known) return fail(nullptr, PT_ERR_INVALID_ARG, f + "unknown flags");
+    if ((!tris && num_tris) || (n && !in) || !offsets || (capacity && !entries) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, f + "null pointer");
+    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, f + "offsets must be 8-byte aligned");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, f + "more than 2^32 - 1 " + noun);
+    return PT_OK;
+}
 } // namespace
 
 int pt_radius_count(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* counts_device) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_count", points_device, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_radius_count", points_device, n, flags, "points")) return rc;
     if (int rc = check_counts(ctx, "pt_radius_count", counts_device)) return rc;
     if (int rc = check_scene(ctx, "pt_radius_count")) return rc;
     return radius_count_on_stream(ctx, points_device, uint32_t(n), flags, counts_device);
@@ -504,7 +521,7 @@ int pt_radius_count(PtContext* ctx, const void* points_device, uint64_t n, uint3
 
 int pt_radius_count_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint32_t* counts) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_count_host", points, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_radius_count_host", points, n, flags, "points")) return rc;
     if (int rc = check_counts(ctx, "pt_radius_count_host", counts)) return rc;
     if (int rc = check_scene(ctx, "pt_radius_count_host")) return rc;
     return staged(ctx, n, points, sizeof(PtPoint), ctx->d_rd_counts, counts, sizeof(uint32_t),
@@ -514,7 +531,7 @@ int pt_radius_count_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint
 // three launches, no host wait (list_device)
 int pt_radius_search(PtContext* ctx, const void* points_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_search", points_device, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_radius_search", points_device, n, flags, "points")) return rc;
     if (int rc = check_list(ctx, "pt_radius_search", offsets_device, entries_device, capacity, "entries")) return rc;
     if (int rc = check_scene(ctx, "pt_radius_search")) return rc;
     return list_device(ctx, kRadiusList, points_device, n, flags, offsets_device, entries_device, capacity);
@@ -522,7 +539,7 @@ int pt_radius_search(PtContext* ctx, const void* points_device, uint64_t n, uint
 
 int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t n, uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_radius(ctx, "pt_radius_search_host", points, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_radius_search_host", points, n, flags, "points")) return rc;
     if (int rc = check_list(ctx, "pt_radius_search_host", offsets, entries, capacity, "entries")) return rc;
     if (int rc = check_scene(ctx, "pt_radius_search_host")) return rc;
     return list_host(ctx, kRadiusList, points, n, flags, offsets, entries, capacity);
@@ -530,12 +547,8 @@ int pt_radius_search_host(PtContext* ctx, const PtPoint* points, uint64_t n, uin
 
 int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtPoint* points, uint64_t n,
                           uint32_t flags, uint64_t* offsets, PtClosest* entries, uint64_t capacity, PtStats* stats) {
-    if (flags & ~kRadiusFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: unknown flags");
     const bool brute = (flags & PT_RADIUS_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && !points) || !offsets || (capacity && !entries) || (!bvh4 && !brute))
-        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: null pointer");
-    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: offsets must be 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_radius_search_bvh4: more than 2^32 - 1 points");
+    if (int rc = check_list_bvh4("pt_radius_search_bvh4", flags, kRadiusFlags, brute, tris, num_tris, bvh4, points, n, "points", offsets, entries, capacity)) return rc;
     std::string err;
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::radius_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n, offsets,
@@ -548,43 +561,21 @@ int pt_radius_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* 
 // ---- box-overlap queries (include/mi355pt.h; pt_overlap.hip) --------------------------------------------------------------------
 
 static_assert(sizeof(PtBox) == 32 && sizeof(PtOverlap) == sizeof(uint4), "PtBox / PtOverlap are read and written as 2 x 16 B and 16 B records");
-static_assert(PT_BOX_STATS == PT_RADIUS_STATS && PT_BOX_SIMPLE_KERNEL == PT_RADIUS_SIMPLE_KERNEL && PT_BOX_BRUTE_FORCE == PT_RADIUS_BRUTE_FORCE,
-              "the PT_BOX_* flags take the values of the PT_RADIUS_* flags");
 
 namespace {
-constexpr uint32_t kBoxFlags = PT_BOX_STATS | PT_BOX_SIMPLE_KERNEL | PT_BOX_BRUTE_FORCE;
-
-// flags, batch size and the boxes; the other pointers are checked by the callers, and the scene behind them
-int check_box(PtContext* ctx, const char* fn, const void* boxes, uint64_t n, uint32_t flags) {
-    if (int rc = check_flags(ctx, fn, flags, kBoxFlags)) return rc;
-    if (int rc = check_n(ctx, fn, n, "boxes")) return rc;
-    return check_records(ctx, fn, "boxes", {boxes});
-}
-
-// One walk: the count walk into `counts` (offsets = nullptr), or the fill walk from `offsets` into `entries`.  PT_BOX_STATS counts over
-// the count walk only; its fill walk is the one-box-per-thread kernel.
-int box_walk_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, void* counts, const unsigned long long* offsets,
-                       void* entries, uint64_t capacity) {
-    const bool fill = offsets != nullptr, brute = (flags & PT_BOX_BRUTE_FORCE) != 0;
-    const bool stats = (flags & PT_BOX_STATS) != 0 && !fill, simple = (flags & (PT_BOX_SIMPLE_KERNEL | PT_BOX_STATS)) != 0;
-    Walk W;
-    if (int rc = begin_walk(ctx, n, PT_BX_WAVES_PER_SIMD, PT_BX_SHORT_STACK, stats, !simple && !brute, W)) return rc;
-    if (W.launch) PT_HIP(ctx, ptk::launch_box(W.A, boxes, n, counts, offsets, entries, capacity, simple, stats, brute,
-                                              ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, W.grid, ctx->stream));
-    return end_walk(ctx, W);
-}
+// the count walk and the fill walk (region_walk_on_stream)
 int box_count_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, void* counts) {
-    return box_walk_on_stream(ctx, boxes, n, flags, counts, nullptr, nullptr, 0);
+    return region_walk_on_stream(ctx, ptk::launch_box, PT_BX_WAVES_PER_SIMD, PT_BX_SHORT_STACK, boxes, n, flags, counts, nullptr, nullptr, 0);
 }
 int box_fill_on_stream(PtContext* ctx, const void* boxes, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* entries, uint64_t capacity) {
-    return box_walk_on_stream(ctx, boxes, n, flags, nullptr, offsets, entries, capacity);
+    return region_walk_on_stream(ctx, ptk::launch_box, PT_BX_WAVES_PER_SIMD, PT_BX_SHORT_STACK, boxes, n, flags, nullptr, offsets, entries, capacity);
 }
 constexpr ListQuery kBoxList = {sizeof(PtBox), box_count_on_stream, box_fill_on_stream};
 } // namespace
 
 int pt_box_count(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags, void* counts_device) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_box(ctx, "pt_box_count", boxes_device, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_box_count", boxes_device, n, flags, "boxes")) return rc;
     if (int rc = check_counts(ctx, "pt_box_count", counts_device)) return rc;
     if (int rc = check_scene(ctx, "pt_box_count")) return rc;
     return box_count_on_stream(ctx, boxes_device, uint32_t(n), flags, counts_device);
@@ -592,7 +583,7 @@ int pt_box_count(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t 
 
 int pt_box_count_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags, uint32_t* counts) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_box(ctx, "pt_box_count_host", boxes, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_box_count_host", boxes, n, flags, "boxes")) return rc;
     if (int rc = check_counts(ctx, "pt_box_count_host", counts)) return rc;
     if (int rc = check_scene(ctx, "pt_box_count_host")) return rc;
     return staged(ctx, n, boxes, sizeof(PtBox), ctx->d_rd_counts, counts, sizeof(uint32_t),
@@ -602,7 +593,7 @@ int pt_box_count_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t f
 // three launches, no host wait (list_device)
 int pt_box_search(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_box(ctx, "pt_box_search", boxes_device, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_box_search", boxes_device, n, flags, "boxes")) return rc;
     if (int rc = check_list(ctx, "pt_box_search", offsets_device, entries_device, capacity, "entries")) return rc;
     if (int rc = check_scene(ctx, "pt_box_search")) return rc;
     return list_device(ctx, kBoxList, boxes_device, n, flags, offsets_device, entries_device, capacity);
@@ -610,7 +601,7 @@ int pt_box_search(PtContext* ctx, const void* boxes_device, uint64_t n, uint32_t
 
 int pt_box_search_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity) {
     if (int rc = bind(ctx)) return rc;
-    if (int rc = check_box(ctx, "pt_box_search_host", boxes, n, flags)) return rc;
+    if (int rc = check_region(ctx, "pt_box_search_host", boxes, n, flags, "boxes")) return rc;
     if (int rc = check_list(ctx, "pt_box_search_host", offsets, entries, capacity, "entries")) return rc;
     if (int rc = check_scene(ctx, "pt_box_search_host")) return rc;
     return list_host(ctx, kBoxList, boxes, n, flags, offsets, entries, capacity);
@@ -618,12 +609,8 @@ int pt_box_search_host(PtContext* ctx, const PtBox* boxes, uint64_t n, uint32_t 
 
 int pt_box_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtBox* boxes, uint64_t n,
                        uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity, PtStats* stats) {
-    if (flags & ~kBoxFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: unknown flags");
     const bool brute = (flags & PT_BOX_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && !boxes) || !offsets || (capacity && !entries) || (!bvh4 && !brute))
-        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: null pointer");
-    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: offsets must be 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_box_search_bvh4: more than 2^32 - 1 boxes");
+    if (int rc = check_list_bvh4("pt_box_search_bvh4", flags, kBoxFlags, brute, tris, num_tris, bvh4, boxes, n, "boxes", offsets, entries, capacity)) return rc;
     std::string err;
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::box_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(boxes), n, offsets,
@@ -683,12 +670,8 @@ int pt_list_hits_host(PtContext* ctx, const PtRay* rays, uint64_t n, uint32_t fl
 
 int pt_list_hits_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtRay* rays, uint64_t n,
                       uint32_t flags, uint64_t* offsets, PtHit* hits, uint64_t capacity, PtStats* stats) {
-    if (flags & ~kHitsFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: unknown flags");
     const bool brute = (flags & PT_HITS_BRUTE_FORCE) != 0;
-    if ((!tris && num_tris) || (n && !rays) || !offsets || (capacity && !hits) || (!bvh4 && !brute))
-        return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: null pointer");
-    if (!aligned8(offsets)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: offsets must be 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_list_hits_bvh4: more than 2^32 - 1 rays");
+    if (int rc = check_list_bvh4("pt_list_hits_bvh4", flags, kHitsFlags, brute, tris, num_tris, bvh4, rays, n, "rays", offsets, hits, capacity)) return rc;
     std::string err;
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::list_hits(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(rays), n, offsets,

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void apply_sign_kernel(const uint4* __restrict
 }
 
 // ------------------------------------------------------------------------------------
-// brute force: one ray per thread, every triangle in index order (pt_rays.h::brute_records)
+// brute force: one ray per thread, every triangle in index order (pt_walk.h::brute_records)
 // ------------------------------------------------------------------------------------
 template <bool STATS>
 __global__ __launch_bounds__(256) void count_hits_brute_kernel(const RenderArgs A, const float4* __restrict__ rays, uint32_t* __restrict__ counts, uint32_t n) {

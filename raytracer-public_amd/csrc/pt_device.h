@@ -300,8 +300,9 @@ __device__ __forceinline__ bool tri_hit(F3 o, F3 d, const uint4 n0, const uint4 
 // VGPRs; 63 with kInfT) are the values those loops were written with, and the resource tests pin their lines.
 // The helper counts in a local and store() keeps no state of its own on purpose: with `sp` behind the functor's reference the compiler
 // folds the two pushes of a slot into one behind a select, 54 instructions more per persistent kernel (profiles/query_walk_isa.txt).
-// traverse() below and pt_pointquery.hip::walk_point keep their own copy of these lines: on this helper render_rays_kernel compiles to
-// other code (the same file), and its instruction count is held where it is.
+// traverse() below keeps its own copy of these lines: on this helper render_rays_kernel compiles to other code (the same file), and
+// its instruction count is held where it is.  Every other stack walk is on the helper: pt_walk.h::persistent_walk,
+// pt_rays.h::cross_traverse and pt_points.h::key_traverse.
 template <class Store>
 __device__ __forceinline__ bool order_children(bool h0, bool h1, bool h2, bool h3, float t0, float t1, float t2, float t3,
                                                uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, float tn, int& sp, uint32_t& enter, Store store) {

@@ -11,7 +11,8 @@
 // the walk is a property of the ray and the tree and the two walks of a ray take the same steps whichever lane, wavefront or kernel runs
 // them.  Entry k lands at offsets[i] + k without an atomic; each store is one plain 16-byte vector store at a 64-bit index.
 // An entry is pt_rays.h::hit_entry of the accepted tri_hit, the function pt_rayquery.hip::hit_record writes its record with; the ray
-// record, the lane state, the one-ray walk and the LDS streaming loop are pt_rays.h's too, shared with pt_crossings.hip's count walk.
+// record, the lane state and the one-ray walk are pt_rays.h's too, shared with pt_crossings.hip's count walk; the LDS streaming loop and
+// the sink's storage are pt_walk.h's, shared with the point side.
 // Records: PtRay = two float4 (org.xyz, t_max | dir.xyz, reserved), an entry = PtHit = one uint4 (t bits, prim, u bits, v bits).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,18 +24,12 @@
 
 namespace ptk {
 
-// What the three kernels do with a crossing: store its entry when its global index is below the capacity.  base + count is 64-bit: the
-// total of a batch may pass 2^32.
-struct HlSink {
-    uint4* __restrict__ entries; unsigned long long capacity;
-    unsigned long long base = 0; uint32_t count = 0;
+// What the three kernels do with a crossing: pt_walk.h::ListSink's accept -- the entry stored when its global index is below the
+// capacity -- behind the triangle test.
+struct HlSink : ListSink<true> {
     __device__ __forceinline__ void leaf(F3 o, F3 d, float best, uint32_t tri, const uint4 n0, const uint4 n1, const uint4 n2) {
         float t;
-        if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) {
-            const unsigned long long g = base + count;
-            if (g < capacity) entries[g] = hit_entry(o, d, t, tri, n0, n1, n2);
-            ++count;
-        }
+        if (tri_hit(o, d, n0, n1, n2, t) & (t < best)) accept([&]() __attribute__((always_inline)) { return hit_entry(o, d, t, tri, n0, n1, n2); });
     }
 };
 
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(256) void hit_fill_simple_kernel(const RenderArgs A
     F3 o, d; float tmax;
     load_ray(rays, i, o, d, tmax);
     if (!ray_traced(o, d, tmax)) return;
-    HlSink sink{entries, capacity};
+    HlSink sink{{entries, capacity}};
     sink.base = offsets[i];
     Ray r; r.o = o; r.d = d; r.inv = safe_inv(d);
     uint2 stk[kStackMax];
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(64) void hit_fill_kernel(const RenderArgs A, const 
 }
 
 // ------------------------------------------------------------------------------------
-// brute force: one ray per thread, every triangle in index order (pt_rays.h::brute_records)
+// brute force: one ray per thread, every triangle in index order (pt_walk.h::brute_records)
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hit_fill_brute_kernel(const RenderArgs A, const float4* __restrict__ rays, const unsigned long long* __restrict__ offsets,
                                                              uint4* __restrict__ entries, unsigned long long capacity, uint32_t n) {
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(256) void hit_fill_brute_kernel(const RenderArgs A,
     if (i < n) load_ray(rays, i, o, d, tmax);
     const bool walked = (i < n) && ray_traced(o, d, tmax);
     const float best = wmin(tmax, kInfT);
-    HlSink sink{entries, capacity};
+    HlSink sink{{entries, capacity}};
     if (walked) sink.base = offsets[i];
     brute_records(A, walked, [&](uint32_t tri, const uint4 n0, const uint4 n1, const uint4 n2) __attribute__((always_inline)) {
         sink.leaf(o, d, best, tri, n0, n1, n2);

@@ -690,26 +690,84 @@ void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& 
         if (d2 < best2) { best2 = d2; best_tri = tri; }
     });
 }
+
+// What every *_bvh4 twin starts from: the wide tree (none with brute force: bvh4 = nullptr), the triangle records, the walk's view of
+// both, and at most 16 workers with a counter block each.  Worker w of parallel() takes the items [n w / workers, n (w + 1) / workers).
+struct TwinScene {
+    WideBvh wide; std::vector<TriRecord> rec; PointWalk W;
+    uint64_t n = 0, workers = 1; std::vector<WalkCounters> per;
+
+    bool init(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, uint64_t items, std::string& err) {
+        const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
+        if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
+        rec.resize(num_tris);
+        build_tri_records(tris, num_tris, rec.data());
+        W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
+        const unsigned hw = std::thread::hardware_concurrency();
+        n = items; workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
+        per.assign(workers, WalkCounters());
+        return true;
+    }
+    // run(w, first, end)
+    template <class Run>
+    void parallel(Run run) const {
+        auto part = [&](uint64_t w) { run(w, n * w / workers, n * (w + 1) / workers); };
+        if (workers == 1) { part(0); return; }
+        std::vector<std::thread> pool;
+        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(part, w);
+        for (std::thread& t : pool) t.join();
+    }
+    // the five counters of PtStats: `items`, and the workers' blocks summed (the stack depth: their maximum)
+    void reduce(uint64_t* counters, uint64_t items) const {
+        if (!counters) return;
+        counters[0] = items; counters[1] = counters[2] = counters[3] = counters[4] = 0;
+        for (const WalkCounters& c : per) {
+            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
+        }
+    }
+};
+
+// The frame of a list query (radius_search, box_search, list_hits), the device's two walks around its scan.  query(i, cnt, accept) walks
+// item i and calls accept(store) for every accepted leaf in visit order, store(o) writing the 16-byte entry at o.  The count walk leaves
+// the count of item i in offsets[i + 1] until the prefix sum; the fill walk takes the same steps and stores entry k of item i at
+// offsets[i] + k where that is below the capacity (its counters are dropped: the device counts over the count walk), then calls
+// stored(worker, i) behind each list.
+template <class Query, class Stored>
+void list_twin(TwinScene& S, uint64_t* offsets, uint32_t* entries, uint64_t capacity, Query query, Stored stored) {
+    offsets[0] = 0;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        for (uint64_t i = first; i < end; ++i) {
+            uint64_t count = 0;
+            query(i, S.per[w], [&](auto&&) { ++count; });
+            offsets[i + 1] = count;
+        }
+    });
+    for (uint64_t i = 0; i < S.n; ++i) offsets[i + 1] += offsets[i];
+    if (!entries || !capacity) return;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        WalkCounters unused;
+        for (uint64_t i = first; i < end; ++i) {
+            uint64_t g = offsets[i];
+            if (g >= capacity) break;                           // the offsets only grow
+            query(i, unused, [&](auto&& store) { if (g < capacity) store(entries + g * 4); ++g; });
+            stored(w, i);
+        }
+    });
+}
 } // namespace
 
 bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                     uint32_t* out, uint64_t* counters, std::string& err) {
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers);
-    auto run = [&](uint64_t w) {
-        WalkCounters& cnt = per[w];
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    const std::vector<TriRecord>& rec = S.rec;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        WalkCounters& cnt = S.per[w];
+        for (uint64_t i = first; i < end; ++i) {
             const float* q = points + i * 4;
             float best2 = q[3] * q[3]; uint32_t tri = kInvalid;
             if (ptcp::point_walked(q[0], q[1], q[2], q[3])) {
-                if (bvh4) walk_point_h(W, q, best2, tri, cnt);
+                if (bvh4) walk_point_h(S.W, q, best2, tri, cnt);
                 else {
                     for (uint32_t t = 0; t < num_tris; ++t) { const float d2 = record_d2(rec[t], q); if (d2 < best2) { best2 = d2; tri = t; } }
                     cnt.tris += num_tris;
@@ -723,19 +781,8 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
                              r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
             o[0] = bits_of(std::sqrt(best2)); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
         }
-    };
-    if (workers == 1) run(0);
-    else {
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    });
+    S.reduce(counters, n);
     return true;
 }
 
@@ -754,63 +801,23 @@ inline float record_uv_d2(const TriRecord& r, const float p[3], float& u, float&
 
 bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                    uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers), unused(workers);
-    // one point: the walk (or every triangle in index order), each accepted leaf handed to `accept`
-    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    // one point: the walk (or every triangle in index order)
+    list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
+        const float* q = points + i * 4;
         if (!ptcp::point_walked(q[0], q[1], q[2], q[3])) return;
         const float r2 = q[3] * q[3];
         auto leaf = [&](uint32_t t) {
             float u, v;
-            const float d2 = record_uv_d2(rec[t], q, u, v);
-            if (d2 < r2) accept(d2, t, u, v);
+            const float d2 = record_uv_d2(S.rec[t], q, u, v);
+            if (d2 < r2) accept([&](uint32_t* o) { o[0] = bits_of(std::sqrt(d2)); o[1] = t; o[2] = bits_of(u); o[3] = bits_of(v); });
         };
-        if (bvh4) { walk_h(W, q, r2, cnt, leaf); return; }      // r2 never moves: every stacked entry passes its re-validation
+        if (bvh4) { walk_h(S.W, q, r2, cnt, leaf); return; }    // r2 never moves: every stacked entry passes its re-validation
         for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
         cnt.tris += num_tris;
-    };
-    auto parallel = [&](auto run) {
-        if (workers == 1) { run(uint64_t(0)); return; }
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    };
-    // the count walk: offsets[i + 1] holds the count of point i until the scan
-    offsets[0] = 0;
-    parallel([&](uint64_t w) {
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-            uint64_t count = 0;
-            query(points + i * 4, per[w], [&](float, uint32_t, float, float) { ++count; });
-            offsets[i + 1] = count;
-        }
-    });
-    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
-    // the fill walk: the same steps, entry k of point i at offsets[i] + k where that is below the capacity
-    if (entries && capacity) {
-        parallel([&](uint64_t w) {
-            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-                uint64_t g = offsets[i];
-                if (g >= capacity) break;                       // the offsets only grow
-                query(points + i * 4, unused[w], [&](float d2, uint32_t tri, float u, float v) {
-                    if (g < capacity) { uint32_t* o = entries + g * 4; o[0] = bits_of(std::sqrt(d2)); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v); }
-                    ++g;
-                });
-            }
-        });
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    }, [](uint64_t, uint64_t) {});
+    S.reduce(counters, n);
     return true;
 }
 
@@ -821,28 +828,22 @@ bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
 // ------------------------------------------------------------------------------------
 bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* boxes, uint64_t n,
                 uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers), unused(workers);
-    // one box: the walk (or every triangle in index order), each accepted leaf handed to `accept`
-    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    // one box: the walk (or every triangle in index order)
+    list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
+        const float* q = boxes + i * 8;
         if (!ptov::box_walked(q[0], q[1], q[2], q[4], q[5], q[6])) return;
         const ptov::Box b = ptov::make_box(q[0], q[1], q[2], q[4], q[5], q[6]);
         auto leaf = [&](uint32_t t) {
-            const TriRecord& r = rec[t];
+            const TriRecord& r = S.rec[t];
             uint32_t in;
             if (ptov::tri_overlaps(b, r.axis[0][0], r.axis[1][0], r.axis[2][0], r.axis[0][1], r.axis[1][1], r.axis[2][1],
-                                   r.axis[0][2], r.axis[1][2], r.axis[2][2], in)) accept(t, in);
+                                   r.axis[0][2], r.axis[1][2], r.axis[2][2], in)) accept([&](uint32_t* o) { o[0] = t; o[1] = in; o[2] = 0u; o[3] = 0u; });
         };
         if (bvh4) {
             const float bound = 1.0f;
-            walk_keys_h(W, [&](const uint32_t* w) {
+            walk_keys_h(S.W, [&](const uint32_t* w) {
                 const bool meets = ptov::node_overlaps(b, half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu),
                                                        half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16));
                 return meets ? 0.0f : std::numeric_limits<float>::infinity();
@@ -851,42 +852,8 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
         }
         for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
         cnt.tris += num_tris;
-    };
-    auto parallel = [&](auto run) {
-        if (workers == 1) { run(uint64_t(0)); return; }
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    };
-    // the count walk: offsets[i + 1] holds the count of box i until the scan
-    offsets[0] = 0;
-    parallel([&](uint64_t w) {
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-            uint64_t count = 0;
-            query(boxes + i * 8, per[w], [&](uint32_t, uint32_t) { ++count; });
-            offsets[i + 1] = count;
-        }
-    });
-    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
-    // the fill walk: the same steps, entry k of box i at offsets[i] + k where that is below the capacity
-    if (entries && capacity) {
-        parallel([&](uint64_t w) {
-            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-                uint64_t g = offsets[i];
-                if (g >= capacity) break;                       // the offsets only grow
-                query(boxes + i * 8, unused[w], [&](uint32_t tri, uint32_t in) {
-                    if (g < capacity) { uint32_t* o = entries + g * 4; o[0] = tri; o[1] = in; o[2] = 0u; o[3] = 0u; }
-                    ++g;
-                });
-            }
-        });
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    }, [](uint64_t, uint64_t) {});
+    S.reduce(counters, n);
     return true;
 }
 
@@ -898,19 +865,13 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
 bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n, uint32_t k,
                uint32_t* out, uint64_t* counters, std::string& err) {
     if (k == 0u || k > kNearestMaxK) { err = "nearest_k: k must be 1 .. 64"; return false; }
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers);
-    auto run = [&](uint64_t w) {
-        WalkCounters& cnt = per[w];
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    const std::vector<TriRecord>& rec = S.rec;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        WalkCounters& cnt = S.per[w];
         struct Pair { float d2; uint32_t tri; } lst[kNearestMaxK];
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
+        for (uint64_t i = first; i < end; ++i) {
             const float* q = points + i * 4;
             float worst2 = q[3] * q[3];
             uint32_t count = 0;
@@ -925,7 +886,7 @@ bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
                 if (count == k) worst2 = lst[k - 1u].d2;
             };
             if (ptcp::point_walked(q[0], q[1], q[2], q[3])) {
-                if (bvh4) walk_h(W, q, worst2, cnt, leaf);
+                if (bvh4) walk_h(S.W, q, worst2, cnt, leaf);
                 else {
                     for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
                     cnt.tris += num_tris;
@@ -939,19 +900,8 @@ bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
             }
             for (uint32_t j = count; j < k; ++j, o += 4) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; }
         }
-    };
-    if (workers == 1) run(0);
-    else {
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    });
+    S.reduce(counters, n);
     return true;
 }
 
@@ -1401,6 +1351,14 @@ uint32_t walk_cross_h(const PointWalk& W, const RayH& r, float best, WalkCounter
 uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt) {
     return walk_cross_h(W, r, best, cnt, [](float, uint32_t) {});
 }
+// a PtRay record (pt_rays.h::load_ray, ray_traced): whether the ray is walked, and then `best` = min(t_max, kInfT)
+inline bool load_ray_h(const float* q, RayH& r, float& best) {
+    for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
+    const float tmax = q[3];
+    const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
+    best = wmin_h(tmax, kInfT_h);
+    return !nan && tmax > 0.0f;
+}
 // pt_rayquery.hip::hit_record on a triangle record, operation by operation: the u, v of the accepted test
 inline void hit_uv_h(const RayH& r, const TriRecord& rec, float& u, float& v) {
     const float v0[3] = {rec.axis[0][0], rec.axis[1][0], rec.axis[2][0]};
@@ -1422,47 +1380,24 @@ inline void hit_uv_h(const RayH& r, const TriRecord& rec, float& u, float& v) {
 
 bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
                 uint32_t* counts, uint64_t* counters, std::string& err) {
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers);
-    auto run = [&](uint64_t w) {
-        WalkCounters& cnt = per[w];
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-            const float* q = rays + i * 8;
-            RayH r;
-            for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
-            const float tmax = q[3];
-            const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        WalkCounters& cnt = S.per[w];
+        for (uint64_t i = first; i < end; ++i) {
+            RayH r; float best;
             uint32_t count = 0;
-            if (!nan && tmax > 0.0f) {
-                const float best = wmin_h(tmax, kInfT_h);
-                if (bvh4) count = walk_count_h(W, r, best, cnt);
+            if (load_ray_h(rays + i * 8, r, best)) {
+                if (bvh4) count = walk_count_h(S.W, r, best, cnt);
                 else {
-                    for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, rec[t], th) && th < best) ++count; }
+                    for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, S.rec[t], th) && th < best) ++count; }
                     cnt.tris += num_tris;
                 }
             }
             counts[i] = count;
         }
-    };
-    if (workers == 1) run(0);
-    else {
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    });
+    S.reduce(counters, n);
     return true;
 }
 
@@ -1498,75 +1433,32 @@ bool contains(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64
 // ------------------------------------------------------------------------------------
 bool list_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
                uint64_t* offsets, uint32_t* entries, uint64_t capacity, bool sorted, uint64_t* counters, std::string& err) {
-    const uint32_t node_base16 = uint32_t((uint64_t(num_tris) + 1u) * 4u);
-    WideBvh wide;
-    if (bvh4 && !build_wide_bvh(bvh4, words, num_tris, node_base16, wide, err)) return false;
-    std::vector<TriRecord> rec(num_tris);
-    build_tri_records(tris, num_tris, rec.data());
-    PointWalk W; W.rec = rec.data(); W.num_tris = num_tris; W.wide = &wide; W.node_base16 = node_base16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const uint64_t workers = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(hw ? hw : 1u, 16u), n / 256u));
-    std::vector<WalkCounters> per(workers), unused(workers);
-    // one ray: the walk (or every triangle in index order), each crossing handed to accept(ray, t, triangle)
-    auto query = [&](const float* q, WalkCounters& cnt, auto accept) {
-        RayH r;
-        for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
-        const float tmax = q[3];
-        const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
-        if (nan || !(tmax > 0.0f)) return;
-        const float best = wmin_h(tmax, kInfT_h);
-        if (bvh4) { walk_cross_h(W, r, best, cnt, [&](float t, uint32_t tri) { accept(r, t, tri); }); return; }
-        for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, rec[t], th) && th < best) accept(r, th, t); }
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    using Entry = std::array<uint32_t, 4>;
+    std::vector<std::vector<Entry>> lists(S.workers);
+    // one ray: the walk (or every triangle in index order); behind a list that was stored in full, its sort
+    list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
+        RayH r; float best;
+        if (!load_ray_h(rays + i * 8, r, best)) return;
+        auto crossing = [&](float t, uint32_t tri) {
+            accept([&](uint32_t* o) {
+                float u, v; hit_uv_h(r, S.rec[tri], u, v);
+                o[0] = bits_of(t); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
+            });
+        };
+        if (bvh4) { walk_cross_h(S.W, r, best, cnt, crossing); return; }
+        for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, S.rec[t], th) && th < best) crossing(th, t); }
         cnt.tris += num_tris;
-    };
-    auto parallel = [&](auto run) {
-        if (workers == 1) { run(uint64_t(0)); return; }
-        std::vector<std::thread> pool;
-        for (uint64_t w = 0; w < workers; ++w) pool.emplace_back(run, w);
-        for (std::thread& t : pool) t.join();
-    };
-    // the count walk: offsets[i + 1] holds the count of ray i until the scan
-    offsets[0] = 0;
-    parallel([&](uint64_t w) {
-        for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-            uint64_t count = 0;
-            query(rays + i * 8, per[w], [&](const RayH&, float, uint32_t) { ++count; });
-            offsets[i + 1] = count;
-        }
+    }, [&](uint64_t w, uint64_t i) {
+        if (!sorted || offsets[i + 1] > capacity || offsets[i + 1] - offsets[i] <= 1u) return;
+        Entry* first = reinterpret_cast<Entry*>(entries + offsets[i] * 4);
+        std::vector<Entry>& list = lists[w];                    // one buffer per worker
+        list.assign(first, first + (offsets[i + 1] - offsets[i]));
+        std::stable_sort(list.begin(), list.end(), [](const Entry& a, const Entry& b) { return ((uint64_t(a[0]) << 32) | a[1]) < ((uint64_t(b[0]) << 32) | b[1]); });
+        std::memcpy(first, list.data(), list.size() * sizeof(Entry));
     });
-    for (uint64_t i = 0; i < n; ++i) offsets[i + 1] += offsets[i];
-    // the fill walk: the same steps, entry k of ray i at offsets[i] + k where that is below the capacity; then the sort of a list that
-    // was stored in full
-    if (entries && capacity) {
-        parallel([&](uint64_t w) {
-            std::vector<std::array<uint32_t, 4>> list;
-            for (uint64_t i = n * w / workers, e = n * (w + 1) / workers; i < e; ++i) {
-                uint64_t g = offsets[i];
-                if (g >= capacity) break;                       // the offsets only grow
-                query(rays + i * 8, unused[w], [&](const RayH& r, float t, uint32_t tri) {
-                    if (g < capacity) {
-                        float u, v; hit_uv_h(r, rec[tri], u, v);
-                        uint32_t* o = entries + g * 4; o[0] = bits_of(t); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
-                    }
-                    ++g;
-                });
-                if (sorted && offsets[i + 1] <= capacity && offsets[i + 1] - offsets[i] > 1u) {
-                    auto* first = reinterpret_cast<std::array<uint32_t, 4>*>(entries + offsets[i] * 4);
-                    list.assign(first, first + (offsets[i + 1] - offsets[i]));
-                    std::stable_sort(list.begin(), list.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) {
-                        return ((uint64_t(a[0]) << 32) | a[1]) < ((uint64_t(b[0]) << 32) | b[1]);
-                    });
-                    std::memcpy(first, list.data(), list.size() * sizeof(list[0]));
-                }
-            }
-        });
-    }
-    if (counters) {
-        counters[0] = n; counters[1] = counters[2] = counters[3] = counters[4] = 0;
-        for (const WalkCounters& c : per) {
-            counters[1] += c.nodes; counters[2] += c.tris; counters[3] += c.drops; counters[4] = std::max(counters[4], c.maxstack);
-        }
-    }
+    S.reduce(counters, n);
     return true;
 }
 

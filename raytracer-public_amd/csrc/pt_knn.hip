@@ -13,7 +13,8 @@
 // goes behind every pair with d2' <= d2, so equal distances keep visit order, and the pair behind the k-th falls off.  The visit order
 // depends on the point and the tree alone, so the three kernels' walks and the host twin (pt_host.cpp::nearest_k) give the same rows, ties
 // included.  The point-triangle arithmetic is pt_closest.h, shared with the twin.
-// The point record, the slack, box_bound2 and tri_d2 are pt_points.h's, shared with pt_pointquery.hip and pt_radius.hip.
+// The point record, the slack, box_bound2, tri_d2 and the one-point-per-thread walk (key_traverse) are pt_points.h's, shared with
+// pt_pointquery.hip, pt_radius.hip and pt_overlap.hip; the LDS streaming loop (brute_records) is pt_walk.h's.
 // Records: PtPoint = one float4 (p.xyz, r_max), an entry = PtClosest = one uint4 (dist bits, prim, u bits, v bits); row i is
 // out[i * k .. i * k + k - 1], padded with (+inf, 0xFFFFFFFF, 0, 0).  Plain vector stores only; the one atomic is the walk's queue claim.
 #include <hip/hip_runtime.h>
@@ -70,63 +71,18 @@ __device__ __forceinline__ void nk_write_row(uint4* __restrict__ out, const floa
 }
 
 // ------------------------------------------------------------------------------------
-// simple kernel: one point per thread, a private 64-entry stack and a private list; the counters of PT_NEAREST_STATS by the rules of
-// PT_CLOSEST_STATS (pt_pointquery.hip::walk_point with worst2 for best2)
+// simple kernel: one point per thread, a private 64-entry stack and a private list; the walk and the counters of PT_NEAREST_STATS are
+// pt_pointquery.hip::walk_point's (pt_points.h::key_traverse) with worst2 for best2
 // ------------------------------------------------------------------------------------
 template <bool STATS>
 __device__ __forceinline__ void nearest_walk_point(const RenderArgs& A, F3 p, float worst2, uint32_t k, unsigned long long* lst, uint32_t& count,
                                                    uint2* __restrict__ stk, Counters& cnt) {
-    if (A.root_ref == kInvalidRef || A.num_tris == 0u) return;
-    if (STATS) { cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u; }      // the root record is fetched before its degenerate check
-    if (A.root_degenerate) return;
     const PointSlack s = point_slack(p);
-    if (!(box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < worst2)) return;
-    uint32_t cur = A.root_ref;
-    int sp = 0;
-    for (;;) {
-        bool need_pop = false;
-        if (cur & kLeaf) {
-            const uint32_t ti4 = cur & 0x7fffffffu;
-            if (ti4 < 4u * A.num_tris) {                          // an out-of-range leaf points at the record behind the last triangle: skipped
-                const float4* tp = (const float4*)arena_record(A, cur);
-                if (STATS) cnt.tris += 1;
-                const float d2 = tri_d2(p, tp[0], tp[1], tp[2]);
-                if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, cur);
-            }
-            need_pop = true;
-        } else {
-            const uint4* np = arena_record(A, cur);
-            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-            const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
-            const float t0 = box_bound2(s, n0.x, n0.y, n0.z), t1 = box_bound2(s, n1.x, n1.y, n1.z);
-            const float t2 = box_bound2(s, n2.x, n2.y, n2.z), t3 = box_bound2(s, n3.x, n3.y, n3.z);
-            const bool h0 = t0 < worst2, h1 = t1 < worst2, h2 = t2 < worst2, h3 = t3 < worst2;
-            if (STATS) cnt.nodes += (r0 != kInvalidRef) + (r1 != kInvalidRef) + (r2 != kInvalidRef) + (r3 != kInvalidRef);
-            uint32_t enter;
-            const int before = sp;
-            const bool any = h0 | h1 | h2 | h3;
-            const uint32_t wanted = (uint32_t)h0 + (uint32_t)h1 + (uint32_t)h2 + (uint32_t)h3;      // one entered, the others pushed
-            const bool go = order_children(h0, h1, h2, h3, t0, t1, t2, t3, r0, r1, r2, r3, 0.0f, sp, enter, [&](int at, uint32_t ref, float key) __attribute__((always_inline)) {
-                stk[at] = make_uint2(ref, __float_as_uint(key));
-            });
-            if (STATS && any) {
-                // pushes that did not fit, and the nearest child's own when the stack is full (pt_pointquery.hip::walk_point)
-                cnt.drops += (wanted - 1u) - (uint32_t)(sp - before) + (go ? 0u : 1u);
-                const uint32_t depth = (uint32_t)sp + (go ? 1u : 0u);
-                if (depth > cnt.maxstack) cnt.maxstack = depth;
-            }
-            if (go) cur = enter; else need_pop = true;
-        }
-        if (need_pop) {
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                const uint2 e = stk[sp];
-                if (__uint_as_float(e.y) < worst2) { cur = e.x; found = true; break; }
-            }
-            if (!found) break;
-        }
-    }
+    key_traverse<STATS>(A, [&](uint32_t w0, uint32_t w1, uint32_t w2, float& key) __attribute__((always_inline)) { key = box_bound2(s, w0, w1, w2); return key < worst2; }, worst2, stk, cnt,
+                        [&](uint32_t cur, const float4 a, const float4 b, const float4 c) __attribute__((always_inline)) {
+        const float d2 = tri_d2(p, a, b, c);
+        if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, cur);
+    });
 }
 
 template <bool STATS>
@@ -193,14 +149,11 @@ __global__ __launch_bounds__(64) void nearest_k_kernel(const RenderArgs A, const
 }
 
 // ------------------------------------------------------------------------------------
-// brute force: one point per thread, every triangle in index order with the same list rule; a workgroup streams the records through LDS,
-// kNkBruteTile at a time
+// brute force: one point per thread, every triangle in index order with the same list rule (pt_walk.h::brute_records)
 // ------------------------------------------------------------------------------------
-constexpr uint32_t kNkBruteTile = 256;
 template <bool STATS>
 __global__ __launch_bounds__(256) void nearest_k_brute_kernel(const RenderArgs A, const float4* __restrict__ pts, uint4* __restrict__ out,
                                                               uint32_t n, uint32_t k) {
-    __shared__ float4 rec[kNkBruteTile][3];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     F3 p = f3(0, 0, 0); float rmax = 0.0f;
     if (i < n) load_point(pts, i, p, rmax);
@@ -208,25 +161,16 @@ __global__ __launch_bounds__(256) void nearest_k_brute_kernel(const RenderArgs A
     float worst2 = rmax * rmax;
     unsigned long long lst[kNearestMaxK];
     uint32_t count = 0;
-    Counters cnt; cnt.nodes = cnt.tris = cnt.drops = cnt.maxstack = 0;
-    for (uint32_t base = 0; base < A.num_tris; base += kNkBruteTile) {
-        const uint32_t tile = min(kNkBruteTile, A.num_tris - base);
-        __syncthreads();
-        if (threadIdx.x < tile) {
-            const float4* tp = A.tris + (size_t)(base + threadIdx.x) * 4;
-            rec[threadIdx.x][0] = tp[0]; rec[threadIdx.x][1] = tp[1]; rec[threadIdx.x][2] = tp[2];
-        }
-        __syncthreads();
-        if (walked) {
-            for (uint32_t t = 0; t < tile; ++t) {
-                const float d2 = tri_d2(p, rec[t][0], rec[t][1], rec[t][2]);
-                if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, base + t);
-            }
-            if (STATS) cnt.tris += tile;
-        }
-    }
+    brute_records(A, walked, [&](uint32_t t, const uint4 n0, const uint4 n1, const uint4 n2) __attribute__((always_inline)) {
+        const float d2 = tri_d2(p, as_float4(n0), as_float4(n1), as_float4(n2));
+        if (d2 < worst2) worst2 = nk_insert<1>(lst, count, k, worst2, d2, t);
+    });
     if (i < n) nk_write_row<1, 0>(out, A.tris, p, lst, count, k, i);
-    if (STATS) add_stats(A, 0, i < n ? 1u : 0u, cnt);
+    if (STATS) {
+        Counters cnt; cnt.nodes = cnt.drops = cnt.maxstack = 0;
+        cnt.tris = walked ? A.num_tris : 0u;                              // a walked point tests every record
+        add_stats(A, 0, i < n ? 1u : 0u, cnt);
+    }
 }
 
 uint32_t nearest_k_waves_per_simd(uint32_t k) { return k <= 4u ? PT_NK_WAVES_PER_SIMD_4 : k <= 16u ? PT_NK_WAVES_PER_SIMD_16 : PT_NK_WAVES_PER_SIMD_64; }

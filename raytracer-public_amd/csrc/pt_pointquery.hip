@@ -8,7 +8,8 @@
 // a child's box, in place of tmin: children with bound2 < best2 keep slot order, the first minimum trades places with the first of them and is
 // entered next, the others are pushed far -> near, a push at 64 entries is dropped, a stacked child is re-validated at pop.  The
 // point-triangle arithmetic is pt_closest.h, shared with the host twin (pt_host.cpp::closest_points), which gives the same bits.
-// The point record, the slack, box_bound2 and tri_d2 are pt_points.h's, shared with pt_radius.hip and pt_knn.hip.
+// The point record, the slack, box_bound2, tri_d2 and the one-point-per-thread walk (key_traverse) are pt_points.h's, shared with
+// pt_radius.hip, pt_knn.hip and pt_overlap.hip; the LDS streaming loop (brute_records) is pt_walk.h's.
 // Records: PtPoint = one float4 (p.xyz, r_max), PtClosest = one uint4 (dist bits, prim, u bits, v bits).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,65 +33,18 @@ __device__ __forceinline__ uint4 closest_record(const float4* __restrict__ tris,
 }
 
 // ------------------------------------------------------------------------------------
-// simple kernel: one point per thread, a private 64-entry stack; the counters of PT_CLOSEST_STATS by the rules of traverse<..., STATS>
+// simple kernel: one point per thread, a private 64-entry stack (pt_points.h::key_traverse, whose bound the leaves lower); the counters
+// of PT_CLOSEST_STATS by the rules of traverse<..., STATS>
 // ------------------------------------------------------------------------------------
 template <bool STATS>
 __device__ __forceinline__ void walk_point(const RenderArgs& A, F3 p, float& best2, uint32_t& best_tri, uint2* __restrict__ stk, Counters& cnt) {
     best_tri = kInvalidRef;
-    if (A.root_ref == kInvalidRef || A.num_tris == 0u) return;
-    if (STATS) { cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u; }      // the root record is fetched before its degenerate check
-    if (A.root_degenerate) return;
     const PointSlack s = point_slack(p);
-    if (!(box_bound2(s, A.root_box[0], A.root_box[1], A.root_box[2]) < best2)) return;
-    uint32_t cur = A.root_ref;
-    int sp = 0;
-    for (;;) {
-        bool need_pop = false;
-        if (cur & kLeaf) {
-            const uint32_t ti4 = cur & 0x7fffffffu;
-            if (ti4 < 4u * A.num_tris) {                          // an out-of-range leaf points at the record behind the last triangle: skipped
-                const float4* tp = (const float4*)arena_record(A, cur);
-                if (STATS) cnt.tris += 1;
-                const float d2 = tri_d2(p, tp[0], tp[1], tp[2]);
-                if (d2 < best2) { best2 = d2; best_tri = ti4 >> 2; }
-            }
-            need_pop = true;
-        } else {
-            const uint4* np = arena_record(A, cur);
-            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-            const uint32_t r0 = n0.w, r1 = n1.w, r2 = n2.w, r3 = n3.w;
-            const float t0 = box_bound2(s, n0.x, n0.y, n0.z), t1 = box_bound2(s, n1.x, n1.y, n1.z);
-            const float t2 = box_bound2(s, n2.x, n2.y, n2.z), t3 = box_bound2(s, n3.x, n3.y, n3.z);
-            const bool h0 = t0 < best2, h1 = t1 < best2, h2 = t2 < best2, h3 = t3 < best2;
-            if (STATS) cnt.nodes += (r0 != kInvalidRef) + (r1 != kInvalidRef) + (r2 != kInvalidRef) + (r3 != kInvalidRef);
-            int nslot = -1, fslot = -1; float tn = 0.0f, tf = 0.0f; uint32_t rn = kInvalidRef, rf = kInvalidRef;
-            if (h0) { nslot = 0; tn = t0; rn = r0; fslot = 0; tf = t0; rf = r0; }
-            if (h1) { if (nslot < 0 || t1 < tn) { nslot = 1; tn = t1; rn = r1; } if (fslot < 0) { fslot = 1; tf = t1; rf = r1; } }
-            if (h2) { if (nslot < 0 || t2 < tn) { nslot = 2; tn = t2; rn = r2; } if (fslot < 0) { fslot = 2; tf = t2; rf = r2; } }
-            if (h3) { if (nslot < 0 || t3 < tn) { nslot = 3; tn = t3; rn = r3; } if (fslot < 0) { fslot = 3; tf = t3; rf = r3; } }
-            if (nslot < 0) {
-                need_pop = true;
-            } else {
-#define PT_PUSH(REF, B2) do { if (sp < kStackMax) { stk[sp] = make_uint2((REF), __float_as_uint(B2)); ++sp; } else if (STATS) { cnt.drops += 1; } } while (0)
-                if (h3) { if (nslot == 3) { if (fslot != 3) PT_PUSH(rf, tf); } else if (fslot != 3) PT_PUSH(r3, t3); }
-                if (h2) { if (nslot == 2) { if (fslot != 2) PT_PUSH(rf, tf); } else if (fslot != 2) PT_PUSH(r2, t2); }
-                if (h1) { if (nslot == 1) { if (fslot != 1) PT_PUSH(rf, tf); } else if (fslot != 1) PT_PUSH(r1, t1); }
-#undef PT_PUSH
-                if (STATS) { const uint32_t depth = (uint32_t)sp + (sp < kStackMax ? 1u : 0u); if (depth > cnt.maxstack) cnt.maxstack = depth; }
-                if (sp < kStackMax) cur = rn;          // the push of the nearest child would have fitted
-                else { need_pop = true; if (STATS) cnt.drops += 1; }
-            }
-        }
-        if (need_pop) {
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                const uint2 e = stk[sp];
-                if (__uint_as_float(e.y) < best2) { cur = e.x; found = true; break; }
-            }
-            if (!found) break;
-        }
-    }
+    key_traverse<STATS>(A, [&](uint32_t w0, uint32_t w1, uint32_t w2, float& key) __attribute__((always_inline)) { key = box_bound2(s, w0, w1, w2); return key < best2; }, best2, stk, cnt,
+                        [&](uint32_t cur, const float4 a, const float4 b, const float4 c) __attribute__((always_inline)) {
+        const float d2 = tri_d2(p, a, b, c);
+        if (d2 < best2) { best2 = d2; best_tri = (cur & 0x7fffffffu) >> 2; }
+    });
 }
 
 template <bool STATS>
@@ -152,36 +106,25 @@ __global__ __launch_bounds__(64) void closest_points_kernel(const RenderArgs A, 
 }
 
 // ------------------------------------------------------------------------------------
-// brute force: one point per thread, every triangle in index order; a workgroup streams the records through LDS, kBruteTile at a time
+// brute force: one point per thread, every triangle in index order (pt_walk.h::brute_records)
 // ------------------------------------------------------------------------------------
-constexpr uint32_t kBruteTile = 256;
 template <bool STATS>
 __global__ __launch_bounds__(256) void closest_points_brute_kernel(const RenderArgs A, const float4* __restrict__ pts, uint4* __restrict__ out, uint32_t n) {
-    __shared__ float4 rec[kBruteTile][3];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     F3 p = f3(0, 0, 0); float rmax = 0.0f;
     if (i < n) load_point(pts, i, p, rmax);
     const bool walked = (i < n) && ptcp::point_walked(p.x, p.y, p.z, rmax);
     float best2 = rmax * rmax; uint32_t tri = kInvalidRef;
-    Counters cnt; cnt.nodes = cnt.tris = cnt.drops = cnt.maxstack = 0;
-    for (uint32_t base = 0; base < A.num_tris; base += kBruteTile) {
-        const uint32_t count = min(kBruteTile, A.num_tris - base);
-        __syncthreads();
-        if (threadIdx.x < count) {
-            const float4* tp = A.tris + (size_t)(base + threadIdx.x) * 4;
-            rec[threadIdx.x][0] = tp[0]; rec[threadIdx.x][1] = tp[1]; rec[threadIdx.x][2] = tp[2];
-        }
-        __syncthreads();
-        if (walked) {
-            for (uint32_t k = 0; k < count; ++k) {
-                const float d2 = tri_d2(p, rec[k][0], rec[k][1], rec[k][2]);
-                if (d2 < best2) { best2 = d2; tri = base + k; }
-            }
-            if (STATS) cnt.tris += count;
-        }
-    }
+    brute_records(A, walked, [&](uint32_t t, const uint4 n0, const uint4 n1, const uint4 n2) __attribute__((always_inline)) {
+        const float d2 = tri_d2(p, as_float4(n0), as_float4(n1), as_float4(n2));
+        if (d2 < best2) { best2 = d2; tri = t; }
+    });
     if (i < n) out[i] = closest_record(A.tris, p, best2, tri);
-    if (STATS) add_stats(A, 0, i < n ? 1u : 0u, cnt);
+    if (STATS) {
+        Counters cnt; cnt.nodes = cnt.drops = cnt.maxstack = 0;
+        cnt.tris = walked ? A.num_tris : 0u;                              // a walked point tests every record
+        add_stats(A, 0, i < n ? 1u : 0u, cnt);
+    }
 }
 
 hipError_t launch_closest_points(const RenderArgs& A, const void* points, void* out, uint32_t n, bool simple, bool stats, bool brute,

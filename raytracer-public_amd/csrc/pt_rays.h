@@ -9,9 +9,9 @@
 //   * magic_of                                    the host's floor(2^32 / d) for divmod_magic
 //   * RayState                                    the lane state of a persistent_walk Q (pt_walk.h) that walks a ray
 //   * cross_traverse<STATS>                       the one-ray-per-thread walk whose `best` never moves, over a leaf functor
-//   * brute_records                               every triangle record in index order, streamed through LDS
 // Records: PtRay = two float4 (org.xyz, t_max | dir.xyz, reserved), PtSurfel = two float4 (p.xyz, r_max | n.xyz, reserved),
 // PtHit = one uint4 (t bits, prim, u bits, v bits).
+// The LDS streaming loop of the brute-force kernels (brute_records) and the list sink (ListSink) are pt_walk.h's, shared with the point side.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -162,26 +162,6 @@ __device__ __forceinline__ void cross_traverse(const RenderArgs& A, const Ray& r
             }
             if (!found) break;
         }
-    }
-}
-
-// Brute force: a 256-thread workgroup streams every triangle record through LDS, kRayBruteTile at a time, and each thread with `walked`
-// set calls body(triangle, n0, n1, n2) on all of them in index order.  Every thread of the workgroup calls this (the barriers).
-constexpr uint32_t kRayBruteTile = 256;
-template <class Body>
-__device__ __forceinline__ void brute_records(const RenderArgs& A, bool walked, Body body) {
-    __shared__ uint4 rec[kRayBruteTile][3];
-    const uint4* recs = (const uint4*)A.tris;
-    for (uint32_t base = 0; base < A.num_tris; base += kRayBruteTile) {
-        const uint32_t tile = min(kRayBruteTile, A.num_tris - base);
-        __syncthreads();
-        if (threadIdx.x < tile) {
-            const uint4* tp = recs + (size_t)(base + threadIdx.x) * 4;
-            rec[threadIdx.x][0] = tp[0]; rec[threadIdx.x][1] = tp[1]; rec[threadIdx.x][2] = tp[2];
-        }
-        __syncthreads();
-        if (walked)
-            for (uint32_t k = 0; k < tile; ++k) body(base + k, rec[k][0], rec[k][1], rec[k][2]);
     }
 }
 

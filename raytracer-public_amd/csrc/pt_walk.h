@@ -6,6 +6,9 @@
 //                                                 contains_kernel), HitWalk (pt_hitlist.hip: hit_fill_kernel)
 //   points (helpers in pt_points.h)               PointWalk (pt_pointquery.hip: closest_points_kernel), RadiusWalk<FILL> (pt_radius.hip:
 //                                                 radius_kernel), NearestWalk (pt_knn.hip: nearest_k_kernel<KCAP>)
+//   boxes                                         BoxWalk<FILL> (pt_overlap.hip: box_kernel)
+// Also here, because the ray side and the point side both use them: brute_records, the LDS streaming loop of every brute-force kernel,
+// and ListSink<FILL>, what a list query does with an accepted leaf.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -137,6 +140,44 @@ __device__ __forceinline__ void persistent_walk(const RenderArgs& A, uint32_t n,
         if (Q::kWaveHooks) q.after_step(done, lane);
     }
 }
+
+// Brute force, rays and points alike: a 256-thread workgroup streams every triangle record through LDS, kBruteTile at a time, and each
+// thread with `walked` set calls body(triangle, n0, n1, n2) on all of them in index order.  Every thread of the workgroup calls this (the
+// barriers).  A walked thread tests every record: its cnt.tris is num_tris.
+constexpr uint32_t kBruteTile = 256;
+template <class Body>
+__device__ __forceinline__ void brute_records(const RenderArgs& A, bool walked, Body body) {
+    __shared__ uint4 rec[kBruteTile][3];
+    const uint4* recs = (const uint4*)A.tris;
+    for (uint32_t base = 0; base < A.num_tris; base += kBruteTile) {
+        const uint32_t tile = min(kBruteTile, A.num_tris - base);
+        __syncthreads();
+        if (threadIdx.x < tile) {
+            const uint4* tp = recs + (size_t)(base + threadIdx.x) * 4;
+            rec[threadIdx.x][0] = tp[0]; rec[threadIdx.x][1] = tp[1]; rec[threadIdx.x][2] = tp[2];
+        }
+        __syncthreads();
+        if (walked)
+            for (uint32_t k = 0; k < tile; ++k) body(base + k, rec[k][0], rec[k][1], rec[k][2]);
+    }
+}
+
+// What the kernels of a list query (radius search, box search, hit lists) do with an accepted leaf: count it, and with FILL store
+// entry() -- one plain 16-byte vector store -- when its global index is below the capacity.  base + count is 64-bit: the total of a batch
+// may pass 2^32.
+template <bool FILL>
+struct ListSink {
+    uint4* __restrict__ entries; unsigned long long capacity;
+    unsigned long long base = 0; uint32_t count = 0;
+    template <class Entry>
+    __device__ __forceinline__ void accept(Entry entry) {
+        if (FILL) {
+            const unsigned long long g = base + count;
+            if (g < capacity) entries[g] = entry();
+        }
+        ++count;
+    }
+};
 
 // the launch side: the queue block zeroed on `stream`, and `grid` clamped to the number of chunks -- more wavefronts would only find
 // the queue dry

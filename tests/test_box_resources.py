@@ -1,7 +1,8 @@
 """What the compiler made of the box-overlap kernels (pt_overlap.hip), pinned -- compile-only, like test_radius_resources.py.
-box_kernel<FILL> is the persistent walk that the other batched queries are too (pt_walk.h), instantiated in its own translation unit; the
-kernels of the other files keep their own lines (their resource tests), and this file adds no kernel to theirs.  The scan between the two
-walks is pt_radius.hip's, so this translation unit holds the project's own kernels only."""
+box_kernel<FILL> is the persistent walk that the other batched queries are too (pt_walk.h), instantiated in its own translation unit.  Its Q
+(BoxWalk) is in pt_overlap.hip; the bodies of the simple and the brute-force kernel and the dispatch are pt_region.h's, the frame
+radius_simple_kernel and radius_brute_kernel are instantiated from as well (test_radius_resources.py); pt_overlap.hip holds the box
+policy and the __global__ wrappers, whose names and variants are counted here.  The scan between the two walks is pt_radius.hip's, so this translation unit holds the project's own kernels only."""
 
 import re
 

@@ -1,8 +1,9 @@
 """What the compiler made of the k-nearest kernels (pt_knn.hip), pinned -- compile-only, like test_radius_resources.py.
 nearest_k_kernel<KCAP> is the persistent walk that the ray, point, occlusion, crossing and radius queries are too (pt_walk.h), instantiated
-in its own translation unit; the kernels of the other files keep their own lines, which their resource tests pin and this change does not
-touch (pt_knn.hip restates box_bound2 and the slack instead of moving them; pt_walk.h, pt_device.h, pt_closest.h and the sibling .hip
-files are not edited): they run unmodified with the rest of the suite (test_pointquery_resources.py and its siblings)."""
+in its own translation unit with its own Q (NearestWalk).  The simple kernel walks pt_points.h::key_traverse and the brute-force kernel
+streams pt_walk.h::brute_records, the functions the closest-point, radius and box kernels use; the figures of those two kernels are
+recorded as compiled on the shared functions (the brute-force kernel with counters went from 37 to 36 VGPRs when its LDS loop became
+the shared one, profiles/point_share_isa.txt)."""
 import pytest
 
 from kres import HIPCC, resources
@@ -39,7 +40,7 @@ def test_knn_kernels_registers_scratch_lds_and_occupancy():
         assert f["ScratchSize [bytes/lane]"] == 1040, (stats, f)
         assert f["LDS Size [bytes/block]"] == 0, (stats, f)
         assert f["Occupancy [waves/SIMD]"] == 8, (stats, f)
-    for stats, vgprs in ((0, 36), (1, 37)):
+    for stats, vgprs in ((0, 36), (1, 36)):
         f = next(v for k, v in brute.items() if k.startswith("_ZN3ptk22nearest_k_brute_kernelILb%dEE" % stats))
         # 256 records of three 16-byte pieces in LDS; the private list (512 B per lane, 16 B of alignment) is the only scratch use
         assert f["VGPRs"] == vgprs and f["AGPRs"] == 0 and f["VGPRs Spill"] == 0 and f["SGPRs Spill"] == 0, (stats, f)

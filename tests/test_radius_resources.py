@@ -1,6 +1,8 @@
 """What the compiler made of the radius-query kernels (pt_radius.hip), pinned -- compile-only, like test_crossings_resources.py.
 radius_kernel<FILL> is the persistent walk that the ray, point, occlusion and crossing queries are too (pt_walk.h), instantiated in its own
-translation unit; the kernels of the other files keep their own lines (their resource tests), and this file adds no kernel to theirs.
+translation unit with its own Q (RadiusWalk); the simple and the brute-force kernel are instantiated from pt_region.h, the frame they
+share with the box query (test_box_resources.py); pt_radius.hip holds the sphere policy, the __global__ wrappers, whose names and
+variants are counted here, and the scan.
 The translation unit also holds the scan's library kernels (hipcub::DeviceScan), whose number depends on the ROCm release: only the
 project's own kernels are counted."""
 
