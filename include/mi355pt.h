@@ -338,6 +338,58 @@ PT_API int pt_closest_points_host(PtContext* ctx, const PtPoint* points, uint64_
 PT_API int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
                                   const PtPoint* points, uint64_t n, uint32_t flags, PtClosest* out, PtStats* stats);
 
+/* ---- sphere-cast queries: when does a moving sphere first touch the mesh, and where? (an extension beyond the reference; DESIGN.md
+ * section 22) -------------------------------------------------------------------------------------------------------------------
+ * For every sweep -- a sphere of radius `radius` whose centre moves from org along dir -- the first contact with a triangle of the scene
+ * at 0 <= t < t_max, over the context's CURRENT tree, whatever set it (built, installed or refitted).  dir need not be unit length: t is
+ * in units of dir.  radius = 0 is a moving point.
+ *   hit:  t = the time of first contact (0 for a sphere that overlaps a triangle at the start); prim = the triangle touched; u, v = the
+ *         contact point on it as v0 + u*e1 + v*e2: pt_closest_points' (u, v) of the centre c = org + t*dir (the product rounded, then the
+ *         sum) against the winning record, recomputed after the walk.
+ *   miss: t = +INFINITY, prim = 0xFFFFFFFF, u = v = 0.
+ * Sweeps with no walk, a miss: a NaN in org, dir, t_max or radius; t_max <= 0; radius < 0; dir = (0, 0, 0).
+ * Arithmetic (f32, every operation rounded once, no contraction), operation by operation in DESIGN.md section 22 and csrc/pt_sweep.h.
+ *   Per triangle record, in this order: (1) the slab test of pt_trace_rays on the bounds of the record's three vertices, the origin moved
+ *   by the radius (near planes against org + radius or org - radius), which rejects the triangle or gives t_in = max(tmin, 0); (2) the
+ *   squared distance d2 of pt_closest_points from org: d2 <= radius^2 gives t_c = 0; (3) otherwise t_c = the smallest valid candidate of
+ *   the face (approached from the side org is on, the touched point's barycentrics inside the triangle), the three edges as cylinders
+ *   (the smaller root, the foot parameter in [0, 1]) and the three vertices as spheres (the smaller root), roots >= 0 only, each root
+ *   taken from the time t0 and the offset w of the closest approach (a vertex: t0 - sqrt((r^2 - |w|^2) / |dir|^2); an edge: the same in
+ *   cross products with the edge; both written out in csrc/pt_sweep.h);
+ *   (4) t_T = max(t_c, t_in), accepted iff t_T < best, strictly; best starts at t_max and the first minimum in visit order wins.  A
+ *   contact at t_T = 0 ends the walk of its sweep: nothing can be accepted behind it.  A NaN fails every comparison and is never accepted.  A component of dir with |dir_k| <= 1e-8 is
+ *   treated by the box tests as parallel to the slab (pt_trace_rays' safe inverse).
+ * The walk: pt_trace_rays' walk, with a child entered iff the slab test passes on its packed f16 box grown by radius + 2^-12 and its
+ *   key tmin < best; the key orders the children and is re-validated at pop.  The stack holds 64 entries; a push at the cap is dropped
+ *   (and counted).
+ * Exactness: for vertex coordinates within [-4, 4], |org_k| <= 32, radius <= 16 and finite dir, wherever the walk drops nothing at the
+ *   cap (stack_drops = 0) and every triangle is reachable from the root, t has the bits of the brute-force minimum over all triangles,
+ *   and prim is a triangle with exactly that t_T (proof: DESIGN.md section 22).
+ * PT_SWEEP_BRUTE_FORCE, PT_SWEEP_STATS, PT_SWEEP_SIMPLE_KERNEL: as PT_CLOSEST_BRUTE_FORCE, PT_CLOSEST_STATS, PT_CLOSEST_SIMPLE_KERNEL
+ *   (rays_closest = the number of sweeps).
+ * Scene contents: triangles only.  Spheres (pt_set_spheres) take no part.
+ * Ordering, errors and alignment: as pt_trace_rays.  Frames queued by pt_set_batch are launched first; pt_sweep_spheres does not wait
+ *   (the caller's buffers must stay allocated until a later pt_synchronize has returned); a scene change after a query does not change
+ *   its results.  A NULL or non-16-byte-aligned pointer, unknown flags or n > UINT32_MAX: PT_ERR_INVALID_ARG (checked before the
+ *   scene).  No triangles + tree: PT_ERR_NO_SCENE.  n = 0: PT_OK, nothing is launched. */
+typedef struct PtSweep { float org[3]; float t_max; float dir[3]; float radius; } PtSweep;   /* 32 B, 16-byte aligned arrays: PtRay with the radius in the reserved word */
+enum {
+    PT_SWEEP_STATS = 1u,
+    PT_SWEEP_SIMPLE_KERNEL = 2u,
+    PT_SWEEP_BRUTE_FORCE = 4u
+};
+/* n sweeps from device memory, n PtHit records into device memory (both 16-byte aligned, on the context's device).  Asynchronous on the
+ * context's stream (pt_get_stream). */
+PT_API int pt_sweep_spheres(PtContext* ctx, const void* sweeps_device, uint64_t n, uint32_t flags, void* hits_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the hits are written. */
+PT_API int pt_sweep_spheres_host(PtContext* ctx, const PtSweep* sweeps, uint64_t n, uint32_t flags, PtHit* hits);
+/* Host twin (no context, no GPU): the same PtHit bits and, with PT_SWEEP_STATS and stats != NULL, the same counters as the device gives
+ * for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).  bvh4 = NULL (words = 0) only with PT_SWEEP_BRUTE_FORCE; stats
+ * may be NULL; PT_SWEEP_SIMPLE_KERNEL is accepted and changes nothing.  A malformed bvh4: PT_ERR_BAD_BVH; a NULL sweeps or out pointer
+ * with n > 0, or unknown flags: PT_ERR_INVALID_ARG. */
+PT_API int pt_sweep_spheres_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                                 const PtSweep* sweeps, uint64_t n, uint32_t flags, PtHit* out, PtStats* stats);
+
 /* ---- batched ambient-occlusion queries: how open is the hemisphere above a surface point? (an extension beyond the reference;
  * DESIGN.md section 16) ---------------------------------------------------------------------------------------------------------
  * For every surfel (a point p with a normal n) `samples` cosine-distributed rays around n are walked any-hit over the context's CURRENT

@@ -42,6 +42,8 @@ PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
 PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL, PT_HITS_BRUTE_FORCE, PT_HITS_SORTED = 1, 2, 4, 8
 # box-overlap queries (include/mi355pt.h pt_box_search)
 PT_BOX_STATS, PT_BOX_SIMPLE_KERNEL, PT_BOX_BRUTE_FORCE = 1, 2, 4
+# sphere-cast queries (include/mi355pt.h pt_sweep_spheres)
+PT_SWEEP_STATS, PT_SWEEP_SIMPLE_KERNEL, PT_SWEEP_BRUTE_FORCE = 1, 2, 4
 # k-nearest queries (include/mi355pt.h pt_nearest_k)
 PT_NEAREST_STATS, PT_NEAREST_SIMPLE_KERNEL, PT_NEAREST_BRUTE_FORCE = 1, 2, 4
 PT_NEAREST_MAX_K = 64
@@ -94,6 +96,12 @@ class PtPoint(C.Structure):
 class PtClosest(C.Structure):
     """include/mi355pt.h PtClosest (16 B): dist (+inf when nothing is found), prim (0xFFFFFFFF then), u, v of the closest point."""
     _fields_ = [("dist", C.c_float), ("prim", C.c_uint32), ("u", C.c_float), ("v", C.c_float)]
+
+
+class PtSweep(C.Structure):
+    """include/mi355pt.h PtSweep (32 B, the shape of PtRay with the radius in the reserved word); arrays of it must be 16-byte aligned.  As
+    numpy / torch data: 8 float32 per sweep (org xyz, t_max, dir xyz, radius)."""
+    _fields_ = [("org", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("radius", C.c_float)]
 
 
 class PtBox(C.Structure):
@@ -154,6 +162,7 @@ EXPORTS = [
     "pt_box_count", "pt_box_count_host", "pt_box_search", "pt_box_search_host", "pt_box_search_bvh4",
     "pt_list_hits", "pt_list_hits_host", "pt_list_hits_bvh4",
     "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
+    "pt_sweep_spheres", "pt_sweep_spheres_host", "pt_sweep_spheres_bvh4",
     "pt_update_triangles", "pt_update_triangles_device", "pt_bvh_cost", "pt_refit_bvh4", "pt_refit_bvh2", "pt_bvh4_cost", "pt_group_update_triangles",
     "pt_traced_tile_rect", "pt_packed_layout", "pt_packed_tile_ids", "pt_pack_shares", "pt_unpack_batch",
     "pt_group_create", "pt_group_destroy", "pt_group_last_error", "pt_group_size", "pt_group_context", "pt_group_set_triangles", "pt_group_build_bvh",
@@ -261,6 +270,27 @@ def _point_records(points, r_max):
     return pack_points(a, r_max)
 
 
+def pack_sweeps(origins, directions, radius, t_max=None):
+    """numpy: (n, 8) float32 PtSweep records (org xyz, t_max, dir xyz, radius) in a 16-byte aligned buffer; radius a scalar or (n,); t_max
+    None = +inf, a scalar or (n,)."""
+    out = pack_rays(origins, directions, t_max)
+    out[:, 7] = np.broadcast_to(np.asarray(radius, np.float32), (out.shape[0],))
+    return out
+
+
+def _sweep_records(origins, directions, radius, t_max):
+    """(n, 3) origins + directions + radius + t_max, or (n, 8) PtSweep records (directions None; radius, t_max None: taken from the records)
+    -> aligned (n, 8) float32 records."""
+    if directions is not None:
+        return pack_sweeps(origins, directions, 0.0 if radius is None else radius, t_max)
+    rec = _ray_records(origins, None, t_max)
+    if radius is not None:
+        if np.shares_memory(rec, origins):
+            r2 = _aligned_zeros(rec.shape, np.float32); r2[...] = rec; rec = r2      # (the caller's records are never written)
+        rec[:, 7] = radius
+    return rec
+
+
 def pack_boxes(lo, hi):
     """numpy: (n, 8) float32 PtBox records (lo xyz, 0, hi xyz, 0) in a 16-byte aligned buffer."""
     a = np.asarray(lo, np.float32).reshape(-1, 3)
@@ -329,6 +359,10 @@ def _box_flags(stats, simple, brute_force):
 
 def _hits_flags(stats, simple, brute_force, sort):
     return (PT_HITS_STATS if stats else 0) | (PT_HITS_SIMPLE_KERNEL if simple else 0) | (PT_HITS_BRUTE_FORCE if brute_force else 0) | (PT_HITS_SORTED if sort else 0)
+
+
+def _sweep_flags(stats, simple, brute_force):
+    return (PT_SWEEP_STATS if stats else 0) | (PT_SWEEP_SIMPLE_KERNEL if simple else 0) | (PT_SWEEP_BRUTE_FORCE if brute_force else 0)
 
 
 def _nearest_flags(stats, simple, brute_force):
@@ -457,6 +491,23 @@ def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=Fals
     _check(lib.pt_closest_points_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
                                       pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(_closest_flags(stats, simple, brute_force)),
                                       out.ctypes.data_as(C.POINTER(PtClosest)), C.byref(st) if stats else None))
+    res = _columns(out)
+    return res + (st.as_dict(),) if stats else res
+
+
+def sweep_spheres_bvh4(tris, bvh4, origins, directions=None, radius=None, t_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.sweep_spheres (no GPU): the first contact of each moving sphere with `tris` over the tree set_bvh4(bvh4)
+    installs, with the device's bits.  bvh4 None needs brute_force=True.  Returns (t, prim, u, v), and the counters as a dict in fifth place
+    with stats=True."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    rec = _sweep_records(origins, directions, radius, t_max)
+    n = rec.shape[0]
+    out = _aligned_zeros((n, 4), np.uint32)
+    st = PtStats()
+    keep, bp, words = _bvh4_arg(bvh4)
+    _check(lib.pt_sweep_spheres_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
+                                     rec.ctypes.data_as(C.POINTER(PtSweep)), C.c_uint64(n), C.c_uint32(_sweep_flags(stats, simple, brute_force)),
+                                     out.ctypes.data_as(C.POINTER(PtHit)), C.byref(st) if stats else None))
     res = _columns(out)
     return res + (st.as_dict(),) if stats else res
 
@@ -1028,6 +1079,37 @@ class Context:
         """Raw device route: n PtPoint records at ptr -> n PtClosest records at out_ptr (16-byte aligned device pointers).  Asynchronous on
         the context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_closest_points(self.h, C.c_void_p(ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(out_ptr)))
+
+    # ---- sphere-cast queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 22) ----
+    def sweep_spheres(self, origins, directions=None, radius=None, t_max=None, stats=False, simple=False, brute_force=False):
+        """When does a sphere of `radius` that moves from each origin along its direction first touch the mesh, and where?  Returns
+        (t, prim, u, v): t in units of the direction (0 for a sphere that overlaps at the start; +inf and prim = 0xFFFFFFFF on a miss); the
+        contact point is v0 + u * (v1 - v0) + v * (v2 - v0) of triangle prim.
+
+        origins, directions: (n, 3) float32 with radius a scalar or (n,), or origins alone as (n, 8) PtSweep records (pack_sweeps; radius,
+        t_max None: taken from the records).  numpy arrays take the host route (staged, returns when done).  torch tensors on the context's
+        device take the device route: zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's
+        current stream both ways; the results are torch tensors (prim as torch.uint32).
+        stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle in index order, no tree."""
+        flags = _sweep_flags(stats, simple, brute_force)
+        if _is_torch(origins):
+            rec = self._ray_tensor(origins, directions, t_max, "sweep_spheres")
+            if radius is not None or directions is not None:
+                if directions is None:
+                    rec = rec.clone() if rec.data_ptr() == origins.data_ptr() else rec
+                rec[:, 7] = 0.0 if radius is None else radius
+            return _torch_columns(self._torch_launch(rec, (4,), lambda p, n, o: self.sweep_spheres_device(p, n, o, flags)))
+        rec = _sweep_records(origins, directions, radius, t_max)
+        n = rec.shape[0]
+        out = _aligned_zeros((n, 4), np.uint32)
+        self._ck(lib.pt_sweep_spheres_host(self.h, rec.ctypes.data_as(C.POINTER(PtSweep)), C.c_uint64(n), C.c_uint32(flags),
+                                           out.ctypes.data_as(C.POINTER(PtHit))))
+        return _columns(out)
+
+    def sweep_spheres_device(self, ptr, n, out_ptr, flags=0):
+        """Raw device route: n PtSweep records at ptr -> n PtHit records at out_ptr (16-byte aligned device pointers).  Asynchronous on the
+        context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_sweep_spheres(self.h, C.c_void_p(ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(out_ptr)))
 
     # ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 16) ----
     def occlusion(self, surfels, samples, seed=0, bias=1e-4, index_base=0, stats=False, simple=False):

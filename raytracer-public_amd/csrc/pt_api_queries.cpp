@@ -1,5 +1,5 @@
 // pt_api_queries.cpp -- the batched queries over the context's tree (include/mi355pt.h): closest hit / any hit, closest point,
-// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, hit lists and k-nearest, with the host twins
+// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, hit lists, k-nearest and sphere casts, with the host twins
 // (*_bvh4) next to them.
 #include "pt_context.h"
 
@@ -195,6 +195,58 @@ int pt_closest_points_bvh4(const float* tris, uint32_t num_tris, const uint32_t*
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::closest_points(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(points), n,
                             reinterpret_cast<uint32_t*>(out), (flags & PT_CLOSEST_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
+// ---- sphere-cast queries (include/mi355pt.h; pt_sweep.hip) ---------------------------------------------------------------------
+
+static_assert(sizeof(PtSweep) == 32, "PtSweep is read as 2 x 16 B");
+
+namespace {
+constexpr uint32_t kSweepFlags = PT_SWEEP_STATS | PT_SWEEP_SIMPLE_KERNEL | PT_SWEEP_BRUTE_FORCE;
+
+int check_sweep(PtContext* ctx, const char* fn, const void* sweeps, uint64_t n, uint32_t flags, const void* hits) {
+    if (int rc = check_flags(ctx, fn, flags, kSweepFlags)) return rc;
+    if (int rc = check_n(ctx, fn, n, "sweeps")) return rc;
+    if (int rc = check_records(ctx, fn, "sweeps and hits", {sweeps, hits})) return rc;
+    return check_scene(ctx, fn);
+}
+
+// the launch itself: sweeps / hits in device memory
+int sweep_on_stream(PtContext* ctx, const void* sweeps, uint32_t n, uint32_t flags, void* hits) {
+    const bool stats = (flags & PT_SWEEP_STATS) != 0, simple = (flags & PT_SWEEP_SIMPLE_KERNEL) != 0, brute = (flags & PT_SWEEP_BRUTE_FORCE) != 0;
+    Walk W;
+    if (int rc = begin_walk(ctx, n, PT_SW_WAVES_PER_SIMD, PT_SW_SHORT_STACK, stats, !simple && !brute, W)) return rc;
+    if (W.launch) PT_HIP(ctx, ptk::launch_sweep(W.A, sweeps, hits, n, simple, stats, brute, ctx->d_rq_queue.ptr, ctx->d_rq_spill.ptr, W.grid, ctx->stream));
+    return end_walk(ctx, W);
+}
+} // namespace
+
+int pt_sweep_spheres(PtContext* ctx, const void* sweeps_device, uint64_t n, uint32_t flags, void* hits_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_sweep(ctx, "pt_sweep_spheres", sweeps_device, n, flags, hits_device)) return rc;
+    return sweep_on_stream(ctx, sweeps_device, uint32_t(n), flags, hits_device);
+}
+
+int pt_sweep_spheres_host(PtContext* ctx, const PtSweep* sweeps, uint64_t n, uint32_t flags, PtHit* hits) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_sweep(ctx, "pt_sweep_spheres_host", sweeps, n, flags, hits)) return rc;
+    return staged(ctx, n, sweeps, sizeof(PtSweep), ctx->d_rq_hits, hits, sizeof(PtHit),
+                  [&](const void* d_in, void* d_out) { return sweep_on_stream(ctx, d_in, uint32_t(n), flags, d_out); });
+}
+
+int pt_sweep_spheres_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words,
+                          const PtSweep* sweeps, uint64_t n, uint32_t flags, PtHit* out, PtStats* stats) {
+    if (flags & ~kSweepFlags) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_sweep_spheres_bvh4: unknown flags");
+    const bool brute = (flags & PT_SWEEP_BRUTE_FORCE) != 0;
+    if ((!tris && num_tris) || (n && (!sweeps || !out)) || (!bvh4 && !brute)) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_sweep_spheres_bvh4: null pointer");
+    if (n > 0xFFFFFFFFull) return fail(nullptr, PT_ERR_INVALID_ARG, "pt_sweep_spheres_bvh4: more than 2^32 - 1 sweeps");
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::sweep_spheres(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(sweeps), n,
+                           reinterpret_cast<uint32_t*>(out), (flags & PT_SWEEP_STATS) && stats ? counters : nullptr, err))
         return fail(nullptr, PT_ERR_BAD_BVH, err);
     if (stats) stats_from(stats, counters);
     return PT_OK;

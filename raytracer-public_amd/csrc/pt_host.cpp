@@ -6,6 +6,7 @@
 #include "pt_expose.h"
 #include "pt_closest.h"
 #include "pt_overlap.h"
+#include "pt_sweep.h"
 
 #include <cmath>
 #include <cstring>
@@ -853,6 +854,59 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
         for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
         cnt.tris += num_tris;
     }, [](uint64_t, uint64_t) {});
+    S.reduce(counters, n);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Sphere-cast queries (host twin of pt_sweep.hip): the walk with the key of a child = tmin of the slab test on its box grown by r + s,
+// +inf where that test fails, against `best`, which starts at t_max and shrinks to each accepted t_T.  The arithmetic is pt_sweep.h, the
+// text the kernels compile.
+// ------------------------------------------------------------------------------------
+bool sweep_spheres(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* sweeps, uint64_t n,
+                   uint32_t* out, uint64_t* counters, std::string& err) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    const std::vector<TriRecord>& rec = S.rec;
+    S.parallel([&](uint64_t w, uint64_t first, uint64_t end) {
+        WalkCounters& cnt = S.per[w];
+        for (uint64_t i = first; i < end; ++i) {
+            const float* q = sweeps + i * 8;
+            const float o[3] = {q[0], q[1], q[2]}, d[3] = {q[4], q[5], q[6]}, r = q[7];
+            float best = q[3]; uint32_t tri = kInvalid;
+            if (ptsw::sweep_walked(o[0], o[1], o[2], q[3], d[0], d[1], d[2], r)) {
+                const float inv[3] = {ptsw::safe_inv(d[0]), ptsw::safe_inv(d[1]), ptsw::safe_inv(d[2])};
+                auto leaf = [&](uint32_t t) {
+                    const TriRecord& tr = rec[t];
+                    const float tt = ptsw::tri_sweep(o[0], o[1], o[2], d[0], d[1], d[2], inv[0], inv[1], inv[2], r, best, tr.axis[0][0], tr.axis[1][0], tr.axis[2][0],
+                                                     tr.axis[0][1], tr.axis[1][1], tr.axis[2][1], tr.axis[0][2], tr.axis[1][2], tr.axis[2][2]);
+                    if (tt < best) { best = ptsw::bound_after(tt); tri = t; }
+                };
+                if (bvh4) {
+                    const float R = r + ptcp::kSlack;
+                    const float op[3] = {o[0] + R, o[1] + R, o[2] + R}, om[3] = {o[0] - R, o[1] - R, o[2] - R};
+                    walk_keys_h(S.W, [&](const uint32_t* bw) {
+                        float tmin;
+                        const bool pass = ptsw::node_pass(half_to_float(bw[0] & 0xffffu), half_to_float(bw[0] >> 16), half_to_float(bw[1] & 0xffffu),
+                                                          half_to_float(bw[1] >> 16), half_to_float(bw[2] & 0xffffu), half_to_float(bw[2] >> 16),
+                                                          op[0], op[1], op[2], om[0], om[1], om[2], inv[0], inv[1], inv[2], best, tmin);
+                        return pass ? tmin : std::numeric_limits<float>::infinity();
+                    }, best, cnt, leaf);
+                } else {
+                    for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+                    cnt.tris += num_tris;
+                }
+            }
+            uint32_t* po = out + i * 4;
+            if (tri == kInvalid) { po[0] = 0x7F800000u; po[1] = kInvalid; po[2] = 0u; po[3] = 0u; continue; }
+            const TriRecord& tr = rec[tri];
+            float u, v;
+            best = ptsw::time_of(best);
+            ptsw::contact_uv(o[0], o[1], o[2], d[0], d[1], d[2], best, tr.axis[0][0], tr.axis[1][0], tr.axis[2][0],
+                             tr.axis[0][1], tr.axis[1][1], tr.axis[2][1], tr.axis[0][2], tr.axis[1][2], tr.axis[2][2], u, v);
+            po[0] = bits_of(best); po[1] = tri; po[2] = bits_of(u); po[3] = bits_of(v);
+        }
+    });
     S.reduce(counters, n);
     return true;
 }

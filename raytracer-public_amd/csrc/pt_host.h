@@ -120,6 +120,14 @@ bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
 bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* boxes, uint64_t n,
                 uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
 
+// ---- sphere-cast queries (pt_sweep_spheres; host twin of pt_sweep.hip, bit for bit) ----------------------------------------------------
+// sweeps: n x (org.xyz, t_max, dir.xyz, radius); out: n x (t bits, prim, u bits, v bits).  bvh4 = nullptr: every triangle in index order;
+// else closest_points' walk with the key of a child = tmin of the slab test on its box grown by r + s (pt_sweep.h::node_pass) and `best`
+// shrinking to each accepted t_T, with the arithmetic of pt_sweep.h.  counters (optional): sweeps, nodes examined, triangles tested,
+// stack drops, max stack -- as the device's PT_SWEEP_STATS counts them.
+bool sweep_spheres(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* sweeps, uint64_t n,
+                   uint32_t* out, uint64_t* counters, std::string& err);
+
 // ---- k-nearest queries (pt_nearest_k; host twin of pt_knn.hip, bit for bit) -----------------------------------------------------------
 // points: n x (x, y, z, r_max); out: n * k records of four words (dist bits, prim, u bits, v bits), row i at out + i * k * 4: the at most k
 // triangles nearest to point i within r_max in ascending order of distance, equal distances in visit order (index order without a tree),

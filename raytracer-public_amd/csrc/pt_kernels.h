@@ -96,6 +96,17 @@
 #ifndef PT_BX_FILL
 #define PT_BX_FILL 8                // idle lanes of a wavefront at which they take the next boxes of its chunk
 #endif
+// sphere-cast queries (pt_sweep.hip): the ray queries' values taken over.  tools/sweep_bench.py ran with them (profiles/sweep_ab.json); no
+// other value has been tried, so as choices they are unmeasured
+#ifndef PT_SW_SHORT_STACK
+#define PT_SW_SHORT_STACK 12        // LDS stack entries per lane of sweep_kernel; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_SW_WAVES_PER_SIMD
+#define PT_SW_WAVES_PER_SIMD 6      // wavefronts of sweep_kernel per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_SW_FILL
+#define PT_SW_FILL 8                // idle lanes of a wavefront at which they take the next sweeps of its chunk
+#endif
 // hit lists (pt_hitlist.hip): the crossing counts' values taken over for the fill walk, unmeasured for it until tools/hitlist_bench.py has run
 #ifndef PT_HL_SHORT_STACK
 #define PT_HL_SHORT_STACK 12        // LDS stack entries per lane of hit_fill_kernel; deeper entries spill to the context's spill area
@@ -290,6 +301,11 @@ hipError_t launch_camera_rays(const RenderArgs& A, void* rays, hipStream_t strea
 // spill entries.
 hipError_t launch_closest_points(const RenderArgs& A, const void* points, void* out, uint32_t n, bool simple, bool stats, bool brute,
                                  unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// ---- sphere-cast queries (pt_sweep.hip) ------------------------------------------------------
+// sweeps: PtSweep[n] (2 x float4 each), hits: PtHit[n] (uint4 each), both 16-byte aligned device memory.  brute, simple, stats, grid,
+// queue and spill as launch_closest_points, with PT_SW_WAVES_PER_SIMD and PT_SW_SHORT_STACK.
+hipError_t launch_sweep(const RenderArgs& A, const void* sweeps, void* hits, uint32_t n, bool simple, bool stats, bool brute,
+                        unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- batched ambient-occlusion queries (pt_occlusion.hip) -------------------------------------
 // surfels: PtSurfel[n] (2 x float4 each), out: PtOcclusion[n] (uint4 each), 16-byte aligned device memory; n * samples <= 2^32 - 1.  The launch
 // zeroes `out`, counts the unoccluded samples of every traced surfel into word 1 of its record and completes the records in a finishing

@@ -193,6 +193,23 @@ class PathTracer {
     const o = options || {};
     return this.group ? native().groupContains(this.group, points, o) : native().contains(this.device, points, o);
   }
+  // ---- sphere-cast queries: an extension beyond the reference (include/mi355pt.h pt_sweep_spheres, DESIGN.md section 22) ----
+  // sweeps: Float32Array, 8 floats per sweep (origin xyz, tMax, direction xyz, radius).  Resolves to { t, prim, u, v } (Float32Array /
+  // Uint32Array): the first contact of the moving sphere with the mesh over the current tree, t in units of the direction (0 for a sphere
+  // that overlaps at the start) and the contact point as v0 + u (v1 - v0) + v (v2 - v0); a miss has t = Infinity, prim = 0xFFFFFFFF,
+  // u = v = 0.  options.bruteForce: every triangle, no tree; options.simple: the one-sweep-per-thread kernel.  Triangles only.  On a
+  // group: member 0, which holds the whole scene.
+  async sweepSpheres(sweeps, options) {
+    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
+    return this.group ? native().groupSweepSpheres(this.group, sweeps, flags) : native().sweepSpheres(this.device, sweeps, flags);
+  }
+  // One sphere of radius r from (ox, oy, oz) along (dx, dy, dz): resolves to { hit, t, prim, u, v, center }, center = origin + t * direction.
+  async sweep(ox, oy, oz, dx, dy, dz, r) {
+    const q = await this.sweepSpheres(Float32Array.of(ox, oy, oz, Infinity, dx, dy, dz, r));
+    const hit = q.prim[0] !== 0xFFFFFFFF, t = q.t[0];
+    return { hit: hit, t: t, prim: q.prim[0], u: q.u[0], v: q.v[0], center: hit ? [ox + t * dx, oy + t * dy, oz + t * dz] : null };
+  }
+
   // closestPoints with the sign of contains: { dist, prim, u, v }, dist negative inside (-Infinity: inside, and nothing within rMax)
   async signedDistance(points, options) {
     const o = options || {};

@@ -398,6 +398,40 @@ static napi_value fn_closest_points(napi_env env, napi_callback_info info) {    
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
 
+/* ---- sphere-cast queries (an extension beyond the reference; include/mi355pt.h pt_sweep_spheres_host) ------------------------------ */
+
+/* sweeps: Float32Array of 8 floats per sweep (PtSweep: org xyz, tMax, dir xyz, radius) -> { t: Float32Array, prim: Uint32Array, u, v };
+ * flags: PT_SWEEP_*.  The records are copied into 16-byte aligned host memory, as the rays are. */
+static napi_value sweep_spheres_on(napi_env env, PtContext* ctx, napi_value sweeps_v, napi_value flags_v) {
+    void* d; size_t len; if (!get_typed(env, sweeps_v, napi_float32_array, &d, &len)) return NULL;
+    if (len % 8) { napi_throw_range_error(env, NULL, "sweepSpheres: 8 floats per sweep"); return NULL; }
+    const uint32_t flags = get_u32(env, flags_v);
+    const size_t n = len / 8;
+    PtSweep* sw = (PtSweep*)aligned_alloc(16, (n ? n : 1) * sizeof(PtSweep));
+    PtHit* hits = (PtHit*)aligned_alloc(16, (n ? n : 1) * sizeof(PtHit));
+    if (!sw || !hits) { free(sw); free(hits); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (n) memcpy(sw, d, n * sizeof(PtSweep));
+    int rc = pt_sweep_spheres_host(ctx, sw, n, flags, hits);
+    free(sw);
+    if (rc != 0) { free(hits); return throw_pt(env, ctx, rc, "pt_sweep_spheres_host"); }
+    napi_value o, t, prim, u, v; void *pt, *pp, *pu, *pv;
+    if (!(t = make_typed(env, napi_float32_array, 4, n, &pt)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
+        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(hits); return NULL; }
+    for (size_t i = 0; i < n; ++i) {
+        ((float*)pt)[i] = hits[i].t; ((uint32_t*)pp)[i] = hits[i].prim; ((float*)pu)[i] = hits[i].u; ((float*)pv)[i] = hits[i].v;
+    }
+    free(hits);
+    NAPI_OK(napi_create_object(env, &o));
+    napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
+    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+    return o;
+}
+static napi_value fn_sweep_spheres(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array sweeps, flags) */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    return sweep_spheres_on(env, ctx, argv[1], argv[2]);
+}
+
 /* ---- k-nearest queries (an extension beyond the reference; include/mi355pt.h pt_nearest_k_host) ------------------------------------- */
 
 /* points: Float32Array of 4 floats per point (PtPoint: x, y, z, rMax), k: 1 .. PT_NEAREST_MAX_K -> { k, dist: Float32Array of n * k, prim:
@@ -981,6 +1015,12 @@ static napi_value fn_group_closest_points(napi_env env, napi_callback_info info)
     PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
     return closest_points_on(env, ctx, argv[1], argv[2]);
 }
+static napi_value fn_group_sweep_spheres(napi_env env, napi_callback_info info) {   /* (group, sweeps, flags): on member 0, which holds the whole scene */
+    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
+    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
+    return sweep_spheres_on(env, ctx, argv[1], argv[2]);
+}
 static napi_value fn_group_occlusion(napi_env env, napi_callback_info info) {       /* (group, surfels, options): on member 0, which holds the whole scene */
     napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -1105,6 +1145,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
         {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
         {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
+        {"sweepSpheres", fn_sweep_spheres}, {"groupSweepSpheres", fn_group_sweep_spheres},
         {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
         {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
         {"nearestK", fn_nearest_k}, {"groupNearestK", fn_group_nearest_k},
