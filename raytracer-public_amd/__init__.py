@@ -10,6 +10,7 @@ host is the Node side in raytracer-public_amd/js/ over the N-API addon.
 There is no CPU fallback: if the shared library is missing the import fails, and creating a
 context without a HIP device raises ``PtError``.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -258,16 +259,62 @@ def pack_points(points, r_max=None):
     return out
 
 
-def _point_records(points, r_max):
-    """(n, 3) points + r_max, or (n, 4) PtPoint records (r_max None: taken from the records) -> aligned (n, 4) float32 records."""
+def _records(a, overrides=()):
+    """The one numpy rule: aligned contiguous float32 (n, w) records for the C side.  The caller's array when it already qualifies and nothing
+    is overridden, a copy otherwise.  overrides: (column, value) pairs; a value of None leaves the column as it is."""
+    rec = a
+    if rec.ctypes.data % 16 or not rec.flags.c_contiguous:
+        rec = _aligned_zeros(a.shape, a.dtype); rec[...] = a
+    for c, v in overrides:
+        if v is not None:
+            if rec is a:
+                rec = _aligned_zeros(a.shape, a.dtype); rec[...] = a       # (the caller's records are never written)
+            rec[:, c] = v
+    return rec
+
+
+def _torch_device(t, what):
+    """the device of a torch argument of query `what`, which must be the context's GPU"""
+    _torch_route()
+    if t.device.type != "cuda":
+        raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, t.device))
+    return t.device
+
+
+def _torch_records(t, what, overrides=(), dtype="float32", width=None):
+    """The one torch rule, the same as _records: aligned contiguous `dtype` records on the context's GPU (reshaped to `width` words each
+    where one is given), the caller's tensor when it already qualifies and nothing is overridden."""
+    import torch
+    _torch_device(t, what)
+    rec, dtype = t if width is None else t.reshape(-1, width), getattr(torch, dtype)
+    if rec.dtype != dtype or not rec.is_contiguous() or rec.data_ptr() % 16:
+        rec = rec.to(dtype).contiguous().clone()
+    for c, v in overrides:
+        if v is not None:
+            rec = rec.clone() if rec.data_ptr() == t.data_ptr() else rec       # (a copy only while the records still alias the caller's tensor)
+            rec[:, c] = v
+    return rec
+
+
+def _torch_column(value, n, dev, default):
+    """(n, 1) float32 on dev: `default` where value is None, else the scalar or (n,) value"""
+    import torch
+    if value is None:
+        return torch.full((n, 1), default, dtype=torch.float32, device=dev)
+    return torch.as_tensor(value, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+
+
+def _point_records(points, r_max, what=None):
+    """(n, 3) points + r_max, or (n, 4) PtPoint records (r_max None: taken from the records) -> aligned (n, 4) float32 records; of a torch
+    tensor (`what` names the query in its errors) the same as a tensor."""
+    if _is_torch(points):
+        if points.dim() == 2 and points.shape[1] == 4:
+            return _torch_records(points, what, ((3, r_max),))
+        import torch
+        dev, p = _torch_device(points, what), points.reshape(-1, 3).to(torch.float32)
+        return torch.cat([p, _torch_column(r_max, p.shape[0], dev, float("inf"))], dim=1).contiguous()
     a = np.asarray(points, np.float32)
-    if a.ndim == 2 and a.shape[1] == 4:
-        if a.ctypes.data % 16 or not a.flags.c_contiguous or r_max is not None:
-            r2 = _aligned_zeros(a.shape, np.float32); r2[...] = a; a = r2          # (the caller's records are never written)
-            if r_max is not None:
-                a[:, 3] = r_max
-        return a
-    return pack_points(a, r_max)
+    return _records(a, ((3, r_max),)) if a.ndim == 2 and a.shape[1] == 4 else pack_points(a, r_max)
 
 
 def pack_sweeps(origins, directions, radius, t_max=None):
@@ -278,17 +325,16 @@ def pack_sweeps(origins, directions, radius, t_max=None):
     return out
 
 
-def _sweep_records(origins, directions, radius, t_max):
+def _sweep_records(origins, directions, radius, t_max, what=None):
     """(n, 3) origins + directions + radius + t_max, or (n, 8) PtSweep records (directions None; radius, t_max None: taken from the records)
-    -> aligned (n, 8) float32 records."""
-    if directions is not None:
-        return pack_sweeps(origins, directions, 0.0 if radius is None else radius, t_max)
-    rec = _ray_records(origins, None, t_max)
-    if radius is not None:
-        if np.shares_memory(rec, origins):
-            r2 = _aligned_zeros(rec.shape, np.float32); r2[...] = rec; rec = r2      # (the caller's records are never written)
-        rec[:, 7] = radius
-    return rec
+    -> aligned (n, 8) float32 records; of torch tensors the same as a tensor."""
+    if directions is None:
+        return _ray_records(origins, None, t_max, what, radius)
+    if _is_torch(origins):
+        rec = _ray_records(origins, directions, t_max, what)
+        rec[:, 7] = 0.0 if radius is None else radius
+        return rec
+    return pack_sweeps(origins, directions, 0.0 if radius is None else radius, t_max)
 
 
 def pack_boxes(lo, hi):
@@ -303,9 +349,21 @@ def pack_boxes(lo, hi):
     return out
 
 
-def _box_records(lo, hi):
-    """(n, 3) lo + hi, or (n, 8) PtBox records (hi None) -> aligned (n, 8) float32 records."""
-    return pack_boxes(lo, hi) if hi is not None else _records8(lo, "box records")
+def _box_records(lo, hi, what=None):
+    """(n, 3) lo + hi, or (n, 8) PtBox records (hi None) -> aligned (n, 8) float32 records; of torch tensors the same as a tensor."""
+    if not _is_torch(lo):
+        return pack_boxes(lo, hi) if hi is not None else _records8(lo, "box records")
+    import torch
+    dev = _torch_device(lo, what)
+    if hi is None:
+        if lo.dim() != 2 or lo.shape[1] != 8:
+            raise ValueError("%s: expected (n, 8) PtBox records or lo and hi of shape (n, 3), got shape %s" % (what, tuple(lo.shape)))
+        return _torch_records(lo, what)
+    a = lo.reshape(-1, 3).to(torch.float32); b = hi.reshape(-1, 3).to(device=dev, dtype=torch.float32)
+    if a.shape != b.shape:
+        raise ValueError("%s: lo and hi differ in shape: %s vs %s" % (what, tuple(a.shape), tuple(b.shape)))
+    z = torch.zeros((a.shape[0], 1), dtype=torch.float32, device=dev)
+    return torch.cat([a, z, b, z], dim=1).contiguous()
 
 
 def pack_surfels(points, normals, r_max=None):
@@ -314,19 +372,36 @@ def pack_surfels(points, normals, r_max=None):
 
 
 def _records8(a, what):
-    """(n, 8) float32 records in a 16-byte aligned, contiguous numpy buffer (the caller's array when it already is one)."""
+    """(n, 8) float32 records in a 16-byte aligned, contiguous numpy buffer (the caller's array when it already is one); of a torch tensor
+    the same as a tensor."""
+    if _is_torch(a):
+        return _torch_records(a, what, width=8)
     a = np.asarray(a, np.float32)
     if a.ndim != 2 or a.shape[1] != 8:
         raise ValueError("%s: expected (n, 8) float32 records, got shape %s" % (what, a.shape))
-    if a.ctypes.data % 16 or not a.flags.c_contiguous:
-        r2 = _aligned_zeros(a.shape, np.float32); r2[...] = a; a = r2
-    return a
+    return _records(a)
+
+
+# one flag word serves every query but trace_rays (whose bit 1 is PT_TRACE_ANY_HIT): the headers' constants share their values, as the C
+# front end asserts for box and radius
+_QUERY_STATS, _QUERY_SIMPLE_KERNEL, _QUERY_BRUTE_FORCE = 1, 2, 4
+assert {PT_CLOSEST_STATS, PT_OCCLUSION_STATS, PT_COUNT_STATS, PT_CONTAIN_STATS, PT_RADIUS_STATS, PT_HITS_STATS, PT_BOX_STATS,
+        PT_SWEEP_STATS, PT_NEAREST_STATS} == {_QUERY_STATS}
+assert {PT_CLOSEST_SIMPLE_KERNEL, PT_OCCLUSION_SIMPLE_KERNEL, PT_COUNT_SIMPLE_KERNEL, PT_CONTAIN_SIMPLE_KERNEL, PT_RADIUS_SIMPLE_KERNEL,
+        PT_HITS_SIMPLE_KERNEL, PT_BOX_SIMPLE_KERNEL, PT_SWEEP_SIMPLE_KERNEL, PT_NEAREST_SIMPLE_KERNEL} == {_QUERY_SIMPLE_KERNEL}
+assert {PT_CLOSEST_BRUTE_FORCE, PT_COUNT_BRUTE_FORCE, PT_RADIUS_BRUTE_FORCE, PT_HITS_BRUTE_FORCE, PT_BOX_BRUTE_FORCE, PT_SWEEP_BRUTE_FORCE,
+        PT_NEAREST_BRUTE_FORCE} == {_QUERY_BRUTE_FORCE}
+
+
+def _flags(stats, simple, brute_force=False, sort=False):
+    """the flag word of a query: PT_*_STATS | PT_*_SIMPLE_KERNEL | PT_*_BRUTE_FORCE | PT_HITS_SORTED"""
+    return (_QUERY_STATS if stats else 0) | (_QUERY_SIMPLE_KERNEL if simple else 0) | (_QUERY_BRUTE_FORCE if brute_force else 0) | (PT_HITS_SORTED if sort else 0)
 
 
 def _occlusion_params(samples, seed, bias, index_base, stats=False, simple=False):
     p = PtOcclusionParams()
     p.samples, p.seed, p.index_base, p.bias = int(samples), int(seed) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, float(bias)
-    p.flags = (PT_OCCLUSION_STATS if stats else 0) | (PT_OCCLUSION_SIMPLE_KERNEL if simple else 0)
+    p.flags = _flags(stats, simple)
     return p
 
 
@@ -341,64 +416,26 @@ def occlusion_rays_host(surfels, samples, seed=0, bias=1e-4, index_base=0):
     return rays
 
 
-def _closest_flags(stats, simple, brute_force):
-    return (PT_CLOSEST_STATS if stats else 0) | (PT_CLOSEST_SIMPLE_KERNEL if simple else 0) | (PT_CLOSEST_BRUTE_FORCE if brute_force else 0)
-
-
-def _count_flags(stats, simple, brute_force):
-    return (PT_COUNT_STATS if stats else 0) | (PT_COUNT_SIMPLE_KERNEL if simple else 0) | (PT_COUNT_BRUTE_FORCE if brute_force else 0)
-
-
-def _radius_flags(stats, simple, brute_force):
-    return (PT_RADIUS_STATS if stats else 0) | (PT_RADIUS_SIMPLE_KERNEL if simple else 0) | (PT_RADIUS_BRUTE_FORCE if brute_force else 0)
-
-
-def _box_flags(stats, simple, brute_force):
-    return (PT_BOX_STATS if stats else 0) | (PT_BOX_SIMPLE_KERNEL if simple else 0) | (PT_BOX_BRUTE_FORCE if brute_force else 0)
-
-
-def _hits_flags(stats, simple, brute_force, sort):
-    return (PT_HITS_STATS if stats else 0) | (PT_HITS_SIMPLE_KERNEL if simple else 0) | (PT_HITS_BRUTE_FORCE if brute_force else 0) | (PT_HITS_SORTED if sort else 0)
-
-
-def _sweep_flags(stats, simple, brute_force):
-    return (PT_SWEEP_STATS if stats else 0) | (PT_SWEEP_SIMPLE_KERNEL if simple else 0) | (PT_SWEEP_BRUTE_FORCE if brute_force else 0)
-
-
-def _nearest_flags(stats, simple, brute_force):
-    return (PT_NEAREST_STATS if stats else 0) | (PT_NEAREST_SIMPLE_KERNEL if simple else 0) | (PT_NEAREST_BRUTE_FORCE if brute_force else 0)
-
-
-def _columns(rec):
-    """(..., 4) uint32 result records (PtHit, PtClosest: f32, u32, f32, f32) -> their four columns, (t | dist, prim, u, v), as copies"""
-    f = rec.view(np.float32)
-    return f[..., 0].copy(), rec[..., 1].copy(), f[..., 2].copy(), f[..., 3].copy()
-
-
-def _torch_columns(rec):
-    """the same of a torch (..., 4) int32 tensor, as views of it (prim as torch.uint32)"""
-    import torch
-    f = rec.view(torch.float32)
-    return f[..., 0], rec.view(torch.uint32)[..., 1], f[..., 2], f[..., 3]
-
-
 def _contain_params(samples, seed, index_base, stats=False, simple=False):
     p = PtContainParams()
     p.samples, p.seed, p.index_base = int(samples) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF
-    p.flags = (PT_CONTAIN_STATS if stats else 0) | (PT_CONTAIN_SIMPLE_KERNEL if simple else 0)
+    p.flags = _flags(stats, simple)
     return p
 
 
-def _ray_records(origins, directions, t_max):
-    """(n, 3) origins + directions + t_max, or (n, 8) PtRay records (t_max None: taken from the records) -> aligned (n, 8) float32 records."""
+def _ray_records(origins, directions, t_max, what=None, radius=None):
+    """(n, 3) origins + directions + t_max, or (n, 8) PtRay records (t_max None: taken from the records) -> aligned (n, 8) float32 records
+    (radius: a sweep's, over the eighth float of packed records); of torch tensors the same as a tensor."""
+    if _is_torch(origins):
+        if directions is None:
+            return _torch_records(origins, what, ((3, t_max), (7, radius)), width=8)
+        import torch
+        dev, o = _torch_device(origins, what), origins.reshape(-1, 3).to(torch.float32)
+        d, n = directions.reshape(-1, 3).to(device=dev, dtype=torch.float32), o.shape[0]
+        return torch.cat([o, _torch_column(t_max, n, dev, float("inf")), d, _torch_column(None, n, dev, 0.0)], dim=1).contiguous()
     if directions is not None:
         return pack_rays(origins, directions, t_max)
-    rays = np.asarray(origins, np.float32).reshape(-1, 8)
-    if rays.ctypes.data % 16 or not rays.flags.c_contiguous or t_max is not None:
-        r2 = _aligned_zeros(rays.shape, np.float32); r2[...] = rays; rays = r2     # (the caller's records are never written)
-        if t_max is not None:
-            rays[:, 3] = t_max
-    return rays
+    return _records(np.asarray(origins, np.float32).reshape(-1, 8), ((3, t_max), (7, radius)))   # (numpy's own error for a wrong size)
 
 
 def _check(rc, ctx=None):
@@ -479,39 +516,6 @@ def refit_bvh4(tris, bvh4):
     return out
 
 
-def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=False, brute_force=False):
-    """Host twin of Context.closest_points (no GPU): the nearest triangle of `tris` to each point over the tree set_bvh4(bvh4) installs, with
-    the device's bits.  bvh4 None needs brute_force=True.  Returns (dist, prim, u, v), and the counters as a dict in fifth place with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    pts = _point_records(points, r_max)
-    n = pts.shape[0]
-    out = _aligned_zeros((n, 4), np.uint32)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    _check(lib.pt_closest_points_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                      pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(_closest_flags(stats, simple, brute_force)),
-                                      out.ctypes.data_as(C.POINTER(PtClosest)), C.byref(st) if stats else None))
-    res = _columns(out)
-    return res + (st.as_dict(),) if stats else res
-
-
-def sweep_spheres_bvh4(tris, bvh4, origins, directions=None, radius=None, t_max=None, stats=False, simple=False, brute_force=False):
-    """Host twin of Context.sweep_spheres (no GPU): the first contact of each moving sphere with `tris` over the tree set_bvh4(bvh4)
-    installs, with the device's bits.  bvh4 None needs brute_force=True.  Returns (t, prim, u, v), and the counters as a dict in fifth place
-    with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    rec = _sweep_records(origins, directions, radius, t_max)
-    n = rec.shape[0]
-    out = _aligned_zeros((n, 4), np.uint32)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    _check(lib.pt_sweep_spheres_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                     rec.ctypes.data_as(C.POINTER(PtSweep)), C.c_uint64(n), C.c_uint32(_sweep_flags(stats, simple, brute_force)),
-                                     out.ctypes.data_as(C.POINTER(PtHit)), C.byref(st) if stats else None))
-    res = _columns(out)
-    return res + (st.as_dict(),) if stats else res
-
-
 def _bvh4_arg(bvh4):
     if bvh4 is None:
         return None, None, 0
@@ -519,20 +523,88 @@ def _bvh4_arg(bvh4):
     return bvh4, _p(bvh4, C.c_uint32), bvh4.size
 
 
+def _unpack(rec, cols):
+    """(..., 4) uint32 result records -> their leading columns as copies: 'f' a float32 column, 'u' a uint32 one (PtHit and PtClosest are
+    "fuff": t | dist, prim, u, v).  cols None: uint32 counts, as they are.  Of a torch int32 tensor the same, as views of it."""
+    if isinstance(rec, np.ndarray):
+        f = rec.view(np.float32)
+        return rec if cols is None else tuple([(f if c == "f" else rec)[..., i].copy() for i, c in enumerate(cols)])
+    import torch
+    u = rec.view(torch.uint32)
+    return u if cols is None else tuple([(rec.view(torch.float32) if c == "f" else u)[..., i] for i, c in enumerate(cols)])
+
+
+# What both routes and the twin of a query read.  record: the ctypes type of an input record (its width is sizeof / 4 floats); entry: that of
+# a result; cols, tail: the result kind (_unpack's columns; the shape of one record's results in words); guess: of a list query, the entries
+# per record of the host route's first run; device, host, twin: the C entry points (twin None where there is none).
+_Query = collections.namedtuple("_Query", "record entry cols tail guess device host twin")
+
+
+def _query(name, record, entry, cols, tail=(4,), guess=0):
+    return _Query(record, entry, cols, tail, guess, getattr(lib, "pt_" + name), getattr(lib, "pt_%s_host" % name), getattr(lib, "pt_%s_bvh4" % name, None))
+
+
+_TRACE = _query("trace_rays", PtRay, PtHit, "fuff")
+_CLOSEST = _query("closest_points", PtPoint, PtClosest, "fuff")
+_SWEEP = _query("sweep_spheres", PtSweep, PtHit, "fuff")
+_NEAREST = _query("nearest_k", PtPoint, PtClosest, "fuff")                  # tail: (k, 4), the caller's
+_SIGNED = _query("signed_distance", PtPoint, PtClosest, "fuff")
+_OCCLUSION = _query("occlusion", PtSurfel, PtOcclusion, "fuu")
+_CONTAINS = _query("contains", PtPoint, PtContainment, "uuu")
+_COUNT = _query("count_hits", PtRay, C.c_uint32, None, ())
+_RADIUS_COUNT = _query("radius_count", PtPoint, C.c_uint32, None, ())
+_BOX_COUNT = _query("box_count", PtBox, C.c_uint32, None, ())
+_RADIUS = _query("radius_search", PtPoint, PtClosest, "fuff", guess=16)
+_BOX = _query("box_search", PtBox, PtOverlap, "uu", guess=16)               # (two columns, not four: prim, verts_inside)
+_HITS = _query("list_hits", PtRay, PtHit, "fuff", guess=4)
+
+
+def _twin(q, tris, bvh4, rec, extra, stats, tail=None, capacity=None):
+    """The host twin of query q (no GPU) for the triangles `tris` under the tree `bvh4` and the numpy records `rec`; extra: the ctypes
+    arguments between the record count and the results.  Returns what the query does, and the counters as a dict after it with stats."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
+    keep, bp, words = _bvh4_arg(bvh4)
+    n, st = rec.shape[0], PtStats()
+
+    def call(*results):
+        _check(q.twin(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words), rec.ctypes.data_as(C.POINTER(q.record)), C.c_uint64(n),
+                      *extra, *results, C.byref(st) if stats else None))
+    if q.guess:                                         # a list query: capacity None runs it twice, once for the total
+        offsets = np.zeros(n + 1, np.uint64)
+        if capacity is None:
+            call(_p(offsets, C.c_uint64), None, C.c_uint64(0))
+            capacity = int(offsets[n])
+        capacity = int(capacity)
+        entries = _aligned_zeros((capacity, 4), np.uint32)
+        call(_p(offsets, C.c_uint64), entries.ctypes.data_as(C.POINTER(q.entry)) if capacity else None, C.c_uint64(capacity))
+        res = (offsets,) + _unpack(entries[: min(int(offsets[n]), capacity)], q.cols)
+    else:
+        out = _aligned_zeros((n,) + (q.tail if tail is None else tail), np.uint32)
+        call(out.ctypes.data_as(C.POINTER(q.entry)))
+        res = _unpack(out, q.cols)
+    if not stats:
+        return res
+    return (res if isinstance(res, tuple) else (res,)) + (st.as_dict(),)
+
+
+def closest_points_bvh4(tris, bvh4, points, r_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.closest_points (no GPU): the nearest triangle of `tris` to each point over the tree set_bvh4(bvh4) installs, with
+    the device's bits.  bvh4 None needs brute_force=True.  Returns (dist, prim, u, v), and the counters as a dict in fifth place with stats=True."""
+    return _twin(_CLOSEST, tris, bvh4, _point_records(points, r_max), (C.c_uint32(_flags(stats, simple, brute_force)),), stats)
+
+
+def sweep_spheres_bvh4(tris, bvh4, origins, directions=None, radius=None, t_max=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.sweep_spheres (no GPU): the first contact of each moving sphere with `tris` over the tree set_bvh4(bvh4)
+    installs, with the device's bits.  bvh4 None needs brute_force=True.  Returns (t, prim, u, v), and the counters as a dict in fifth place
+    with stats=True."""
+    return _twin(_SWEEP, tris, bvh4, _sweep_records(origins, directions, radius, t_max), (C.c_uint32(_flags(stats, simple, brute_force)),), stats)
+
+
 def count_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, stats=False, simple=False, brute_force=False):
     """Host twin of Context.count_hits (no GPU): how many triangles of `tris` each ray crosses over the tree set_bvh4(bvh4) installs, with
     the device's counts.  bvh4 None needs brute_force=True.  Returns the (n,) uint32 counts, and the counters as a dict in second place
     with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    rays = _ray_records(origins, directions, t_max)
-    n = rays.shape[0]
-    counts = np.zeros(n, np.uint32)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    _check(lib.pt_count_hits_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                  rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(_count_flags(stats, simple, brute_force)),
-                                  _p(counts, C.c_uint32), C.byref(st) if stats else None))
-    return (counts, st.as_dict()) if stats else counts
+    return _twin(_COUNT, tris, bvh4, _ray_records(origins, directions, t_max), (C.c_uint32(_flags(stats, simple, brute_force)),), stats)
 
 
 def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=False, simple=False, brute_force=False):
@@ -541,26 +613,7 @@ def radius_search_bvh4(tris, bvh4, points, r_max=None, capacity=None, stats=Fals
     list of point i at offsets[i]:offsets[i + 1], in visit order (index order with brute_force).  capacity None: every entry (the twin runs
     twice, once for the total); else the first min(offsets[-1], capacity) entries, offsets complete.  The counters as a dict in sixth place
     with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    pts = _point_records(points, r_max)
-    n = pts.shape[0]
-    offsets = np.zeros(n + 1, np.uint64)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    flags = _radius_flags(stats, simple, brute_force)
-
-    def call(entries, cap):
-        _check(lib.pt_radius_search_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                         pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                         entries.ctypes.data_as(C.POINTER(PtClosest)) if cap else None, C.c_uint64(cap),
-                                         C.byref(st) if stats else None))
-    if capacity is None:
-        call(None, 0)
-        capacity = int(offsets[n])
-    entries = _aligned_zeros((int(capacity), 4), np.uint32)
-    call(entries, int(capacity))
-    res = (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
-    return res + (st.as_dict(),) if stats else res
+    return _twin(_RADIUS, tris, bvh4, _point_records(points, r_max), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
 
 
 def box_search_bvh4(tris, bvh4, lo, hi=None, capacity=None, stats=False, simple=False, brute_force=False):
@@ -569,27 +622,7 @@ def box_search_bvh4(tris, bvh4, lo, hi=None, capacity=None, stats=False, simple=
     (offsets, prim, verts_inside): offsets (n + 1,) uint64, the list of box i at offsets[i]:offsets[i + 1], in visit order (index order with
     brute_force).  capacity None: every entry (the twin runs twice, once for the total); else the first min(offsets[-1], capacity) entries,
     offsets complete.  The counters as a dict in fourth place with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    boxes = _box_records(lo, hi)
-    n = boxes.shape[0]
-    offsets = np.zeros(n + 1, np.uint64)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    flags = _box_flags(stats, simple, brute_force)
-
-    def call(entries, cap):
-        _check(lib.pt_box_search_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                      boxes.ctypes.data_as(C.POINTER(PtBox)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                      entries.ctypes.data_as(C.POINTER(PtOverlap)) if cap else None, C.c_uint64(cap),
-                                      C.byref(st) if stats else None))
-    if capacity is None:
-        call(None, 0)
-        capacity = int(offsets[n])
-    entries = _aligned_zeros((int(capacity), 4), np.uint32)
-    call(entries, int(capacity))
-    held = entries[: min(int(offsets[n]), int(capacity))]
-    res = (offsets, held[:, 0].copy(), held[:, 1].copy())
-    return res + (st.as_dict(),) if stats else res
+    return _twin(_BOX, tris, bvh4, _box_records(lo, hi), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
 
 
 def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):
@@ -598,60 +631,23 @@ def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=No
     at offsets[i]:offsets[i + 1], in visit order (index order with brute_force; ascending (t, prim) with sort=True).  capacity None: every
     entry (the twin runs twice, once for the total); else the first min(offsets[-1], capacity) entries, offsets complete.  The counters as
     a dict in sixth place with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    rays = _ray_records(origins, directions, t_max)
-    n = rays.shape[0]
-    offsets = np.zeros(n + 1, np.uint64)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    flags = _hits_flags(stats, simple, brute_force, sort)
-
-    def call(entries, cap):
-        _check(lib.pt_list_hits_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                     rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                     entries.ctypes.data_as(C.POINTER(PtHit)) if cap else None, C.c_uint64(cap),
-                                     C.byref(st) if stats else None))
-    if capacity is None:
-        call(None, 0)
-        capacity = int(offsets[n])
-    entries = _aligned_zeros((int(capacity), 4), np.uint32)
-    call(entries, int(capacity))
-    res = (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
-    return res + (st.as_dict(),) if stats else res
+    return _twin(_HITS, tris, bvh4, _ray_records(origins, directions, t_max), (C.c_uint32(_flags(stats, simple, brute_force, sort)),), stats,
+                 capacity=capacity)
 
 
 def nearest_k_bvh4(tris, bvh4, points, k, r_max=None, stats=False, simple=False, brute_force=False):
     """Host twin of Context.nearest_k (no GPU): the k triangles of `tris` nearest to each point over the tree set_bvh4(bvh4) installs, with the
     device's bits and order.  bvh4 None needs brute_force=True.  Returns (dist, prim, u, v), each (n, k): row i in ascending order of
     distance, padded with dist = +inf and prim = 0xFFFFFFFF.  The counters as a dict in fifth place with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    pts = _point_records(points, r_max)
-    n, k = pts.shape[0], int(k)
-    rows = _aligned_zeros((n * min(max(k, 0), PT_NEAREST_MAX_K), 4), np.uint32)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
-    _check(lib.pt_nearest_k_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                 pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF),
-                                 C.c_uint32(_nearest_flags(stats, simple, brute_force)), rows.ctypes.data_as(C.POINTER(PtClosest)),
-                                 C.byref(st) if stats else None))
-    res = _columns(rows.reshape(n, k, 4))
-    return res + (st.as_dict(),) if stats else res
+    k = int(k)                                          # (the rows are sized for a k in range; the C side refuses any other)
+    return _twin(_NEAREST, tris, bvh4, _point_records(points, r_max), (C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(_flags(stats, simple, brute_force))), stats,
+                 tail=(min(max(k, 0), PT_NEAREST_MAX_K), 4))
 
 
 def contains_bvh4(tris, bvh4, points, samples=3, seed=0, index_base=0, stats=False, simple=False):
     """Host twin of Context.contains (no GPU): (inside, odd, samples) per point, and the counters as a dict in fourth place with stats=True."""
-    tris = np.ascontiguousarray(tris, np.float32).reshape(-1)
-    pts = _point_records(points, None)
-    n = pts.shape[0]
-    out = _aligned_zeros((n, 4), np.uint32)
-    st = PtStats()
-    keep, bp, words = _bvh4_arg(bvh4)
     p = _contain_params(samples, seed, index_base, stats, simple)
-    _check(lib.pt_contains_bvh4(_p(tris, C.c_float), C.c_uint32(tris.size // 9), bp, C.c_uint64(words),
-                                pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p),
-                                out.ctypes.data_as(C.POINTER(PtContainment)), C.byref(st) if stats else None))
-    res = (out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy())
-    return res + (st.as_dict(),) if stats else res
+    return _twin(_CONTAINS, tris, bvh4, _point_records(points, None), (C.byref(p),), stats)     # (r_max is ignored)
 
 
 def refit_bvh2(tris, bvh2):
@@ -1004,15 +1000,7 @@ class Context:
         zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's current stream both ways; the
         results are torch tensors (prim as torch.uint32).  stats: the counting kernel, counters in stats() afterwards."""
         flags = (PT_TRACE_ANY_HIT if any_hit else 0) | (PT_TRACE_STATS if stats else 0) | (PT_TRACE_SIMPLE_KERNEL if simple else 0)
-        if _is_torch(origins):
-            rays = self._ray_tensor(origins, directions, t_max, "trace_rays")
-            return _torch_columns(self._torch_launch(rays, (4,), lambda r, n, o: self.trace_rays_device(r, n, o, flags)))
-        rays = _ray_records(origins, directions, t_max)
-        n = rays.shape[0]
-        hits = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_trace_rays_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags),
-                                        hits.ctypes.data_as(C.POINTER(PtHit))))
-        return _columns(hits)
+        return self._run(_TRACE, _ray_records(origins, directions, t_max, "trace_rays"), C.c_uint32(flags))
 
     def trace_rays_device(self, rays_ptr, n, hits_ptr, flags=0):
         """Raw device route: n PtRay records at rays_ptr -> n PtHit records at hits_ptr (16-byte aligned device pointers).  Asynchronous on
@@ -1036,14 +1024,25 @@ class Context:
         launch()
         after = torch.cuda.Event(); after.record(ext); cur.wait_event(after)
 
-    def _torch_launch(self, rec, tail, launch):
-        """The torch route of a query that is one call: an int32 result tensor of shape (n,) + tail next to the n records `rec`, and
-        launch(records pointer, n, results pointer) on the context's stream, ordered with torch's current stream both ways."""
+    def _run(self, q, rec, *extra, tail=None):
+        """Query q (a _Query) over the n records `rec` as one call, extra being the ctypes arguments between the record count and the results."""
+        return (self._run_host if isinstance(rec, np.ndarray) else self._run_torch)(q, rec, extra, q.tail if tail is None else tail)
+
+    def _run_host(self, q, rec, extra, tail):
+        """The host route: numpy records in, (n,) + tail result words out and unpacked; returns when done."""
+        n = rec.shape[0]
+        out = _aligned_zeros((n,) + tail, np.uint32)
+        self._ck(q.host(self.h, rec.ctypes.data_as(C.POINTER(q.record)), C.c_uint64(n), *extra, out.ctypes.data_as(C.POINTER(q.entry))))
+        return _unpack(out, q.cols)
+
+    def _run_torch(self, q, rec, extra, tail):
+        """The torch route: an int32 result tensor of shape (n,) + tail next to the records, the launch on the context's stream, ordered with
+        torch's current stream both ways; no host wait."""
         import torch
         n = rec.shape[0]
         out = torch.empty((n,) + tail, dtype=torch.int32, device=rec.device)
-        self._on_context_stream(rec.device, lambda: launch(rec.data_ptr(), n, out.data_ptr()))
-        return out
+        self._on_context_stream(rec.device, lambda: self._ck(q.device(self.h, C.c_void_p(rec.data_ptr()), C.c_uint64(n), *extra, C.c_void_p(out.data_ptr()))))
+        return _unpack(out, q.cols)
 
     def camera_rays(self, params, device=None):
         """The rays PT_MODE_REFERENCE traces through each pixel centre of `params` (make_params): a torch (height * width, 8) float32 tensor of
@@ -1064,16 +1063,7 @@ class Context:
         returns when done).  torch tensors on the context's device take the device route: zero-copy for contiguous (n, 4) float32 records,
         no host synchronisation, ordered with torch's current stream both ways; the results are torch tensors (prim as torch.uint32).
         stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle in index order, no tree."""
-        flags = _closest_flags(stats, simple, brute_force)
-        if _is_torch(points):
-            pts = self._point_tensor(points, r_max, "closest_points")
-            return _torch_columns(self._torch_launch(pts, (4,), lambda p, n, o: self.closest_points_device(p, n, o, flags)))
-        pts = _point_records(points, r_max)
-        n = pts.shape[0]
-        out = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_closest_points_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags),
-                                            out.ctypes.data_as(C.POINTER(PtClosest))))
-        return _columns(out)
+        return self._run(_CLOSEST, _point_records(points, r_max, "closest_points"), C.c_uint32(_flags(stats, simple, brute_force)))
 
     def closest_points_device(self, ptr, n, out_ptr, flags=0):
         """Raw device route: n PtPoint records at ptr -> n PtClosest records at out_ptr (16-byte aligned device pointers).  Asynchronous on
@@ -1091,20 +1081,7 @@ class Context:
         device take the device route: zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's
         current stream both ways; the results are torch tensors (prim as torch.uint32).
         stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle in index order, no tree."""
-        flags = _sweep_flags(stats, simple, brute_force)
-        if _is_torch(origins):
-            rec = self._ray_tensor(origins, directions, t_max, "sweep_spheres")
-            if radius is not None or directions is not None:
-                if directions is None:
-                    rec = rec.clone() if rec.data_ptr() == origins.data_ptr() else rec
-                rec[:, 7] = 0.0 if radius is None else radius
-            return _torch_columns(self._torch_launch(rec, (4,), lambda p, n, o: self.sweep_spheres_device(p, n, o, flags)))
-        rec = _sweep_records(origins, directions, radius, t_max)
-        n = rec.shape[0]
-        out = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_sweep_spheres_host(self.h, rec.ctypes.data_as(C.POINTER(PtSweep)), C.c_uint64(n), C.c_uint32(flags),
-                                           out.ctypes.data_as(C.POINTER(PtHit))))
-        return _columns(out)
+        return self._run(_SWEEP, _sweep_records(origins, directions, radius, t_max, "sweep_spheres"), C.c_uint32(_flags(stats, simple, brute_force)))
 
     def sweep_spheres_device(self, ptr, n, out_ptr, flags=0):
         """Raw device route: n PtSweep records at ptr -> n PtHit records at out_ptr (16-byte aligned device pointers).  Asynchronous on the
@@ -1121,26 +1098,7 @@ class Context:
         with torch's current stream both ways; the results are torch tensors (the counts as torch.uint32).  stats: the counting kernel,
         counters in stats() afterwards; simple: the one-ray-per-thread kernel."""
         p = _occlusion_params(samples, seed, bias, index_base, stats, simple)
-        if _is_torch(surfels):
-            import torch
-            sf = self._surfel_tensor(surfels, "occlusion")
-            out = self._torch_launch(sf, (4,), lambda r, n, o: self.occlusion_device(r, n, p, o))
-            return out.view(torch.float32)[:, 0], out.view(torch.uint32)[:, 1], out.view(torch.uint32)[:, 2]
-        sf = _records8(surfels, "occlusion")
-        n = sf.shape[0]
-        out = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_occlusion_host(self.h, sf.ctypes.data_as(C.POINTER(PtSurfel)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtOcclusion))))
-        return out.view(np.float32)[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
-
-    def _surfel_tensor(self, surfels, what):
-        _torch_route()
-        import torch
-        if surfels.device.type != "cuda":
-            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, surfels.device))
-        sf = surfels.reshape(-1, 8)
-        if sf.dtype != torch.float32 or not sf.is_contiguous() or sf.data_ptr() % 16:
-            sf = sf.to(torch.float32).contiguous().clone()
-        return sf
+        return self._run(_OCCLUSION, _records8(surfels, "occlusion"), C.byref(p))
 
     def occlusion_device(self, surfels_ptr, n, params, out_ptr):
         """Raw device route: n PtSurfel records at surfels_ptr -> n PtOcclusion records at out_ptr (16-byte aligned device pointers; params:
@@ -1154,7 +1112,7 @@ class Context:
         if not _is_torch(surfels):
             return occlusion_rays_host(surfels, samples, seed, bias, index_base)
         import torch
-        sf = self._surfel_tensor(surfels, "occlusion_rays")
+        sf = _records8(surfels, "occlusion_rays")
         n = sf.shape[0]
         p = _occlusion_params(samples, seed, bias, index_base)
         rays = torch.empty((n * int(samples), 8), dtype=torch.float32, device=sf.device)
@@ -1177,31 +1135,21 @@ class Context:
             else:
                 hits = np.stack([np.asarray(t, np.float32).view(np.uint32), np.asarray(prim, np.uint32),
                                  np.asarray(u, np.float32).view(np.uint32), np.asarray(v, np.float32).view(np.uint32)], axis=1)
+        r = _records8(rays, "hit_surfels")
+        if (hits.element_size() if _is_torch(hits) else np.asarray(hits).dtype.itemsize) != 4:
+            raise ValueError("hit_surfels: hits must be 4-byte words")
         if _is_torch(rays):
             import torch
-            r = self._surfel_tensor(rays, "hit_surfels")
-            h = hits.reshape(-1, 4)
-            if h.element_size() != 4:
-                raise ValueError("hit_surfels: hits must be 4-byte words")
-            h = h.view(torch.int32)
-            if not h.is_contiguous() or h.data_ptr() % 16:
-                h = h.contiguous().clone()
-            n = r.shape[0]
-            if h.shape[0] != n:
-                raise ValueError("hit_surfels: %d rays but %d hits" % (n, h.shape[0]))
-            out = torch.empty((n, 8), dtype=torch.float32, device=r.device)
-            self._on_context_stream(r.device, lambda: self.hit_surfels_device(r.data_ptr(), h.data_ptr(), n, r_max, out.data_ptr()))
-            return out
-        r = _records8(rays, "hit_surfels")
-        h = np.asarray(hits)
-        if h.dtype.itemsize != 4:
-            raise ValueError("hit_surfels: hits must be 4-byte words")
-        h = h.reshape(-1, 4).view(np.uint32)
-        if h.ctypes.data % 16 or not h.flags.c_contiguous:
-            h2 = _aligned_zeros(h.shape, np.uint32); h2[...] = h; h = h2
+            h = _torch_records(hits.reshape(-1, 4).view(torch.int32), "hit_surfels", dtype="int32")
+        else:
+            h = _records(np.asarray(hits).reshape(-1, 4).view(np.uint32))
         n = r.shape[0]
         if h.shape[0] != n:
             raise ValueError("hit_surfels: %d rays but %d hits" % (n, h.shape[0]))
+        if _is_torch(rays):
+            out = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+            self._on_context_stream(r.device, lambda: self.hit_surfels_device(r.data_ptr(), h.data_ptr(), n, r_max, out.data_ptr()))
+            return out
         out = _aligned_zeros((n, 8), np.float32)
         self._ck(lib.pt_hit_surfels_host(self.h, r.ctypes.data_as(C.POINTER(PtRay)), h.ctypes.data_as(C.POINTER(PtHit)), C.c_uint64(n),
                                          C.c_float(r_max), out.ctypes.data_as(C.POINTER(PtSurfel))))
@@ -1219,59 +1167,12 @@ class Context:
         numpy arrays take the host route (staged, returns when done).  torch tensors on the context's device take the device route:
         zero-copy for contiguous (n, 8) float32 records, no host synchronisation, ordered with torch's current stream both ways; the
         result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards; brute_force: every triangle, no tree."""
-        flags = _count_flags(stats, simple, brute_force)
-        if _is_torch(origins):
-            import torch
-            rays = self._ray_tensor(origins, directions, t_max, "count_hits")
-            return self._torch_launch(rays, (), lambda r, n, o: self.count_hits_device(r, n, o, flags)).view(torch.uint32)
-        rays = _ray_records(origins, directions, t_max)
-        n = rays.shape[0]
-        counts = np.zeros(n, np.uint32)
-        self._ck(lib.pt_count_hits_host(self.h, rays.ctypes.data_as(C.POINTER(PtRay)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
-        return counts
+        return self._run(_COUNT, _ray_records(origins, directions, t_max, "count_hits"), C.c_uint32(_flags(stats, simple, brute_force)))
 
     def count_hits_device(self, rays_ptr, n, counts_ptr, flags=0):
         """Raw device route: n PtRay records at rays_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the context's
         stream (get_stream); the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_count_hits(self.h, C.c_void_p(rays_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
-
-    def _ray_tensor(self, origins, directions, t_max, what):
-        _torch_route()
-        import torch
-        dev = origins.device
-        if dev.type != "cuda":
-            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
-        if directions is None:
-            rays = origins.reshape(-1, 8)
-            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.data_ptr() % 16:
-                rays = rays.to(torch.float32).contiguous().clone()
-            if t_max is not None:
-                rays = rays.clone(); rays[:, 3] = t_max
-            return rays
-        o = origins.reshape(-1, 3).to(torch.float32); d = directions.reshape(-1, 3).to(device=dev, dtype=torch.float32)
-        n = o.shape[0]
-        tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if t_max is None else \
-            torch.as_tensor(t_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
-        return torch.cat([o, tm, d, torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
-
-    def _point_tensor(self, points, r_max, what):
-        _torch_route()
-        import torch
-        dev = points.device
-        if dev.type != "cuda":
-            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
-        if points.dim() == 2 and points.shape[1] == 4:
-            pts = points
-            if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.data_ptr() % 16:
-                pts = pts.to(torch.float32).contiguous().clone()
-            if r_max is not None:
-                pts = pts.clone(); pts[:, 3] = r_max
-            return pts
-        p = points.reshape(-1, 3).to(torch.float32)
-        n = p.shape[0]
-        rm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if r_max is None else \
-            torch.as_tensor(r_max, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
-        return torch.cat([p, rm], dim=1).contiguous()
 
     def contains(self, points, samples=3, seed=0, index_base=0, stats=False, simple=False):
         """Is each point inside the mesh?  Crossing parity by majority vote over `samples` (odd, 1..255) rays per point: returns
@@ -1281,16 +1182,7 @@ class Context:
         points: (n, 3) float32 or (n, 4) PtPoint records (r_max is ignored).  numpy takes the host route; torch tensors on the context's
         device stay there, on the context's stream, with no host synchronisation."""
         p = _contain_params(samples, seed, index_base, stats, simple)
-        if _is_torch(points):
-            import torch
-            pts = self._point_tensor(points, None, "contains")
-            o = self._torch_launch(pts, (4,), lambda r, n, o: self.contains_device(r, n, p, o)).view(torch.uint32)
-            return o[:, 0], o[:, 1], o[:, 2]
-        pts = _point_records(points, None)
-        n = pts.shape[0]
-        out = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_contains_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtContainment))))
-        return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+        return self._run(_CONTAINS, _point_records(points, None, "contains"), C.byref(p))        # (r_max is ignored)
 
     def contains_device(self, points_ptr, n, params, out_ptr):
         """Raw device route: n PtPoint records at points_ptr -> n PtContainment records at out_ptr (16-byte aligned device pointers; params:
@@ -1305,16 +1197,7 @@ class Context:
         returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host synchronisation; the
         result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0 means that triangles
         were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
-        flags = _radius_flags(stats, simple, brute_force)
-        if _is_torch(points):
-            import torch
-            pts = self._point_tensor(points, r_max, "radius_count")
-            return self._torch_launch(pts, (), lambda r, n, o: self.radius_count_device(r, n, o, flags)).view(torch.uint32)
-        pts = _point_records(points, r_max)
-        n = pts.shape[0]
-        counts = np.zeros(n, np.uint32)
-        self._ck(lib.pt_radius_count_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
-        return counts
+        return self._run(_RADIUS_COUNT, _point_records(points, r_max, "radius_count"), C.c_uint32(_flags(stats, simple, brute_force)))
 
     def radius_count_device(self, points_ptr, n, counts_ptr, flags=0):
         """Raw device route: n PtPoint records at points_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
@@ -1336,45 +1219,49 @@ class Context:
         are then walked a second time); pass a capacity to avoid it.
         stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack cap,
         which large radii over deep trees reach sooner than any other query; brute_force lists every triangle within r_max regardless."""
-        flags = _radius_flags(stats, simple, brute_force)
-        if _is_torch(points):
-            return self._list_torch(self._point_tensor(points, r_max, "radius_search"), self.radius_search_device, flags, capacity)
-        return self._list_host(_point_records(points, r_max), PtPoint, lib.pt_radius_search_host, PtClosest, flags, capacity, 16)
+        return self._list(_RADIUS, _point_records(points, r_max, "radius_search"), _flags(stats, simple, brute_force), capacity)
 
-    def _list_torch(self, rec, search_device, flags, capacity):
-        """The torch route of a list query over the n records `rec`: with a capacity one call of `search_device` (radius_search_device,
-        list_hits_device) and no host wait; without, one for the offsets, the read of offsets[-1], and one for the entries."""
+    def _list(self, q, rec, flags, capacity):
+        """List query q over the n records `rec`: (offsets,) + the entry columns."""
+        return (self._list_host if isinstance(rec, np.ndarray) else self._list_torch)(q, rec, flags, capacity)
+
+    def _list_torch(self, q, rec, flags, capacity):
+        """The torch route of a list query: with a capacity one call and no host wait; without, one for the offsets, the read of
+        offsets[-1], and one for the entries."""
         import torch
         n, dev = rec.shape[0], rec.device
         offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+
+        def call(entries_ptr, cap):
+            self._on_context_stream(dev, lambda: self._ck(q.device(self.h, C.c_void_p(rec.data_ptr()), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets.data_ptr()),
+                                                                   C.c_void_p(entries_ptr) if cap else None, C.c_uint64(cap))))
         if capacity is None:
-            self._on_context_stream(dev, lambda: search_device(rec.data_ptr(), n, offsets.data_ptr(), 0, 0, flags))
+            call(0, 0)
             capacity = int(offsets[-1].item())          # the one host wait
         cap = int(capacity)
         entries = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-        self._on_context_stream(dev, lambda: search_device(rec.data_ptr(), n, offsets.data_ptr(), entries.data_ptr() if cap else 0, cap, flags))
-        return (offsets,) + _torch_columns(entries)
+        call(entries.data_ptr(), cap)
+        return (offsets,) + _unpack(entries, q.cols)
 
-    def _list_host(self, rec, record, search_host, entry, flags, capacity, guess):
-        """The host route of a list query over the n numpy records `rec` (of ctypes type `record`; entries of type `entry`) through
-        `search_host` (pt_radius_search_host, pt_list_hits_host).  capacity None: room for `guess` entries per record at first, and a second
-        run when offsets[n] says that this was too little."""
+    def _list_host(self, q, rec, flags, capacity):
+        """The host route of a list query.  capacity None: room for q.guess entries per record at first (16 for radius and box lists, 4 for
+        hit lists), and a second run when offsets[n] says that this was too little."""
         n = rec.shape[0]
         offsets = np.zeros(n + 1, np.uint64)
 
         def call(entries, cap):
-            self._ck(search_host(self.h, rec.ctypes.data_as(C.POINTER(record)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
-                                 entries.ctypes.data_as(C.POINTER(entry)) if cap else None, C.c_uint64(cap)))
+            self._ck(q.host(self.h, rec.ctypes.data_as(C.POINTER(q.record)), C.c_uint64(n), C.c_uint32(flags), _p(offsets, C.c_uint64),
+                            entries.ctypes.data_as(C.POINTER(q.entry)) if cap else None, C.c_uint64(cap)))
         retry = capacity is None
         if retry:
-            capacity = guess * n + 64               # a first guess; offsets[n] says how large the retry must be
+            capacity = q.guess * n + 64             # a first guess; offsets[n] says how large the retry must be
         entries = _aligned_zeros((int(capacity), 4), np.uint32)
         call(entries, int(capacity))
         if retry and int(offsets[n]) > capacity:
             capacity = int(offsets[n])
             entries = _aligned_zeros((capacity, 4), np.uint32)
             call(entries, capacity)
-        return (offsets,) + _columns(entries[: min(int(offsets[n]), int(capacity))])
+        return (offsets,) + _unpack(entries[: min(int(offsets[n]), int(capacity))], q.cols)
 
     def radius_search_device(self, points_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
         """Raw device route: n PtPoint records at points_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
@@ -1384,25 +1271,6 @@ class Context:
                                       C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
 
     # ---- box-overlap queries (an extension beyond the reference; include/mi355pt.h) ----
-    def _box_tensor(self, lo, hi, what):
-        _torch_route()
-        import torch
-        dev = lo.device
-        if dev.type != "cuda":
-            raise ValueError("%s: torch tensors must be on the context's GPU (got %s)" % (what, dev))
-        if hi is None:
-            if lo.dim() != 2 or lo.shape[1] != 8:
-                raise ValueError("%s: expected (n, 8) PtBox records or lo and hi of shape (n, 3), got shape %s" % (what, tuple(lo.shape)))
-            boxes = lo
-            if boxes.dtype != torch.float32 or not boxes.is_contiguous() or boxes.data_ptr() % 16:
-                boxes = boxes.to(torch.float32).contiguous().clone()
-            return boxes
-        a = lo.reshape(-1, 3).to(torch.float32); b = hi.reshape(-1, 3).to(device=dev, dtype=torch.float32)
-        if a.shape != b.shape:
-            raise ValueError("%s: lo and hi differ in shape: %s vs %s" % (what, tuple(a.shape), tuple(b.shape)))
-        z = torch.zeros((a.shape[0], 1), dtype=torch.float32, device=dev)
-        return torch.cat([a, z, b, z], dim=1).contiguous()
-
     def box_count(self, lo, hi=None, stats=False, simple=False, brute_force=False):
         """How many triangles overlap each axis-aligned box?  Returns the (n,) uint32 counts (0 for a box with a NaN, an infinity or lo > hi).
 
@@ -1410,16 +1278,7 @@ class Context:
         (staged, returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host
         synchronisation; the result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0
         means that triangles were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
-        flags = _box_flags(stats, simple, brute_force)
-        if _is_torch(lo):
-            import torch
-            boxes = self._box_tensor(lo, hi, "box_count")
-            return self._torch_launch(boxes, (), lambda r, n, o: self.box_count_device(r, n, o, flags)).view(torch.uint32)
-        boxes = _box_records(lo, hi)
-        n = boxes.shape[0]
-        counts = np.zeros(n, np.uint32)
-        self._ck(lib.pt_box_count_host(self.h, boxes.ctypes.data_as(C.POINTER(PtBox)), C.c_uint64(n), C.c_uint32(flags), _p(counts, C.c_uint32)))
-        return counts
+        return self._run(_BOX_COUNT, _box_records(lo, hi, "box_count"), C.c_uint32(_flags(stats, simple, brute_force)))
 
     def box_count_device(self, boxes_ptr, n, counts_ptr, flags=0):
         """Raw device route: n PtBox records at boxes_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
@@ -1441,13 +1300,7 @@ class Context:
         of this call (the boxes are then counted a second time); pass a capacity to avoid it.
         stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack cap,
         which large boxes over deep trees reach as large radii do; brute_force lists every overlapping triangle regardless."""
-        flags = _box_flags(stats, simple, brute_force)
-        if _is_torch(lo):
-            import torch
-            res = self._list_torch(self._box_tensor(lo, hi, "box_search"), self.box_search_device, flags, capacity)
-            return res[0], res[1].view(torch.uint32), res[2].view(torch.uint32)         # the four entry columns: prim, verts_inside, 0, 0
-        res = self._list_host(_box_records(lo, hi), PtBox, lib.pt_box_search_host, PtOverlap, flags, capacity, 16)
-        return res[0], res[1].view(np.uint32), res[2]
+        return self._list(_BOX, _box_records(lo, hi, "box_search"), _flags(stats, simple, brute_force), capacity)
 
     def box_search_device(self, boxes_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
         """Raw device route: n PtBox records at boxes_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
@@ -1473,10 +1326,7 @@ class Context:
         are then counted a second time); pass a capacity to avoid it.
         stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that crossings were lost at the 64-entry stack cap;
         brute_force lists every crossing regardless."""
-        flags = _hits_flags(stats, simple, brute_force, sort)
-        if _is_torch(origins):
-            return self._list_torch(self._ray_tensor(origins, directions, t_max, "list_hits"), self.list_hits_device, flags, capacity)
-        return self._list_host(_ray_records(origins, directions, t_max), PtRay, lib.pt_list_hits_host, PtHit, flags, capacity, 4)
+        return self._list(_HITS, _ray_records(origins, directions, t_max, "list_hits"), _flags(stats, simple, brute_force, sort), capacity)
 
     def list_hits_device(self, rays_ptr, n, offsets_ptr, hits_ptr, capacity, flags=0):
         """Raw device route: n PtRay records at rays_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
@@ -1497,17 +1347,10 @@ class Context:
         ways; the results are torch tensors (prim as torch.uint32).
         stats: the counting kernel, counters in stats() afterwards (stack_drops > 0 means that nearer triangles may be missing);
         brute_force: every triangle in index order, no tree."""
-        flags = _nearest_flags(stats, simple, brute_force)
-        k = int(k)
-        if _is_torch(points):
-            pts = self._point_tensor(points, r_max, "nearest_k")
-            return _torch_columns(self._torch_launch(pts, (min(max(k, 1), PT_NEAREST_MAX_K), 4), lambda p, n, o: self.nearest_k_device(p, n, k, o, flags)))
-        pts = _point_records(points, r_max)
-        n = pts.shape[0]
-        rows = _aligned_zeros((n * min(max(k, 0), PT_NEAREST_MAX_K), 4), np.uint32)
-        self._ck(lib.pt_nearest_k_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(flags),
-                                       rows.ctypes.data_as(C.POINTER(PtClosest))))
-        return _columns(rows.reshape(n, k, 4))
+        k = int(k)        # (numpy rows for max(k, 0), torch rows for max(k, 1), both capped at 64: the C side refuses a k out of range)
+        pts = _point_records(points, r_max, "nearest_k")
+        return self._run(_NEAREST, pts, C.c_uint32(k & 0xFFFFFFFF), C.c_uint32(_flags(stats, simple, brute_force)),
+                         tail=(min(max(k, 1 if _is_torch(pts) else 0), PT_NEAREST_MAX_K), 4))
 
     def nearest_k_device(self, ptr, n, k, out_ptr, flags=0):
         """Raw device route: n PtPoint records at ptr -> n * k PtClosest records at out_ptr, row i at record i * k (16-byte aligned device
@@ -1517,15 +1360,8 @@ class Context:
     def signed_distance(self, points, r_max=None, samples=3, seed=0, index_base=0, simple=False):
         """closest_points with the sign of contains: returns (dist, prim, u, v), dist negative where the point is inside (-inf: inside, and
         nothing within r_max).  Arguments as closest_points and contains; three launches on the context's stream, no host wait."""
-        p = _contain_params(samples, seed, index_base, False, simple)
-        if _is_torch(points):
-            pts = self._point_tensor(points, r_max, "signed_distance")
-            return _torch_columns(self._torch_launch(pts, (4,), lambda r, n, o: self.signed_distance_device(r, n, p, o)))
-        pts = _point_records(points, r_max)
-        n = pts.shape[0]
-        out = _aligned_zeros((n, 4), np.uint32)
-        self._ck(lib.pt_signed_distance_host(self.h, pts.ctypes.data_as(C.POINTER(PtPoint)), C.c_uint64(n), C.byref(p), out.ctypes.data_as(C.POINTER(PtClosest))))
-        return _columns(out)
+        p = _contain_params(samples, seed, index_base, False, simple)                  # (never the stats flag)
+        return self._run(_SIGNED, _point_records(points, r_max, "signed_distance"), C.byref(p))
 
     def signed_distance_device(self, points_ptr, n, params, out_ptr):
         """Raw device route: n PtPoint records at points_ptr -> n PtClosest records at out_ptr (16-byte aligned; params: PtContainParams)."""

@@ -15,6 +15,7 @@ function native() {
 }
 
 const MODE_REFERENCE_PACKET = 0, MODE_REFERENCE = 1, MODE_PATH = 2;
+const FLAG_SIMPLE_KERNEL = 2, FLAG_BRUTE_FORCE = 4, HITS_SORTED = 8;
 
 class PathTracer {
   // reference: constructor(canvas), PathTracer.js:60-95 -- uses only canvas.width / canvas.height
@@ -137,13 +138,23 @@ class PathTracer {
     else native().render(this.device, UBO, this.options);                  // asynchronous on the GPU, like queue.submit (:821)
   }
 
+  // The batched queries below run on this context or, on a group, on member 0, which holds the whole scene: the addon registers each
+  // under two names, `traceRays(context, ...)` and `groupTraceRays(group, ...)`.
+  _query(name, ...args) {
+    return this.group ? native()["group" + name[0].toUpperCase() + name.slice(1)](this.group, ...args) : native()[name](this.device, ...args);
+  }
+  // options -> the flag word of a query (include/mi355pt.h PT_*_SIMPLE_KERNEL, PT_*_BRUTE_FORCE: the same bits in every query)
+  _flags(options) {
+    const o = options || {};
+    return (o.simple ? FLAG_SIMPLE_KERNEL : 0) | (o.bruteForce ? FLAG_BRUTE_FORCE : 0);
+  }
+
   // ---- batched ray queries: an extension beyond the reference (include/mi355pt.h pt_trace_rays, DESIGN.md section 13) ----
   // rays: Float32Array, 8 floats per ray (origin xyz, tMax, direction xyz, 0).  Resolves to { t, prim, u, v } (Float32Array / Uint32Array):
   // the closest hit (anyHit: the first hit in traversal order) over the current tree; a miss has t = Infinity, prim = 0xFFFFFFFF, u = v = 0.
   // Triangles only (the spheres of a brute-force scene take no part).  On a group: member 0, which holds the whole scene.
   async traceRays(rays, options) {
-    const anyHit = !!(options && options.anyHit);
-    return this.group ? native().groupTraceRays(this.group, rays, anyHit) : native().traceRays(this.device, rays, anyHit);
+    return this._query("traceRays", rays, !!(options && options.anyHit));
   }
   // What is under pixel (x, y) of the current camera (setCameraPosition / setCameraQuaternion)?  The ray render() traces through the
   // pixel's centre in mode 1 (row 0 at the bottom of the image, as in the radiance); resolves to { hit, t, prim, point }, point = origin + t * direction.
@@ -161,8 +172,7 @@ class PathTracer {
   // nothing within rMax: dist = Infinity, prim = 0xFFFFFFFF, u = v = 0.  options.bruteForce: every triangle, no tree; options.simple: the
   // one-point-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
   async closestPoints(points, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
-    return this.group ? native().groupClosestPoints(this.group, points, flags) : native().closestPoints(this.device, points, flags);
+    return this._query("closestPoints", points, this._flags(options));
   }
   // The nearest triangle to (x, y, z): resolves to { found, dist, prim, u, v, point }.  point = v0 + u (v1 - v0) + v (v2 - v0) from
   // `trianglesData`, the Float32Array the scene was built from (9 floats per triangle), when the caller passes it; null without it or
@@ -183,15 +193,13 @@ class PathTracer {
   // crosses before tMax -- every one, not only the first.  options.bruteForce: every triangle, no tree; options.simple: the
   // one-ray-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
   async countHits(rays, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
-    return this.group ? native().groupCountHits(this.group, rays, flags) : native().countHits(this.device, rays, flags);
+    return this._query("countHits", rays, this._flags(options));
   }
   // points: Float32Array, 4 floats per point (x, y, z, ignored).  options: { samples (3; odd, 1..255), seed (0), indexBase (0), simple }.
   // Resolves to { inside, odd, samples } (Uint32Array): crossing parity by majority vote over `samples` rays per point -- on a closed mesh
   // the point-in-solid test; on an open or self-intersecting mesh whatever the parity is, odd / samples telling how much the rays disagreed.
   async contains(points, options) {
-    const o = options || {};
-    return this.group ? native().groupContains(this.group, points, o) : native().contains(this.device, points, o);
+    return this._query("contains", points, options || {});
   }
   // ---- sphere-cast queries: an extension beyond the reference (include/mi355pt.h pt_sweep_spheres, DESIGN.md section 22) ----
   // sweeps: Float32Array, 8 floats per sweep (origin xyz, tMax, direction xyz, radius).  Resolves to { t, prim, u, v } (Float32Array /
@@ -200,8 +208,7 @@ class PathTracer {
   // u = v = 0.  options.bruteForce: every triangle, no tree; options.simple: the one-sweep-per-thread kernel.  Triangles only.  On a
   // group: member 0, which holds the whole scene.
   async sweepSpheres(sweeps, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
-    return this.group ? native().groupSweepSpheres(this.group, sweeps, flags) : native().sweepSpheres(this.device, sweeps, flags);
+    return this._query("sweepSpheres", sweeps, this._flags(options));
   }
   // One sphere of radius r from (ox, oy, oz) along (dx, dy, dz): resolves to { hit, t, prim, u, v, center }, center = origin + t * direction.
   async sweep(ox, oy, oz, dx, dy, dz, r) {
@@ -212,8 +219,7 @@ class PathTracer {
 
   // closestPoints with the sign of contains: { dist, prim, u, v }, dist negative inside (-Infinity: inside, and nothing within rMax)
   async signedDistance(points, options) {
-    const o = options || {};
-    return this.group ? native().groupSignedDistance(this.group, points, o) : native().signedDistance(this.device, points, o);
+    return this._query("signedDistance", points, options || {});
   }
   // Is (x, y, z) inside the mesh?  Resolves to { inside, odd, samples }.
   async inside(x, y, z, options) {
@@ -236,12 +242,10 @@ class PathTracer {
     return p;
   }
   async radiusSearch(points, rMax, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0), p = this._radiusPoints(points, rMax);
-    return this.group ? native().groupRadiusSearch(this.group, p, flags) : native().radiusSearch(this.device, p, flags);
+    return this._query("radiusSearch", this._radiusPoints(points, rMax), this._flags(options));
   }
   async radiusCount(points, rMax, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0), p = this._radiusPoints(points, rMax);
-    return this.group ? native().groupRadiusCount(this.group, p, flags) : native().radiusCount(this.device, p, flags);
+    return this._query("radiusCount", this._radiusPoints(points, rMax), this._flags(options));
   }
   // The triangles within r of (x, y, z): resolves to { count, dist, prim, u, v }.
   async within(x, y, z, r, options) {
@@ -258,12 +262,10 @@ class PathTracer {
   // A box that covers much of a deep tree can lose triangles at the 64-entry stack cap (the header says when); bruteForce never does.
   // Triangles only.  On a group: member 0, which holds the whole scene.
   async boxSearch(boxes, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
-    return this.group ? native().groupBoxSearch(this.group, boxes, flags) : native().boxSearch(this.device, boxes, flags);
+    return this._query("boxSearch", boxes, this._flags(options));
   }
   async boxCount(boxes, options) {
-    const flags = (options && options.simple ? 2 : 0) | (options && options.bruteForce ? 4 : 0);
-    return this.group ? native().groupBoxCount(this.group, boxes, flags) : native().boxCount(this.device, boxes, flags);
+    return this._query("boxCount", boxes, this._flags(options));
   }
   // The triangles that overlap the box lo = [x, y, z] .. hi = [x, y, z]: resolves to { count, prim, vertsInside }.
   async overlapping(lo, hi, options) {
@@ -279,8 +281,7 @@ class PathTracer {
   // empty list.  options.simple: the one-ray-per-thread kernels.  A ray through a very deep tree can lose crossings at the 64-entry stack
   // cap (the header says when); bruteForce never does.  Triangles only.  On a group: member 0, which holds the whole scene.
   async listHits(rays, options) {
-    const o = options || {}, flags = (o.simple ? 2 : 0) | (o.bruteForce ? 4 : 0) | (o.sort ? 8 : 0);
-    return this.group ? native().groupListHits(this.group, rays, flags) : native().listHits(this.device, rays, flags);
+    return this._query("listHits", rays, this._flags(options) | (options && options.sort ? HITS_SORTED : 0));
   }
   // Every crossing of the ray from (ox, oy, oz) along (dx, dy, dz), nearest first: resolves to { count, t, prim, u, v }.  options.tMax
   // (default: no limit), options.simple, options.bruteForce.
@@ -308,8 +309,7 @@ class PathTracer {
   // options.rMax: a number that replaces the fourth float of every point (the caller's array is not written); options.bruteForce: every
   // triangle, no tree; options.simple: the one-point-per-thread kernel.  Triangles only.  On a group: member 0, which holds the whole scene.
   async nearestK(points, k, options) {
-    const o = options || {}, flags = (o.simple ? 2 : 0) | (o.bruteForce ? 4 : 0), p = this._radiusPoints(points, o.rMax);
-    return this.group ? native().groupNearestK(this.group, p, k, flags) : native().nearestK(this.device, p, k, flags);
+    return this._query("nearestK", this._radiusPoints(points, options && options.rMax), k, this._flags(options));
   }
   // The k triangles nearest to (x, y, z): resolves to { count, dist, prim, u, v } without the padding, nearest first.
   async kNearest(x, y, z, k, options) {
@@ -325,14 +325,12 @@ class PathTracer {
   // cosine-distributed rays around the normal, how many reach nothing within rMax; all zero for a surfel that is not traced (a NaN, rMax <= 0).
   // On a group: member 0, which holds the whole scene.
   async occlusion(surfels, options) {
-    const o = options || {};
-    return this.group ? native().groupOcclusion(this.group, surfels, o) : native().occlusion(this.device, surfels, o);
+    return this._query("occlusion", surfels, options || {});
   }
   // rays + what traceRays resolved to for them -> Float32Array of surfels (8 floats each): the hit point, rMax, the triangle's normal turned
   // against the ray; a miss gives a surfel that occlusion() does not trace.
   async hitSurfels(rays, hits, rMax) {
-    const r = rMax === undefined ? Infinity : rMax;
-    return this.group ? native().groupHitSurfels(this.group, rays, hits.t, hits.prim, hits.u, hits.v, r) : native().hitSurfels(this.device, rays, hits.t, hits.prim, hits.u, hits.v, r);
+    return this._query("hitSurfels", rays, hits.t, hits.prim, hits.u, hits.v, rMax === undefined ? Infinity : rMax);
   }
   // An ambient-occlusion frame of the current camera: camera rays -> traceRays -> hitSurfels -> occlusion.  Resolves to a Float32Array of
   // width * height visibilities, row-major like the radiance; 0 where the camera ray misses.

@@ -330,445 +330,143 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {          /*
     return NULL;
 }
 
-/* ---- batched ray queries (an extension beyond the reference; include/mi355pt.h pt_trace_rays_host) ------------------------- */
+/* ---- batched queries over the context's tree (extensions beyond the reference; include/mi355pt.h pt_*_host) ----------------------------- */
 
-/* rays: Float32Array of 8 floats per ray (PtRay: org xyz, t_max, dir xyz, reserved) -> { t: Float32Array, prim: Uint32Array, u, v }.
- * The records are copied into 16-byte aligned host memory (a typed array's data need not be aligned). */
-static napi_value trace_rays_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value any_v) {
-    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, "traceRays: 8 floats per ray"); return NULL; }
-    bool any = false; napi_get_value_bool(env, any_v, &any);
-    const size_t n = len / 8;
-    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
-    PtHit* hits = (PtHit*)aligned_alloc(16, (n ? n : 1) * sizeof(PtHit));
-    if (!rays || !hits) { free(rays); free(hits); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(rays, d, n * sizeof(PtRay));
-    int rc = pt_trace_rays_host(ctx, rays, n, any ? PT_TRACE_ANY_HIT : 0u, hits);
-    free(rays);
-    if (rc != 0) { free(hits); return throw_pt(env, ctx, rc, "pt_trace_rays_host"); }
-    napi_value o, t, prim, u, v; void *pt, *pp, *pu, *pv;
-    if (!(t = make_typed(env, napi_float32_array, 4, n, &pt)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
-        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(hits); return NULL; }
-    for (size_t i = 0; i < n; ++i) {
-        ((float*)pt)[i] = hits[i].t; ((uint32_t*)pp)[i] = hits[i].prim; ((float*)pu)[i] = hits[i].u; ((float*)pv)[i] = hits[i].v;
+/* Every query takes a Float32Array of records and answers with 16-byte result records or with uint32 counts.  What differs is said once, here:
+ *   traceRays       rays: 8 floats per ray (PtRay: org xyz, tMax, dir xyz, reserved); anyHit -> { t: Float32Array, prim: Uint32Array, u, v }
+ *   closestPoints   points: 4 floats per point (PtPoint: x, y, z, rMax); flags: PT_CLOSEST_* -> { dist, prim, u, v }
+ *   sweepSpheres    sweeps: 8 floats per sweep (PtSweep: org xyz, tMax, dir xyz, radius); flags: PT_SWEEP_* -> { t, prim, u, v }
+ *   nearestK        points, k: 1 .. PT_NEAREST_MAX_K, flags: PT_NEAREST_* -> { k, dist: Float32Array of n * k, prim, u, v }: row i at
+ *                   [i * k, i * k + k), ascending by dist, padded with dist = Infinity and prim = 0xFFFFFFFF
+ *   signedDistance  points; opt as contains -> { dist, prim, u, v }, dist negative inside
+ *   contains        points (rMax ignored); opt: { samples (3), seed, indexBase, simple } -> { inside: Uint32Array, odd, samples }
+ *   occlusion       surfels: 8 floats per surfel (PtSurfel: p xyz, rMax, n xyz, reserved); opt: { samples (16), seed, bias, indexBase, simple }
+ *                   -> { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }
+ *   countHits, radiusCount, boxCount   rays | points | boxes (8 floats per box: lo xyz, pad, hi xyz, pad); flags -> Uint32Array
+ *   radiusSearch, boxSearch, listHits  the same records; flags -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53),
+ *                   dist | t, prim, u, v } or, of boxes, { offsets, prim, vertsInside }: every entry.  The first call has room for 16 entries
+ *                   per point or box and 4 per ray; when offsets[n] says that this was too little, the query runs again with room for all. */
+typedef enum { Q_TRACE, Q_CLOSEST, Q_SWEEP, Q_NEAREST, Q_SIGNED, Q_CONTAINS, Q_OCCLUSION, Q_COUNT, Q_RADIUS_COUNT, Q_BOX_COUNT,
+               Q_RADIUS, Q_BOX, Q_HITS, Q_SURFELS } Query;
+
+/* floats per record, the range error of a partial record, throw_pt's label, the result columns and their types (f: Float32Array, u:
+ * Uint32Array; none: counts), and of a list query the entries per record of the first call */
+static const struct QueryKind { size_t floats; const char* partial; const char* label; const char* names[4]; const char* types; uint64_t guess; } KINDS[] = {
+    [Q_TRACE]        = {8, "traceRays: 8 floats per ray", "pt_trace_rays_host", {"t", "prim", "u", "v"}, "fuff", 0},
+    [Q_CLOSEST]      = {4, "closestPoints: 4 floats per point", "pt_closest_points_host", {"dist", "prim", "u", "v"}, "fuff", 0},
+    [Q_SWEEP]        = {8, "sweepSpheres: 8 floats per sweep", "pt_sweep_spheres_host", {"t", "prim", "u", "v"}, "fuff", 0},
+    [Q_NEAREST]      = {4, "nearestK: 4 floats per point", "pt_nearest_k_host", {"dist", "prim", "u", "v"}, "fuff", 0},
+    [Q_SIGNED]       = {4, "signedDistance: 4 floats per point", "pt_signed_distance_host", {"dist", "prim", "u", "v"}, "fuff", 0},
+    [Q_CONTAINS]     = {4, "contains: 4 floats per point", "pt_contains_host", {"inside", "odd", "samples"}, "uuu", 0},
+    [Q_OCCLUSION]    = {8, "occlusion: 8 floats per surfel", "pt_occlusion_host", {"visibility", "unoccluded", "samples"}, "fuu", 0},
+    [Q_COUNT]        = {8, "countHits: 8 floats per ray", "pt_count_hits_host", {0}, NULL, 0},
+    [Q_RADIUS_COUNT] = {4, "radiusCount: 4 floats per point", "pt_radius_count_host", {0}, NULL, 0},
+    [Q_BOX_COUNT]    = {8, "boxCount: 8 floats per box", "pt_box_count_host", {0}, NULL, 0},
+    [Q_RADIUS]       = {4, "radiusSearch: 4 floats per point", "pt_radius_search_host", {"dist", "prim", "u", "v"}, "fuff", 16},
+    [Q_BOX]          = {8, "boxSearch: 8 floats per box", "pt_box_search_host", {"prim", "vertsInside"}, "uu", 16},
+    [Q_HITS]         = {8, "listHits: 8 floats per ray", "pt_list_hits_host", {"t", "prim", "u", "v"}, "fuff", 4},
+};
+
+/* the one place that calls the pt_*_host entry points, each with its own types */
+static int call_host(Query q, PtContext* ctx, const void* rec, size_t n, uint32_t flags, uint32_t k, const void* params,
+                     void* out, uint64_t* off, uint64_t cap) {
+    switch (q) {
+    case Q_TRACE:        return pt_trace_rays_host(ctx, (const PtRay*)rec, n, flags, (PtHit*)out);
+    case Q_CLOSEST:      return pt_closest_points_host(ctx, (const PtPoint*)rec, n, flags, (PtClosest*)out);
+    case Q_SWEEP:        return pt_sweep_spheres_host(ctx, (const PtSweep*)rec, n, flags, (PtHit*)out);
+    case Q_NEAREST:      return pt_nearest_k_host(ctx, (const PtPoint*)rec, n, k, flags, (PtClosest*)out);
+    case Q_SIGNED:       return pt_signed_distance_host(ctx, (const PtPoint*)rec, n, (const PtContainParams*)params, (PtClosest*)out);
+    case Q_CONTAINS:     return pt_contains_host(ctx, (const PtPoint*)rec, n, (const PtContainParams*)params, (PtContainment*)out);
+    case Q_OCCLUSION:    return pt_occlusion_host(ctx, (const PtSurfel*)rec, n, (const PtOcclusionParams*)params, (PtOcclusion*)out);
+    case Q_COUNT:        return pt_count_hits_host(ctx, (const PtRay*)rec, n, flags, (uint32_t*)out);
+    case Q_RADIUS_COUNT: return pt_radius_count_host(ctx, (const PtPoint*)rec, n, flags, (uint32_t*)out);
+    case Q_BOX_COUNT:    return pt_box_count_host(ctx, (const PtBox*)rec, n, flags, (uint32_t*)out);
+    case Q_RADIUS:       return pt_radius_search_host(ctx, (const PtPoint*)rec, n, flags, off, (PtClosest*)out, cap);
+    case Q_BOX:          return pt_box_search_host(ctx, (const PtBox*)rec, n, flags, off, (PtOverlap*)out, cap);
+    case Q_HITS:         return pt_list_hits_host(ctx, (const PtRay*)rec, n, flags, off, (PtHit*)out, cap);
+    default:             return -1;
     }
-    free(hits);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
+}
+
+/* The record intake: a Float32Array of `floats` per record -> a copy in 16-byte aligned host memory (a typed array's data need not be
+ * aligned) and the record count; the caller frees it. */
+static void* records_in(napi_env env, napi_value v, size_t floats, const char* partial, size_t* n) {
+    void* d; size_t len; if (!get_typed(env, v, napi_float32_array, &d, &len)) return NULL;
+    if (len % floats) { napi_throw_range_error(env, NULL, partial); return NULL; }
+    *n = len / floats;
+    void* rec = aligned_alloc(16, (*n ? *n : 1) * floats * sizeof(float));
+    if (!rec) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (*n) memcpy(rec, d, *n * floats * sizeof(float));
+    return rec;
+}
+
+/* The result builder: m 16-byte records -> an object of their leading columns, one typed array of m per letter of `types`, under `names`;
+ * before them `k` when it is not 0 and `offsets` (n + 1 of them) when off is not NULL. */
+static napi_value columns_out(napi_env env, const char* const* names, const char* types, const void* rec, size_t m,
+                              uint32_t k, const uint64_t* off, size_t n) {
+    napi_value o; NAPI_OK(napi_create_object(env, &o));
+    if (k) { napi_value kv; NAPI_OK(napi_create_uint32(env, k, &kv)); napi_set_named_property(env, o, "k", kv); }
+    if (off) {
+        void* po; napi_value offs = make_typed(env, napi_float64_array, 8, n + 1, &po); if (!offs) return NULL;
+        for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
+        napi_set_named_property(env, o, "offsets", offs);
+    }
+    for (size_t c = 0; types[c]; ++c) {
+        void* p; napi_value col = make_typed(env, types[c] == 'f' ? napi_float32_array : napi_uint32_array, 4, m, &p); if (!col) return NULL;
+        for (size_t i = 0; i < m; ++i) memcpy((char*)p + 4 * i, (const char*)rec + 16 * i + 4 * c, 4);
+        napi_set_named_property(env, o, names[c], col);
+    }
     return o;
 }
-static napi_value fn_trace_rays(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array rays, anyHit) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return trace_rays_on(env, ctx, argv[1], argv[2]);
+
+/* A query that is one call: n records in, n (nearestK: n * k) result records out. */
+static napi_value run_query(napi_env env, PtContext* ctx, Query q, napi_value records_v, uint32_t flags, uint32_t k, const void* params) {
+    const struct QueryKind* kind = &KINDS[q];
+    size_t n; void* rec = records_in(env, records_v, kind->floats, kind->partial, &n); if (!rec) return NULL;
+    const size_t m = n * (k ? k : 1);
+    napi_value result = NULL; void* out = NULL; int rc;
+    if (q == Q_NEAREST && (k == 0 || k > PT_NEAREST_MAX_K)) napi_throw_range_error(env, NULL, "nearestK: k must be 1 .. 64");
+    else if (!(out = aligned_alloc(16, (m ? m : 1) * 16))) napi_throw_error(env, NULL, "out of memory");
+    else if ((rc = call_host(q, ctx, rec, n, flags, k, params, out, NULL, 0)) != 0) throw_pt(env, ctx, rc, kind->label);
+    else result = columns_out(env, kind->names, kind->types, out, m, k, NULL, 0);
+    free(rec); free(out);
+    return result;
 }
 
-/* ---- batched closest-point queries (an extension beyond the reference; include/mi355pt.h pt_closest_points_host) ---------------- */
-
-/* points: Float32Array of 4 floats per point (PtPoint: x, y, z, rMax) -> { dist: Float32Array, prim: Uint32Array, u, v }; flags: PT_CLOSEST_*.
- * The records are copied into 16-byte aligned host memory, as the rays are. */
-static napi_value closest_points_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
-    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 4) { napi_throw_range_error(env, NULL, "closestPoints: 4 floats per point"); return NULL; }
-    const uint32_t flags = get_u32(env, flags_v);
-    const size_t n = len / 4;
-    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
-    PtClosest* res = (PtClosest*)aligned_alloc(16, (n ? n : 1) * sizeof(PtClosest));
-    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(pts, d, n * sizeof(PtPoint));
-    int rc = pt_closest_points_host(ctx, pts, n, flags, res);
-    free(pts);
-    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_closest_points_host"); }
-    napi_value o, dist, prim, u, v; void *pd, *pp, *pu, *pv;
-    if (!(dist = make_typed(env, napi_float32_array, 4, n, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
-        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(res); return NULL; }
-    for (size_t i = 0; i < n; ++i) {
-        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
-    }
-    free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_closest_points(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array points, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return closest_points_on(env, ctx, argv[1], argv[2]);
-}
-
-/* ---- sphere-cast queries (an extension beyond the reference; include/mi355pt.h pt_sweep_spheres_host) ------------------------------ */
-
-/* sweeps: Float32Array of 8 floats per sweep (PtSweep: org xyz, tMax, dir xyz, radius) -> { t: Float32Array, prim: Uint32Array, u, v };
- * flags: PT_SWEEP_*.  The records are copied into 16-byte aligned host memory, as the rays are. */
-static napi_value sweep_spheres_on(napi_env env, PtContext* ctx, napi_value sweeps_v, napi_value flags_v) {
-    void* d; size_t len; if (!get_typed(env, sweeps_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, "sweepSpheres: 8 floats per sweep"); return NULL; }
-    const uint32_t flags = get_u32(env, flags_v);
-    const size_t n = len / 8;
-    PtSweep* sw = (PtSweep*)aligned_alloc(16, (n ? n : 1) * sizeof(PtSweep));
-    PtHit* hits = (PtHit*)aligned_alloc(16, (n ? n : 1) * sizeof(PtHit));
-    if (!sw || !hits) { free(sw); free(hits); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(sw, d, n * sizeof(PtSweep));
-    int rc = pt_sweep_spheres_host(ctx, sw, n, flags, hits);
-    free(sw);
-    if (rc != 0) { free(hits); return throw_pt(env, ctx, rc, "pt_sweep_spheres_host"); }
-    napi_value o, t, prim, u, v; void *pt, *pp, *pu, *pv;
-    if (!(t = make_typed(env, napi_float32_array, 4, n, &pt)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
-        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(hits); return NULL; }
-    for (size_t i = 0; i < n; ++i) {
-        ((float*)pt)[i] = hits[i].t; ((uint32_t*)pp)[i] = hits[i].prim; ((float*)pu)[i] = hits[i].u; ((float*)pv)[i] = hits[i].v;
-    }
-    free(hits);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_sweep_spheres(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array sweeps, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return sweep_spheres_on(env, ctx, argv[1], argv[2]);
-}
-
-/* ---- k-nearest queries (an extension beyond the reference; include/mi355pt.h pt_nearest_k_host) ------------------------------------- */
-
-/* points: Float32Array of 4 floats per point (PtPoint: x, y, z, rMax), k: 1 .. PT_NEAREST_MAX_K -> { k, dist: Float32Array of n * k, prim:
- * Uint32Array, u, v }: row i at [i * k, i * k + k), ascending by dist, padded with dist = Infinity and prim = 0xFFFFFFFF; flags: PT_NEAREST_* */
-static napi_value nearest_k_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value k_v, napi_value flags_v) {
-    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 4) { napi_throw_range_error(env, NULL, "nearestK: 4 floats per point"); return NULL; }
-    const uint32_t k = get_u32(env, k_v), flags = get_u32(env, flags_v);
-    if (k == 0 || k > PT_NEAREST_MAX_K) { napi_throw_range_error(env, NULL, "nearestK: k must be 1 .. 64"); return NULL; }
-    const size_t n = len / 4, m = n * k;
-    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
-    PtClosest* res = (PtClosest*)aligned_alloc(16, (m ? m : 1) * sizeof(PtClosest));
-    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(pts, d, n * sizeof(PtPoint));
-    int rc = pt_nearest_k_host(ctx, pts, n, k, flags, res);
-    free(pts);
-    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_nearest_k_host"); }
-    napi_value o, kv, dist, prim, u, v; void *pd, *pp, *pu, *pv;
-    if (!(dist = make_typed(env, napi_float32_array, 4, m, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) ||
-        !(u = make_typed(env, napi_float32_array, 4, m, &pu)) || !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(res); return NULL; }
-    for (size_t i = 0; i < m; ++i) {
-        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
-    }
-    free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    NAPI_OK(napi_create_uint32(env, k, &kv));
-    napi_set_named_property(env, o, "k", kv);
-    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_nearest_k(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array points, k, flags) */
-    napi_value argv[4]; if (!get_args(env, info, 4, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return nearest_k_on(env, ctx, argv[1], argv[2], argv[3]);
-}
-
-/* ---- radius queries (an extension beyond the reference; include/mi355pt.h pt_radius_count_host, pt_radius_search_host) ---------------- */
-
-static PtPoint* radius_points(napi_env env, napi_value points_v, const char* what, size_t* n) {
-    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 4) { napi_throw_range_error(env, NULL, what); return NULL; }
-    *n = len / 4;
-    PtPoint* pts = (PtPoint*)aligned_alloc(16, (*n ? *n : 1) * sizeof(PtPoint));
-    if (!pts) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (*n) memcpy(pts, d, *n * sizeof(PtPoint));
-    return pts;
-}
-/* points: Float32Array of 4 floats per point (x, y, z, rMax) -> Uint32Array: the triangles within rMax of each point; flags: PT_RADIUS_* */
-static napi_value radius_count_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
-    size_t n; PtPoint* pts = radius_points(env, points_v, "radiusCount: 4 floats per point", &n); if (!pts) return NULL;
-    const uint32_t flags = get_u32(env, flags_v);
+/* A count query: the counts go straight into the Uint32Array. */
+static napi_value run_count(napi_env env, PtContext* ctx, Query q, napi_value records_v, uint32_t flags) {
+    size_t n; void* rec = records_in(env, records_v, KINDS[q].floats, KINDS[q].partial, &n); if (!rec) return NULL;
     void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
-    if (!counts) { free(pts); return NULL; }
-    uint32_t none = 0;
-    int rc = pt_radius_count_host(ctx, pts, n, flags, n ? (uint32_t*)pc : &none);
-    free(pts);
-    if (rc != 0) return throw_pt(env, ctx, rc, "pt_radius_count_host");
-    return counts;
+    uint32_t none = 0;                                                          /* an empty typed array may have no data pointer */
+    const int rc = counts ? call_host(q, ctx, rec, n, flags, 0, NULL, n ? pc : (void*)&none, NULL, 0) : 0;
+    free(rec);
+    return rc != 0 ? throw_pt(env, ctx, rc, KINDS[q].label) : counts;
 }
-/* points as above -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), dist, prim, u, v }: every entry.  The first
- * call has room for 16 entries per point; when offsets[n] says that this was too little, the query runs again with room for all. */
-static napi_value radius_search_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value flags_v) {
-    size_t n; PtPoint* pts = radius_points(env, points_v, "radiusSearch: 4 floats per point", &n); if (!pts) return NULL;
-    const uint32_t flags = get_u32(env, flags_v);
+
+/* A list query: room for `guess` entries per record at first, and again with room for all when offsets[n] says that this was too little.
+ * Every path leaves through `done`, which frees what there is. */
+static napi_value run_list(napi_env env, PtContext* ctx, Query q, napi_value records_v, uint32_t flags) {
+    const struct QueryKind* kind = &KINDS[q];
+    size_t n; void* rec = records_in(env, records_v, kind->floats, kind->partial, &n); if (!rec) return NULL;
+    napi_value result = NULL;
+    uint64_t cap = kind->guess * (uint64_t)n + 64;
     uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
-    uint64_t cap = 16 * (uint64_t)n + 64;
-    PtClosest* res = (PtClosest*)aligned_alloc(16, (size_t)cap * sizeof(PtClosest));
-    if (!off || !res) { free(pts); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    int rc = pt_radius_search_host(ctx, pts, n, flags, off, res, cap);
+    void* out = aligned_alloc(16, (size_t)cap * 16);
+    if (!off || !out) { napi_throw_error(env, NULL, "out of memory"); goto done; }
+    int rc = call_host(q, ctx, rec, n, flags, 0, NULL, out, off, cap);
     if (rc == 0 && off[n] > cap) {
         cap = off[n];
-        free(res);
-        res = (PtClosest*)aligned_alloc(16, (size_t)cap * sizeof(PtClosest));
-        if (!res) { free(pts); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-        rc = pt_radius_search_host(ctx, pts, n, flags, off, res, cap);
+        free(out);
+        out = aligned_alloc(16, (size_t)cap * 16);
+        if (!out) { napi_throw_error(env, NULL, "out of memory"); goto done; }
+        rc = call_host(q, ctx, rec, n, flags, 0, NULL, out, off, cap);
     }
-    free(pts);
-    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_radius_search_host"); }
-    const size_t m = (size_t)off[n];
-    napi_value o, offs, dist, prim, u, v; void *po, *pd, *pp, *pu, *pv;
-    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(dist = make_typed(env, napi_float32_array, 4, m, &pd)) ||
-        !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) || !(u = make_typed(env, napi_float32_array, 4, m, &pu)) ||
-        !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(off); free(res); return NULL; }
-    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
-    for (size_t i = 0; i < m; ++i) {
-        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
-    }
-    free(off); free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_radius_count(napi_env env, napi_callback_info info) {        /* (ctx, Float32Array points, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return radius_count_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_radius_search(napi_env env, napi_callback_info info) {       /* (ctx, Float32Array points, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return radius_search_on(env, ctx, argv[1], argv[2]);
+    result = rc != 0 ? throw_pt(env, ctx, rc, kind->label) : columns_out(env, kind->names, kind->types, out, (size_t)off[n], 0, off, n);
+done:
+    free(rec); free(off); free(out);
+    return result;
 }
 
-/* ---- box-overlap queries (an extension beyond the reference; include/mi355pt.h pt_box_count_host, pt_box_search_host) ----------------- */
-
-static PtBox* box_records(napi_env env, napi_value boxes_v, const char* what, size_t* n) {
-    void* d; size_t len; if (!get_typed(env, boxes_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, what); return NULL; }
-    *n = len / 8;
-    PtBox* boxes = (PtBox*)aligned_alloc(16, (*n ? *n : 1) * sizeof(PtBox));
-    if (!boxes) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (*n) memcpy(boxes, d, *n * sizeof(PtBox));
-    return boxes;
-}
-/* boxes: Float32Array of 8 floats per box (lo xyz, pad, hi xyz, pad) -> Uint32Array: the triangles that overlap each box; flags: PT_BOX_* */
-static napi_value box_count_on(napi_env env, PtContext* ctx, napi_value boxes_v, napi_value flags_v) {
-    size_t n; PtBox* boxes = box_records(env, boxes_v, "boxCount: 8 floats per box", &n); if (!boxes) return NULL;
-    const uint32_t flags = get_u32(env, flags_v);
-    void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
-    if (!counts) { free(boxes); return NULL; }
-    uint32_t none = 0;
-    int rc = pt_box_count_host(ctx, boxes, n, flags, n ? (uint32_t*)pc : &none);
-    free(boxes);
-    if (rc != 0) return throw_pt(env, ctx, rc, "pt_box_count_host");
-    return counts;
-}
-/* boxes as above -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), prim, vertsInside }: every entry.  The first
- * call has room for 16 entries per box; when offsets[n] says that this was too little, the query runs again with room for all. */
-static napi_value box_search_on(napi_env env, PtContext* ctx, napi_value boxes_v, napi_value flags_v) {
-    size_t n; PtBox* boxes = box_records(env, boxes_v, "boxSearch: 8 floats per box", &n); if (!boxes) return NULL;
-    const uint32_t flags = get_u32(env, flags_v);
-    uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
-    uint64_t cap = 16 * (uint64_t)n + 64;
-    PtOverlap* res = (PtOverlap*)aligned_alloc(16, (size_t)cap * sizeof(PtOverlap));
-    if (!off || !res) { free(boxes); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    int rc = pt_box_search_host(ctx, boxes, n, flags, off, res, cap);
-    if (rc == 0 && off[n] > cap) {
-        cap = off[n];
-        free(res);
-        res = (PtOverlap*)aligned_alloc(16, (size_t)cap * sizeof(PtOverlap));
-        if (!res) { free(boxes); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-        rc = pt_box_search_host(ctx, boxes, n, flags, off, res, cap);
-    }
-    free(boxes);
-    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_box_search_host"); }
-    const size_t m = (size_t)off[n];
-    napi_value o, offs, prim, in; void *po, *pp, *pi;
-    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) ||
-        !(in = make_typed(env, napi_uint32_array, 4, m, &pi))) { free(off); free(res); return NULL; }
-    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
-    for (size_t i = 0; i < m; ++i) { ((uint32_t*)pp)[i] = res[i].prim; ((uint32_t*)pi)[i] = res[i].verts_inside; }
-    free(off); free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "prim", prim); napi_set_named_property(env, o, "vertsInside", in);
-    return o;
-}
-static napi_value fn_box_count(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array boxes, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return box_count_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_box_search(napi_env env, napi_callback_info info) {          /* (ctx, Float32Array boxes, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return box_search_on(env, ctx, argv[1], argv[2]);
-}
-
-/* ---- hit lists (an extension beyond the reference; include/mi355pt.h pt_list_hits_host) ------------------------------------------------ */
-
-/* rays: Float32Array of 8 floats per ray; flags: PT_HITS_* -> { offsets: Float64Array of n + 1 (exact: the total is far below 2^53), t, prim,
- * u, v }: every entry.  The first call has room for 4 entries per ray; when offsets[n] says that this was too little, the query runs again
- * with room for all. */
-static napi_value list_hits_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value flags_v) {
-    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, "listHits: 8 floats per ray"); return NULL; }
-    const uint32_t flags = get_u32(env, flags_v);
-    const size_t n = len / 8;
-    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
-    uint64_t* off = (uint64_t*)malloc((n + 1) * sizeof(uint64_t));
-    uint64_t cap = 4 * (uint64_t)n + 64;
-    PtHit* res = (PtHit*)aligned_alloc(16, (size_t)cap * sizeof(PtHit));
-    if (!rays || !off || !res) { free(rays); free(off); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(rays, d, n * sizeof(PtRay));
-    int rc = pt_list_hits_host(ctx, rays, n, flags, off, res, cap);
-    if (rc == 0 && off[n] > cap) {
-        cap = off[n];
-        free(res);
-        res = (PtHit*)aligned_alloc(16, (size_t)cap * sizeof(PtHit));
-        if (!res) { free(rays); free(off); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-        rc = pt_list_hits_host(ctx, rays, n, flags, off, res, cap);
-    }
-    free(rays);
-    if (rc != 0) { free(off); free(res); return throw_pt(env, ctx, rc, "pt_list_hits_host"); }
-    const size_t m = (size_t)off[n];
-    napi_value o, offs, t, prim, u, v; void *po, *pt_, *pp, *pu, *pv;
-    if (!(offs = make_typed(env, napi_float64_array, 8, n + 1, &po)) || !(t = make_typed(env, napi_float32_array, 4, m, &pt_)) ||
-        !(prim = make_typed(env, napi_uint32_array, 4, m, &pp)) || !(u = make_typed(env, napi_float32_array, 4, m, &pu)) ||
-        !(v = make_typed(env, napi_float32_array, 4, m, &pv))) { free(off); free(res); return NULL; }
-    for (size_t i = 0; i <= n; ++i) ((double*)po)[i] = (double)off[i];
-    for (size_t i = 0; i < m; ++i) {
-        ((float*)pt_)[i] = res[i].t; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
-    }
-    free(off); free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "offsets", offs); napi_set_named_property(env, o, "t", t); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_list_hits(napi_env env, napi_callback_info info) {           /* (ctx, Float32Array rays, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return list_hits_on(env, ctx, argv[1], argv[2]);
-}
-
-/* ---- batched ambient-occlusion queries (an extension beyond the reference; include/mi355pt.h pt_occlusion_host, pt_hit_surfels_host) ---- */
-
-/* surfels: Float32Array of 8 floats per surfel (PtSurfel: p xyz, rMax, n xyz, reserved); opt: { samples, seed, bias, indexBase, simple }
- * -> { visibility: Float32Array, unoccluded: Uint32Array, samples: Uint32Array }.  Copied into 16-byte aligned host memory, as the rays are. */
-static napi_value occlusion_on(napi_env env, PtContext* ctx, napi_value surfels_v, napi_value opt) {
-    void* d; size_t len; if (!get_typed(env, surfels_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, "occlusion: 8 floats per surfel"); return NULL; }
-    PtOcclusionParams p; memset(&p, 0, sizeof p);
-    p.samples = prop_u32(env, opt, "samples", 16); p.seed = prop_u32(env, opt, "seed", 0); p.index_base = prop_u32(env, opt, "indexBase", 0);
-    p.bias = (float)prop_f64(env, opt, "bias", 1e-4);
-    p.flags = prop_u32(env, opt, "simple", 0) ? PT_OCCLUSION_SIMPLE_KERNEL : 0u;
-    const size_t n = len / 8;
-    PtSurfel* sf = (PtSurfel*)aligned_alloc(16, (n ? n : 1) * sizeof(PtSurfel));
-    PtOcclusion* res = (PtOcclusion*)aligned_alloc(16, (n ? n : 1) * sizeof(PtOcclusion));
-    if (!sf || !res) { free(sf); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(sf, d, n * sizeof(PtSurfel));
-    int rc = pt_occlusion_host(ctx, sf, n, &p, res);
-    free(sf);
-    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_occlusion_host"); }
-    napi_value o, vis, un, sm; void *pv, *pu, *ps;
-    if (!(vis = make_typed(env, napi_float32_array, 4, n, &pv)) || !(un = make_typed(env, napi_uint32_array, 4, n, &pu)) ||
-        !(sm = make_typed(env, napi_uint32_array, 4, n, &ps))) { free(res); return NULL; }
-    for (size_t i = 0; i < n; ++i) { ((float*)pv)[i] = res[i].visibility; ((uint32_t*)pu)[i] = res[i].unoccluded; ((uint32_t*)ps)[i] = res[i].samples; }
-    free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "visibility", vis); napi_set_named_property(env, o, "unoccluded", un); napi_set_named_property(env, o, "samples", sm);
-    return o;
-}
-static napi_value fn_occlusion(napi_env env, napi_callback_info info) {      /* (ctx, Float32Array surfels, options) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return occlusion_on(env, ctx, argv[1], argv[2]);
-}
-/* ---- crossing counts, containment, signed distance (an extension beyond the reference; include/mi355pt.h pt_count_hits_host,
- * pt_contains_host, pt_signed_distance_host) ---------------------------------------------------------------------------------- */
-
-/* rays: Float32Array of 8 floats per ray -> Uint32Array of crossing counts; flags: PT_COUNT_*.  Copied into aligned host memory, as above. */
-static napi_value count_hits_on(napi_env env, PtContext* ctx, napi_value rays_v, napi_value flags_v) {
-    void* d; size_t len; if (!get_typed(env, rays_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 8) { napi_throw_range_error(env, NULL, "countHits: 8 floats per ray"); return NULL; }
-    const uint32_t flags = get_u32(env, flags_v);
-    const size_t n = len / 8;
-    PtRay* rays = (PtRay*)aligned_alloc(16, (n ? n : 1) * sizeof(PtRay));
-    if (!rays) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(rays, d, n * sizeof(PtRay));
-    void* pc; napi_value counts = make_typed(env, napi_uint32_array, 4, n, &pc);
-    if (!counts) { free(rays); return NULL; }
-    uint32_t none = 0;
-    int rc = pt_count_hits_host(ctx, rays, n, flags, n ? (uint32_t*)pc : &none);
-    free(rays);
-    if (rc != 0) return throw_pt(env, ctx, rc, "pt_count_hits_host");
-    return counts;
-}
-static void contain_params(napi_env env, napi_value opt, PtContainParams* p) {
-    memset(p, 0, sizeof *p);
-    p->samples = prop_u32(env, opt, "samples", 3); p->seed = prop_u32(env, opt, "seed", 0); p->index_base = prop_u32(env, opt, "indexBase", 0);
-    p->flags = prop_u32(env, opt, "simple", 0) ? PT_CONTAIN_SIMPLE_KERNEL : 0u;
-}
-/* points: Float32Array of 4 floats per point (rMax ignored); opt: { samples (3), seed, indexBase, simple }
- * -> { inside: Uint32Array, odd: Uint32Array, samples: Uint32Array } */
-static napi_value contains_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value opt) {
-    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 4) { napi_throw_range_error(env, NULL, "contains: 4 floats per point"); return NULL; }
-    PtContainParams p; contain_params(env, opt, &p);
-    const size_t n = len / 4;
-    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
-    PtContainment* res = (PtContainment*)aligned_alloc(16, (n ? n : 1) * sizeof(PtContainment));
-    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(pts, d, n * sizeof(PtPoint));
-    int rc = pt_contains_host(ctx, pts, n, &p, res);
-    free(pts);
-    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_contains_host"); }
-    napi_value o, in, od, sm; void *pi, *po, *ps;
-    if (!(in = make_typed(env, napi_uint32_array, 4, n, &pi)) || !(od = make_typed(env, napi_uint32_array, 4, n, &po)) ||
-        !(sm = make_typed(env, napi_uint32_array, 4, n, &ps))) { free(res); return NULL; }
-    for (size_t i = 0; i < n; ++i) { ((uint32_t*)pi)[i] = res[i].inside; ((uint32_t*)po)[i] = res[i].odd; ((uint32_t*)ps)[i] = res[i].samples; }
-    free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "inside", in); napi_set_named_property(env, o, "odd", od); napi_set_named_property(env, o, "samples", sm);
-    return o;
-}
-/* points: Float32Array of 4 floats per point (x, y, z, rMax); opt as contains -> { dist, prim, u, v }, dist negative inside */
-static napi_value signed_distance_on(napi_env env, PtContext* ctx, napi_value points_v, napi_value opt) {
-    void* d; size_t len; if (!get_typed(env, points_v, napi_float32_array, &d, &len)) return NULL;
-    if (len % 4) { napi_throw_range_error(env, NULL, "signedDistance: 4 floats per point"); return NULL; }
-    PtContainParams p; contain_params(env, opt, &p);
-    const size_t n = len / 4;
-    PtPoint* pts = (PtPoint*)aligned_alloc(16, (n ? n : 1) * sizeof(PtPoint));
-    PtClosest* res = (PtClosest*)aligned_alloc(16, (n ? n : 1) * sizeof(PtClosest));
-    if (!pts || !res) { free(pts); free(res); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (n) memcpy(pts, d, n * sizeof(PtPoint));
-    int rc = pt_signed_distance_host(ctx, pts, n, &p, res);
-    free(pts);
-    if (rc != 0) { free(res); return throw_pt(env, ctx, rc, "pt_signed_distance_host"); }
-    napi_value o, dist, prim, u, v; void *pd, *pp, *pu, *pv;
-    if (!(dist = make_typed(env, napi_float32_array, 4, n, &pd)) || !(prim = make_typed(env, napi_uint32_array, 4, n, &pp)) ||
-        !(u = make_typed(env, napi_float32_array, 4, n, &pu)) || !(v = make_typed(env, napi_float32_array, 4, n, &pv))) { free(res); return NULL; }
-    for (size_t i = 0; i < n; ++i) {
-        ((float*)pd)[i] = res[i].dist; ((uint32_t*)pp)[i] = res[i].prim; ((float*)pu)[i] = res[i].u; ((float*)pv)[i] = res[i].v;
-    }
-    free(res);
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "dist", dist); napi_set_named_property(env, o, "prim", prim);
-    napi_set_named_property(env, o, "u", u); napi_set_named_property(env, o, "v", v);
-    return o;
-}
-static napi_value fn_count_hits(napi_env env, napi_callback_info info) {          /* (ctx, Float32Array rays, flags) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return count_hits_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_contains(napi_env env, napi_callback_info info) {            /* (ctx, Float32Array points, options) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return contains_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_signed_distance(napi_env env, napi_callback_info info) {     /* (ctx, Float32Array points, options) */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return signed_distance_on(env, ctx, argv[1], argv[2]);
-}
 /* rays: Float32Array (8 floats per ray); t, prim, u, v: what traceRays resolved to; rMax -> Float32Array of 8 floats per surfel */
 static napi_value hit_surfels_on(napi_env env, PtContext* ctx, napi_value* a) {
     void *d, *pt, *pp, *pu, *pv; size_t len, nt, np, nu, nv;
@@ -791,11 +489,6 @@ static napi_value hit_surfels_on(napi_env env, PtContext* ctx, napi_value* a) {
     if (ta && n) memcpy(out, sf, n * sizeof(PtSurfel));
     free(sf);
     return ta;
-}
-static napi_value fn_hit_surfels(napi_env env, napi_callback_info info) {    /* (ctx, rays, t, prim, u, v, rMax) */
-    napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
-    PtContext* ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
-    return hit_surfels_on(env, ctx, argv + 1);
 }
 
 /* The camera ray of PT_MODE_REFERENCE through the centre of pixel (x, y) of the UBO's camera, as one PtRay record (8 floats, t_max = +inf):
@@ -929,6 +622,54 @@ static napi_value throw_group(napi_env env, PtGroup* g, int rc, const char* wher
 }
 #define PTG_CALL(g, call, where) do { int rc__ = (call); if (rc__ != 0) return throw_group(env, (g), rc__, (where)); } while (0)
 
+/* Every query is registered under two names (init): `traceRays` takes a context as its first argument, `groupTraceRays` a group, and runs
+ * on the group's member 0, which holds the whole scene.  The function's data pointer says which. */
+static const struct QueryName { const char* name; Query q; int group; } QUERY_NAMES[] = {
+    {"traceRays", Q_TRACE, 0}, {"groupTraceRays", Q_TRACE, 1}, {"closestPoints", Q_CLOSEST, 0}, {"groupClosestPoints", Q_CLOSEST, 1},
+    {"sweepSpheres", Q_SWEEP, 0}, {"groupSweepSpheres", Q_SWEEP, 1}, {"nearestK", Q_NEAREST, 0}, {"groupNearestK", Q_NEAREST, 1},
+    {"signedDistance", Q_SIGNED, 0}, {"groupSignedDistance", Q_SIGNED, 1}, {"contains", Q_CONTAINS, 0}, {"groupContains", Q_CONTAINS, 1},
+    {"occlusion", Q_OCCLUSION, 0}, {"groupOcclusion", Q_OCCLUSION, 1}, {"countHits", Q_COUNT, 0}, {"groupCountHits", Q_COUNT, 1},
+    {"radiusCount", Q_RADIUS_COUNT, 0}, {"groupRadiusCount", Q_RADIUS_COUNT, 1}, {"boxCount", Q_BOX_COUNT, 0}, {"groupBoxCount", Q_BOX_COUNT, 1},
+    {"radiusSearch", Q_RADIUS, 0}, {"groupRadiusSearch", Q_RADIUS, 1}, {"boxSearch", Q_BOX, 0}, {"groupBoxSearch", Q_BOX, 1},
+    {"listHits", Q_HITS, 0}, {"groupListHits", Q_HITS, 1}, {"hitSurfels", Q_SURFELS, 0}, {"groupHitSurfels", Q_SURFELS, 1},
+};
+
+/* (ctx | group, records, the query's own arguments): anyHit | flags | k, flags | options; hitSurfels: (ctx | group, rays, t, prim, u, v, rMax) */
+static napi_value fn_query(napi_env env, napi_callback_info info) {
+    napi_value argv[7]; size_t argc = 7; void* data = NULL;
+    const napi_status got = napi_get_cb_info(env, info, &argc, argv, NULL, &data);
+    const struct QueryName* name = (const struct QueryName*)data;
+    const Query q = name->q;
+    if (got != napi_ok || argc < (q == Q_SURFELS ? 7u : q == Q_NEAREST ? 4u : 3u)) { napi_throw_type_error(env, NULL, "wrong number of arguments"); return NULL; }
+    PtContext* ctx = NULL;
+    if (name->group) {
+        PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
+        int rc = pt_group_context(g, 0, &ctx); if (rc != 0) return throw_group(env, g, rc, "pt_group_context");
+    } else if (!(ctx = get_ctx(env, argv[0]))) return NULL;
+    const napi_value opt = argv[2];
+    switch (q) {
+    case Q_SURFELS: return hit_surfels_on(env, ctx, argv + 1);
+    case Q_TRACE: { bool any = false; napi_get_value_bool(env, opt, &any); return run_query(env, ctx, q, argv[1], any ? PT_TRACE_ANY_HIT : 0u, 0, NULL); }
+    case Q_NEAREST: return run_query(env, ctx, q, argv[1], get_u32(env, argv[3]), get_u32(env, argv[2]), NULL);
+    case Q_OCCLUSION: {
+        PtOcclusionParams p; memset(&p, 0, sizeof p);
+        p.samples = prop_u32(env, opt, "samples", 16); p.seed = prop_u32(env, opt, "seed", 0); p.index_base = prop_u32(env, opt, "indexBase", 0);
+        p.bias = (float)prop_f64(env, opt, "bias", 1e-4);
+        p.flags = prop_u32(env, opt, "simple", 0) ? PT_OCCLUSION_SIMPLE_KERNEL : 0u;
+        return run_query(env, ctx, q, argv[1], 0, 0, &p);
+    }
+    case Q_CONTAINS: case Q_SIGNED: {
+        PtContainParams p; memset(&p, 0, sizeof p);
+        p.samples = prop_u32(env, opt, "samples", 3); p.seed = prop_u32(env, opt, "seed", 0); p.index_base = prop_u32(env, opt, "indexBase", 0);
+        p.flags = prop_u32(env, opt, "simple", 0) ? PT_CONTAIN_SIMPLE_KERNEL : 0u;
+        return run_query(env, ctx, q, argv[1], 0, 0, &p);
+    }
+    case Q_COUNT: case Q_RADIUS_COUNT: case Q_BOX_COUNT: return run_count(env, ctx, q, argv[1], get_u32(env, opt));
+    case Q_RADIUS: case Q_BOX: case Q_HITS: return run_list(env, ctx, q, argv[1], get_u32(env, opt));
+    default: return run_query(env, ctx, q, argv[1], get_u32(env, opt), 0, NULL);           /* closestPoints, sweepSpheres */
+    }
+}
+
 static napi_value fn_group_create(napi_env env, napi_callback_info info) {    /* (Int32Array devices | number of devices, transport) */
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     bool is_ta = false; napi_is_typedarray(env, argv[0], &is_ta);
@@ -1003,90 +744,6 @@ static napi_value fn_group_read_bvh2(napi_env env, napi_callback_info info) {  /
     PT_CALL(c0, pt_read_bvh2(c0, (uint32_t*)out, (size / 4) * 4), "pt_read_bvh2");
     return ta;
 }
-static napi_value fn_group_trace_rays(napi_env env, napi_callback_info info) {      /* (group, rays, anyHit): on member 0, which holds the whole scene */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return trace_rays_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_closest_points(napi_env env, napi_callback_info info) {  /* (group, points, flags): on member 0, which holds the whole scene */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return closest_points_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_sweep_spheres(napi_env env, napi_callback_info info) {   /* (group, sweeps, flags): on member 0, which holds the whole scene */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return sweep_spheres_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_occlusion(napi_env env, napi_callback_info info) {       /* (group, surfels, options): on member 0, which holds the whole scene */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return occlusion_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_count_hits(napi_env env, napi_callback_info info) {      /* (group, rays, flags): on member 0, which holds the whole scene */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return count_hits_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_contains(napi_env env, napi_callback_info info) {        /* (group, points, options): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return contains_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_signed_distance(napi_env env, napi_callback_info info) { /* (group, points, options): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return signed_distance_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_nearest_k(napi_env env, napi_callback_info info) {     /* (group, points, k, flags): on member 0 */
-    napi_value argv[4]; if (!get_args(env, info, 4, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return nearest_k_on(env, ctx, argv[1], argv[2], argv[3]);
-}
-static napi_value fn_group_radius_count(napi_env env, napi_callback_info info) {   /* (group, points, flags): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return radius_count_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_radius_search(napi_env env, napi_callback_info info) {  /* (group, points, flags): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return radius_search_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_box_count(napi_env env, napi_callback_info info) {      /* (group, boxes, flags): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return box_count_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_box_search(napi_env env, napi_callback_info info) {     /* (group, boxes, flags): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return box_search_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_list_hits(napi_env env, napi_callback_info info) {      /* (group, rays, flags): on member 0 */
-    napi_value argv[3]; if (!get_args(env, info, 3, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return list_hits_on(env, ctx, argv[1], argv[2]);
-}
-static napi_value fn_group_hit_surfels(napi_env env, napi_callback_info info) {     /* (group, rays, t, prim, u, v, rMax): on member 0 */
-    napi_value argv[7]; if (!get_args(env, info, 7, argv)) return NULL;
-    PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
-    PtContext* ctx = NULL; PTG_CALL(g, pt_group_context(g, 0, &ctx), "pt_group_context");
-    return hit_surfels_on(env, ctx, argv + 1);
-}
 static napi_value fn_group_set_batch(napi_env env, napi_callback_info info) {
     napi_value argv[2]; if (!get_args(env, info, 2, argv)) return NULL;
     PtGroup* g = get_group(env, argv[0]); if (!g) return NULL;
@@ -1143,16 +800,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render}, {"setBatch", fn_set_batch}, {"flush", fn_flush}, {"lastRenderMs", fn_last_ms}, {"synchronize", fn_sync}, {"getStats", fn_stats},
         {"readRadiance", fn_read_radiance}, {"readRGBA8", fn_read_rgba8}, {"readTonemapped", fn_read_tonemapped},
         {"readAccumulation", fn_read_accum}, {"restoreAccumulation", fn_set_accum},
-        {"traceRays", fn_trace_rays}, {"cameraRay", fn_camera_ray}, {"groupTraceRays", fn_group_trace_rays},
-        {"closestPoints", fn_closest_points}, {"groupClosestPoints", fn_group_closest_points},
-        {"sweepSpheres", fn_sweep_spheres}, {"groupSweepSpheres", fn_group_sweep_spheres},
-        {"countHits", fn_count_hits}, {"groupCountHits", fn_group_count_hits}, {"contains", fn_contains}, {"groupContains", fn_group_contains},
-        {"signedDistance", fn_signed_distance}, {"groupSignedDistance", fn_group_signed_distance},
-        {"nearestK", fn_nearest_k}, {"groupNearestK", fn_group_nearest_k},
-        {"listHits", fn_list_hits}, {"groupListHits", fn_group_list_hits},
-        {"boxCount", fn_box_count}, {"groupBoxCount", fn_group_box_count}, {"boxSearch", fn_box_search}, {"groupBoxSearch", fn_group_box_search},
-        {"radiusCount", fn_radius_count}, {"groupRadiusCount", fn_group_radius_count}, {"radiusSearch", fn_radius_search}, {"groupRadiusSearch", fn_group_radius_search},
-        {"occlusion", fn_occlusion}, {"groupOcclusion", fn_group_occlusion}, {"hitSurfels", fn_hit_surfels}, {"groupHitSurfels", fn_group_hit_surfels},
+        {"cameraRay", fn_camera_ray},
         {"groupCreate", fn_group_create}, {"groupDestroy", fn_group_destroy}, {"groupSize", fn_group_size},
         {"groupSetTriangles", fn_group_set_triangles}, {"groupUpdateTriangles", fn_group_update_triangles}, {"groupBvhCost", fn_group_bvh_cost}, {"groupBuildBVH", fn_group_build_bvh}, {"groupSetBVH4", fn_group_set_bvh4}, {"groupSetBVH2", fn_group_set_bvh2},
         {"groupReadBVH2", fn_group_read_bvh2}, {"groupSetBatch", fn_group_set_batch}, {"groupRender", fn_group_render}, {"groupFlush", fn_group_flush},
@@ -1162,6 +810,11 @@ static napi_value init(napi_env env, napi_value exports) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
         if (napi_set_named_property(env, exports, fns[i].name, f) != napi_ok) return NULL;
+    }
+    for (size_t i = 0; i < sizeof QUERY_NAMES / sizeof QUERY_NAMES[0]; ++i) {
+        napi_value f;
+        if (napi_create_function(env, QUERY_NAMES[i].name, NAPI_AUTO_LENGTH, fn_query, (void*)&QUERY_NAMES[i], &f) != napi_ok) return NULL;
+        if (napi_set_named_property(env, exports, QUERY_NAMES[i].name, f) != napi_ok) return NULL;
     }
     return exports;
 }
