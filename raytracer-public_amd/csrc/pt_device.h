@@ -1,11 +1,15 @@
 // pt_device.h -- device-side arithmetic shared by the HIP kernels (pt_kernels.hip,
 // pt_megakernel.hip, pt_rayquery.hip, pt_walk.h): explicit-order f32 vector helpers, the reference's ray setup and slab
 // test, the build-defined sampling functions of DESIGN.md section 4 and the one-ray traversal of the simple kernels.
+// What the host twin (pt_host.cpp) computes as well -- the constants, safe_inv, tri_hit, the sampling functions -- is written once, in
+// pt_raymath.h, and forwarded to from here; the forms that stay here are the device's own (v_fma_mix, v_perm, the BOUNDED short forms,
+// traverse()'s early-out triangle test).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pt_kernels.h"
+#include "pt_raymath.h"
 
 namespace ptk {
 
@@ -60,8 +64,8 @@ __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_b
 __device__ __forceinline__ float half_lo_minus(uint32_t w, float o) { float r; asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
 __device__ __forceinline__ float half_hi_minus(uint32_t w, float o) { float r; asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(w), "v"(o)); return r; }
 
-constexpr float kInfT = 1e30f;          // renderer.wgsl:64
-constexpr float kTriEps = 1e-7f;        // renderer.wgsl:178
+using ptry::kInfT;
+using ptry::kTriEps;
 constexpr uint32_t kLeaf = 0x80000000u;
 constexpr uint32_t kInvalidRef = 0xFFFFFFFFu;
 constexpr uint32_t kDegenerateRef = 0xFFFFFFFEu;   // child slot whose record the reference fetches and rejects (renderer.wgsl:289-291): counted, never entered
@@ -69,6 +73,7 @@ constexpr uint32_t kDegenerateRef = 0xFFFFFFFEu;   // child slot whose record th
 struct Ray { F3 o, d, inv; };
 
 template <bool B = false> __device__ __forceinline__ F3 safe_inv(F3 d) {      // renderer.wgsl:74-80
+    if constexpr (!B) return f3(ptry::safe_inv(d.x), ptry::safe_inv(d.y), ptry::safe_inv(d.z));
     return f3(fabsf(d.x) > 1e-8f ? rcp_f<B>(d.x) : kInfT,
               fabsf(d.y) > 1e-8f ? rcp_f<B>(d.y) : kInfT,
               fabsf(d.z) > 1e-8f ? rcp_f<B>(d.z) : kInfT);
@@ -149,43 +154,22 @@ __device__ __forceinline__ unsigned long long slab_sel(const F3& o, const F3& in
 __device__ __forceinline__ bool lane_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
 // ---- build-defined sampling; integer hash + fixed fmaf polynomials ----
-__device__ __forceinline__ uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-__device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t pixel, uint32_t sidx) {
-    uint32_t h = mix32(seed + 0x9E3779B9u);
-    h = mix32(h ^ pixel);
-    return mix32(h ^ sidx);
-}
-__device__ __forceinline__ float rnd(uint32_t key, uint32_t bounce, uint32_t dim) {
-    const uint32_t h = mix32(key ^ (bounce * 8u + dim + 1u) * 0x9E3779B1u);
-    return (float)(h >> 8) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ void sincos_2pi(float u, float& c, float& s) {
-    const float q = u * 4.0f;
-    const float kf = floorf(q + 0.5f);
-    const float y = (q - kf) * 1.57079632679489662f;
-    const float y2 = y * y;
-    float sp = __builtin_fmaf(y2, 2.7557319e-6f, -1.9841270e-4f);
-    sp = __builtin_fmaf(y2, sp, 8.3333333e-3f);
-    sp = __builtin_fmaf(y2, sp, -1.6666667e-1f);
-    sp = __builtin_fmaf(y2, sp, 1.0f);
-    const float sy = y * sp;
-    float cp = __builtin_fmaf(y2, -2.7557319e-7f, 2.4801587e-5f);
-    cp = __builtin_fmaf(y2, cp, -1.3888889e-3f);
-    cp = __builtin_fmaf(y2, cp, 4.1666667e-2f);
-    cp = __builtin_fmaf(y2, cp, -0.5f);
-    const float cy = __builtin_fmaf(y2, cp, 1.0f);
-    const int k = (int)kf & 3;
-    c = (k == 0) ? cy : (k == 1) ? -sy : (k == 2) ? -cy : sy;
-    s = (k == 0) ? sy : (k == 1) ? cy : (k == 2) ? -sy : -cy;
-}
+// (the text is pt_raymath.h's, which the host twin compiles as well)
+__device__ __forceinline__ uint32_t mix32(uint32_t x) { return ptry::mix32(x); }
+__device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t pixel, uint32_t sidx) { return ptry::sample_key(seed, pixel, sidx); }
+__device__ __forceinline__ float rnd(uint32_t key, uint32_t bounce, uint32_t dim) { return ptry::rnd(key, bounce, dim); }
+__device__ __forceinline__ void sincos_2pi(float u, float& c, float& s) { ptry::sincos_2pi(u, c, s); }
 // cosine-weighted direction around n in two halves: the sample in the local frame (independent of n: the megakernel's shade pass computes it while the hit
 // triangle's normal is still on its way from memory) and its transfer into the branch-free orthonormal basis of n (Duff et al.)
+// (the general forms are pt_raymath.h's; the BOUNDED ones below them differ in sqrt_normal and rcp_normal alone)
 template <bool B = false> __device__ __forceinline__ F3 cosine_local(float u1, float u2) {
+    if constexpr (!B) { F3 l; ptry::cosine_local(u1, u2, l.x, l.y, l.z); return l; }
     float c, s; sincos_2pi(u2, c, s);
     const float r = sqrt_f<B>(u1);
     return f3(r * c, r * s, sqrt_f<B>(1.0f - u1));
 }
 template <bool B = false> __device__ __forceinline__ F3 cosine_world(F3 n, F3 l) {
+    if constexpr (!B) { F3 w; ptry::cosine_world(n.x, n.y, n.z, l.x, l.y, l.z, w.x, w.y, w.z); return w; }
     const float sign = copysignf(1.0f, n.z);
     const float a = B ? -rcp_normal(sign + n.z) : -1.0f / (sign + n.z);        // (the quotient's sign is exact: -(1 / x) and (-1) / x are the same bits)
     const float b = n.x * n.y * a;
@@ -269,25 +253,13 @@ __device__ __forceinline__ void add_stats(const RenderArgs& A, int slot_of_n, ui
     }
 }
 
-// Branch-free Moller-Trumbore (renderer.wgsl:185-205) on a fetched triangle record (three axis-major pieces: v0[a], e1[a], e2[a]): the
+// Branch-free Moller-Trumbore (pt_raymath.h::tri_hit) on a fetched triangle record (three axis-major pieces: v0[a], e1[a], e2[a]): the
 // operations and comparisons of traverse(), rejections combined at the end.  Returns whether the ray hits the triangle at t > kTriEps; the
 // caller compares t with its `best`.  The all-zero record behind the last triangle (an out-of-range leaf) is rejected: |det| < eps.
 __device__ __forceinline__ bool tri_hit(F3 o, F3 d, const uint4 n0, const uint4 n1, const uint4 n2, float& t) {
-    const F3 v0 = f3(__uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x));
-    const F3 e1 = f3(__uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y));
-    const F3 e2 = f3(__uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z));
-    const F3 pv = cross3(d, e2);
-    const float det = dot3(e1, pv);
-    const bool ok_det = !(fabsf(det) < kTriEps);
-    const float inv_det = 1.0f / det;
-    const F3 sv = o - v0;
-    const float u = inv_det * dot3(sv, pv);
-    const bool ok_u = !((u < 0.0f) | (u > 1.0f));
-    const F3 q = cross3(sv, e1);
-    const float v = inv_det * dot3(d, q);
-    const bool ok_v = !((v < 0.0f) | ((u + v) > 1.0f));
-    t = inv_det * dot3(e2, q);
-    return ok_det & ok_u & ok_v & (t > kTriEps);
+    return ptry::tri_hit(o.x, o.y, o.z, d.x, d.y, d.z, __uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x),
+                         __uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y),
+                         __uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z), t);
 }
 
 // The order in which the visited children (h) of a wide node are walked, by key (t), and the stack-cap rule: they keep slot order, except

@@ -5,6 +5,7 @@
 #include "pt_host.h"
 #include "pt_expose.h"
 #include "pt_closest.h"
+#include "pt_raymath.h"
 #include "pt_overlap.h"
 #include "pt_sweep.h"
 
@@ -607,31 +608,39 @@ struct PointWalk {
 };
 struct WalkCounters { uint64_t nodes = 0, tris = 0, drops = 0, maxstack = 0; };
 
-inline float record_d2(const TriRecord& r, const float p[3]) {
+// d2 of one record with the u, v it was computed from
+inline float record_uv_d2(const TriRecord& r, const float p[3], float& u, float& v) {
     const float ax = p[0] - r.axis[0][0], ay = p[1] - r.axis[1][0], az = p[2] - r.axis[2][0];
-    float u, v;
     ptcp::closest_uv(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
     return ptcp::closest_d2(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
 }
+// the six halves of a packed box: w = {mn.x | mn.y << 16, mn.z | mx.x << 16, mx.y | mx.z << 16}
+inline Box unpack_box(const uint32_t w[3]) {
+    return {{half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)},
+            {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)}};
+}
+// the record of an item that found nothing: {+inf bits, 0xFFFFFFFF, 0, 0}
+inline void write_miss(uint32_t* o) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; }
 // pt_pointquery.hip::box_bound2: per axis max(mn - (p + s), (p - s) - mx, 0), each difference rounded once
 inline float box_bound2_h(const float hi[3], const float lo[3], const uint32_t w[3]) {
-    const float mn[3] = {half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)};
-    const float mx[3] = {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)};
+    const Box b = unpack_box(w);
     float g[3];
-    for (int k = 0; k < 3; ++k) g[k] = wmax_h(wmax_h(mn[k] - hi[k], lo[k] - mx[k]), 0.0f);
+    for (int k = 0; k < 3; ++k) g[k] = wmax_h(wmax_h(b.mn[k] - hi[k], lo[k] - b.mx[k]), 0.0f);
     return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
 }
 
-// The walk of both point queries: `best2` is what child boxes and stacked entries are compared with, and `leaf(tri)` is called for every
-// reached leaf with tri < num_tris, in visit order -- the closest-point query lowers best2 there, the radius query leaves it alone.
-// `key(box words)` is what a child box is ordered and stacked by: bound2 of a point, or 0 / +inf of a box query (box_search).
+// The walk of every twin, the point queries' and the ray queries': `best2` is what child keys and stacked entries are compared with, and
+// `leaf(tri)` is called for every reached leaf with tri < num_tris, in visit order -- the closest-point query lowers best2 there, the
+// radius query and the crossing counts leave it alone.  `key(box words, reference)` is what a child is ordered and stacked by: bound2 of
+// a point, 0 / +inf of a box query (box_search), tmin / +inf of a sweep or a ray (sweep_spheres, walk_ray_h).  A child is visited iff its
+// key is below best2, so a key of +inf is a child that is never visited.
 template <class Key, class Leaf>
 void walk_keys_h(const PointWalk& W, Key key, const float& best2, WalkCounters& cnt, Leaf leaf) {
     const WideBvh& wb = *W.wide;
     if (wb.root_ref == kInvalid || W.num_tris == 0u) return;
     cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
     if (wb.root_degenerate) return;
-    if (!(key(wb.root_box) < best2)) return;
+    if (!(key(wb.root_box, wb.root_ref) < best2)) return;
     struct Entry { uint32_t ref; float b2; } stk[kStackCap];
     uint32_t cur = wb.root_ref;
     int sp = 0;
@@ -648,7 +657,7 @@ void walk_keys_h(const PointWalk& W, Key key, const float& best2, WalkCounters& 
             const WideNode& nd = wb.nodes[(cur - W.node_base16) >> 2];
             float t[4]; bool h[4]; uint32_t r[4];
             for (int k = 0; k < 4; ++k) {
-                r[k] = nd.child[k].ref; t[k] = key(nd.child[k].box); h[k] = t[k] < best2;
+                r[k] = nd.child[k].ref; t[k] = key(nd.child[k].box, r[k]); h[k] = t[k] < best2;
                 cnt.nodes += (r[k] != kInvalid);
             }
             int nslot = -1, fslot = -1;
@@ -682,12 +691,13 @@ template <class Leaf>
 void walk_h(const PointWalk& W, const float p[3], const float& best2, WalkCounters& cnt, Leaf leaf) {
     const float hi[3] = {p[0] + ptcp::kSlack, p[1] + ptcp::kSlack, p[2] + ptcp::kSlack};
     const float lo[3] = {p[0] - ptcp::kSlack, p[1] - ptcp::kSlack, p[2] - ptcp::kSlack};
-    walk_keys_h(W, [&](const uint32_t* w) { return box_bound2_h(hi, lo, w); }, best2, cnt, leaf);
+    walk_keys_h(W, [&](const uint32_t* w, uint32_t) { return box_bound2_h(hi, lo, w); }, best2, cnt, leaf);
 }
 void walk_point_h(const PointWalk& W, const float p[3], float& best2, uint32_t& best_tri, WalkCounters& cnt) {
     best_tri = kInvalid;
     walk_h(W, p, best2, cnt, [&](uint32_t tri) {
-        const float d2 = record_d2(W.rec[tri], p);
+        float u, v;
+        const float d2 = record_uv_d2(W.rec[tri], p, u, v);
         if (d2 < best2) { best2 = d2; best_tri = tri; }
     });
 }
@@ -770,12 +780,12 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
             if (ptcp::point_walked(q[0], q[1], q[2], q[3])) {
                 if (bvh4) walk_point_h(S.W, q, best2, tri, cnt);
                 else {
-                    for (uint32_t t = 0; t < num_tris; ++t) { const float d2 = record_d2(rec[t], q); if (d2 < best2) { best2 = d2; tri = t; } }
+                    for (uint32_t t = 0; t < num_tris; ++t) { float u, v; const float d2 = record_uv_d2(rec[t], q, u, v); if (d2 < best2) { best2 = d2; tri = t; } }
                     cnt.tris += num_tris;
                 }
             }
             uint32_t* o = out + i * 4;
-            if (tri == kInvalid) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; continue; }
+            if (tri == kInvalid) { write_miss(o); continue; }
             const TriRecord& r = rec[tri];
             float u, v;
             ptcp::closest_uv(q[0] - r.axis[0][0], q[1] - r.axis[1][0], q[2] - r.axis[2][0],
@@ -791,15 +801,6 @@ bool closest_points(const float* tris, uint32_t num_tris, const uint32_t* bvh4, 
 // Radius queries (host twin of pt_radius.hip): the closest-point walk with best2 held at r_max^2, every accepted leaf counted and, in a
 // second walk of the same steps, listed at offsets[i] + k -- the device's two walks around its scan
 // ------------------------------------------------------------------------------------
-namespace {
-// d2 of one record with the u, v it was computed from (record_d2's operations)
-inline float record_uv_d2(const TriRecord& r, const float p[3], float& u, float& v) {
-    const float ax = p[0] - r.axis[0][0], ay = p[1] - r.axis[1][0], az = p[2] - r.axis[2][0];
-    ptcp::closest_uv(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
-    return ptcp::closest_d2(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
-}
-} // namespace
-
 bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* points, uint64_t n,
                    uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
     TwinScene S;
@@ -844,9 +845,9 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
         };
         if (bvh4) {
             const float bound = 1.0f;
-            walk_keys_h(S.W, [&](const uint32_t* w) {
-                const bool meets = ptov::node_overlaps(b, half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu),
-                                                       half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16));
+            walk_keys_h(S.W, [&](const uint32_t* w, uint32_t) {
+                const Box c = unpack_box(w);
+                const bool meets = ptov::node_overlaps(b, c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2]);
                 return meets ? 0.0f : std::numeric_limits<float>::infinity();
             }, bound, cnt, leaf);
             return;
@@ -875,7 +876,7 @@ bool sweep_spheres(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
             const float o[3] = {q[0], q[1], q[2]}, d[3] = {q[4], q[5], q[6]}, r = q[7];
             float best = q[3]; uint32_t tri = kInvalid;
             if (ptsw::sweep_walked(o[0], o[1], o[2], q[3], d[0], d[1], d[2], r)) {
-                const float inv[3] = {ptsw::safe_inv(d[0]), ptsw::safe_inv(d[1]), ptsw::safe_inv(d[2])};
+                const float inv[3] = {ptry::safe_inv(d[0]), ptry::safe_inv(d[1]), ptry::safe_inv(d[2])};
                 auto leaf = [&](uint32_t t) {
                     const TriRecord& tr = rec[t];
                     const float tt = ptsw::tri_sweep(o[0], o[1], o[2], d[0], d[1], d[2], inv[0], inv[1], inv[2], r, best, tr.axis[0][0], tr.axis[1][0], tr.axis[2][0],
@@ -885,10 +886,10 @@ bool sweep_spheres(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
                 if (bvh4) {
                     const float R = r + ptcp::kSlack;
                     const float op[3] = {o[0] + R, o[1] + R, o[2] + R}, om[3] = {o[0] - R, o[1] - R, o[2] - R};
-                    walk_keys_h(S.W, [&](const uint32_t* bw) {
+                    walk_keys_h(S.W, [&](const uint32_t* bw, uint32_t) {
+                        const Box c = unpack_box(bw);
                         float tmin;
-                        const bool pass = ptsw::node_pass(half_to_float(bw[0] & 0xffffu), half_to_float(bw[0] >> 16), half_to_float(bw[1] & 0xffffu),
-                                                          half_to_float(bw[1] >> 16), half_to_float(bw[2] & 0xffffu), half_to_float(bw[2] >> 16),
+                        const bool pass = ptsw::node_pass(c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2],
                                                           op[0], op[1], op[2], om[0], om[1], om[2], inv[0], inv[1], inv[2], best, tmin);
                         return pass ? tmin : std::numeric_limits<float>::infinity();
                     }, best, cnt, leaf);
@@ -898,7 +899,7 @@ bool sweep_spheres(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
                 }
             }
             uint32_t* po = out + i * 4;
-            if (tri == kInvalid) { po[0] = 0x7F800000u; po[1] = kInvalid; po[2] = 0u; po[3] = 0u; continue; }
+            if (tri == kInvalid) { write_miss(po); continue; }
             const TriRecord& tr = rec[tri];
             float u, v;
             best = ptsw::time_of(best);
@@ -931,7 +932,8 @@ bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
             uint32_t count = 0;
             // pt_knn.hip::nk_insert: behind every pair with d2' <= d2, the tail shifted down from the end, the pair behind the k-th lost
             auto leaf = [&](uint32_t t) {
-                const float d2 = record_d2(rec[t], q);
+                float u, v;
+                const float d2 = record_uv_d2(rec[t], q, u, v);
                 if (!(d2 < worst2)) return;
                 uint32_t j = count < k ? count : k - 1u;
                 for (; j > 0u && lst[j - 1u].d2 > d2; --j) lst[j] = lst[j - 1u];
@@ -952,7 +954,7 @@ bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
                 (void)record_uv_d2(rec[lst[j].tri], q, u, v);
                 o[0] = bits_of(std::sqrt(lst[j].d2)); o[1] = lst[j].tri; o[2] = bits_of(u); o[3] = bits_of(v);
             }
-            for (uint32_t j = count; j < k; ++j, o += 4) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; }
+            for (uint32_t j = count; j < k; ++j, o += 4) write_miss(o);
         }
     });
     S.reduce(counters, n);
@@ -1231,60 +1233,12 @@ bool procedural_scene(uint32_t kind, uint32_t seed, uint32_t num_tris, float* ou
     return false;
 }
 
-// ---- ambient-occlusion sample rays: pt_device.h's sampling functions restated for the host, operation by operation ----
-// f32 throughout, every operation rounded once (the library is built with -ffp-contract=off), fmaf exactly where the device code has it.
-namespace {
-inline uint32_t mix32_h(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-inline uint32_t sample_key_h(uint32_t seed, uint32_t pixel, uint32_t sidx) {
-    uint32_t h = mix32_h(seed + 0x9E3779B9u);
-    h = mix32_h(h ^ pixel);
-    return mix32_h(h ^ sidx);
-}
-inline float rnd_h(uint32_t key, uint32_t bounce, uint32_t dim) {
-    const uint32_t h = mix32_h(key ^ (bounce * 8u + dim + 1u) * 0x9E3779B1u);
-    return float(h >> 8) * (1.0f / 16777216.0f);
-}
-inline void sincos_2pi_h(float u, float& c, float& s) {
-    const float q = u * 4.0f;
-    const float kf = std::floor(q + 0.5f);
-    const float y = (q - kf) * 1.57079632679489662f;
-    const float y2 = y * y;
-    float sp = std::fmaf(y2, 2.7557319e-6f, -1.9841270e-4f);
-    sp = std::fmaf(y2, sp, 8.3333333e-3f);
-    sp = std::fmaf(y2, sp, -1.6666667e-1f);
-    sp = std::fmaf(y2, sp, 1.0f);
-    const float sy = y * sp;
-    float cp = std::fmaf(y2, -2.7557319e-7f, 2.4801587e-5f);
-    cp = std::fmaf(y2, cp, -1.3888889e-3f);
-    cp = std::fmaf(y2, cp, 4.1666667e-2f);
-    cp = std::fmaf(y2, cp, -0.5f);
-    const float cy = std::fmaf(y2, cp, 1.0f);
-    const int k = int(kf) & 3;
-    c = (k == 0) ? cy : (k == 1) ? -sy : (k == 2) ? -cy : sy;
-    s = (k == 0) ? sy : (k == 1) ? cy : (k == 2) ? -sy : -cy;
-}
-inline void cosine_local_h(float u1, float u2, float l[3]) {
-    float c, s; sincos_2pi_h(u2, c, s);
-    const float r = std::sqrt(u1);
-    l[0] = r * c; l[1] = r * s; l[2] = std::sqrt(1.0f - u1);
-}
-// the branch-free orthonormal basis of n (Duff et al.), (t * l.x + bt * l.y) + n * l.z per component
-inline void cosine_world_h(const float n[3], const float l[3], float out[3]) {
-    const float sign = std::copysign(1.0f, n[2]);
-    const float a = -1.0f / (sign + n[2]);
-    const float b = n[0] * n[1] * a;
-    const float t[3] = {1.0f + sign * n[0] * n[0] * a, sign * b, -sign * n[0]};
-    const float bt[3] = {b, sign + n[1] * n[1] * a, -n[1]};
-    for (int k = 0; k < 3; ++k) out[k] = (t[k] * l[0] + bt[k] * l[1]) + n[k] * l[2];
-}
-} // namespace
-
+// ---- ambient-occlusion sample rays: the sampling functions of pt_raymath.h, the text the kernels compile ----
 void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, float* rays) {
     for (uint64_t i = 0; i < n; ++i) {
         const float* sf = surfels + i * 8;
         const float* p = sf; const float r_max = sf[3]; const float* nr = sf + 4;
-        const bool nan = std::isnan(p[0]) || std::isnan(p[1]) || std::isnan(p[2]) || std::isnan(nr[0]) || std::isnan(nr[1]) || std::isnan(nr[2]);
-        const bool traced = !nan && (r_max > 0.0f);
+        const bool traced = ptry::surfel_walked(p[0], p[1], p[2], nr[0], nr[1], nr[2], r_max);
         const uint32_t pixel = index_base + uint32_t(i);
         for (uint32_t s = 0; s < samples; ++s) {
             float* r = rays + (i * samples + s) * 8;
@@ -1292,12 +1246,12 @@ void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t
                 r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = 0.0f; r[4] = nr[0]; r[5] = nr[1]; r[6] = nr[2]; r[7] = 0.0f;
                 continue;
             }
-            const uint32_t key = sample_key_h(seed, pixel, s);
-            const float u1 = rnd_h(key, 0u, 2u), u2 = rnd_h(key, 0u, 3u);
-            float l[3], d[3];
-            cosine_local_h(u1, u2, l);
-            cosine_world_h(nr, l, d);
-            for (int k = 0; k < 3; ++k) { r[k] = p[k] + nr[k] * bias; r[4 + k] = d[k]; }
+            const uint32_t key = ptry::sample_key(seed, pixel, s);
+            const float u1 = ptry::rnd(key, 0u, 2u), u2 = ptry::rnd(key, 0u, 3u);
+            float l[3];
+            ptry::cosine_local(u1, u2, l[0], l[1], l[2]);
+            ptry::cosine_world(nr[0], nr[1], nr[2], l[0], l[1], l[2], r[4], r[5], r[6]);
+            ptry::offset_origin(p[0], p[1], p[2], nr[0], nr[1], nr[2], bias, r[0], r[1], r[2]);
             r[3] = r_max; r[7] = 0.0f;
         }
     }
@@ -1307,128 +1261,50 @@ void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t
 // Crossing counts and containment (host twin of pt_crossings.hip): the same records, operations, order, cap and counters
 // ------------------------------------------------------------------------------------
 namespace {
-constexpr float kInfT_h = 1e30f, kTriEps_h = 1e-7f;
 struct RayH { float o[3], d[3], inv[3]; };
 
 // pt_device.h::slab: the min / max form of the one-ray kernels (the sign-selected form of the persistent kernels gives the same bits)
 inline bool slab_h(const RayH& r, const uint32_t w[3], float best, float& tmin_out) {
-    const float mn[3] = {half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)};
-    const float mx[3] = {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)};
+    const Box b = unpack_box(w);
     float t1[3], t2[3];
-    for (int k = 0; k < 3; ++k) { t1[k] = (mn[k] - r.o[k]) * r.inv[k]; t2[k] = (mx[k] - r.o[k]) * r.inv[k]; }
+    for (int k = 0; k < 3; ++k) { t1[k] = (b.mn[k] - r.o[k]) * r.inv[k]; t2[k] = (b.mx[k] - r.o[k]) * r.inv[k]; }
     const float tmin = wmax_h(wmax_h(wmin_h(t1[0], t2[0]), wmin_h(t1[1], t2[1])), wmin_h(t1[2], t2[2]));
     const float tmax = wmin_h(wmin_h(wmax_h(t1[0], t2[0]), wmax_h(t1[1], t2[1])), wmax_h(t1[2], t2[2]));
     tmin_out = tmin;
     return (tmax >= wmax_h(tmin, 0.0f)) && (tmin < best);
 }
-// pt_device.h::tri_hit on a triangle record, operation by operation
-inline bool tri_hit_h(const RayH& r, const TriRecord& rec, float& t) {
-    const float v0[3] = {rec.axis[0][0], rec.axis[1][0], rec.axis[2][0]};
-    const float e1[3] = {rec.axis[0][1], rec.axis[1][1], rec.axis[2][1]};
-    const float e2[3] = {rec.axis[0][2], rec.axis[1][2], rec.axis[2][2]};
-    auto dot = [](const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-    auto cross = [](const float a[3], const float b[3], float c[3]) {
-        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    float pv[3]; cross(r.d, e2, pv);
-    const float det = dot(e1, pv);
-    const bool ok_det = !(std::fabs(det) < kTriEps_h);
-    const float inv_det = 1.0f / det;
-    const float sv[3] = {r.o[0] - v0[0], r.o[1] - v0[1], r.o[2] - v0[2]};
-    const float u = inv_det * dot(sv, pv);
-    const bool ok_u = !((u < 0.0f) || (u > 1.0f));
-    float q[3]; cross(sv, e1, q);
-    const float v = inv_det * dot(r.d, q);
-    const bool ok_v = !((v < 0.0f) || ((u + v) > 1.0f));
-    t = inv_det * dot(e2, q);
-    return ok_det && ok_u && ok_v && (t > kTriEps_h);
+// ptry::tri_hit and ptry::hit_uv on a triangle record
+inline bool record_hit(const RayH& r, const TriRecord& rec, float& t) {
+    return ptry::tri_hit(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], rec.axis[0][0], rec.axis[1][0], rec.axis[2][0],
+                         rec.axis[0][1], rec.axis[1][1], rec.axis[2][1], rec.axis[0][2], rec.axis[1][2], rec.axis[2][2], t);
 }
-
-// the counting walk; every crossing is handed to accept(t, triangle)
-template <class Accept>
-uint32_t walk_cross_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt, Accept accept) {
-    const WideBvh& wb = *W.wide;
-    uint32_t count = 0;
-    if (wb.root_ref == kInvalid || W.num_tris == 0u) return 0u;
-    cnt.nodes += 1; if (cnt.maxstack < 1u) cnt.maxstack = 1u;
-    if (wb.root_degenerate) return 0u;
-    float troot;
-    if (!slab_h(r, wb.root_box, best, troot)) return 0u;
-    struct Entry { uint32_t ref; float tmin; } stk[kStackCap];
-    uint32_t cur = wb.root_ref;
-    int sp = 0;
-    for (;;) {
-        bool need_pop = false;
-        if (cur & kLeafFlag) {
-            const uint32_t ti4 = cur & 0x7fffffffu;
-            if (ti4 < 4u * W.num_tris) {
-                cnt.tris += 1;
-                float t;
-                if (tri_hit_h(r, W.rec[ti4 >> 2], t) && t < best) { accept(t, ti4 >> 2); ++count; }
-            }
-            need_pop = true;
-        } else {
-            const WideNode& nd = wb.nodes[(cur - W.node_base16) >> 2];
-            float t[4] = {0, 0, 0, 0}; bool h[4]; uint32_t c[4];
-            for (int k = 0; k < 4; ++k) {
-                c[k] = nd.child[k].ref; h[k] = (c[k] < kDegenerate) && slab_h(r, nd.child[k].box, best, t[k]);
-                cnt.nodes += (c[k] != kInvalid);
-            }
-            int nslot = -1, fslot = -1;
-            for (int k = 0; k < 4; ++k) if (h[k]) { if (nslot < 0 || t[k] < t[nslot]) nslot = k; if (fslot < 0) fslot = k; }
-            if (nslot < 0) {
-                need_pop = true;
-            } else {
-                // pushes far -> near; the slot the nearest child left holds the first visited child
-                for (int k = 3; k >= 1; --k) {
-                    if (!h[k] || fslot == k) continue;
-                    const int src = (nslot == k) ? fslot : k;
-                    if (sp < kStackCap) { stk[sp].ref = c[src]; stk[sp].tmin = t[src]; ++sp; } else cnt.drops += 1;
-                }
-                const uint64_t depth = uint64_t(sp) + (sp < kStackCap ? 1u : 0u);
-                if (depth > cnt.maxstack) cnt.maxstack = depth;
-                if (sp < kStackCap) cur = c[nslot];
-                else { need_pop = true; cnt.drops += 1; }
-            }
-        }
-        if (need_pop) {
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                if (stk[sp].tmin < best) { cur = stk[sp].ref; found = true; break; }      // always passes: `best` never moves
-            }
-            if (!found) break;
-        }
-    }
-    return count;
+inline void record_hit_uv(const RayH& r, const TriRecord& rec, float& u, float& v) {
+    ptry::hit_uv(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], rec.axis[0][0], rec.axis[1][0], rec.axis[2][0],
+                 rec.axis[0][1], rec.axis[1][1], rec.axis[2][1], rec.axis[0][2], rec.axis[1][2], rec.axis[2][2], u, v);
 }
-uint32_t walk_count_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt) {
-    return walk_cross_h(W, r, best, cnt, [](float, uint32_t) {});
+// The ray walk: walk_keys_h with the key of a child = tmin of its slab test, +inf where that test fails or the child is a degenerate or
+// empty slot (reference >= kDegenerate: its inverted box would pass the min / max form, pt_device.h::kEmptyBox*).  best <= 1e30 < +inf,
+// so "key < best" is "the slab test passes"; `best` never moves, and every stacked entry passes its re-validation.
+template <class Leaf>
+void walk_ray_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt, Leaf leaf) {
+    walk_keys_h(W, [&](const uint32_t* w, uint32_t ref) {
+        float tmin;
+        return (ref < kDegenerate && slab_h(r, w, best, tmin)) ? tmin : std::numeric_limits<float>::infinity();
+    }, best, cnt, leaf);
 }
 // a PtRay record (pt_rays.h::load_ray, ray_traced): whether the ray is walked, and then `best` = min(t_max, kInfT)
 inline bool load_ray_h(const float* q, RayH& r, float& best) {
-    for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = std::fabs(q[4 + k]) > 1e-8f ? 1.0f / q[4 + k] : kInfT_h; }
-    const float tmax = q[3];
-    const bool nan = std::isnan(r.o[0]) || std::isnan(r.o[1]) || std::isnan(r.o[2]) || std::isnan(r.d[0]) || std::isnan(r.d[1]) || std::isnan(r.d[2]);
-    best = wmin_h(tmax, kInfT_h);
-    return !nan && tmax > 0.0f;
+    for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = ptry::safe_inv(q[4 + k]); }
+    best = wmin_h(q[3], ptry::kInfT);
+    return ptry::ray_walked(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], q[3]);
 }
-// pt_rayquery.hip::hit_record on a triangle record, operation by operation: the u, v of the accepted test
-inline void hit_uv_h(const RayH& r, const TriRecord& rec, float& u, float& v) {
-    const float v0[3] = {rec.axis[0][0], rec.axis[1][0], rec.axis[2][0]};
-    const float e1[3] = {rec.axis[0][1], rec.axis[1][1], rec.axis[2][1]};
-    const float e2[3] = {rec.axis[0][2], rec.axis[1][2], rec.axis[2][2]};
-    auto dot = [](const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-    auto cross = [](const float a[3], const float b[3], float c[3]) {
-        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    float pv[3]; cross(r.d, e2, pv);
-    const float det = dot(e1, pv);
-    const float inv_det = 1.0f / det;
-    const float sv[3] = {r.o[0] - v0[0], r.o[1] - v0[1], r.o[2] - v0[2]};
-    u = inv_det * dot(sv, pv);
-    float q[3]; cross(sv, e1, q);
-    v = inv_det * dot(r.d, q);
+// every crossing of a walked ray below `best`, handed to accept(t, triangle) in visit order (or in index order with brute force)
+template <class Accept>
+void ray_crossings(const TwinScene& S, bool walk, const RayH& r, float best, WalkCounters& cnt, Accept accept) {
+    auto leaf = [&](uint32_t tri) { float t; if (record_hit(r, S.rec[tri], t) && t < best) accept(t, tri); };
+    if (walk) { walk_ray_h(S.W, r, best, cnt, leaf); return; }
+    for (uint32_t t = 0; t < S.W.num_tris; ++t) leaf(t);
+    cnt.tris += S.W.num_tris;
 }
 } // namespace
 
@@ -1441,13 +1317,7 @@ bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
         for (uint64_t i = first; i < end; ++i) {
             RayH r; float best;
             uint32_t count = 0;
-            if (load_ray_h(rays + i * 8, r, best)) {
-                if (bvh4) count = walk_count_h(S.W, r, best, cnt);
-                else {
-                    for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, S.rec[t], th) && th < best) ++count; }
-                    cnt.tris += num_tris;
-                }
-            }
+            if (load_ray_h(rays + i * 8, r, best)) ray_crossings(S, bvh4 != nullptr, r, best, cnt, [&](float, uint32_t) { ++count; });
             counts[i] = count;
         }
     });
@@ -1495,15 +1365,12 @@ bool list_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
     list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
         RayH r; float best;
         if (!load_ray_h(rays + i * 8, r, best)) return;
-        auto crossing = [&](float t, uint32_t tri) {
+        ray_crossings(S, bvh4 != nullptr, r, best, cnt, [&](float t, uint32_t tri) {
             accept([&](uint32_t* o) {
-                float u, v; hit_uv_h(r, S.rec[tri], u, v);
+                float u, v; record_hit_uv(r, S.rec[tri], u, v);
                 o[0] = bits_of(t); o[1] = tri; o[2] = bits_of(u); o[3] = bits_of(v);
             });
-        };
-        if (bvh4) { walk_cross_h(S.W, r, best, cnt, crossing); return; }
-        for (uint32_t t = 0; t < num_tris; ++t) { float th; if (tri_hit_h(r, S.rec[t], th) && th < best) crossing(th, t); }
-        cnt.tris += num_tris;
+        });
     }, [&](uint64_t w, uint64_t i) {
         if (!sorted || offsets[i + 1] > capacity || offsets[i + 1] - offsets[i] <= 1u) return;
         Entry* first = reinterpret_cast<Entry*>(entries + offsets[i] * 4);

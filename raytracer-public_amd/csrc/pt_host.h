@@ -140,7 +140,7 @@ bool nearest_k(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint6
 // ---- crossing counts and containment (pt_count_hits, pt_contains; host twin of pt_crossings.hip, bit for bit) --------------------------
 // rays: n x (org, t_max, dir, reserved); counts: n words.  bvh4 = nullptr: every triangle in index order; else the walk of the kernels over
 // build_wide_bvh(bvh4) and build_tri_records(tris): a record is counted when tri_hit holds and t < best = min(t_max, 1e30), which never
-// moves.  counters (optional): rays, nodes examined, triangles tested, stack drops, max stack -- as the device's PT_COUNT_STATS counts them.
+// moves.  The ray arithmetic (ray_walked, safe_inv, tri_hit, hit_uv) is pt_raymath.h, the text the kernels compile.  counters (optional): rays, nodes examined, triangles tested, stack drops, max stack -- as the device's PT_COUNT_STATS counts them.
 bool count_hits(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* rays, uint64_t n,
                 uint32_t* counts, uint64_t* counters, std::string& err);
 // points: n x (x, y, z, ignored); out: n x (inside, odd, samples, 0): occlusion_rays of {p, +inf, (0, 0, 1)} with bias 0 -> count_hits ->
@@ -169,6 +169,7 @@ uint32_t rect_tile_count_of(uint32_t rank, uint32_t count, const uint32_t rect[4
 
 // ---- ambient-occlusion sample rays (host twin of pt_occlusion.hip::occlusion_rays_kernel; pt_occlusion_rays_host) ----
 // surfels: 8 floats each (p, r_max, n, reserved); rays: n * samples records of 8 floats (org, t_max, dir, 0), item i * samples + s.
+// The sampling functions are pt_raymath.h's, the text the kernels compile.
 void occlusion_rays(const float* surfels, uint64_t n, uint32_t samples, uint32_t seed, uint32_t index_base, float bias, float* rays);
 
 } // namespace pt

@@ -1,7 +1,8 @@
 // pt_rays.h -- what the ray-side batched queries hold in common, once: pt_rayquery.hip (pt_trace_rays), pt_occlusion.hip (pt_occlusion),
 // pt_crossings.hip (pt_count_hits, pt_contains) and pt_hitlist.hip (pt_list_hits).  The bit-for-bit contract between them -- a hit-list
 // entry equals the pt_trace_rays record of its triangle, count >= 1 exactly where any-hit hits, a sample ray of pt_contains equals the
-// pt_occlusion_rays record -- holds because each of these is one function here and not a copy per file:
+// pt_occlusion_rays record -- holds because each of these is one function here and not a copy per file; the arithmetic among them
+// (ray_traced, hit_entry's u and v, surfel_traced, sample_ray) forwards to pt_raymath.h, the text the host twin compiles as well:
 //   * load_ray, ray_traced                        a PtRay record and whether it is walked
 //   * hit_entry                                   t, triangle, u, v of an accepted hit
 //   * Surfel, load_surfel, surfel_traced, sample_ray
@@ -27,23 +28,16 @@ __device__ __forceinline__ void load_ray(const float4* __restrict__ rays, uint32
 }
 // a ray with a NaN anywhere, or with t_max <= 0, is a miss and is not traversed (a NaN t_max fails the comparison as well)
 __device__ __forceinline__ bool ray_traced(F3 o, F3 d, float tmax) {
-    const bool nan = __builtin_isnan(o.x) | __builtin_isnan(o.y) | __builtin_isnan(o.z) | __builtin_isnan(d.x) | __builtin_isnan(d.y) | __builtin_isnan(d.z);
-    return !nan & (tmax > 0.0f);
+    return ptry::ray_walked(o.x, o.y, o.z, d.x, d.y, d.z, tmax);
 }
 // The 16-byte record of a hit at t on a fetched triangle record (three axis-major pieces: v0[a], e1[a], e2[a]; pt_host.h::TriRecord).
-// u, v are recomputed with the arithmetic of the accepted test (renderer.wgsl:185-205, pt_device.h::traverse and tri_hit): the same
-// operations on the same operands, so the same bits, and the traversal step keeps no registers for them.
+// u, v are recomputed with the arithmetic of the accepted test (renderer.wgsl:185-205, pt_device.h::traverse and pt_raymath.h::tri_hit;
+// pt_raymath.h::hit_uv): the same operations on the same operands, so the same bits, and the traversal step keeps no registers for them.
 __device__ __forceinline__ uint4 hit_entry(F3 o, F3 d, float t, uint32_t tri, const uint4 n0, const uint4 n1, const uint4 n2) {
-    const F3 v0 = f3(__uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x));
-    const F3 e1 = f3(__uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y));
-    const F3 e2 = f3(__uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z));
-    const F3 p = cross3(d, e2);
-    const float det = dot3(e1, p);
-    const float inv_det = 1.0f / det;
-    const F3 s = o - v0;
-    const float u = inv_det * dot3(s, p);
-    const F3 q = cross3(s, e1);
-    const float v = inv_det * dot3(d, q);
+    float u, v;
+    ptry::hit_uv(o.x, o.y, o.z, d.x, d.y, d.z, __uint_as_float(n0.x), __uint_as_float(n1.x), __uint_as_float(n2.x),
+                 __uint_as_float(n0.y), __uint_as_float(n1.y), __uint_as_float(n2.y),
+                 __uint_as_float(n0.z), __uint_as_float(n1.z), __uint_as_float(n2.z), u, v);
     return make_uint4(__float_as_uint(t), tri, __float_as_uint(u), __float_as_uint(v));
 }
 
@@ -55,15 +49,14 @@ __device__ __forceinline__ Surfel load_surfel(const float4* __restrict__ surfels
 }
 // a surfel with a NaN in p, n or r_max, or with r_max <= 0, is not traced (a NaN r_max fails the comparison as well)
 __device__ __forceinline__ bool surfel_traced(const Surfel& s) {
-    const bool nan = __builtin_isnan(s.p.x) | __builtin_isnan(s.p.y) | __builtin_isnan(s.p.z) | __builtin_isnan(s.n.x) | __builtin_isnan(s.n.y) | __builtin_isnan(s.n.z);
-    return !nan & (s.r_max > 0.0f);
+    return ptry::surfel_walked(s.p.x, s.p.y, s.p.z, s.n.x, s.n.y, s.n.z, s.r_max);
 }
 // sample ray s of the surfel with sample index `pixel` = index_base + i (mod 2^32): DESIGN.md section 4's cosine sampling around n as given
 __device__ __forceinline__ void sample_ray(const Surfel& sf, uint32_t seed, uint32_t pixel, uint32_t s, float bias, F3& o, F3& d) {
     const uint32_t key = sample_key(seed, pixel, s);
     const float u1 = rnd(key, 0u, 2u), u2 = rnd(key, 0u, 3u);
     d = cosine_dir(sf.n, u1, u2);
-    o = sf.p + sf.n * bias;
+    ptry::offset_origin(sf.p.x, sf.p.y, sf.p.z, sf.n.x, sf.n.y, sf.n.z, bias, o.x, o.y, o.z);
 }
 
 // The lanes of `flag` that hold the same id add their number to word 1 of out[id] with ONE atomic (the first of them issues it): the

@@ -5,7 +5,7 @@
 // a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), every product rounded, then the difference.
 //
 // A sweep is (o, t_max, d, r): the centre o + t*d, 0 <= t < t_max, of a sphere of radius r.  Per sweep, once: inv = safe_inv(d) (1 / d_k,
-// or 1e30 where |d_k| <= 1e-8: pt_device.h), best = t_max.  Per triangle record (v0, e1, e2), in this order (tri_sweep):
+// or 1e30 where |d_k| <= 1e-8: pt_raymath.h), best = t_max.  Per triangle record (v0, e1, e2), in this order (tri_sweep):
 //   1. own box.  v1 = v0 + e1, v2 = v0 + e2 per component; mn_k, mx_k = the smallest and largest of v0_k, v1_k, v2_k; the origin moved
 //      by the radius, op_k = o_k + r, om_k = o_k - r; a_k = (mn_k - op_k) * inv_k, b_k = (mx_k - om_k) * inv_k; near_k, far_k = a_k, b_k
 //      for inv_k >= 0 and b_k, a_k for inv_k < 0; tmin = max(near), tmax = min(far); t_in = tmin > 0 ? tmin : 0.  The triangle is
@@ -49,7 +49,6 @@ PT_CP_FN bool sweep_walked(float ox, float oy, float oz, float tmax, float dx, f
 }
 PT_CP_FN float bound_after(float t) { return t > 0.0f ? t : -kNoContact; }
 PT_CP_FN float time_of(float bound) { return bound > 0.0f ? bound : 0.0f; }
-PT_CP_FN float safe_inv(float d) { return __builtin_fabsf(d) > 1e-8f ? 1.0f / d : 1e30f; }      // pt_device.h::safe_inv, per component
 
 PT_CP_FN float sel_min(float a, float b) { return b < a ? b : a; }
 PT_CP_FN float sel_max(float a, float b) { return b > a ? b : a; }
