@@ -1,23 +1,17 @@
-"""The torch-route cases of tests/test_gpu_closest_points.py, run in a child process each: torch is imported BEFORE the package there, so
-that libmi355pt binds to torch's copy of the HIP runtime (as tests/rayquery_torch_cases.py does).  python tests/closest_torch_cases.py NAME"""
-import os
-import sys
+"""The torch-route cases of tests/test_gpu_closest_points.py, one child process each (tests/torchroute.py).
+python tests/closest_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
-
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import closest_cases as cc  # noqa: E402
-from scenes import TETRA, random_soup  # noqa: E402
+import closest_cases as cc
+from scenes import TETRA, random_soup
+from torchroute import bits
 
 
 def to_numpy(res):
-    return [x.cpu().view(torch.int32).numpy() for x in res]
+    return [bits(x) for x in res]
 
 
 def torch_route_equals_the_host_route(rt, gpu_ctx):
@@ -44,45 +38,25 @@ def torch_route_equals_the_host_route(rt, gpu_ctx):
 def ordering_with_batched_frames_and_scene_changes(rt, gpu_ctx):
     tris = random_soup(1000, 3)
     gpu_ctx.set_triangles(tris); gpu_ctx.build_bvh()
-    bvh4 = gpu_ctx.read_bvh4()
     pts = cc.query_points(tris, 20000, 43)
-    want = rt.closest_points_bvh4(tris, bvh4, pts)
-    gpu_ctx.set_batch(8)
-    for f in range(3):                                   # queued by pt_set_batch, not launched yet
-        gpu_ctx.render(gpu_ctx.make_params(64, 48, mode=rt.PT_MODE_REFERENCE, frame=f))
-    res = gpu_ctx.closest_points(torch.from_numpy(pts).cuda())      # launches the three frames first, then the query
-    other = random_soup(5000, 47)
-    gpu_ctx.set_triangles(other); gpu_ctx.build_bvh()    # after the query: its results stay those of the first scene
+    want = rt.closest_points_bvh4(tris, gpu_ctx.read_bvh4(), pts)
+    res, other = tr.queued_frames_then(rt, gpu_ctx, lambda: gpu_ctx.closest_points(torch.from_numpy(pts).cuda()))
     for a, b in zip(want, to_numpy(res)):
         assert cc.same_bits(a, b)
-    after = gpu_ctx.closest_points(pts)                  # and the next query sees the second scene
-    for a, b in zip(after, rt.closest_points_bvh4(other, gpu_ctx.read_bvh4(), pts)):
+    for a, b in zip(gpu_ctx.closest_points(pts), rt.closest_points_bvh4(other, gpu_ctx.read_bvh4(), pts)):      # the next query sees the second scene
         assert cc.same_bits(a, b)
 
 
 def errors(rt, gpu_ctx):
     pts = torch.zeros((64, 4), dtype=torch.float32, device="cuda"); out = torch.zeros((64, 4), dtype=torch.int32, device="cuda")
     pp, op = pts.data_ptr(), out.data_ptr()
+    closest = (gpu_ctx.closest_points_device, [pp, 1, op, 0], [(0, 0), (2, 0), (0, pp + 4), (2, op + 8), (3, 8), (1, 1 << 32)])      # null, not 16-byte aligned, unknown flag, n > UINT32_MAX
+    brute = (gpu_ctx.closest_points_device, [pp, 1, op, rt.PT_CLOSEST_BRUTE_FORCE], [])      # brute force walks no tree, and needs the scene all the same
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, op)) == 4                   # no scene
-    assert code(lambda: gpu_ctx.closest_points(np.zeros((1, 3), np.float32))) == 4
-    assert code(lambda: gpu_ctx.closest_points_device(pp + 4, 1, op)) == 1               # the pointers are checked before the scene
-    gpu_ctx.set_triangles(TETRA)
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, op)) == 4                   # triangles without a tree
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, op, flags=rt.PT_CLOSEST_BRUTE_FORCE)) == 4
-    gpu_ctx.build_bvh()
-    assert code(lambda: gpu_ctx.closest_points_device(0, 1, op)) == 1                    # null
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, 0)) == 1
-    assert code(lambda: gpu_ctx.closest_points_device(pp + 4, 1, op)) == 1               # not 16-byte aligned
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, op + 8)) == 1
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1, op, flags=8)) == 1          # unknown flag
-    assert code(lambda: gpu_ctx.closest_points_device(pp, 1 << 32, op)) == 1             # n > UINT32_MAX
+    def tetra():
+        gpu_ctx.set_triangles(TETRA); gpu_ctx.build_bvh()
+    tr.refusals(rt, gpu_ctx, [closest, brute], tetra, host=[lambda: gpu_ctx.closest_points(np.zeros((1, 3), np.float32))],
+                cpu=[lambda: gpu_ctx.closest_points(torch.zeros((4, 4)))])
     out.fill_(7)
     torch.cuda.synchronize()
     gpu_ctx.closest_points_device(pp, 0, op)                                              # n = 0: OK, nothing launched
@@ -93,11 +67,4 @@ def errors(rt, gpu_ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

@@ -1,30 +1,19 @@
-"""The torch-route cases of tests/test_gpu_crossings.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/occlusion_torch_cases.py does).  python tests/crossings_torch_cases.py NAME"""
-import os
-import sys
-import time
+"""The torch-route cases of tests/test_gpu_crossings.py, one child process each (tests/torchroute.py).  python tests/crossings_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
-
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import crossing_cases as cc  # noqa: E402
-from scenes import TETRA, random_soup  # noqa: E402
+import crossing_cases as cc
+from routecheck import same_bits
+from scenes import TETRA
+from torchroute import bits
 
 N_RAYS, N_POINTS = 4096, 2048
 
 
 def to_numpy(res):
-    return [x.cpu().view(torch.int32).numpy().view(np.uint32) for x in res]
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    return [bits(x) for x in res]
 
 
 def scene(rt, ctx, name="torus"):
@@ -62,7 +51,7 @@ def torch_route_equals_the_host_route(rt, ctx):
 def device_composition(rt, ctx):
     """pt_contains equals occlusion_rays -> count_hits -> a torch parity count, all on the device; and the signed distance is
     closest_points with the sign of contains."""
-    tris = scene(rt, ctx)
+    scene(rt, ctx)
     pts = cc.cube_points(N_POINTS, 43, half=1.0)
     pts[5, 1] = np.nan
     sft = torch.from_numpy(cc.surfels_of(pts)).cuda()
@@ -76,7 +65,7 @@ def device_composition(rt, ctx):
             inside, got_odd, smp = ctx.contains(pt_, samples=samples, seed=seed, index_base=base, simple=simple)
             assert torch.equal(got_odd.view(torch.int32), odd.to(torch.int32))
             assert torch.equal(inside.view(torch.int32), (2 * odd > samples).to(torch.int32))
-            s = to_numpy([smp])[0]
+            s = bits(smp)
             assert s[5] == 0 and np.all(np.delete(s, 5) == samples)
         dist, prim, u, v = ctx.closest_points(pt_)
         sd, sprim, su, sv = ctx.signed_distance(pt_, samples=samples, seed=seed, index_base=base)
@@ -87,50 +76,29 @@ def device_composition(rt, ctx):
 
 
 def no_host_synchronisation(rt, ctx):
-    """The calls return while earlier work of the stream is still running: behind a long spin kernel on torch's stream they come back, and an
-    event recorded after them has not completed yet."""
     tris = scene(rt, ctx)
     rays = torch.from_numpy(cc.ray_set(rt, tris, N_RAYS, 47)).cuda()
     pts = torch.from_numpy(cc.cube_points(N_POINTS, 53, half=1.0)).cuda()
 
     def sequence():
         return [ctx.count_hits(rays)] + list(ctx.contains(pts, samples=3)) + list(ctx.signed_distance(pts, samples=3))
-    want = to_numpy(sequence())                            # warm-up: first-touch allocations may wait, a steady-state call does not
+    want = to_numpy(sequence())                            # warm-up
     torch.cuda.synchronize()
-    t0 = time.perf_counter(); torch.cuda._sleep(5_000_000); torch.cuda.synchronize(); probe = time.perf_counter() - t0
-    cycles = int(min(max(5_000_000 * 0.3 / probe, 5_000_000), 2_000_000_000))      # about 0.3 s, whatever the counter's rate
-    t0 = time.perf_counter(); torch.cuda._sleep(cycles); torch.cuda.synchronize(); spin = time.perf_counter() - t0
-    assert spin > 0.05, spin                              # the spin is long enough to tell
-    torch.cuda._sleep(cycles)
-    t0 = time.perf_counter()
-    res = sequence()
-    took = time.perf_counter() - t0
-    done = torch.cuda.Event(); done.record()
-    pending = not done.query()
-    torch.cuda.synchronize()
-    assert pending and took < spin / 2, (pending, took, spin)
+    res = tr.returns_before_the_stream(sequence)
     assert all(same_bits(a, b) for a, b in zip(want, to_numpy(res)))
 
 
 def ordering_with_batched_frames_and_scene_changes(rt, ctx):
     import orc as orc_mod
-    orc = orc_mod.load()
     tris = scene(rt, ctx)
     bvh4 = ctx.read_bvh4()
     rays = cc.ray_set(rt, tris, N_RAYS, 59)
     pts = cc.cube_points(N_POINTS, 61, half=1.0)
     want = [ctx.count_hits(rays)] + list(ctx.contains(pts, samples=3)) + list(ctx.signed_distance(pts, samples=3))
-    ctx.set_batch(8)
-    for f in range(3):                                   # queued by pt_set_batch, not launched yet
-        ctx.render(ctx.make_params(64, 48, mode=rt.PT_MODE_REFERENCE, frame=f))
     rt_, pt_ = torch.from_numpy(rays).cuda(), torch.from_numpy(pts).cuda()
-    got = [ctx.count_hits(rt_)] + list(ctx.contains(pt_, samples=3)) + list(ctx.signed_distance(pt_, samples=3))     # launches the frames first
-    other = random_soup(5000, 47)
-    ctx.set_triangles(other); ctx.build_bvh()            # after the queries: their results stay those of the first scene
+    got, _ = tr.queued_frames_then(rt, ctx, lambda: [ctx.count_hits(rt_)] + list(ctx.contains(pt_, samples=3)) + list(ctx.signed_distance(pt_, samples=3)))
     assert all(same_bits(a, b) for a, b in zip(want, to_numpy(got)))
-    img = ctx.read_radiance(64, 48)                      # the queued frames saw the first scene
-    ref, _, _ = orc.render(orc.make_params(64, 48, tris.size // 9, mode=orc_mod.MODE_SINGLE), tris, bvh4)
-    assert same_bits(img, ref)
+    tr.queued_frames_saw(orc_mod.load(), ctx, tris, bvh4)
     assert not np.array_equal(ctx.count_hits(rays), want[0])      # and the new scene answers differently
 
 
@@ -142,34 +110,19 @@ def errors(rt, ctx):
 
     def params(samples=3, flags=0):
         return rt.PtContainParams(samples, 0, 0, flags)
+    count = (ctx.count_hits_device, [rp, 1, cp, 0], [
+        (0, 0), (2, 0), (0, rp + 4), (2, cp + 2),         # null, rays not 16-byte aligned, counts not 4-byte aligned
+        (3, 8), (1, 1 << 32)])                            # unknown flag, n > UINT32_MAX
+    bad = [(0, 0), (3, 0), (0, pp + 4), (3, op + 8), (2, params(flags=4)), (2, params(samples=0)), (2, params(samples=2)), (2, params(samples=256)),
+           (1, (1 << 32) // 3 + 1)]                       # n * samples > 2^32 - 1
+    inside, signed = ((fn, [pp, 1, params(), op], bad) for fn in (ctx.contains_device, ctx.signed_distance_device))
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: ctx.count_hits_device(rp, 1, cp)) == 4                             # no scene
-    assert code(lambda: ctx.count_hits_device(0, 1, cp)) == 1                              # ... but the arguments are checked first
-    assert code(lambda: ctx.contains_device(pp, 1, params(), op)) == 4
-    assert code(lambda: ctx.signed_distance_device(pp, 1, params(), op)) == 4
-    ctx.set_triangles(TETRA)
-    assert code(lambda: ctx.count_hits_device(rp, 1, cp)) == 4                             # triangles without a tree
-    ctx.build_bvh()
-    assert code(lambda: ctx.count_hits_device(rp, 1, 0)) == 1                              # null
-    assert code(lambda: ctx.count_hits_device(rp + 4, 1, cp)) == 1                         # rays not 16-byte aligned
-    assert code(lambda: ctx.count_hits_device(rp, 1, cp + 2)) == 1                         # counts not 4-byte aligned
-    assert code(lambda: ctx.count_hits_device(rp, 1, cp, 8)) == 1                          # unknown flag
-    assert code(lambda: ctx.count_hits_device(rp, 1 << 32, cp)) == 1                       # n > UINT32_MAX
-    for fn in (ctx.contains_device, ctx.signed_distance_device):
-        assert code(lambda: fn(0, 1, params(), op)) == 1
-        assert code(lambda: fn(pp, 1, params(), 0)) == 1
-        assert code(lambda: fn(pp + 4, 1, params(), op)) == 1
-        assert code(lambda: fn(pp, 1, params(), op + 8)) == 1
-        assert code(lambda: fn(pp, 1, params(flags=4), op)) == 1
-        for bad in (0, 2, 256):
-            assert code(lambda: fn(pp, 1, params(samples=bad), op)) == 1
-        assert code(lambda: fn(pp, (1 << 32) // 3 + 1, params(), op)) == 1                  # n * samples > 2^32 - 1
+    def tetra():
+        ctx.set_triangles(TETRA); ctx.build_bvh()
+    one = np.zeros((1, 3), np.float32)
+    tr.refusals(rt, ctx, [count, inside, signed], tetra,
+                host=[lambda: ctx.count_hits(rt.pack_rays(one, one + 1)), lambda: ctx.contains(one), lambda: ctx.signed_distance(one)],
+                cpu=[lambda: ctx.count_hits(torch.zeros((4, 8))), lambda: ctx.contains(torch.zeros((4, 4))), lambda: ctx.signed_distance(torch.zeros((4, 4)))])
     counts.fill_(7); out.fill_(7)
     torch.cuda.synchronize()
     ctx.count_hits_device(rp, 0, cp); ctx.contains_device(pp, 0, params(), op); ctx.signed_distance_device(pp, 0, params(), op)      # n = 0: OK, nothing launched
@@ -186,11 +139,4 @@ def errors(rt, ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

@@ -1,22 +1,12 @@
-"""The torch-route cases of tests/test_gpu_hitlist.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/radius_torch_cases.py does).  python tests/hitlist_torch_cases.py NAME"""
-import os
-import sys
+"""The torch-route cases of tests/test_gpu_hitlist.py, one child process each (tests/torchroute.py).  python tests/hitlist_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
-
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import crossing_cases as cc  # noqa: E402
-import hitlist_cases as hc  # noqa: E402
-from scenes import random_soup  # noqa: E402
-
-N = 4097
+import crossing_cases as cc
+import hitlist_cases as hc
+from torchroute import N, bits
 
 
 def scene(rt, ctx):
@@ -29,7 +19,7 @@ def to_host(res):
     """(offsets, t, prim, u, v) of torch tensors -> the numpy form of the host route, cut at the total"""
     off = res[0].cpu().numpy()
     m = int(off[-1])
-    return (off.astype(np.uint64),) + tuple(x.cpu().view(torch.int32).numpy()[:m].view(t) for x, t in zip(res[1:], (np.float32, np.uint32, np.float32, np.float32)))
+    return (off.astype(np.uint64),) + tuple(bits(x)[:m].view(t) for x, t in zip(res[1:], (np.float32, np.uint32, np.float32, np.float32)))
 
 
 def torch_route_equals_the_host_route(rt, ctx):
@@ -56,80 +46,59 @@ def torch_route_equals_the_host_route(rt, ctx):
 
 
 def truncation_on_the_device_route(rt, ctx):
-    """pt_list_hits itself, per kernel, unsorted and sorted, at the capacities 0 (NULL entries), 1, total - 1, total, total + 7 and two
-    inside a list: the entries go into a device tensor of capacity + 8 records filled with a guard pattern, so a store at or beyond
-    `capacity` lands where it is seen."""
+    """pt_list_hits itself, per kernel, unsorted and sorted, into guarded device tensors (torchroute.truncation_on_the_device_route): at
+    the shared capacities, at 1 and at two inside a list."""
+    tris = scene(rt, ctx)
+    rays_h = cc.ray_set(rt, tris, N, 11)
+    seen = tr.truncation_on_the_device_route(
+        rt, ctx, rays_h, (0, rt.PT_HITS_SIMPLE_KERNEL, rt.PT_HITS_BRUTE_FORCE),
+        lambda tree: hc.words(rt.list_hits_bvh4(tris, tree, rays_h, brute_force=tree is None)), ctx.list_hits_device, hc.GUARD,
+        more_capacities=lambda off: [1] + [int(off[i] + 1) for i in range(N) if off[i + 1] - off[i] > 2][:2],
+        variants=((0, None), (rt.PT_HITS_SORTED, hc.sorted_records)))
+    for off, _, caps in seen:                             # some capacity cuts a list of more than one hit in two
+        assert any(np.any((off[:-1] < cap) & (off[1:] > cap) & (off[1:] - off[:-1] > 1)) for cap in caps)
+    want = seen[-1][1]
+    # the torch route with a capacity below the total: the entry tensors hold `capacity` records, all of them written
+    res = ctx.list_hits(torch.from_numpy(rays_h).cuda(), capacity=len(want) - 1, brute_force=True)
+    assert len(res[2]) == len(want) - 1 and np.array_equal(bits(res[2]), want[:-1, 1])
+
+
+def no_host_synchronisation_with_a_capacity(rt, ctx):
     tris = scene(rt, ctx)
     rays_h = cc.ray_set(rt, tris, N, 11)
     rays = torch.from_numpy(rays_h).cuda()
-    guard = np.uint32(hc.GUARD).astype(np.int32)
-    for base, tree in ((0, ctx.read_bvh4()), (rt.PT_HITS_SIMPLE_KERNEL, ctx.read_bvh4()), (rt.PT_HITS_BRUTE_FORCE, None)):
-        want_off, want = hc.words(rt.list_hits_bvh4(tris, tree, rays_h, brute_force=tree is None))
-        total = int(want_off[-1])
-        assert total > N
-        inner = [int(want_off[i] + 1) for i in range(N) if want_off[i + 1] - want_off[i] > 2][:2]
-        straddles = 0
-        for cap in [0, 1, total - 1, total, total + 7] + inner:
-            for sort in (False, True):
-                flags = base | (rt.PT_HITS_SORTED if sort else 0)
-                off = torch.full((N + 1,), -1, dtype=torch.int64, device="cuda")
-                ent = torch.full((cap + 8, 4), int(guard), dtype=torch.int32, device="cuda")
-                torch.cuda.synchronize()
-                ctx.list_hits_device(rays.data_ptr(), N, off.data_ptr(), ent.data_ptr() if cap else 0, cap, flags)
-                ctx.synchronize()
-                got = ent.cpu().numpy().view(np.uint32)
-                held = min(total, cap)
-                expect = hc.sorted_records(want_off, want[:held], held) if sort else want[:held]
-                assert np.array_equal(off.cpu().numpy(), want_off), (flags, cap)                  # complete whatever the capacity
-                assert np.array_equal(got[:held], expect), (flags, cap, np.flatnonzero((got[:held] != expect).any(1))[:8])
-                assert np.all(got[held:] == hc.GUARD), (flags, cap, np.flatnonzero((got[held:] != hc.GUARD).any(1))[:8] + held)
-            straddles += int(np.any((want_off[:-1] < cap) & (want_off[1:] > cap) & (want_off[1:] - want_off[:-1] > 1)))
-        assert straddles > 0
-    # the torch route with a capacity below the total: the entry tensors hold `capacity` records, all of them written
-    res = ctx.list_hits(rays, capacity=total - 1, brute_force=True)
-    assert len(res[2]) == total - 1 and np.array_equal(res[2].cpu().view(torch.int32).numpy().view(np.uint32), want[:total - 1, 1])
+    cap = int(rt.list_hits_bvh4(tris, ctx.read_bvh4(), rays_h)[0][-1])
+
+    def sequence():
+        return list(ctx.list_hits(rays, capacity=cap)) + list(ctx.list_hits(rays, capacity=cap, sort=True))
+    want = sequence()                                     # warm-up
+    torch.cuda.synchronize()
+    assert int(want[0][-1]) == cap > N
+    res = tr.returns_before_the_stream(sequence)
+    assert torch.equal(res[0], want[0]) and all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(res[1:], want[1:]))
 
 
 def ordering_with_batched_frames_and_scene_changes(rt, ctx):
     tris = scene(rt, ctx)
-    bvh4 = ctx.read_bvh4()
     rays = cc.ray_set(rt, tris, N, 11)
-    want = rt.list_hits_bvh4(tris, bvh4, rays, sort=True)
-    ctx.set_batch(8)
-    for f in range(3):                                    # queued by pt_set_batch, not launched yet
-        ctx.render(ctx.make_params(64, 48, mode=rt.PT_MODE_REFERENCE, frame=f))
-    res = ctx.list_hits(torch.from_numpy(rays).cuda(), capacity=int(want[0][-1]), sort=True)      # launches the three frames first, then the query
-    other = random_soup(5000, 47)
-    ctx.set_triangles(other); ctx.build_bvh()             # after the query: its results stay those of the first scene
+    want = rt.list_hits_bvh4(tris, ctx.read_bvh4(), rays, sort=True)
+    res, other = tr.queued_frames_then(rt, ctx, lambda: ctx.list_hits(torch.from_numpy(rays).cuda(), capacity=int(want[0][-1]), sort=True))
     hc.assert_same_lists(to_host(res), want)
-    hc.assert_same_lists(ctx.list_hits(rays, sort=True), rt.list_hits_bvh4(other, ctx.read_bvh4(), rays, sort=True))      # the next query sees the second
+    hc.assert_same_lists(ctx.list_hits(rays, sort=True), rt.list_hits_bvh4(other, ctx.read_bvh4(), rays, sort=True))
 
 
 def errors(rt, ctx):
     rays = torch.zeros((64, 8), dtype=torch.float32, device="cuda"); rays[:, 0] = 0.2; rays[:, 1] = 0.1; rays[:, 2] = 3.0; rays[:, 3] = float("inf"); rays[:, 6] = -1.0
     off = torch.zeros((65,), dtype=torch.int64, device="cuda"); ent = torch.zeros((1024, 4), dtype=torch.int32, device="cuda")
     rp, op, ep = rays.data_ptr(), off.data_ptr(), ent.data_ptr()
+    hits = (ctx.list_hits_device, [rp, 1, op, ep, 16, 0], [
+        (0, 0), (2, 0), (3, 0),                           # null (NULL hits only with capacity 0)
+        (0, rp + 4), (2, op + 4), (3, ep + 8),            # rays and hits: 16-byte aligned, offsets: 8-byte aligned
+        (5, 16), (1, 1 << 32)])                           # unknown flag, n > UINT32_MAX
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: ctx.list_hits_device(rp, 1, op, ep, 16)) == 4                     # no scene
-    assert code(lambda: ctx.list_hits_device(rp + 4, 1, op, ep, 16)) == 1                 # the pointers are checked before the scene
-    assert code(lambda: ctx.list_hits_device(rp, 1, op, ep, 16, flags=16)) == 1           # ... and the flags
-    assert code(lambda: ctx.list_hits_device(rp, 1 << 32, op, ep, 16)) == 1               # ... and n > UINT32_MAX
-    tris, z = hc.deck(10, 7)
-    ctx.set_triangles(tris); ctx.build_bvh()
-    assert code(lambda: ctx.list_hits_device(0, 1, op, ep, 16)) == 1                      # null
-    assert code(lambda: ctx.list_hits_device(rp, 1, 0, ep, 16)) == 1
-    assert code(lambda: ctx.list_hits_device(rp, 1, op, 0, 16)) == 1                      # NULL hits only with capacity 0
-    assert code(lambda: ctx.list_hits_device(rp + 4, 1, op, ep, 16)) == 1                 # rays: 16-byte aligned
-    assert code(lambda: ctx.list_hits_device(rp, 1, op + 4, ep, 16)) == 1                 # offsets: 8-byte aligned
-    assert code(lambda: ctx.list_hits_device(rp, 1, op, ep + 8, 16)) == 1                 # hits: 16-byte aligned
-    assert code(lambda: ctx.list_hits_device(rp, 1, op, ep, 16, flags=16)) == 1           # unknown flag
-    assert code(lambda: ctx.list_hits_device(rp, 1 << 32, op, ep, 16)) == 1               # n > UINT32_MAX
+    def deck():
+        ctx.set_triangles(hc.deck(10, 7)[0]); ctx.build_bvh()
+    tr.refusals(rt, ctx, [hits], deck, host=[lambda: ctx.list_hits(np.zeros((1, 8), np.float32))], cpu=[lambda: ctx.list_hits(torch.zeros((4, 8)))])
     off.fill_(7); ent.fill_(7)
     torch.cuda.synchronize()
     ctx.list_hits_device(rp, 0, op, ep, 16)                                               # n = 0: offsets[0] = 0, nothing else
@@ -142,11 +111,4 @@ def errors(rt, ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

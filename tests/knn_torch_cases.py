@@ -1,30 +1,15 @@
-"""The torch-route cases of tests/test_gpu_knn.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/radius_torch_cases.py does).  python tests/knn_torch_cases.py NAME"""
-import os
-import sys
-import time
+"""The torch-route cases of tests/test_gpu_knn.py, one child process each (tests/torchroute.py).  python tests/knn_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
+import knn_cases as kc
+import radius_cases as rc
+from routecheck import assert_guarded, code
+from torchroute import N, bits, soup_scene as scene
 
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import knn_cases as kc  # noqa: E402
-import radius_cases as rc  # noqa: E402
-from scenes import random_soup  # noqa: E402
-
-N = 4097
 KS = (1, 4, 5, 16, 17, 64)
-
-
-def scene(rt, ctx):
-    tris = random_soup(3000, 5)
-    ctx.set_triangles(tris); ctx.build_bvh()
-    return tris
 
 
 def points(rt, tris, n=N):
@@ -35,7 +20,7 @@ def points(rt, tris, n=N):
 
 def to_host(res):
     """(dist, prim, u, v) of (n, k) torch tensors -> the numpy form of the host route"""
-    return tuple(x.contiguous().cpu().view(torch.int32).numpy().view(t) for x, t in zip(res, (np.float32, np.uint32, np.float32, np.float32)))
+    return tuple(bits(x).view(t) for x, t in zip(res, (np.float32, np.uint32, np.float32, np.float32)))
 
 
 def torch_route_equals_the_host_route(rt, ctx):
@@ -68,83 +53,49 @@ def guard_on_the_device_route(rt, ctx):
     pts_h = points(rt, tris)
     pts_h[1::8, 3] = 0.0; pts_h[5::16, 0] = np.nan        # rows of points that are not walked are written too
     pts = torch.from_numpy(pts_h).cuda()
-    guard = int(np.uint32(rc.GUARD).astype(np.int32))
     b4 = ctx.read_bvh4()
     for flags, tree, n in ((0, b4, N), (rt.PT_NEAREST_SIMPLE_KERNEL, b4, N), (rt.PT_NEAREST_BRUTE_FORCE, None, 513)):
         for k in KS:
             want = kc.words(rt.nearest_k_bvh4(tris, tree, pts_h[:n], k, brute_force=tree is None)).reshape(n * k, 4)
-            buf = torch.full((n * k + 8, 4), guard, dtype=torch.int32, device="cuda")
-            torch.cuda.synchronize()
+            buf = tr.guarded(n * k + 8, rc.GUARD)
             ctx.nearest_k_device(pts.data_ptr(), n, k, buf.data_ptr(), flags)
             ctx.synchronize()
-            got = buf.cpu().numpy().view(np.uint32)
+            got = bits(buf)
             kc.assert_guard(got, n, k)
-            assert np.array_equal(got[:n * k], want), (flags, k, np.flatnonzero((got[:n * k] != want).any(1))[:8])
+            assert_guarded(got, want, rc.GUARD, (flags, k))
 
 
 def no_host_synchronisation(rt, ctx):
-    """The call returns while earlier work of the stream is still running: behind a long spin kernel on torch's stream it comes back, and an
-    event recorded after it has not completed yet."""
     tris = scene(rt, ctx)
     pts = torch.from_numpy(points(rt, tris)).cuda()
 
     def sequence():
         return [x for k in (4, 16, 64) for x in ctx.nearest_k(pts, k)]
-    want = sequence()                                     # warm-up: first-touch allocations may wait, a steady-state call does not
+    want = sequence()                                     # warm-up
     torch.cuda.synchronize()
-    t0 = time.perf_counter(); torch.cuda._sleep(5_000_000); torch.cuda.synchronize(); probe = time.perf_counter() - t0
-    cycles = int(min(max(5_000_000 * 0.3 / probe, 5_000_000), 2_000_000_000))      # about 0.3 s, whatever the counter's rate
-    t0 = time.perf_counter(); torch.cuda._sleep(cycles); torch.cuda.synchronize(); spin = time.perf_counter() - t0
-    assert spin > 0.05, spin                              # the spin is long enough to tell
-    torch.cuda._sleep(cycles)
-    t0 = time.perf_counter()
-    res = sequence()
-    took = time.perf_counter() - t0
-    done = torch.cuda.Event(); done.record()
-    pending = not done.query()
-    torch.cuda.synchronize()
-    assert pending and took < spin / 2, (pending, took, spin)
+    res = tr.returns_before_the_stream(sequence)
     assert all(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)) for a, b in zip(res, want))
 
 
 def ordering_with_batched_frames_and_scene_changes(rt, ctx):
     tris = scene(rt, ctx)
-    bvh4 = ctx.read_bvh4()
     pts = points(rt, tris)
-    want = rt.nearest_k_bvh4(tris, bvh4, pts, 16)
-    ctx.set_batch(8)
-    for f in range(3):                                    # queued by pt_set_batch, not launched yet
-        ctx.render(ctx.make_params(64, 48, mode=rt.PT_MODE_REFERENCE, frame=f))
-    res = ctx.nearest_k(torch.from_numpy(pts).cuda(), 16)      # launches the three frames first, then the query
-    other = random_soup(5000, 47)
-    ctx.set_triangles(other); ctx.build_bvh()             # after the query: its results stay those of the first scene
+    want = rt.nearest_k_bvh4(tris, ctx.read_bvh4(), pts, 16)
+    res, other = tr.queued_frames_then(rt, ctx, lambda: ctx.nearest_k(torch.from_numpy(pts).cuda(), 16))
     kc.assert_same_rows(to_host(res), want)
-    kc.assert_same_rows(ctx.nearest_k(pts, 16), rt.nearest_k_bvh4(other, ctx.read_bvh4(), pts, 16))      # the next query sees the second
+    kc.assert_same_rows(ctx.nearest_k(pts, 16), rt.nearest_k_bvh4(other, ctx.read_bvh4(), pts, 16))
 
 
 def errors(rt, ctx):
     pts = torch.zeros((64, 4), dtype=torch.float32, device="cuda"); pts[:, 3] = 10.0
     out = torch.full((64 * 64 + 8, 4), 7, dtype=torch.int32, device="cuda")
     pp, op = pts.data_ptr(), out.data_ptr()
-
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 3, op)) == 4                          # no scene
-    assert code(lambda: ctx.nearest_k_device(pp + 4, 1, 3, op)) == 1                      # the pointers are checked before the scene
-    scene(rt, ctx)
-    assert code(lambda: ctx.nearest_k_device(0, 1, 3, op)) == 1                           # null
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 3, 0)) == 1
-    assert code(lambda: ctx.nearest_k_device(pp + 4, 1, 3, op)) == 1                      # 16-byte aligned
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 3, op + 8)) == 1
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 0, op)) == 1                          # k
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 65, op)) == 1
-    assert code(lambda: ctx.nearest_k_device(pp, 1, 3, op, flags=8)) == 1                 # unknown flag
-    assert code(lambda: ctx.nearest_k_device(pp, 1 << 32, 3, op)) == 1                    # n > UINT32_MAX
-    assert code(lambda: ctx.nearest_k(pts, 0)) == 1 and code(lambda: ctx.nearest_k(pts, 65)) == 1
+    nearest = (ctx.nearest_k_device, [pp, 1, 3, op, 0], [
+        (0, 0), (3, 0), (0, pp + 4), (3, op + 8),         # null, not 16-byte aligned
+        (2, 0), (2, 65),                                  # k
+        (4, 8), (1, 1 << 32)])                            # unknown flag, n > UINT32_MAX
+    tr.refusals(rt, ctx, [nearest], lambda: scene(rt, ctx), host=[lambda: ctx.nearest_k(np.zeros((1, 4), np.float32), 3)], cpu=[lambda: ctx.nearest_k(torch.zeros((4, 4)), 3)])
+    assert code(rt, lambda: ctx.nearest_k(pts, 0)) == 1 and code(rt, lambda: ctx.nearest_k(pts, 65)) == 1
     torch.cuda.synchronize()
     ctx.nearest_k_device(pp, 0, 3, op)                                                    # n = 0: nothing is written
     ctx.synchronize()
@@ -158,11 +109,4 @@ def errors(rt, ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

@@ -1,24 +1,19 @@
-"""The torch-route cases of tests/test_gpu_occlusion.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/rayquery_torch_cases.py does).  python tests/occlusion_torch_cases.py NAME"""
-import os
+"""The torch-route cases of tests/test_gpu_occlusion.py, one child process each (tests/torchroute.py).  python tests/occlusion_torch_cases.py NAME"""
 import sys
-import time
 
-import torch      # first
+import torchroute as tr      # first: it imports torch before the package
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
+import numpy as np
+import torch
 
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-from scenes import TETRA, random_soup  # noqa: E402
-from test_gpu_occlusion import MISS, SCENE_SEED, composition, same_bits, scene, surface_surfels, traced_mask  # noqa: E402
+from routecheck import code
+from scenes import TETRA
+from test_gpu_occlusion import MISS, SCENE_SEED, composition, same_bits, scene, surface_surfels, traced_mask
+from torchroute import bits
 
 
 def to_numpy(res):
-    return [x.cpu().view(torch.int32).numpy().view(np.uint32) for x in res]
+    return [bits(x) for x in res]
 
 
 def torch_route_equals_the_host_route(rt, gpu_ctx):
@@ -55,8 +50,8 @@ def device_rays_equal_the_host_twin(rt, gpu_ctx):
         assert len(bad) == 0, (samples, len(bad), bad[:5], got[bad[:2]], host[bad[:2]])
         _, prim, _, _ = gpu_ctx.trace_rays(dev, any_hit=True)
         miss = (prim.view(torch.int32) == -1).reshape(len(sf), samples).sum(dim=1)
-        tr = torch.from_numpy(traced_mask(sf)).cuda()
-        want = torch.where(tr, miss, torch.zeros_like(miss)).cpu().numpy().astype(np.uint32)
+        traced = torch.from_numpy(traced_mask(sf)).cuda()
+        want = torch.where(traced, miss, torch.zeros_like(miss)).cpu().numpy().astype(np.uint32)
         _, unocc, smp = gpu_ctx.occlusion(sft, samples, seed=seed, index_base=base, bias=2e-4)
         assert np.array_equal(to_numpy([unocc])[0], want)
         assert np.array_equal(to_numpy([smp])[0], np.where(traced_mask(sf), samples, 0).astype(np.uint32))
@@ -71,8 +66,6 @@ def device_rays_equal_the_host_twin(rt, gpu_ctx):
 
 
 def no_host_synchronisation(rt, gpu_ctx):
-    """pt_occlusion returns while earlier work of the stream is still running: behind a long spin kernel on torch's stream, the call comes
-    back, and an event recorded after it has not completed yet."""
     tris, _ = scene(rt, gpu_ctx, "soup1k")
     sf = torch.from_numpy(surface_surfels(rt, tris, 20000, 59)).cuda()
 
@@ -80,22 +73,11 @@ def no_host_synchronisation(rt, gpu_ctx):
         res = gpu_ctx.occlusion(sf, 16)
         rays = gpu_ctx.occlusion_rays(sf, 4)
         return res, gpu_ctx.hit_surfels(rays, gpu_ctx.trace_rays(rays), 1.0)
-    res, surf = sequence()                                # warm-up: first-touch allocations may wait, a steady-state call does not
+    res, surf = sequence()                                # warm-up
     want = to_numpy(res)
     del res, surf
     torch.cuda.synchronize()
-    t0 = time.perf_counter(); torch.cuda._sleep(5_000_000); torch.cuda.synchronize(); probe = time.perf_counter() - t0
-    cycles = int(min(max(5_000_000 * 0.3 / probe, 5_000_000), 2_000_000_000))      # about 0.3 s, whatever the counter's rate
-    t0 = time.perf_counter(); torch.cuda._sleep(cycles); torch.cuda.synchronize(); spin = time.perf_counter() - t0
-    assert spin > 0.05, spin                              # the spin is long enough to tell
-    torch.cuda._sleep(cycles)
-    t0 = time.perf_counter()
-    res, surf = sequence()
-    took = time.perf_counter() - t0
-    done = torch.cuda.Event(); done.record()
-    pending = not done.query()
-    torch.cuda.synchronize()
-    assert pending and took < spin / 2, (pending, took, spin)
+    res, surf = tr.returns_before_the_stream(sequence)
     for a, b in zip(want, to_numpy(res)):
         assert same_bits(a, b)
     assert surf.shape == (len(sf) * 4, 8)
@@ -103,21 +85,12 @@ def no_host_synchronisation(rt, gpu_ctx):
 
 def ordering_with_batched_frames_and_scene_changes(rt, gpu_ctx):
     import orc as orc_mod
-    orc = orc_mod.load()
     tris, bvh4 = scene(rt, gpu_ctx, "soup1k")
     sf = surface_surfels(rt, tris, 5000, 43)
     want_u, want_s = composition(rt, gpu_ctx, sf, 16)
-    gpu_ctx.set_batch(8)
-    for f in range(3):                                   # queued by pt_set_batch, not launched yet
-        gpu_ctx.render(gpu_ctx.make_params(64, 48, mode=rt.PT_MODE_REFERENCE, frame=f))
-    sft = torch.from_numpy(sf).cuda()
-    _, unocc, smp = gpu_ctx.occlusion(sft, 16)           # launches the three frames first, then the query
-    other = random_soup(5000, 47)
-    gpu_ctx.set_triangles(other); gpu_ctx.build_bvh()    # after the query: its results stay those of the first scene
-    assert np.array_equal(to_numpy([unocc])[0], want_u) and np.array_equal(to_numpy([smp])[0], want_s)
-    img = gpu_ctx.read_radiance(64, 48)                  # the queued frames saw the first scene
-    ref, _, _ = orc.render(orc.make_params(64, 48, tris.size // 9, mode=orc_mod.MODE_SINGLE), tris, bvh4)
-    assert same_bits(img, ref)
+    (_, unocc, smp), _ = tr.queued_frames_then(rt, gpu_ctx, lambda: gpu_ctx.occlusion(torch.from_numpy(sf).cuda(), 16))
+    assert np.array_equal(bits(unocc), want_u) and np.array_equal(bits(smp), want_s)
+    tr.queued_frames_saw(orc_mod.load(), gpu_ctx, tris, bvh4)
     after, _ = composition(rt, gpu_ctx, sf, 16)          # and the new scene answers differently
     assert not np.array_equal(after, want_u)
 
@@ -158,37 +131,26 @@ def errors(rt, gpu_ctx):
         p = rt.PtOcclusionParams(); p.samples, p.bias, p.flags = samples, bias, flags
         return p
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(), op)) == 4                 # no scene
-    assert code(lambda: gpu_ctx.occlusion_device(0, 1, params(), op)) == 1                  # ... but the arguments are checked first
-    assert code(lambda: gpu_ctx.hit_surfels_device(rp, hp, 1, 1.0, sp)) == 4
+    dev = gpu_ctx.occlusion_device
+    occlusion = (dev, [sp, 1, params(), op], [
+        (0, 0), (3, 0), (0, sp + 4), (3, op + 8),         # null, not 16-byte aligned
+        (2, params(flags=4)), (2, params(samples=0)), (2, params(samples=65537)), (2, params(bias=-1.0)), (2, params(bias=float("nan")))])
+    many = (dev, [sp, 1, params(samples=1), op], [(1, 1 << 32)])                              # n > UINT32_MAX
+    product = (dev, [sp, 1, params(samples=65536), op], [(1, 65536)])                         # n * samples = 2^32
+    assert code(rt, lambda: gpu_ctx.hit_surfels_device(rp, hp, 1, 1.0, sp)) == 4                # no scene
     gpu_ctx.occlusion_rays_device(sp, 64, params(), rp)                                       # needs no scene
     gpu_ctx.synchronize()
     assert same_bits(rays.cpu().numpy(), rt.occlusion_rays_host(sf.cpu().numpy(), 4))
-    gpu_ctx.set_triangles(TETRA)
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(), op)) == 4                 # triangles without a tree
-    gpu_ctx.build_bvh()
-    assert code(lambda: gpu_ctx.occlusion_device(0, 1, params(), op)) == 1                  # null
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(), 0)) == 1
-    assert code(lambda: gpu_ctx.occlusion_device(sp + 4, 1, params(), op)) == 1             # not 16-byte aligned
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(), op + 8)) == 1
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(flags=4), op)) == 1          # unknown flag
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1 << 32, params(samples=1), op)) == 1  # n > UINT32_MAX
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(samples=0), op)) == 1
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(samples=65537), op)) == 1
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 65536, params(samples=65536), op)) == 1   # n * samples = 2^32
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(bias=-1.0), op)) == 1
-    assert code(lambda: gpu_ctx.occlusion_device(sp, 1, params(bias=float("nan")), op)) == 1
-    assert code(lambda: gpu_ctx.occlusion_rays_device(sp, 1, params(), 0)) == 1
-    assert code(lambda: gpu_ctx.occlusion_rays_device(sp, 1, params(), rp + 4)) == 1
-    assert code(lambda: gpu_ctx.hit_surfels_device(rp, hp, 1, 1.0, 0)) == 1
-    assert code(lambda: gpu_ctx.hit_surfels_device(rp, hp + 4, 1, 1.0, sp)) == 1
-    assert code(lambda: gpu_ctx.hit_surfels_device(rp, hp, 1 << 32, 1.0, sp)) == 1
+
+    def tetra():
+        gpu_ctx.set_triangles(TETRA); gpu_ctx.build_bvh()
+    tr.refusals(rt, gpu_ctx, [occlusion, many, product], tetra, host=[lambda: gpu_ctx.occlusion(np.zeros((1, 8), np.float32), 4)],
+                cpu=[lambda: gpu_ctx.occlusion(torch.zeros((4, 8)), 4)])
+    assert code(rt, lambda: gpu_ctx.occlusion_rays_device(sp, 1, params(), 0)) == 1
+    assert code(rt, lambda: gpu_ctx.occlusion_rays_device(sp, 1, params(), rp + 4)) == 1
+    assert code(rt, lambda: gpu_ctx.hit_surfels_device(rp, hp, 1, 1.0, 0)) == 1
+    assert code(rt, lambda: gpu_ctx.hit_surfels_device(rp, hp + 4, 1, 1.0, sp)) == 1
+    assert code(rt, lambda: gpu_ctx.hit_surfels_device(rp, hp, 1 << 32, 1.0, sp)) == 1
     out.fill_(7)
     torch.cuda.synchronize()
     gpu_ctx.occlusion_device(sp, 0, params(), op)                                             # n = 0: OK, nothing launched
@@ -210,11 +172,4 @@ def ao_frame(rt, gpu_ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

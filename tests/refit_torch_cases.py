@@ -1,26 +1,15 @@
-"""The torch-route cases of tests/test_gpu_refit.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/rayquery_torch_cases.py does).  python tests/refit_torch_cases.py NAME"""
-import os
-import sys
+"""The torch-route cases of tests/test_gpu_refit.py, one child process each (tests/torchroute.py).  python tests/refit_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
-
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import orc as orc_mod  # noqa: E402
-from refit_cases import wave  # noqa: E402
-from scenes import random_soup  # noqa: E402
+import orc as orc_mod
+from refit_cases import wave
+from routecheck import same_bits
+from scenes import random_soup
 
 SCENE_SEED = 20260109
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def device_route_equals_the_host_route(rt, orc, gpu_ctx):
@@ -60,11 +49,7 @@ def device_route_equals_the_host_route(rt, orc, gpu_ctx):
     gpu_ctx.synchronize()
     assert np.array_equal(gpu_ctx.read_bvh4(), b4)
     for bad in (torch.from_numpy(tris), torch.zeros(10, device="cuda")):
-        try:
-            gpu_ctx.update_triangles(bad)
-        except ValueError:
-            continue
-        raise AssertionError("accepted")
+        tr.raises_value_error(lambda: gpu_ctx.update_triangles(bad))
 
 
 def ordering_with_batched_frames(rt, orc, gpu_ctx):
@@ -114,11 +99,4 @@ def device_route_on_c2(rt, orc, gpu_ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, orc_mod.load(), ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals(), with_orc=True)

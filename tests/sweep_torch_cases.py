@@ -1,38 +1,23 @@
-"""The torch-route cases of tests/test_gpu_sweep.py, run in a child process each: torch is imported BEFORE the package there, so that
-libmi355pt binds to torch's copy of the HIP runtime (as tests/box_torch_cases.py does).  python tests/sweep_torch_cases.py NAME"""
-import os
-import sys
-import time
+"""The torch-route cases of tests/test_gpu_sweep.py, one child process each (tests/torchroute.py).  python tests/sweep_torch_cases.py NAME"""
+import torchroute as tr      # first: it imports torch before the package
 
-import torch      # first
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
+import sweep_cases as sc
+from routecheck import assert_guarded, same_bits
+from torchroute import N, bits, soup_scene as scene
 
-import importlib  # noqa: E402
-
-import numpy as np  # noqa: E402
-
-import sweep_cases as sc  # noqa: E402
-from scenes import random_soup  # noqa: E402
-
-N = 4097
 GUARD = 0x5A5A5A5A
 
 
-def scene(rt, ctx):
-    tris = random_soup(3000, 5)
-    ctx.set_triangles(tris); ctx.build_bvh()
-    return tris
-
-
 def to_host(res):
-    return tuple(x.cpu().view(torch.int32).numpy().view(np.uint32) for x in res)
+    return tuple(bits(x) for x in res)
 
 
 def same(got, want):
     for a, b in zip(got, want):
-        assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+        assert same_bits(a, b)
 
 
 def torch_route_equals_the_host_route(rt, ctx):
@@ -65,18 +50,13 @@ def device_route_into_guarded_tensors(rt, ctx):
     tris = scene(rt, ctx)
     S = sc.sweep_set(rt, tris, N, 4)
     rec = torch.from_numpy(S).cuda()
-    guard = int(np.uint32(GUARD).astype(np.int32))
     for flags, tree in ((0, ctx.read_bvh4()), (rt.PT_SWEEP_SIMPLE_KERNEL, ctx.read_bvh4()), (rt.PT_SWEEP_BRUTE_FORCE, None)):
-        want = rt.sweep_spheres_bvh4(tris, tree, S, brute_force=tree is None)
+        want = np.stack([np.ascontiguousarray(w).view(np.uint32) for w in rt.sweep_spheres_bvh4(tris, tree, S, brute_force=tree is None)], axis=1)
         for n in (1, 64, N):
-            out = torch.full((n + 8, 4), guard, dtype=torch.int32, device="cuda")
-            torch.cuda.synchronize()
+            out = tr.guarded(n + 8, GUARD)
             ctx.sweep_spheres_device(rec.data_ptr(), n, out.data_ptr(), flags)
             ctx.synchronize()
-            got = out.cpu().numpy().view(np.uint32)
-            assert np.all(got[n:] == GUARD), (flags, n)
-            for k in range(4):
-                assert np.array_equal(got[:n, k], np.ascontiguousarray(want[k][:n]).view(np.uint32)), (flags, n, k)
+            assert_guarded(bits(out), want[:n], GUARD, (flags, n))
 
 
 def no_host_synchronisation_then_a_scene_change(rt, ctx):
@@ -85,22 +65,11 @@ def no_host_synchronisation_then_a_scene_change(rt, ctx):
     S = sc.sweep_set(rt, tris, N, 5)
     want = rt.sweep_spheres_bvh4(tris, ctx.read_bvh4(), S)
     rec = torch.from_numpy(S).cuda()
-    ctx.sweep_spheres(rec)                                # warm-up: first-touch allocations may wait, a steady-state call does not
+    ctx.sweep_spheres(rec)                                # warm-up
     torch.cuda.synchronize()
-    t0 = time.perf_counter(); torch.cuda._sleep(5_000_000); torch.cuda.synchronize(); probe = time.perf_counter() - t0
-    cycles = int(min(max(5_000_000 * 0.3 / probe, 5_000_000), 2_000_000_000))      # about 0.3 s, whatever the counter's rate
-    t0 = time.perf_counter(); torch.cuda._sleep(cycles); torch.cuda.synchronize(); spin = time.perf_counter() - t0
-    assert spin > 0.05, spin
-    torch.cuda._sleep(cycles)
-    t0 = time.perf_counter()
-    res = ctx.sweep_spheres(rec)
-    took = time.perf_counter() - t0
-    done = torch.cuda.Event(); done.record()
-    pending = not done.query()
-    other = random_soup(5000, 47)
-    ctx.set_triangles(other); ctx.build_bvh()             # after the query: its results stay those of the first scene
+    res = tr.returns_before_the_stream(lambda: ctx.sweep_spheres(rec))
+    other = tr.second_scene(ctx)                          # after the query: its results stay those of the first scene
     torch.cuda.synchronize()
-    assert pending and took < spin / 2, (pending, took, spin)
     same(to_host(res), want)
     same(ctx.sweep_spheres(S), rt.sweep_spheres_bvh4(other, ctx.read_bvh4(), S))      # the next query sees the second
 
@@ -109,28 +78,8 @@ def errors(rt, ctx):
     rec = torch.zeros((64, 8), dtype=torch.float32, device="cuda"); rec[:, 2] = 3.0; rec[:, 3] = float("inf"); rec[:, 6] = -1.0; rec[:, 7] = 0.1
     out = torch.full((64, 4), 7, dtype=torch.int32, device="cuda")
     pp, op = rec.data_ptr(), out.data_ptr()
-
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: ctx.sweep_spheres_device(pp, 1, op)) == 4                          # no scene
-    assert code(lambda: ctx.sweep_spheres_device(pp + 4, 1, op)) == 1                      # the pointers are checked before the scene
-    assert code(lambda: ctx.sweep_spheres(np.zeros((1, 8), np.float32))) == 4              # the host route
-    scene(rt, ctx)
-    assert code(lambda: ctx.sweep_spheres_device(0, 1, op)) == 1                           # null
-    assert code(lambda: ctx.sweep_spheres_device(pp, 1, 0)) == 1
-    assert code(lambda: ctx.sweep_spheres_device(pp + 4, 1, op)) == 1                      # 16-byte aligned
-    assert code(lambda: ctx.sweep_spheres_device(pp, 1, op + 8)) == 1
-    assert code(lambda: ctx.sweep_spheres_device(pp, 1, op, flags=8)) == 1                 # unknown flag
-    assert code(lambda: ctx.sweep_spheres_device(pp, 1 << 32, op)) == 1                    # n > UINT32_MAX
-    try:
-        ctx.sweep_spheres(torch.zeros((4, 8)))                                            # a CPU tensor
-        raise AssertionError("no error")
-    except ValueError:
-        pass
+    sweep = (ctx.sweep_spheres_device, [pp, 1, op, 0], [(0, 0), (2, 0), (0, pp + 4), (2, op + 8), (3, 8), (1, 1 << 32)])      # null, not 16-byte aligned, unknown flag, n > UINT32_MAX
+    tr.refusals(rt, ctx, [sweep], lambda: scene(rt, ctx), host=[lambda: ctx.sweep_spheres(np.zeros((1, 8), np.float32))], cpu=[lambda: ctx.sweep_spheres(torch.zeros((4, 8)))])
     torch.cuda.synchronize()
     ctx.sweep_spheres_device(pp, 0, op)                                                   # n = 0: nothing is launched
     ctx.synchronize()
@@ -140,11 +89,4 @@ def errors(rt, ctx):
 
 
 if __name__ == "__main__":
-    rt = importlib.import_module("raytracer-public_amd")
-    assert rt._TORCH_FIRST
-    ctx = rt.Context(0)
-    try:
-        globals()[sys.argv[1]](rt, ctx)
-    finally:
-        ctx.close()
-    print("ok", sys.argv[1])
+    tr.main(globals())

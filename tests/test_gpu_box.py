@@ -2,19 +2,16 @@
 equality: of the persistent, the one-box-per-thread and the brute-force kernels with the host twin (tests/test_box_host.py pins that to a
 float32 restatement, to brute force and to float64) -- counts, offsets, the entries' words including the zero reserved words, their ORDER,
 and the counters of PT_BOX_STATS; of truncated results with the full one; of the counts with the offsets."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import box_cases as bc
 import crossing_cases as cc
+from routecheck import run_case
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 N_BOXES = 2048
 SCENES = ["tetra", "torus", "soup1k", "dragon50k_l0", "dragon50k_l2", "refit", "bvh2", "comb", "deepcomb", "spoiled"]
 COUNTERS = ("rays_closest", "rays_shadow", "nodes_examined", "tris_tested", "stack_drops", "max_stack", "samples")
@@ -138,6 +135,4 @@ def test_exact_cases(rt, gpu_ctx):
                                   "ordering_with_batched_frames_and_scene_changes", "errors"])
 def test_torch_route(case):
     """The device route: tests/box_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "box_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("box_torch_cases", case)

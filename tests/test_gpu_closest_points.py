@@ -1,9 +1,6 @@
 """Batched closest-point queries on the GPU (pt_closest_points / pt_closest_points_host) against the host twin
 pt_closest_points_bvh4, bit for bit: dist, prim, u, v of the persistent and of the simple kernel on every point, and the counters of
 PT_CLOSEST_STATS.  The twin itself is pinned to an independent float64 reference on the CPU (tests/test_closest_points_host.py)."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -11,11 +8,11 @@ import pytest
 import closest_cases as cc
 import closestref
 from refit_cases import host_trees, wave
+from routecheck import run_case
 from scenes import TETRA, comb_bvh4, random_soup, spoil_bvh4
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SCENE_SEED = 20260109
 KERNELS = [False, True]       # simple=False: the persistent kernel; True: the one-point-per-thread kernel
 COUNTERS = ("rays_closest", "rays_shadow", "nodes_examined", "tris_tested", "stack_drops", "max_stack", "samples")
@@ -126,6 +123,4 @@ def test_full_size_dragon(rt, gpu_ctx):
 def test_torch_route(case):
     """The zero-copy torch route vs the host route, ordering behind pt_set_batch frames and before scene changes, every error code:
     tests/closest_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "closest_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("closest_torch_cases", case)

@@ -5,7 +5,6 @@ both containment kernels with the composition occlusion_rays -> count_hits -> pa
 closest_points and contains; and containment against the float64 winding number on a closed mesh."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import closestref
 import crossing_cases as cc
 import crossref
 from refit_cases import wave
+from routecheck import code, run_case
 from scenes import random_soup
 
 pytestmark = pytest.mark.gpu
@@ -200,17 +200,11 @@ def test_signed_distance(rt, gpu_ctx, name):
 
 
 def test_argument_errors(rt, gpu_ctx):
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
     pts = np.zeros((3, 3), np.float32); rays = rt.pack_rays(pts, pts + 1)
-    assert code(lambda: gpu_ctx.count_hits(rays)) == 4 and code(lambda: gpu_ctx.contains(pts)) == 4 and code(lambda: gpu_ctx.signed_distance(pts)) == 4
+    assert code(rt, lambda: gpu_ctx.count_hits(rays)) == 4 and code(rt, lambda: gpu_ctx.contains(pts)) == 4 and code(rt, lambda: gpu_ctx.signed_distance(pts)) == 4
     gpu_ctx.set_triangles(cc.geometry(rt, "tetra")); gpu_ctx.build_bvh()
     for bad in (0, 2, 256):
-        assert code(lambda: gpu_ctx.contains(pts, samples=bad)) == 1 and code(lambda: gpu_ctx.signed_distance(pts, samples=bad)) == 1
+        assert code(rt, lambda: gpu_ctx.contains(pts, samples=bad)) == 1 and code(rt, lambda: gpu_ctx.signed_distance(pts, samples=bad)) == 1
     import ctypes as C
     p = rt.PtContainParams(3, 0, 0, 0); out = rt._aligned_zeros((4, 4), np.uint32); rec = rt.pack_points(pts)
     assert rt.lib.pt_contains_host(gpu_ctx.h, rec.ctypes.data_as(C.POINTER(rt.PtPoint)), C.c_uint64((1 << 32) // 3 + 1), C.byref(p),
@@ -227,9 +221,7 @@ def test_argument_errors(rt, gpu_ctx):
                                   "ordering_with_batched_frames_and_scene_changes", "errors"])
 def test_torch_route(case):
     """The device route: tests/crossings_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "crossings_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("crossings_torch_cases", case)
 
 
 NODE = "/usr/bin/node" if os.path.exists("/usr/bin/node") else "node"

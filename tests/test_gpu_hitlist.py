@@ -3,9 +3,6 @@ of the persistent, the one-ray-per-thread and the brute-force kernels, unsorted 
 pins that to a float32 restatement, to brute force and to float64) -- offsets, the entries' bits and their ORDER, and the counters of
 PT_HITS_STATS; of the list lengths with pt_count_hits; of the sort kernel's classes with the twin on a deck whose lists have every length
 around the class boundaries; of truncated results with the full one."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,10 +12,10 @@ import hitlist_cases as hc
 import hitlistref
 import radius_cases as rc
 from radius_cases import install
+from routecheck import run_case
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 N_RAYS = 2048
 SCENES = ["tetra", "torus", "soup1k", "dragon50k_l0", "dragon50k_l2", "refit", "bvh2", "comb", "spoiled"]
 COUNTERS = ("rays_closest", "rays_shadow", "nodes_examined", "tris_tested", "stack_drops", "max_stack", "samples")
@@ -131,9 +128,8 @@ def test_truncation_at_a_capacity_on_the_host_route(rt, orc, gpu_ctx, kernel):
     assert np.array_equal(part[0], want[0]) and len(part[2]) == total - 5 and np.array_equal(part[2], want[2][:total - 5])
 
 
-@pytest.mark.parametrize("case", ["torch_route_equals_the_host_route", "truncation_on_the_device_route", "ordering_with_batched_frames_and_scene_changes", "errors"])
+@pytest.mark.parametrize("case", ["torch_route_equals_the_host_route", "truncation_on_the_device_route", "no_host_synchronisation_with_a_capacity",
+                                  "ordering_with_batched_frames_and_scene_changes", "errors"])
 def test_torch_route(case):
     """The device route: tests/hitlist_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "hitlist_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("hitlist_torch_cases", case)

@@ -6,7 +6,6 @@ k = 1 with the closest-point query."""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import pytest
 import closest_cases as clc
 import knn_cases as kc
 import radius_cases as rc
+from routecheck import run_case
 
 pytestmark = pytest.mark.gpu
 
@@ -148,9 +148,7 @@ def test_arguments(rt, orc, gpu_ctx):
                                   "ordering_with_batched_frames_and_scene_changes", "errors"])
 def test_torch_route(case):
     """The device route: tests/knn_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "knn_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("knn_torch_cases", case)
 
 
 NODE = "/usr/bin/node" if os.path.exists("/usr/bin/node") else "node"

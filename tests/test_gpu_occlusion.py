@@ -4,11 +4,11 @@ holds with stack drops too), with the CPU oracle's orc_trace_ray over the host t
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from routecheck import code, run_case
 from scenes import TETRA, closed_box, comb_bvh4, random_soup, spoil_bvh4
 
 pytestmark = pytest.mark.gpu
@@ -320,16 +320,10 @@ def test_sample_count_limits(rt, gpu_ctx):
     scene(rt, gpu_ctx, "tetra")
     sf = rt.pack_surfels(np.zeros((3, 3), np.float32), np.float32([[0, 0, 1]] * 3))
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: gpu_ctx.occlusion(sf, 0)) == 1
-    assert code(lambda: gpu_ctx.occlusion(sf, 65537)) == 1
-    assert code(lambda: gpu_ctx.occlusion(sf, 16, bias=-1.0)) == 1
-    assert code(lambda: gpu_ctx.occlusion(sf, 16, bias=float("nan"))) == 1
+    assert code(rt, lambda: gpu_ctx.occlusion(sf, 0)) == 1
+    assert code(rt, lambda: gpu_ctx.occlusion(sf, 65537)) == 1
+    assert code(rt, lambda: gpu_ctx.occlusion(sf, 16, bias=-1.0)) == 1
+    assert code(rt, lambda: gpu_ctx.occlusion(sf, 16, bias=float("nan"))) == 1
     vis, unocc, smp = gpu_ctx.occlusion(sf, 65536)                     # the largest sample count
     assert np.all(smp == 65536) and np.all(unocc <= 65536)
     # n * samples must fit 32 bits: refused before anything is read (the host route is handed a short array on purpose)
@@ -348,9 +342,7 @@ def test_sample_count_limits(rt, gpu_ctx):
                                   "ordering_with_batched_frames_and_scene_changes", "camera_pipeline_stays_on_the_device", "errors"])
 def test_torch_route(case):
     """The device route: tests/occlusion_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "occlusion_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("occlusion_torch_cases", case)
 
 
 NODE = "/usr/bin/node" if os.path.exists("/usr/bin/node") else "node"
@@ -403,9 +395,7 @@ const f32 = (p) => { const raw = fs.readFileSync(p); return new Float32Array(raw
     assert line["ao"] == 16 and line["radius"] == 0.5 and line["width"] == w and line["height"] == h
     big = rt.procedural_scene(rt.SCENE_DRAGON_CLASS, 20000, SCENE_SEED)
     gpu_ctx.set_triangles(big); gpu_ctx.build_bvh()
-    r = subprocess.run([sys.executable, os.path.join(HERE, "occlusion_torch_cases.py"), "ao_frame", str(w), str(h), "16", "0.5", str(tmp_path / "want.f32")],
-                       capture_output=True, text=True, timeout=300, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    run_case("occlusion_torch_cases", "ao_frame", w, h, 16, 0.5, tmp_path / "want.f32", timeout=300)
     want = np.fromfile(str(tmp_path / "want.f32"), np.float32).reshape(h, w)
     got = np.fromfile(str(out), np.float32).reshape(h, w, 4)
     assert 0 < (want > 0).sum() < w * h

@@ -6,7 +6,6 @@ the closest-point query."""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import closest_cases as clc
 import crossing_cases as cc
 import radius_cases as rc
 from radius_cases import install
+from routecheck import run_case
 
 pytestmark = pytest.mark.gpu
 
@@ -129,9 +129,7 @@ def test_nearest_entry_is_the_closest_point(rt, orc, gpu_ctx):
                                   "ordering_with_batched_frames_and_scene_changes", "errors"])
 def test_torch_route(case):
     """The device route: tests/radius_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "radius_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("radius_torch_cases", case)
 
 
 NODE = "/usr/bin/node" if os.path.exists("/usr/bin/node") else "node"

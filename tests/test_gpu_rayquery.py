@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import orc as orc_mod
+from routecheck import run_case
 from scenes import TETRA, comb_bvh4, random_soup, spoil_bvh4
 
 pytestmark = pytest.mark.gpu
@@ -206,9 +207,7 @@ def test_batch_shapes(rt, orc, gpu_ctx, n):
 def test_torch_route(case):
     """Camera rays vs a mode-1 render of C2 (prim on every pixel, the oracle's counters), ordering behind pt_set_batch frames and before
     scene changes, the zero-copy torch route vs the host route, every error code: tests/rayquery_torch_cases.py in a child process."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "rayquery_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("rayquery_torch_cases", case)
 
 
 def test_torch_route_needs_torch_first():

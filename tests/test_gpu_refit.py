@@ -6,13 +6,13 @@ import ctypes as C
 import os
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import orc as orc_mod
 from refit_cases import host_trees, wave
+from routecheck import code, run_case
 from scenes import TETRA, random_soup, quat_yaw_pitch, spoil_bvh4
 from test_accel_host import DEGENERATE, degenerate
 from test_gpu_rayquery import MISS, oracle_batch, random_rays
@@ -249,26 +249,20 @@ def test_refused_updates_leave_the_context_as_it_was(rt, orc, gpu_ctx):
     moved = wave(tris, 0.2, 1)
     fp = C.POINTER(C.c_float)
 
-    def code(fn):
-        try:
-            fn()
-        except rt.PtError as e:
-            return e.code
-        raise AssertionError("no error")
-    assert code(lambda: gpu_ctx.update_triangles(moved)) == 4              # PT_ERR_NO_SCENE: no triangles yet
-    assert code(lambda: gpu_ctx.bvh_cost()) == 4
+    assert code(rt, lambda: gpu_ctx.update_triangles(moved)) == 4              # PT_ERR_NO_SCENE: no triangles yet
+    assert code(rt, lambda: gpu_ctx.bvh_cost()) == 4
     gpu_ctx.set_triangles(tris)
-    assert code(lambda: gpu_ctx.bvh_cost()) == 4                           # triangles without a tree
+    assert code(rt, lambda: gpu_ctx.bvh_cost()) == 4                           # triangles without a tree
     gpu_ctx.build_bvh(2)
     b4, b2 = gpu_ctx.read_bvh4(), gpu_ctx.read_bvh2()
     p = gpu_ctx.make_params(128, 72, mode=rt.PT_MODE_PATH, spp=2, max_bounces=4, seed=2)
     gpu_ctx.render(p)
     frame = gpu_ctx.read_radiance().copy()
-    assert code(lambda: gpu_ctx.update_triangles(moved[:-9])) == 1         # another count
-    assert code(lambda: gpu_ctx.update_triangles(np.concatenate([moved, moved[:9]]))) == 1
+    assert code(rt, lambda: gpu_ctx.update_triangles(moved[:-9])) == 1         # another count
+    assert code(rt, lambda: gpu_ctx.update_triangles(np.concatenate([moved, moved[:9]]))) == 1
     assert rt.lib.pt_update_triangles(gpu_ctx.h, None, C.c_uint32(n)) == 1                  # NULL
     assert rt.lib.pt_update_triangles_device(gpu_ctx.h, None, C.c_uint32(n)) == 1
-    assert code(lambda: gpu_ctx.update_triangles_device(0x1000 + 4, n)) == 1                # not 16-byte aligned: refused before it is read
+    assert code(rt, lambda: gpu_ctx.update_triangles_device(0x1000 + 4, n)) == 1                # not 16-byte aligned: refused before it is read
     assert rt.lib.pt_bvh_cost(gpu_ctx.h, None) == 1
     assert np.array_equal(gpu_ctx.read_bvh4(), b4) and np.array_equal(gpu_ctx.read_bvh2(), b2)
     gpu_ctx.render(p)
@@ -306,8 +300,7 @@ def test_group_update_triangles(rt, orc):
 def test_torch_route(case):
     """The zero-copy device route (a torch tensor of vertices), its ordering with queued frames and with torch's streams:
     tests/refit_torch_cases.py in a child process (torch has to be imported before the package)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "refit_torch_cases.py"), case], capture_output=True, text=True, timeout=900, cwd=HERE)
-    assert r.returncode == 0 and ("ok " + case) in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    run_case("refit_torch_cases", case, timeout=900)
 
 
 @pytest.mark.skipif(NODE is None, reason="node is not installed")

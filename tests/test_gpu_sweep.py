@@ -1,9 +1,6 @@
 """Sphere-cast queries on the GPU (pt_sweep_spheres / pt_sweep_spheres_host) against the host twin
 pt_sweep_spheres_bvh4, word for word: t, prim, u, v of the persistent, the simple and the brute-force kernel on every item, and the counters
 of PT_SWEEP_STATS.  The twin itself is pinned to the numpy restatement and to a float64 reference on the CPU (tests/test_sweep_host.py)."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -11,11 +8,11 @@ import pytest
 import crossing_cases as xc
 import sweep_cases as sc
 from refit_cases import host_trees, wave
+from routecheck import run_case
 from scenes import comb_bvh4
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 N = 2048
 COUNTERS = ("rays_closest", "rays_shadow", "nodes_examined", "tris_tested", "stack_drops", "max_stack", "samples")
 f32 = np.float32
@@ -109,6 +106,4 @@ def test_one_wavefront_of_mixed_items(rt, gpu_ctx):
 @pytest.mark.parametrize("case", ["torch_route_equals_the_host_route", "device_route_into_guarded_tensors", "no_host_synchronisation_then_a_scene_change", "errors"])
 def test_torch_route(case):
     """The device route: tests/sweep_torch_cases.py in a child process (torch is imported before the package there)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "sweep_torch_cases.py"), case], capture_output=True, text=True, timeout=600, cwd=HERE)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert ("ok " + case) in r.stdout
+    run_case("sweep_torch_cases", case)
