@@ -44,8 +44,7 @@ int sync_refit_meta(PtContext* ctx) {
     if (ctx->meta_has_root && ctx->have_bvh) {
         pt::WideBvh& w = ctx->wide_meta;
         w.root_box[0] = h[0]; w.root_box[1] = h[1]; w.root_box[2] = h[2];
-        w.root_degenerate = pt::half_to_float(h[0] & 0xffffu) > pt::half_to_float(h[1] >> 16) || pt::half_to_float(h[0] >> 16) > pt::half_to_float(h[2] & 0xffffu) ||
-                            pt::half_to_float(h[1] & 0xffffu) > pt::half_to_float(h[2] >> 16);
+        w.root_degenerate = ptbd::box_degenerate(h[0], h[1], h[2]);
     }
     return PT_OK;
 }
@@ -168,8 +167,7 @@ bool root_box_rect(const pt::WideBvh& w, const ptk::FrameParams& f, uint32_t wid
     // scales and shears the direction by about |q|^2 - 1, i.e. up to that times half the image width in pixels at the screen edge --
     // 1e-5 x 16384 px stays far inside the two-pixel margin below; anything sloppier traces every tile
     if (!(qn > 1.0 - 1e-5 && qn < 1.0 + 1e-5) || !(f.focal > 1e-3f) || !(f.aspect > 1e-3f)) return false;
-    const double mn[3] = {pt::half_to_float(w.root_box[0] & 0xffffu), pt::half_to_float(w.root_box[0] >> 16), pt::half_to_float(w.root_box[1] & 0xffffu)};
-    const double mx[3] = {pt::half_to_float(w.root_box[1] >> 16), pt::half_to_float(w.root_box[2] & 0xffffu), pt::half_to_float(w.root_box[2] >> 16)};
+    double mn[3], mx[3]; ptbd::unpack_box(w.root_box[0], w.root_box[1], w.root_box[2], mn, mx);
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
     for (int c = 0; c < 8; ++c) {
         const double p[3] = {((c & 1) ? mx[0] : mn[0]) - f.cam[0], ((c & 2) ? mx[1] : mn[1]) - f.cam[1], ((c & 4) ? mx[2] : mn[2]) - f.cam[2]};
@@ -476,8 +474,7 @@ double expose_cam_norm(const ptk::FrameParams* frames, uint32_t nf) {
 // the largest distance of a corner of the root box (grown as pt_expose.h grows a box) from the origin, or -1 when it is not finite
 double expose_scene_norm(const PtContext* ctx) {
     const uint32_t* b = ctx->wide_meta.root_box;
-    const double mn[3] = {pt::half_to_float(b[0] & 0xffffu), pt::half_to_float(b[0] >> 16), pt::half_to_float(b[1] & 0xffffu)};
-    const double mx[3] = {pt::half_to_float(b[1] >> 16), pt::half_to_float(b[2] & 0xffffu), pt::half_to_float(b[2] >> 16)};
+    double mn[3], mx[3]; ptbd::unpack_box(b[0], b[1], b[2], mn, mx);
     double r2 = 0.0;
     for (int a = 0; a < 3; ++a) { const double m = std::max(std::fabs(mn[a]), std::fabs(mx[a])) + ptex::kBoxGrow; r2 += m * m; }
     const double r = std::sqrt(r2);
@@ -1156,8 +1153,7 @@ int pt_build_bvh_accel(PtContext* ctx, uint32_t accel) {
     pt::WideBvh meta;
     meta.num_nodes4 = m;
     meta.root_box[0] = root[0]; meta.root_box[1] = root[1]; meta.root_box[2] = root[2];
-    meta.root_degenerate = pt::half_to_float(root[0] & 0xffffu) > pt::half_to_float(root[1] >> 16) || pt::half_to_float(root[0] >> 16) > pt::half_to_float(root[2] & 0xffffu) ||
-                           pt::half_to_float(root[1] & 0xffffu) > pt::half_to_float(root[2] >> 16);
+    meta.root_degenerate = ptbd::box_degenerate(root[0], root[1], root[2]);
     meta.root_ref = (root[7] & pt::kLeafFlag) ? pt::packed_leaf_ref(root[7] & 0x7fffffffu, n) : uint32_t(ctx->node_off / 16u);
     ctx->wide_meta = meta;
     ctx->num_nodes4 = m;

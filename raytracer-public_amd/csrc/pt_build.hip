@@ -32,9 +32,6 @@ __device__ __forceinline__ double dunkey(unsigned long long k) {
     const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     return __longlong_as_double((long long)u);
 }
-__device__ __forceinline__ double centroid_axis(const float* p, int k) {
-    return (((double)p[k] + (double)p[3 + k]) + (double)p[6 + k]) / 3;      // (a + b + c) / 3, PathTracer.js:419-421
-}
 
 __global__ void build_init_kernel(unsigned long long* bounds, uint32_t* counters, uint32_t n_counters) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(256) void centroid_bounds_kernel(const float* __res
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
         const float* p = tris + (size_t)t * 9;
         for (int k = 0; k < 3; ++k) {
-            const double c = centroid_axis(p, k);
+            const double c = ptbd::centroid_axis(p, k);
             if (c == c) { const unsigned long long key = dkey(c); lo[k] = key < lo[k] ? key : lo[k]; hi[k] = key > hi[k] ? key : hi[k]; }
         }
     }
@@ -72,22 +69,6 @@ __global__ __launch_bounds__(256) void centroid_bounds_kernel(const float* __res
     }
 }
 
-__device__ __forceinline__ uint32_t spread10(uint32_t v) {      // PathTracer.js:440-447
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t quantize1023(double x) {    // max(0, min(1023, (x * 1023) | 0))
-    const double s = x * 1023;
-    if (!(s == s)) return 0u;
-    if (s >= 1023.0) return 1023u;
-    if (s <= 0.0) return 0u;
-    return (uint32_t)(int32_t)s;
-}
-
 __global__ __launch_bounds__(256) void morton_kernel(const float* __restrict__ tris, uint32_t n, const unsigned long long* __restrict__ bounds,
                                                       uint32_t* __restrict__ code, uint32_t* __restrict__ index) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -97,15 +78,15 @@ __global__ __launch_bounds__(256) void morton_kernel(const float* __restrict__ t
     for (int k = 0; k < 3; ++k) {
         const double lo = dunkey(bounds[k]), hi = dunkey(bounds[3 + k]);
         const double d = hi - lo, ext = d > 1e-20 ? d : 1e-20;               // PathTracer.js:431-433
-        q[k] = quantize1023((centroid_axis(p, k) - lo) / ext);
+        q[k] = ptbd::quantize1023((ptbd::centroid_axis(p, k) - lo) / ext);
     }
-    code[t] = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+    code[t] = (ptbd::spread10(q[0]) << 2) | (ptbd::spread10(q[1]) << 1) | ptbd::spread10(q[2]);
     index[t] = t;
 }
 
 // ------------------------------------------------------------------------------------
 // Triangle records: v0, e1, e2, n = normalize(cross(e1, e2)) -- the f32 operations
-// renderer.wgsl:179-180,269 performs per visit (same as pt::build_tri_records on the host)
+// renderer.wgsl:179-180,269 performs per visit (same as pt::build_tri_records on the host; pt_bounds.h says why this one is written twice)
 // ------------------------------------------------------------------------------------
 // edge_max (optional): the largest |component| of any edge vector as f32 bits -- positive floats order like their bits, and a NaN's bits lie
 // above those of infinity, so "small enough" is one unsigned compare on the host (what the traversal's short reciprocal may assume, pt_api.cpp)
@@ -138,20 +119,9 @@ __global__ __launch_bounds__(256) void tri_records_kernel(const float* __restric
 //   id(child s) = id(parent) + 1 + sum of the subtree sizes of the children in slots < s.
 // A BVH4 node is identified during the build by its position in the breadth-first order.
 // ------------------------------------------------------------------------------------
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNone = ptbd::kInvalid;
 
 __device__ __forceinline__ bool leaf2(const uint32_t* __restrict__ bvh2, uint32_t node) { return (bvh2[1 + (size_t)node * 6 + 5] & kLeaf) != 0u; }
-
-// surface area of a BVH2 node from its stored f16 box words, decoded exactly: ((dx*dy) + (dy*dz)) + (dz*dx), f32, no fma
-// (-ffp-contract=off; pt_host.cpp::node_area2 is the same expression)
-__device__ __forceinline__ float node_area2(const uint32_t* __restrict__ bvh2, uint32_t node) {
-    const uint32_t* p = bvh2 + 1 + (size_t)node * 6;
-    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-    const float dx = half_exact(w1 >> 16) - half_exact(w0 & 0xffffu);
-    const float dy = half_exact(w2 & 0xffffu) - half_exact(w0 >> 16);
-    const float dz = half_exact(w2 >> 16) - half_exact(w1 & 0xffffu);
-    return ((dx * dy) + (dy * dz)) + (dz * dx);
-}
 
 // one thread per BVH4 node of this level: greedy expansion of its BVH2 subtree top into <= 4 entries
 // (repeatedly replace the first internal entry by its two children), children appended to the next level.
@@ -175,7 +145,8 @@ __global__ __launch_bounds__(256) void collapse_expand_kernel(const uint32_t* __
                 for (uint32_t s = 0; s < nk; ++s) {
                     if (!(kid[s] < nn2 && !leaf2(bvh2, kid[s]))) continue;
                     if (!AREA) { pos = s; break; }
-                    const float a = node_area2(bvh2, kid[s]);
+                    const uint32_t* q = bvh2 + 1 + (size_t)kid[s] * 6;
+                    const float a = ptbd::node_area2(q[0], q[1], q[2]);
                     if (pos == nk || a > best) { pos = s; best = a; }
                 }
                 if (pos == nk) break;
@@ -230,12 +201,13 @@ __global__ __launch_bounds__(256) void collapse_up_kernel(const uint32_t* __rest
             size += subtree[c[s]];
             const uint32_t* b = bnd + (size_t)c[s] * 3;
             const uint32_t b0 = b[0], b1 = b[1], b2 = b[2];
+            using ptbd::js_min_f; using ptbd::js_max_f; using ptbd::half_exact;
             mn[0] = js_min_f(mn[0], half_exact(b0 & 0xffffu)); mn[1] = js_min_f(mn[1], half_exact(b0 >> 16)); mn[2] = js_min_f(mn[2], half_exact(b1 & 0xffffu));
             mx[0] = js_max_f(mx[0], half_exact(b1 >> 16)); mx[1] = js_max_f(mx[1], half_exact(b2 & 0xffffu)); mx[2] = js_max_f(mx[2], half_exact(b2 >> 16));
         }
-        w0 = half_trunc(mn[0]) | (half_trunc(mn[1]) << 16);
-        w1 = half_trunc(mn[2]) | (half_trunc(mx[0]) << 16);
-        w2 = half_trunc(mx[1]) | (half_trunc(mx[2]) << 16);
+        w0 = ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 0);
+        w1 = ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 1);
+        w2 = ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 2);
     }
     subtree[p] = size;
     uint32_t* o = bnd + (size_t)p * 3;
@@ -288,10 +260,9 @@ __global__ __launch_bounds__(256) void wide_nodes_kernel(const uint32_t* __restr
         if (c == kInvalidRef || c >= m) continue;
         const uint32_t* cr = bvh4 + 1 + (size_t)c * 8;
         const uint32_t w0 = cr[0], w1 = cr[1], w2 = cr[2];
-        if (box_degenerate(w0, w1, w2)) { ref[s] = kDegenerateRef; continue; }   // fetched by the reference, entered by no ray
+        if (ptbd::box_degenerate(w0, w1, w2)) { ref[s] = kDegenerateRef; continue; }   // fetched by the reference, entered by no ray
         box[3 * s] = w0; box[3 * s + 1] = w1; box[3 * s + 2] = w2;
-        const uint32_t tri = cr[7] & 0x7fffffffu;
-        ref[s] = (cr[7] & kLeaf) ? (kLeaf | (4u * (tri < num_tris ? tri : num_tris))) : node_base16 + 4u * wide_index[c];     // packed references (pt_host.h)
+        ref[s] = (cr[7] & kLeaf) ? ptbd::packed_leaf_ref(cr[7] & 0x7fffffffu, num_tris) : node_base16 + 4u * wide_index[c];
     }
     uint4* o = wide + (size_t)wide_index[i] * 4;
     o[0] = make_uint4(box[0], box[1], box[2], ref[0]);       // child-major (pt_host.h::WideNode): piece k = child k's box + reference
@@ -301,16 +272,16 @@ __global__ __launch_bounds__(256) void wide_nodes_kernel(const uint32_t* __restr
 }
 
 // ------------------------------------------------------------------------------------
-// PLOC BVH2 (PT_ACCEL_PLOC; Meister & Bittner, TVCG 2018).  Host twin: pt_host.cpp::build_bvh2_ploc, word for word.
+// PLOC BVH2 (PT_ACCEL_PLOC; Meister & Bittner, TVCG 2018).  Host twin: pt_host.cpp::build_bvh2_ploc.
 // Clusters live in SoA ping-pong buffers (six f32 box planes + the BVH2 node id), in Morton order; per iteration:
 // nearest neighbour in [i-R, i+R] (ploc_nn_kernel), mutual pairs and survivors flagged (ploc_flags_kernel), one inclusive
 // scan of (merge << 32 | keep), then merge + stable compaction (ploc_merge_kernel).
 // ------------------------------------------------------------------------------------
-constexpr uint32_t kPlocRadius = 16;      // pt_host.h::kPlocRadius
+using ptbd::kPlocRadius;
 constexpr uint32_t kPlocSpan = 256u + 2u * kPlocRadius;
 
-__device__ __forceinline__ float sel_min(float a, float b) { return b < a ? b : a; }    // pt_host.cpp: the same expressions
-__device__ __forceinline__ float sel_max(float a, float b) { return b > a ? b : a; }
+using ptbd::sel_min;
+using ptbd::sel_max;
 
 __global__ __launch_bounds__(256) void ploc_init_kernel(const float* __restrict__ tris, const uint32_t* __restrict__ tri_index, uint32_t n,
                                                          float* __restrict__ box, uint32_t* __restrict__ node) {
@@ -344,11 +315,10 @@ __global__ __launch_bounds__(256) void ploc_nn_kernel(const float* __restrict__ 
         if (j == i) continue;
         const uint32_t a = i < j ? i : j, b = i < j ? j : i;
         const uint32_t la = a + kPlocRadius - base, lb = b + kPlocRadius - base;
-        const float dx = sel_max(sb[3][la], sb[3][lb]) - sel_min(sb[0][la], sb[0][lb]);
-        const float dy = sel_max(sb[4][la], sb[4][lb]) - sel_min(sb[1][la], sb[1][lb]);
-        const float dz = sel_max(sb[5][la], sb[5][lb]) - sel_min(sb[2][la], sb[2][lb]);
-        float d = ((dx * dy) + (dy * dz)) + (dz * dx);
-        if (!(d == d)) d = __uint_as_float(0x7f800000u);
+        const float dx = ptbd::union_extent(sb[3][la], sb[3][lb], sb[0][la], sb[0][lb]);
+        const float dy = ptbd::union_extent(sb[4][la], sb[4][lb], sb[1][la], sb[1][lb]);
+        const float dz = ptbd::union_extent(sb[5][la], sb[5][lb], sb[2][la], sb[2][lb]);
+        const float d = ptbd::ploc_area(dx, dy, dz);
         if (bj == kNone || d < bd || (d == bd && (a < blo || (a == blo && b < bhi)))) { bd = d; bj = j; blo = a; bhi = b; }
     }
     nn[i] = bj;

@@ -90,10 +90,9 @@ __global__ __launch_bounds__(kCoverBlock) void tile_cover_kernel(const uint4* __
     if (i >= count) return;
     const uint32_t e = cut[i];
     const uint4 piece = wide[(size_t)(e >> 2) * 4u + (e & 3u)];
-    if (piece.w == kCutEmpty || box_degenerate(piece.x, piece.y, piece.z)) return;       // no ray enters it (the traversal's own rule)
+    if (piece.w == kCutEmpty || ptbd::box_degenerate(piece.x, piece.y, piece.z)) return;       // no ray enters it (the traversal's own rule)
     const CoverCam& c = cams.c[blockIdx.y];
-    const double mn[3] = {half_exact(piece.x & 0xffffu), half_exact(piece.x >> 16), half_exact(piece.y & 0xffffu)};
-    const double mx[3] = {half_exact(piece.y >> 16), half_exact(piece.z & 0xffffu), half_exact(piece.z >> 16)};
+    double mn[3], mx[3]; ptbd::unpack_box(piece.x, piece.y, piece.z, mn, mx);
     const double qx = c.quat[0], qy = c.quat[1], qz = c.quat[2], qw = c.quat[3];
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
     bool ok = true;

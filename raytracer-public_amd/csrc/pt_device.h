@@ -10,6 +10,7 @@
 
 #include "pt_kernels.h"
 #include "pt_raymath.h"
+#include "pt_bounds.h"
 
 namespace ptk {
 
@@ -54,8 +55,9 @@ template <bool B = false> __device__ __forceinline__ F3 normalize3(F3 v) { const
 // -> v_min_f32 / v_max_f32 / v_min3_f32 / v_max3_f32
 // v_min_f32 / v_max_f32: -0 orders below +0 (the ISA's pseudo-code names the two zero cases).  In the slab test the sign of a zero never reaches a
 // comparison; in the LBVH2 builder it does (incrementF16 steps -0 and +0 differently), and the oracle's builder pins the same order (min_oz / max_oz).
-__device__ __forceinline__ float wmin(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ float wmax(float a, float b) { return __builtin_fmaxf(a, b); }
+// (the text is pt_bounds.h's, which the host twin compiles as well, with the instruction's rule spelt out)
+__device__ __forceinline__ float wmin(float a, float b) { return ptbd::wmin(a, b); }
+__device__ __forceinline__ float wmax(float a, float b) { return ptbd::wmax(a, b); }
 
 __device__ __forceinline__ float half_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
 __device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
@@ -66,9 +68,7 @@ __device__ __forceinline__ float half_hi_minus(uint32_t w, float o) { float r; a
 
 using ptry::kInfT;
 using ptry::kTriEps;
-constexpr uint32_t kLeaf = 0x80000000u;
-constexpr uint32_t kInvalidRef = 0xFFFFFFFFu;
-constexpr uint32_t kDegenerateRef = 0xFFFFFFFEu;   // child slot whose record the reference fetches and rejects (renderer.wgsl:289-291): counted, never entered
+constexpr uint32_t kLeaf = ptbd::kLeafFlag, kInvalidRef = ptbd::kInvalid, kDegenerateRef = ptbd::kDegenerate;     // the layout constants of pt_bounds.h under the kernels' names
 
 struct Ray { F3 o, d, inv; };
 
@@ -135,7 +135,7 @@ __device__ __forceinline__ RaySel ray_selectors(F3 inv) {
     s.z = inv.z < 0.0f ? 0x01000706u : 0x07060100u;     // v_perm_b32(w2, w1): mn.z = bytes 0-1, mx.z = bytes 6-7
     return s;
 }
-constexpr uint32_t kEmptyBox0 = 0x7C007C00u, kEmptyBox1 = 0xFC007C00u, kEmptyBox2 = 0xFC00FC00u;   // mn = +inf, mx = -inf (f16)
+using ptbd::kEmptyBox0; using ptbd::kEmptyBox1; using ptbd::kEmptyBox2;     // mn = +inf, mx = -inf (f16)
 // returns the hit mask of the wavefront's active lanes (the two comparisons are ballots of their own, combined on the scalar unit)
 // (Round 4 tried the 18 instructions up to max(tmin, 0) as ONE asm statement in a fixed order: on gfx950 the compiler puts an `s_nop 0` behind
 // every one-instruction asm statement -- it must assume a partial register write, the dst_sel forwarding hazard --, 24 idle issue slots per

@@ -81,8 +81,7 @@ __global__ __launch_bounds__(kExBlock) void expose_query_kernel(const uint4* __r
                 for (uint32_t s = 0; s < 4u; ++s) {
                     const uint4 piece = scene[(size_t)cur + s];
                     if (piece.w >= kDegenerateRef) continue;                  // empty, or entered by no ray
-                    const double mn[3] = {half_exact(piece.x & 0xffffu), half_exact(piece.x >> 16), half_exact(piece.y & 0xffffu)};
-                    const double mx[3] = {half_exact(piece.y >> 16), half_exact(piece.z & 0xffffu), half_exact(piece.z >> 16)};
+                    double mn[3], mx[3]; ptbd::unpack_box(piece.x, piece.y, piece.z, mn, mx);
                     if (!ptex::box_may_block(q, mn, mx, g)) continue;
                     if (sp >= kExStack) { gave_up = true; break; }
                     stack[sp++] = piece.w;

@@ -18,73 +18,17 @@
 
 namespace pt {
 
-// ------------------------------------------------------------------------------------
-// f16
-// ------------------------------------------------------------------------------------
-static inline uint32_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline float float_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-
-float half_to_float(uint32_t h) {
-    const uint32_t sign = (h & 0x8000u) << 16;
-    const uint32_t mag = h & 0x7fffu;
-    if (mag >= 0x7c00u) return float_of(sign | 0x7f800000u | ((mag & 0x3ffu) << 13));   // inf / nan
-    if (mag >= 0x0400u) return float_of(sign | ((mag + (112u << 10)) << 13));            // normal: rebias 15 -> 127
-    // zero / subnormal: value = mag * 2^-24, exact in f32
-    const float v = float(mag) * 5.9604644775390625e-8f;
-    return float_of(bits_of(v) | sign);
-}
-
-uint32_t float_to_half_trunc(float v) {   // PathTracer.js:42-51
-    const uint32_t u = bits_of(v);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t e = int32_t((u >> 23) & 0xffu) - 112;
-    if (e <= 0) return sign;                       // below the f16 normal range -> signed zero
-    if (e >= 31) return sign | 0x7c00u;            // saturate (also inf / nan)
-    return sign | (uint32_t(e) << 10) | ((u >> 13) & 0x3ffu);
-}
-
-uint32_t float_to_half_rtne(float v) {
-    const uint32_t u = bits_of(v);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    uint32_t a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return sign | 0x7e00u;    // nan
-    if (a >= 0x477ff000u) return sign | 0x7c00u;   // rounds to / is infinity
-    if (a < 0x38800000u) {                         // below 2^-14: subnormal half
-        if (a < 0x33000000u) return sign;          // < 2^-25
-        // align the 24-bit significand so that bit 0 of the result is 2^-24
-        const uint32_t sig = (a & 0x007fffffu) | 0x00800000u;
-        const uint32_t shift = 126u - (a >> 23);   // 14..24
-        const uint32_t q = sig >> shift;
-        const uint32_t rest = sig & ((1u << shift) - 1u);
-        const uint32_t halfway = 1u << (shift - 1u);
-        return sign | (q + ((rest > halfway) || (rest == halfway && (q & 1u)) ? 1u : 0u));
-    }
-    // normal: add rounding bias in the f32 domain, then rebias the exponent
-    const uint32_t lsb = (a >> 13) & 1u;
-    a += 0x0fffu + lsb;
-    return sign | ((a - (112u << 23)) >> 13);
-}
+// The box and build arithmetic -- the f16 codecs, the min / max flavours, the packers, the areas, the Morton pieces -- is pt_bounds.h's,
+// the text the kernels compile.
+using ptbd::bits_of;
+using ptbd::Box; using ptbd::unpack_box; using ptbd::box_degenerate;
+using ptbd::js_min_f; using ptbd::js_max_f; using ptbd::sel_min; using ptbd::sel_max;
 
 // ------------------------------------------------------------------------------------
 // Morton codes + sort (PathTracer.js:411-481).  Doubles throughout, like the JS.
 // Sort key is (code, triangle index); triangles start in index order, so a stable sort on
 // the 30-bit code alone gives the same permutation -> 3-pass LSD radix sort.
 // ------------------------------------------------------------------------------------
-static inline uint32_t spread10(uint32_t v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-static inline uint32_t quantize1023(double x) {    // max(0, min(1023, (x*1023)|0))
-    const double s = x * 1023;
-    if (!(s == s)) return 0;                       // NaN | 0 == 0
-    if (s >= 1023.0) return 1023;
-    if (s <= 0.0) return 0;
-    return uint32_t(int32_t(s));                   // truncation toward zero
-}
 
 void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32_t* tri_index) {
     if (n == 0) return;
@@ -93,7 +37,7 @@ void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32
     for (uint32_t t = 0; t < n; ++t) {
         const float* p = tris + size_t(t) * 9;
         for (int k = 0; k < 3; ++k) {
-            const double c = (double(p[k]) + double(p[3 + k]) + double(p[6 + k])) / 3;
+            const double c = ptbd::centroid_axis(p, k);
             cen[size_t(t) * 3 + k] = c;
             if (c < lo[k]) lo[k] = c;
             if (c > hi[k]) hi[k] = c;
@@ -103,10 +47,9 @@ void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32
     for (int k = 0; k < 3; ++k) { const double d = hi[k] - lo[k]; ext[k] = d > 1e-20 ? d : 1e-20; }
     std::vector<uint32_t> code(n), idxA(n), idxB(n);
     for (uint32_t t = 0; t < n; ++t) {
-        const uint32_t qx = quantize1023((cen[size_t(t) * 3 + 0] - lo[0]) / ext[0]);
-        const uint32_t qy = quantize1023((cen[size_t(t) * 3 + 1] - lo[1]) / ext[1]);
-        const uint32_t qz = quantize1023((cen[size_t(t) * 3 + 2] - lo[2]) / ext[2]);
-        code[t] = (spread10(qx) << 2) | (spread10(qy) << 1) | spread10(qz);
+        uint32_t q[3];
+        for (int k = 0; k < 3; ++k) q[k] = ptbd::quantize1023((cen[size_t(t) * 3 + k] - lo[k]) / ext[k]);
+        code[t] = (ptbd::spread10(q[0]) << 2) | (ptbd::spread10(q[1]) << 1) | ptbd::spread10(q[2]);
         idxA[t] = t;
     }
     uint32_t* src = idxA.data(); uint32_t* dst = idxB.data();
@@ -127,17 +70,20 @@ void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32
 //          greedy child sets; pass 2 walks the indices backwards (children always have larger
 //          pre-order indices than their parent) and unions the already-final child boxes.
 // ------------------------------------------------------------------------------------
-static inline float js_min_f(float a, float b) { if (a < b) return a; if (b < a) return b; return std::signbit(a) ? a : b; }
-static inline float js_max_f(float a, float b) { if (a > b) return a; if (b > a) return b; return std::signbit(a) ? b : a; }
-
-// Surface area of a BVH2 node from its stored f16 box words, decoded exactly: ((dx*dy) + (dy*dz)) + (dz*dx) in f32, no fma
-// (pt_build.hip::node_area2 is the same expression)
-static inline float node_area2(const uint32_t* bvh2, uint32_t node) {
-    const uint32_t* p = bvh2 + 1 + size_t(node) * kNode2Stride;
-    const float dx = half_to_float(p[1] >> 16) - half_to_float(p[0] & 0xffffu);
-    const float dy = half_to_float(p[2] & 0xffffu) - half_to_float(p[0] >> 16);
-    const float dz = half_to_float(p[2] >> 16) - half_to_float(p[1] & 0xffffu);
-    return ((dx * dy) + (dy * dz)) + (dz * dx);
+// the union of the valid children's boxes of BVH4 node `node` in slot order (m: children at or beyond m are skipped), js_min_f / js_max_f
+// from (+inf, -inf); returns the number of children taken
+static uint32_t union_children4(const uint32_t* bvh4, uint32_t node, uint32_t m, Box& u) {
+    const uint32_t* r = bvh4 + 1 + size_t(node) * kNode4Stride;
+    u = {{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+    uint32_t valid = 0;
+    for (int s = 0; s < 4; ++s) {
+        const uint32_t c = r[3 + s];
+        if (c == kInvalid || c >= m) continue;
+        ++valid;
+        const Box b = unpack_box(bvh4 + 1 + size_t(c) * kNode4Stride);
+        for (int k = 0; k < 3; ++k) { u.mn[k] = js_min_f(u.mn[k], b.mn[k]); u.mx[k] = js_max_f(u.mx[k], b.mx[k]); }
+    }
+    return valid;
 }
 
 bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint32_t>& out, std::string& err) {
@@ -182,7 +128,7 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std
                 if (kid[i] >= nn2) { err = "BVH2 child index out of range"; return false; }
                 if (leaf(kid[i])) continue;
                 if (!by_area) { pos = i; break; }
-                const float a = node_area2(bvh2, kid[i]);
+                const float a = ptbd::node_area2(word(kid[i], 0), word(kid[i], 1), word(kid[i], 2));
                 if (pos == nk || a > best) { pos = i; best = a; }
             }
             if (pos == nk) break;
@@ -199,19 +145,9 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std
     for (uint32_t id = count4; id-- > 0;) {
         const size_t base = 1 + size_t(id) * kNode4Stride;
         if (out[base + 7] & kLeafFlag) continue;
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int s = 0; s < 4; ++s) {
-            const uint32_t c = out[base + 3 + s];
-            if (c == kInvalid) continue;
-            const size_t cb = 1 + size_t(c) * kNode4Stride;
-            const uint32_t w0 = out[cb], w1 = out[cb + 1], w2 = out[cb + 2];
-            const float cmn[3] = {half_to_float(w0 & 0xffffu), half_to_float(w0 >> 16), half_to_float(w1 & 0xffffu)};
-            const float cmx[3] = {half_to_float(w1 >> 16), half_to_float(w2 & 0xffffu), half_to_float(w2 >> 16)};
-            for (int k = 0; k < 3; ++k) { mn[k] = js_min_f(mn[k], cmn[k]); mx[k] = js_max_f(mx[k], cmx[k]); }
-        }
-        out[base + 0] = float_to_half_trunc(mn[0]) | (float_to_half_trunc(mn[1]) << 16);
-        out[base + 1] = float_to_half_trunc(mn[2]) | (float_to_half_trunc(mx[0]) << 16);
-        out[base + 2] = float_to_half_trunc(mx[1]) | (float_to_half_trunc(mx[2]) << 16);
+        Box u;
+        union_children4(out.data(), id, kInvalid, u);
+        ptbd::pack_trunc(u, &out[base]);
     }
     return true;
 }
@@ -224,30 +160,22 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std
 // the survivors are compacted in order.  Then the LBVH's leaf words and the reference's refit (BVHBuilder.wgsl:242-306).
 // ------------------------------------------------------------------------------------
 namespace {
-struct Box { float mn[3], mx[3]; };
-inline float sel_min(float a, float b) { return b < a ? b : a; }       // the same expression on the device
-inline float sel_max(float a, float b) { return b > a ? b : a; }
 inline Box box_union(const Box& a, const Box& b) {                    // a = the cluster at the lower position
     Box u;
     for (int k = 0; k < 3; ++k) { u.mn[k] = sel_min(a.mn[k], b.mn[k]); u.mx[k] = sel_max(a.mx[k], b.mx[k]); }
     return u;
 }
-inline float box_area(const Box& b) {                                 // NaN counts as +inf
-    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
-    const float a = ((dx * dy) + (dy * dz)) + (dz * dx);
-    return a == a ? a : INFINITY;
+inline float union_area(const Box& a, const Box& b) {                 // PLOC's key
+    return ptbd::ploc_area(ptbd::union_extent(a.mx[0], b.mx[0], a.mn[0], b.mn[0]), ptbd::union_extent(a.mx[1], b.mx[1], a.mn[1], b.mn[1]),
+                           ptbd::union_extent(a.mx[2], b.mx[2], a.mn[2], b.mn[2]));
 }
-// BVHBuilder.wgsl:63-102 (pt_kernels.hip::step_f16 / store_bounds2): round to f16, then one f16 step outwards
-inline uint32_t step_f16(float v, bool up) {
-    const uint32_t bits = float_to_half_rtne(v);
-    uint32_t ord = (bits & 0x8000u) ? ((~bits) & 0xFFFFu) : (bits ^ 0x8000u);
-    ord = up ? ord + 1u : ord - 1u;
-    return ((ord & 0x8000u) ? (ord ^ 0x8000u) : ((~ord) & 0xFFFFu)) & 0xFFFFu;
-}
-inline void store_bounds2(uint32_t* p, const float mn[3], const float mx[3]) {
-    p[0] = step_f16(mn[0], false) | (step_f16(mn[1], false) << 16);
-    p[1] = step_f16(mn[2], false) | (step_f16(mx[0], true) << 16);
-    p[2] = step_f16(mx[1], true) | (step_f16(mx[2], true) << 16);
+// the box of BVH2 nodes l and r united by `lo` / `hi` (js_min_f / js_max_f, or wmin / wmax), stepped outwards into node p
+template <class Min, class Max>
+inline void union_bounds2(uint32_t* p, const uint32_t* l, const uint32_t* r, Min lo, Max hi) {
+    const Box a = unpack_box(l), b = unpack_box(r);
+    Box u;
+    for (int k = 0; k < 3; ++k) { u.mn[k] = lo(a.mn[k], b.mn[k]); u.mx[k] = hi(a.mx[k], b.mx[k]); }
+    ptbd::store_bounds2(u, p);
 }
 } // namespace
 
@@ -278,7 +206,7 @@ bool build_bvh2_ploc(const float* tris, uint32_t n, std::vector<uint32_t>& out, 
             for (uint32_t j = lo; j <= hi; ++j) {
                 if (j == i) continue;
                 const uint32_t a = std::min(i, j), b = std::max(i, j);
-                const float d = box_area(box_union(box[a], box[b]));
+                const float d = union_area(box[a], box[b]);
                 if (bj == kInvalid || d < bd || (d == bd && (a < blo || (a == blo && b < bhi)))) { bd = d; bj = j; blo = a; bhi = b; }
             }
             nn[i] = bj;
@@ -304,27 +232,21 @@ bool build_bvh2_ploc(const float* tris, uint32_t n, std::vector<uint32_t>& out, 
         count = kept;
         std::swap(box, box2); std::swap(node, node2);
     }
-    // leaves: writeLeaf2 (BVHBuilder.wgsl:124-132, 278-306), exactly the LBVH's leaf words; WGSL min / max as the device's
-    // v_min_f32 / v_max_f32 compute them, -0 below +0 (js_min_f / js_max_f above)
+    // leaves: writeLeaf2 (BVHBuilder.wgsl:124-132, 278-306), the LBVH's leaf words; min / max here are js_min_f / js_max_f over
+    // (a, b), c (pt_bounds.h names the pair: lbvh2_leaves_kernel uses wmin / wmax over a, (b, c), equal except on NaN vertices)
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t ti = tri_index[k];
         const float* t = tris + size_t(ti) * 9;
-        float mn[3], mx[3];
-        for (int a = 0; a < 3; ++a) { mn[a] = js_min_f(js_min_f(t[a], t[3 + a]), t[6 + a]); mx[a] = js_max_f(js_max_f(t[a], t[3 + a]), t[6 + a]); }
+        Box b;
+        for (int a = 0; a < 3; ++a) { b.mn[a] = js_min_f(js_min_f(t[a], t[3 + a]), t[6 + a]); b.mx[a] = js_max_f(js_max_f(t[a], t[3 + a]), t[6 + a]); }
         uint32_t* p = out.data() + 1 + size_t(internal + k) * kNode2Stride;
-        store_bounds2(p, mn, mx);
+        ptbd::store_bounds2(b, p);
         p[3] = 0u; p[4] = 0u; p[5] = kLeafFlag | (ti & 0x7fffffffu);
     }
     // refit (propagateUp, BVHBuilder.wgsl:242-275): children have larger ids than their parent, so descending ids see final children
     for (uint32_t id = internal; id-- > 0;) {
         uint32_t* p = out.data() + 1 + size_t(id) * kNode2Stride;
-        const uint32_t* l = out.data() + 1 + size_t(p[3]) * kNode2Stride;
-        const uint32_t* r = out.data() + 1 + size_t(p[4]) * kNode2Stride;
-        const float mn[3] = {js_min_f(half_to_float(l[0] & 0xffffu), half_to_float(r[0] & 0xffffu)), js_min_f(half_to_float(l[0] >> 16), half_to_float(r[0] >> 16)),
-                             js_min_f(half_to_float(l[1] & 0xffffu), half_to_float(r[1] & 0xffffu))};
-        const float mx[3] = {js_max_f(half_to_float(l[1] >> 16), half_to_float(r[1] >> 16)), js_max_f(half_to_float(l[2] & 0xffffu), half_to_float(r[2] & 0xffffu)),
-                             js_max_f(half_to_float(l[2] >> 16), half_to_float(r[2] >> 16))};
-        store_bounds2(p, mn, mx);
+        union_bounds2(p, out.data() + 1 + size_t(p[3]) * kNode2Stride, out.data() + 1 + size_t(p[4]) * kNode2Stride, js_min_f, js_max_f);
     }
     return true;
 }
@@ -365,13 +287,6 @@ bool promote_to_bvh4_wide(const uint32_t* bvh2, uint64_t words, std::vector<uint
 // ------------------------------------------------------------------------------------
 // Device layouts
 // ------------------------------------------------------------------------------------
-static inline bool box_degenerate(uint32_t w0, uint32_t w1, uint32_t w2) {
-    // any(mn > mx), renderer.wgsl:133,244,291 (false when a NaN is involved, like WGSL's >)
-    return half_to_float(w0 & 0xffffu) > half_to_float(w1 >> 16) ||
-           half_to_float(w0 >> 16) > half_to_float(w2 & 0xffffu) ||
-           half_to_float(w1 & 0xffffu) > half_to_float(w2 >> 16);
-}
-
 bool build_wide_bvh(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uint32_t node_base16, WideBvh& out, std::string& err) {
     out = WideBvh();
     if (words < 1) { err = "empty BVH buffer"; return false; }
@@ -428,15 +343,7 @@ bool build_wide_bvh(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uin
 // Refit in place (host twins of pt_refit.hip)
 // ------------------------------------------------------------------------------------
 namespace {
-// the device's v_min_f32 / v_max_f32 (pt_device.h::wmin / wmax): a NaN operand loses, -0 lies below +0
-inline float wmin_h(float a, float b) { if (a != a) return b; if (b != b) return a; return js_min_f(a, b); }
-inline float wmax_h(float a, float b) { if (a != a) return b; if (b != b) return a; return js_max_f(a, b); }
-// the leaf rule (BVHBuilder.wgsl:278-306): min / max of the three vertices, associated as the kernels do, stepped outwards
-inline void leaf_box_words(const float* t, uint32_t* p) {
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = wmin_h(t[a], wmin_h(t[3 + a], t[6 + a])); mx[a] = wmax_h(t[a], wmax_h(t[3 + a], t[6 + a])); }
-    store_bounds2(p, mn, mx);
-}
+using ptbd::wmin; using ptbd::wmax;     // the device's v_min_f32 / v_max_f32, spelt out for the host
 // reachable nodes of a reference-layout BVH4 in pre-order (build_wide_bvh's walk)
 bool reachable4(const uint32_t* bvh4, uint64_t words, std::vector<uint32_t>& order, std::string& err) {
     order.clear();
@@ -462,14 +369,6 @@ bool reachable4(const uint32_t* bvh4, uint64_t words, std::vector<uint32_t>& ord
     }
     return true;
 }
-inline double half_area(const uint32_t* r) {
-    const double x0 = half_to_float(r[0] & 0xffffu), y0 = half_to_float(r[0] >> 16), z0 = half_to_float(r[1] & 0xffffu);
-    const double x1 = half_to_float(r[1] >> 16), y1 = half_to_float(r[2] & 0xffffu), z1 = half_to_float(r[2] >> 16);
-    if (!(x0 <= x1 && y0 <= y1 && z0 <= z1)) return 0.0;            // degenerate, or a NaN
-    const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
-    const double a = (dx * dy + dy * dz) + dz * dx;
-    return a == a ? a : 0.0;                                        // inf * 0
-}
 } // namespace
 
 bool refit_bvh4(const float* tris, uint32_t n, uint32_t* bvh4, uint64_t words, std::string& err) {
@@ -480,24 +379,11 @@ bool refit_bvh4(const float* tris, uint32_t n, uint32_t* bvh4, uint64_t words, s
         uint32_t* r = bvh4 + 1 + size_t(order[k]) * kNode4Stride;
         if (r[7] & kLeafFlag) {
             const uint32_t t = r[7] & 0x7fffffffu;
-            if (t < n) leaf_box_words(tris + size_t(t) * 9, r);
+            if (t < n) ptbd::leaf_box_words(tris + size_t(t) * 9, r);
             continue;
         }
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        uint32_t valid = 0;
-        for (int s = 0; s < 4; ++s) {
-            const uint32_t c = r[3 + s];
-            if (c == kInvalid || c >= m) continue;
-            ++valid;
-            const uint32_t* cr = bvh4 + 1 + size_t(c) * kNode4Stride;
-            const float cmn[3] = {half_to_float(cr[0] & 0xffffu), half_to_float(cr[0] >> 16), half_to_float(cr[1] & 0xffffu)};
-            const float cmx[3] = {half_to_float(cr[1] >> 16), half_to_float(cr[2] & 0xffffu), half_to_float(cr[2] >> 16)};
-            for (int a = 0; a < 3; ++a) { mn[a] = js_min_f(mn[a], cmn[a]); mx[a] = js_max_f(mx[a], cmx[a]); }
-        }
-        if (!valid) continue;
-        r[0] = float_to_half_trunc(mn[0]) | (float_to_half_trunc(mn[1]) << 16);
-        r[1] = float_to_half_trunc(mn[2]) | (float_to_half_trunc(mx[0]) << 16);
-        r[2] = float_to_half_trunc(mx[1]) | (float_to_half_trunc(mx[2]) << 16);
+        Box u;
+        if (union_children4(bvh4, order[k], m, u)) ptbd::pack_trunc(u, r);
     }
     return true;
 }
@@ -519,19 +405,14 @@ bool refit_bvh2(const float* tris, uint32_t n, uint32_t* bvh2, uint64_t words, s
         uint32_t* p = rec(i);
         if (!(p[5] & kLeafFlag)) continue;
         const uint32_t t = p[5] & 0x7fffffffu;
-        if (t < n) leaf_box_words(tris + size_t(t) * 9, p);
+        if (t < n) ptbd::leaf_box_words(tris + size_t(t) * 9, p);
         for (uint32_t cur = i;;) {                                  // propagateUp (BVHBuilder.wgsl:242-275): the second child to arrive unions
             const uint32_t par = parent[cur];
             if (par >= nn2) break;
             if (arrive[par]++ == 0u) break;
             arrive[par] = 0u;
             uint32_t* pp = rec(par);
-            const uint32_t* l = rec(pp[3]); const uint32_t* r = rec(pp[4]);
-            const float mn[3] = {wmin_h(half_to_float(l[0] & 0xffffu), half_to_float(r[0] & 0xffffu)), wmin_h(half_to_float(l[0] >> 16), half_to_float(r[0] >> 16)),
-                                 wmin_h(half_to_float(l[1] & 0xffffu), half_to_float(r[1] & 0xffffu))};
-            const float mx[3] = {wmax_h(half_to_float(l[1] >> 16), half_to_float(r[1] >> 16)), wmax_h(half_to_float(l[2] & 0xffffu), half_to_float(r[2] & 0xffffu)),
-                                 wmax_h(half_to_float(l[2] >> 16), half_to_float(r[2] >> 16))};
-            store_bounds2(pp, mn, mx);
+            union_bounds2(pp, rec(pp[3]), rec(pp[4]), wmin, wmax);
             cur = par;
         }
     }
@@ -543,12 +424,12 @@ bool bvh4_cost(const uint32_t* bvh4, uint64_t words, double& cost, std::string& 
     std::vector<uint32_t> order;
     if (!reachable4(bvh4, words, order, err)) return false;
     if (order.empty()) return true;
-    const double root = half_area(bvh4 + 1);
+    const double root = ptbd::half_area(bvh4[1], bvh4[2], bvh4[3]);
     if (!(root > 0.0) || root == double(INFINITY)) return true;
     std::sort(order.begin(), order.end());
     for (uint32_t i : order) {
         const uint32_t* r = bvh4 + 1 + size_t(i) * kNode4Stride;
-        if (!(r[7] & kLeafFlag)) cost += half_area(r) / root;
+        if (!(r[7] & kLeafFlag)) cost += ptbd::half_area(r[0], r[1], r[2]) / root;
     }
     return true;
 }
@@ -614,18 +495,13 @@ inline float record_uv_d2(const TriRecord& r, const float p[3], float& u, float&
     ptcp::closest_uv(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
     return ptcp::closest_d2(ax, ay, az, r.axis[0][1], r.axis[1][1], r.axis[2][1], r.axis[0][2], r.axis[1][2], r.axis[2][2], u, v);
 }
-// the six halves of a packed box: w = {mn.x | mn.y << 16, mn.z | mx.x << 16, mx.y | mx.z << 16}
-inline Box unpack_box(const uint32_t w[3]) {
-    return {{half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)},
-            {half_to_float(w[1] >> 16), half_to_float(w[2] & 0xffffu), half_to_float(w[2] >> 16)}};
-}
 // the record of an item that found nothing: {+inf bits, 0xFFFFFFFF, 0, 0}
 inline void write_miss(uint32_t* o) { o[0] = 0x7F800000u; o[1] = kInvalid; o[2] = 0u; o[3] = 0u; }
 // pt_pointquery.hip::box_bound2: per axis max(mn - (p + s), (p - s) - mx, 0), each difference rounded once
 inline float box_bound2_h(const float hi[3], const float lo[3], const uint32_t w[3]) {
     const Box b = unpack_box(w);
     float g[3];
-    for (int k = 0; k < 3; ++k) g[k] = wmax_h(wmax_h(b.mn[k] - hi[k], lo[k] - b.mx[k]), 0.0f);
+    for (int k = 0; k < 3; ++k) g[k] = wmax(wmax(b.mn[k] - hi[k], lo[k] - b.mx[k]), 0.0f);
     return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
 }
 
@@ -1268,10 +1144,10 @@ inline bool slab_h(const RayH& r, const uint32_t w[3], float best, float& tmin_o
     const Box b = unpack_box(w);
     float t1[3], t2[3];
     for (int k = 0; k < 3; ++k) { t1[k] = (b.mn[k] - r.o[k]) * r.inv[k]; t2[k] = (b.mx[k] - r.o[k]) * r.inv[k]; }
-    const float tmin = wmax_h(wmax_h(wmin_h(t1[0], t2[0]), wmin_h(t1[1], t2[1])), wmin_h(t1[2], t2[2]));
-    const float tmax = wmin_h(wmin_h(wmax_h(t1[0], t2[0]), wmax_h(t1[1], t2[1])), wmax_h(t1[2], t2[2]));
+    const float tmin = wmax(wmax(wmin(t1[0], t2[0]), wmin(t1[1], t2[1])), wmin(t1[2], t2[2]));
+    const float tmax = wmin(wmin(wmax(t1[0], t2[0]), wmax(t1[1], t2[1])), wmax(t1[2], t2[2]));
     tmin_out = tmin;
-    return (tmax >= wmax_h(tmin, 0.0f)) && (tmin < best);
+    return (tmax >= wmax(tmin, 0.0f)) && (tmin < best);
 }
 // ptry::tri_hit and ptry::hit_uv on a triangle record
 inline bool record_hit(const RayH& r, const TriRecord& rec, float& t) {
@@ -1295,7 +1171,7 @@ void walk_ray_h(const PointWalk& W, const RayH& r, float best, WalkCounters& cnt
 // a PtRay record (pt_rays.h::load_ray, ray_traced): whether the ray is walked, and then `best` = min(t_max, kInfT)
 inline bool load_ray_h(const float* q, RayH& r, float& best) {
     for (int k = 0; k < 3; ++k) { r.o[k] = q[k]; r.d[k] = q[4 + k]; r.inv[k] = ptry::safe_inv(q[4 + k]); }
-    best = wmin_h(q[3], ptry::kInfT);
+    best = wmin(q[3], ptry::kInfT);
     return ptry::ray_walked(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], q[3]);
 }
 // every crossing of a walked ray below `best`, handed to accept(t, triangle) in visit order (or in index order with brute force)

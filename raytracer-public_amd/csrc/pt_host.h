@@ -4,19 +4,14 @@
 #include <string>
 #include <vector>
 
+#include "pt_bounds.h"
+
 namespace pt {
 
-constexpr uint32_t kNode2Stride = 6;            // BVHBuilder.wgsl:5
-constexpr uint32_t kNode4Stride = 8;            // renderer.wgsl:10
-constexpr uint32_t kLeafFlag    = 0x80000000u;  // renderer.wgsl:11
-constexpr uint32_t kInvalid     = 0xFFFFFFFFu;  // renderer.wgsl:12
-constexpr uint32_t kEmptyBox0 = 0x7C007C00u, kEmptyBox1 = 0xFC007C00u, kEmptyBox2 = 0xFC00FC00u;   // wide layout: box words of an empty or degenerate child slot, mn = +inf, mx = -inf (f16)
-constexpr uint32_t kDegenerate  = 0xFFFFFFFEu;  // wide layout only: a child the reference fetches and then rejects for every ray (renderer.wgsl:291)
-
-// ---- f16 codec -------------------------------------------------------------------
-float    half_to_float(uint32_t h);             // exact widening (PathTracer.js:16-40)
-uint32_t float_to_half_trunc(float v);          // PathTracer.js:42-51 semantics
-uint32_t float_to_half_rtne(float v);           // pinned rounding of WGSL pack2x16float
+// the layout constants and the packed leaf reference are pt_bounds.h's, which the kernels compile as well
+using ptbd::kNode2Stride; using ptbd::kNode4Stride; using ptbd::kLeafFlag; using ptbd::kInvalid; using ptbd::kDegenerate;
+using ptbd::kEmptyBox0; using ptbd::kEmptyBox1; using ptbd::kEmptyBox2;
+using ptbd::packed_leaf_ref;
 
 // ---- scene build -----------------------------------------------------------------
 void morton_codes_sorted(const float* tris, uint32_t n, uint32_t* morton, uint32_t* tri_index);
@@ -26,8 +21,8 @@ bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, std::vector<uint3
 // largest surface area instead of the first one; reads the internal BVH2 bounds, so bvh2 must be a complete (refitted) BVH2
 bool collapse_to_bvh4(const uint32_t* bvh2, uint32_t num_tris, bool by_area, std::vector<uint32_t>& out, std::string& err);
 // PLOC BVH2 (PT_ACCEL_PLOC) in the reference's BVH2 layout: u32[1 + 6(2N-1)], root 0, leaves = the LBVH's leaf words,
-// internal bounds = the reference's bottom-up refit on this topology.  The device build (pt_build.hip) equals it word for word.
-constexpr uint32_t kPlocRadius = 16;
+// internal bounds = the reference's bottom-up refit on this topology.  The device build (pt_build.hip) gives the same words.
+using ptbd::kPlocRadius;
 bool build_bvh2_ploc(const float* tris, uint32_t n, std::vector<uint32_t>& out, std::string& err);
 bool promote_to_bvh4_wide(const uint32_t* bvh2, uint64_t words, std::vector<uint32_t>& out, std::string& err);
 
@@ -39,18 +34,12 @@ bool promote_to_bvh4_wide(const uint32_t* bvh2, uint64_t words, std::vector<uint
 struct WideNode {
     struct Child {
         uint32_t box[3];
-        uint32_t ref;  // kInvalid = empty slot; kDegenerate = examined, never entered; else a packed reference (below)
+        uint32_t ref;  // kInvalid = empty slot; kDegenerate = examined, never entered; else a packed reference (pt_bounds.h)
     } child[4];
 };
 static_assert(sizeof(WideNode) == 64, "WideNode must be 64 bytes");
 
-// Packed references: the traversal gathers triangle records (64 B) and wide nodes (64 B) from ONE arena, so a child reference
-// is the record's position in it in 16-byte units -- `ref << 4` is the byte offset, and the shift drops the leaf flag:
-//   leaf        kLeafFlag | 4 * tri                 (triangle record `tri` at byte 64 * tri)
-//   wide node   node_base16 + 4 * index             (node `index` at byte 16 * node_base16 + 64 * index)
-// A leaf whose triangle index is >= num_tris (the reference enters such a leaf and tests nothing, renderer.wgsl:262) points at
-// the all-zero record behind the last triangle (index num_tris: never hit, |det| < eps).
-inline uint32_t packed_leaf_ref(uint32_t tri, uint32_t num_tris) { return kLeafFlag | (4u * (tri < num_tris ? tri : num_tris)); }
+// (child references are the packed references of pt_bounds.h)
 struct WideBvh {
     std::vector<WideNode> nodes;
     uint32_t root_ref = kInvalid;      // same encoding as WideNode::ref; kInvalid = empty BVH
@@ -65,7 +54,7 @@ struct WideBvh {
 // no ray enters but which counts as an examined record, exactly as in the reference.
 bool build_wide_bvh(const uint32_t* bvh4, uint64_t words, uint32_t num_tris, uint32_t node_base16, WideBvh& out, std::string& err);
 
-// ---- refit in place (pt_update_triangles; host twins of pt_refit.hip, word for word) ------------------------------------------
+// ---- refit in place (pt_update_triangles; host twins of pt_refit.hip, the arithmetic of pt_bounds.h) ---------------------------
 // New boxes for an unchanged topology.  BVH4: the nodes reachable from the root (the walk of build_wide_bvh; a node reachable
 // twice is an error); a leaf whose triangle index is >= n, an internal node without a valid child and every unreachable node keep
 // their words.  BVH2: every leaf, and every internal node both of whose children (two different nodes in range) are refitted.

@@ -347,16 +347,12 @@ __global__ __launch_bounds__(256) void render_packet_kernel(const RenderArgs A) 
 }
 
 // ------------------------------------------------------------------------------------
-// LBVH2 build (BVHBuilder.wgsl).  f32 -> f16 is round-to-nearest-even (v_cvt_f16_f32): step_f16, pt_bounds.h.
+// LBVH2 build (BVHBuilder.wgsl).  The words of a box are pt_bounds.h's (store_bounds2, leaf_box_words); how they reach memory is decided here.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ void store_bounds2(uint32_t* bvh2, uint32_t node, F3 mn, F3 mx) {   // BVHBuilder.wgsl:83-102
-    uint32_t* p = bvh2 + 1 + (size_t)node * 6;
-    const uint32_t w0 = step_f16(mn.x, false) | (step_f16(mn.y, false) << 16);
-    const uint32_t w1 = step_f16(mn.z, false) | (step_f16(mx.x, true) << 16);
-    const uint32_t w2 = step_f16(mx.y, true) | (step_f16(mx.z, true) << 16);
-    __hip_atomic_store(p + 0, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 2, w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ void store_words2(uint32_t* p, const uint32_t w[3]) {
+    __hip_atomic_store(p + 0, w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + 1, w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + 2, w[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ int lbvh_delta(const uint32_t* __restrict__ morton, int i, int j, int n) {   // BVHBuilder.wgsl:134-149
     if (j < 0 || j >= n) return -1;
@@ -408,12 +404,10 @@ __global__ __launch_bounds__(256) void lbvh2_leaves_kernel(uint32_t* bvh2, const
     const uint32_t node = internal + leaf;
     if (LEAVES) {
         const uint32_t ti = tri_index[leaf];
-        const float* tp = tris + (size_t)ti * 9;
-        const F3 v0 = f3(tp[0], tp[1], tp[2]), v1 = f3(tp[3], tp[4], tp[5]), v2 = f3(tp[6], tp[7], tp[8]);
-        const F3 mn = f3(wmin(v0.x, wmin(v1.x, v2.x)), wmin(v0.y, wmin(v1.y, v2.y)), wmin(v0.z, wmin(v1.z, v2.z)));
-        const F3 mx = f3(wmax(v0.x, wmax(v1.x, v2.x)), wmax(v0.y, wmax(v1.y, v2.y)), wmax(v0.z, wmax(v1.z, v2.z)));
-        store_bounds2(bvh2, node, mn, mx);
         uint32_t* p = bvh2 + 1 + (size_t)node * 6;
+        uint32_t w[3];
+        ptbd::leaf_box_words(tris + (size_t)ti * 9, w);
+        store_words2(p, w);
         p[3] = 0u; p[4] = 0u; p[5] = kLeaf | (ti & 0x7fffffffu);
     }
     if (!REFIT || internal == 0u) return;
@@ -435,9 +429,12 @@ __global__ __launch_bounds__(256) void lbvh2_leaves_kernel(uint32_t* bvh2, const
         const uint32_t* lp = bvh2 + 1 + (size_t)l * 6; const uint32_t* rp = bvh2 + 1 + (size_t)r * 6;
         const uint32_t l0 = __hip_atomic_load(lp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), l1 = __hip_atomic_load(lp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), l2 = __hip_atomic_load(lp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t r0 = __hip_atomic_load(rp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r1 = __hip_atomic_load(rp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r2 = __hip_atomic_load(rp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const F3 umn = f3(wmin(half_lo(l0), half_lo(r0)), wmin(half_hi(l0), half_hi(r0)), wmin(half_lo(l1), half_lo(r1)));
-        const F3 umx = f3(wmax(half_hi(l1), half_hi(r1)), wmax(half_lo(l2), half_lo(r2)), wmax(half_hi(l2), half_hi(r2)));
-        store_bounds2(bvh2, par, umn, umx);
+        const ptbd::Box u = {{wmin(half_lo(l0), half_lo(r0)), wmin(half_hi(l0), half_hi(r0)), wmin(half_lo(l1), half_lo(r1))},
+                             {wmax(half_hi(l1), half_hi(r1)), wmax(half_lo(l2), half_lo(r2)), wmax(half_hi(l2), half_hi(r2))}};
+        uint32_t* q = bvh2 + 1 + (size_t)par * 6;
+        uint32_t w[3];
+        ptbd::store_bounds2(u, w);
+        store_words2(q, w);
         cur = par;
     }
 }

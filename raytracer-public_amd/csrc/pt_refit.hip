@@ -17,7 +17,7 @@
 // counters need no reset between updates.
 //
 // The climb needs what the reference's BVH4 does not store: parent links.  A prepare pass derives them once per installed tree.
-// Host twins, word for word: pt_host.cpp (refit_bvh4, refit_bvh2, bvh4_cost).
+// Host twins: pt_host.cpp (refit_bvh4, refit_bvh2, bvh4_cost), on the arithmetic the kernels compile, pt_bounds.h.
 #include "pt_kernels.h"
 #include "pt_device.h"
 #include "pt_bounds.h"
@@ -30,16 +30,6 @@ inline uint32_t blocks(uint32_t n) { return (n + 255u) / 256u; }
 
 __device__ __forceinline__ uint32_t load_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void store_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the leaf rule: the words store_bounds2 (pt_kernels.hip) writes for the triangle's box
-__device__ __forceinline__ void leaf_box_words(const float* __restrict__ tp, uint32_t& w0, uint32_t& w1, uint32_t& w2) {
-    const F3 v0 = f3(tp[0], tp[1], tp[2]), v1 = f3(tp[3], tp[4], tp[5]), v2 = f3(tp[6], tp[7], tp[8]);
-    const F3 mn = f3(wmin(v0.x, wmin(v1.x, v2.x)), wmin(v0.y, wmin(v1.y, v2.y)), wmin(v0.z, wmin(v1.z, v2.z)));
-    const F3 mx = f3(wmax(v0.x, wmax(v1.x, v2.x)), wmax(v0.y, wmax(v1.y, v2.y)), wmax(v0.z, wmax(v1.z, v2.z)));
-    w0 = step_f16(mn.x, false) | (step_f16(mn.y, false) << 16);
-    w1 = step_f16(mn.z, false) | (step_f16(mx.x, true) << 16);
-    w2 = step_f16(mx.y, true) | (step_f16(mx.z, true) << 16);
-}
 
 // ------------------------------------------------------------------------------------
 // prepare, for a tree this library built itself: every node is reachable, ids are the pre-order, wide_index is the internal scan
@@ -60,8 +50,7 @@ __global__ __launch_bounds__(256) void refit_prepare4_kernel(const uint32_t* __r
         const uint32_t c = r[3 + s];
         if (c == kInvalidRef || c >= m) continue;
         const uint32_t w7 = bvh4[1 + (size_t)c * 8 + 7];
-        const uint32_t tri = w7 & 0x7fffffffu;
-        ref[s] = (w7 & kLeaf) ? (kLeaf | (4u * (tri < num_tris ? tri : num_tris))) : node_base16 + 4u * wide_index[c];     // packed references (pt_host.h)
+        ref[s] = (w7 & kLeaf) ? ptbd::packed_leaf_ref(w7 & 0x7fffffffu, num_tris) : node_base16 + 4u * wide_index[c];
         up[c] = make_uint2(i, s);
         ++valid;
     }
@@ -94,19 +83,20 @@ __device__ __forceinline__ void finish_node(uint32_t* bvh4, uint32_t node, uint4
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if (ref[s] == kInvalidRef) continue;
+            using ptbd::js_min_f; using ptbd::js_max_f; using ptbd::half_exact;
             const uint32_t b0 = cw[s][0], b1 = cw[s][1], b2 = cw[s][2];
             mn[0] = js_min_f(mn[0], half_exact(b0 & 0xffffu)); mn[1] = js_min_f(mn[1], half_exact(b0 >> 16)); mn[2] = js_min_f(mn[2], half_exact(b1 & 0xffffu));
             mx[0] = js_max_f(mx[0], half_exact(b1 >> 16)); mx[1] = js_max_f(mx[1], half_exact(b2 & 0xffffu)); mx[2] = js_max_f(mx[2], half_exact(b2 >> 16));
         }
-        store_agent(rec + 0, half_trunc(mn[0]) | (half_trunc(mn[1]) << 16));
-        store_agent(rec + 1, half_trunc(mn[2]) | (half_trunc(mx[0]) << 16));
-        store_agent(rec + 2, half_trunc(mx[1]) | (half_trunc(mx[2]) << 16));
+        store_agent(rec + 0, ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 0));
+        store_agent(rec + 1, ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 1));
+        store_agent(rec + 2, ptbd::pack_trunc_word(mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], 2));
     }
     if (WIDE) {
         uint4 o[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const bool degenerate = ref[s] != kInvalidRef && box_degenerate(cw[s][0], cw[s][1], cw[s][2]);
+            const bool degenerate = ref[s] != kInvalidRef && ptbd::box_degenerate(cw[s][0], cw[s][1], cw[s][2]);
             o[s] = degenerate ? make_uint4(kEmptyBox0, kEmptyBox1, kEmptyBox2, kDegenerateRef) : make_uint4(cw[s][0], cw[s][1], cw[s][2], ref[s]);
         }
         wide_rec[0] = o[0]; wide_rec[1] = o[1]; wide_rec[2] = o[2]; wide_rec[3] = o[3];     // child-major (pt_host.h::WideNode)
@@ -125,9 +115,9 @@ __global__ __launch_bounds__(256) void refit4_kernel(const float* __restrict__ t
         uint32_t* rec = bvh4 + 1 + (size_t)i * 8;
         const uint32_t t = rec[7] & 0x7fffffffu;
         if (t < num_tris) {                                     // a leaf beyond the triangle count keeps its words
-            uint32_t w0, w1, w2;
-            leaf_box_words(tris + (size_t)t * 9, w0, w1, w2);
-            store_agent(rec + 0, w0); store_agent(rec + 1, w1); store_agent(rec + 2, w2);
+            uint32_t w[3];
+            ptbd::leaf_box_words(tris + (size_t)t * 9, w);
+            store_agent(rec + 0, w[0]); store_agent(rec + 1, w[1]); store_agent(rec + 2, w[2]);
         }
     }
     uint32_t cur = i;
@@ -176,9 +166,9 @@ __global__ __launch_bounds__(256) void refit2_kernel(const float* __restrict__ t
     if (!(w5 & kLeaf)) return;
     const uint32_t t = w5 & 0x7fffffffu;
     if (t < num_tris) {
-        uint32_t w0, w1, w2;
-        leaf_box_words(tris + (size_t)t * 9, w0, w1, w2);
-        store_agent(p + 0, w0); store_agent(p + 1, w1); store_agent(p + 2, w2);
+        uint32_t w[3];
+        ptbd::leaf_box_words(tris + (size_t)t * 9, w);
+        store_agent(p + 0, w[0]); store_agent(p + 1, w[1]); store_agent(p + 2, w[2]);
     }
     uint32_t cur = i;
     for (;;) {
@@ -193,27 +183,18 @@ __global__ __launch_bounds__(256) void refit2_kernel(const float* __restrict__ t
         const uint32_t l0 = load_agent(lp + 0), l1 = load_agent(lp + 1), l2 = load_agent(lp + 2);
         const uint32_t r0 = load_agent(rp + 0), r1 = load_agent(rp + 1), r2 = load_agent(rp + 2);
         // propagateUp (BVHBuilder.wgsl:242-275): the union, stepped outwards once more by store_bounds2
-        const F3 umn = f3(wmin(half_lo(l0), half_lo(r0)), wmin(half_hi(l0), half_hi(r0)), wmin(half_lo(l1), half_lo(r1)));
-        const F3 umx = f3(wmax(half_hi(l1), half_hi(r1)), wmax(half_lo(l2), half_lo(r2)), wmax(half_hi(l2), half_hi(r2)));
-        store_agent(pp + 0, step_f16(umn.x, false) | (step_f16(umn.y, false) << 16));
-        store_agent(pp + 1, step_f16(umn.z, false) | (step_f16(umx.x, true) << 16));
-        store_agent(pp + 2, step_f16(umx.y, true) | (step_f16(umx.z, true) << 16));
+        const ptbd::Box u = {{wmin(half_lo(l0), half_lo(r0)), wmin(half_hi(l0), half_hi(r0)), wmin(half_lo(l1), half_lo(r1))},
+                             {wmax(half_hi(l1), half_hi(r1)), wmax(half_lo(l2), half_lo(r2)), wmax(half_hi(l2), half_hi(r2))}};
+        ptbd::store_bounds2(u, [&](int k, uint32_t w) { store_agent(pp + k, w); });
         cur = par;
     }
 }
 
 // ------------------------------------------------------------------------------------
 // Tree quality (pt_bvh_cost): sum over the reachable internal nodes of halfArea(node) / halfArea(root), boxes decoded exactly,
-// f64 throughout.  Host twin: pt::bvh4_cost.  A degenerate box or one with a NaN bound has half-area 0.
+// f64 throughout (pt_bounds.h::half_area).  Host twin: pt::bvh4_cost.  A degenerate box or one with a NaN bound has half-area 0.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ double half_area(uint32_t w0, uint32_t w1, uint32_t w2) {
-    const double x0 = (double)half_exact(w0 & 0xffffu), y0 = (double)half_exact(w0 >> 16), z0 = (double)half_exact(w1 & 0xffffu);
-    const double x1 = (double)half_exact(w1 >> 16), y1 = (double)half_exact(w2 & 0xffffu), z1 = (double)half_exact(w2 >> 16);
-    if (!(x0 <= x1 && y0 <= y1 && z0 <= z1)) return 0.0;        // degenerate, or a NaN
-    const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
-    const double a = (dx * dy + dy * dz) + dz * dx;
-    return a == a ? a : 0.0;                                    // inf * 0
-}
+using ptbd::half_area;
 
 __global__ __launch_bounds__(256) void bvh_cost_kernel(const uint32_t* __restrict__ bvh4, uint32_t m, const uint2* __restrict__ self, double* __restrict__ out) {
     __shared__ double part[4];

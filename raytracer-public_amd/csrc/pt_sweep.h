@@ -36,7 +36,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "pt_closest.h"
+#include "pt_bounds.h"
 
 namespace ptsw {
 
@@ -50,8 +50,8 @@ PT_CP_FN bool sweep_walked(float ox, float oy, float oz, float tmax, float dx, f
 PT_CP_FN float bound_after(float t) { return t > 0.0f ? t : -kNoContact; }
 PT_CP_FN float time_of(float bound) { return bound > 0.0f ? bound : 0.0f; }
 
-PT_CP_FN float sel_min(float a, float b) { return b < a ? b : a; }
-PT_CP_FN float sel_max(float a, float b) { return b > a ? b : a; }
+using ptbd::sel_min;       // b < a ? b : a, the select flavour of pt_bounds.h
+using ptbd::sel_max;
 
 // one axis of a slab test with the growth g on the origin's side: op = o + g, om = o - g
 PT_CP_FN void axis_slab(float mn, float mx, float op, float om, float inv, float& near, float& far) {

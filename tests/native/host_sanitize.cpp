@@ -3,6 +3,7 @@
 // Built and run by tests/test_sanitizers.py (CPU only).
 #include "../../raytracer-public_amd/csrc/pt_host.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,7 +69,49 @@ static void one_case(uint32_t n, uint32_t seed, int flavour) {
     }
 }
 
+// The f16 codecs and the min / max flavours of pt_bounds.h against facts of the number formats, not against another copy of the code.
+// The non-NaN half patterns in ascending order of value are ord 0x03ff (-inf) .. 0x7fff (-0), 0x8000 (+0) .. 0xfc00 (+inf), with
+// ord = ~bits for a set sign bit and bits ^ 0x8000 otherwise.
+static uint32_t pattern_of(uint32_t ord) { return ((ord & 0x8000u) ? (ord ^ 0x8000u) : ~ord) & 0xffffu; }
+static void codec_facts() {
+    using namespace ptbd;
+    const float nan = std::nanf("");
+    for (uint32_t h = 0; h < 0x10000u; ++h) {
+        const uint32_t mag = h & 0x7fffu;
+        if (mag > 0x7c00u) continue;                                              // NaN patterns
+        const bool subnormal = mag != 0u && mag < 0x0400u;
+        CHECK(half_trunc(half_exact(h)) == (subnormal ? (h & 0x8000u) : h), "trunc(exact(h)) == h, subnormals flushed to the signed zero");
+        CHECK(f16_bits_rtne(half_exact(h)) == h, "rtne(exact(h)) == h");
+    }
+    for (uint32_t ord = 0x03ffu; ord <= 0xfc00u; ++ord) {
+        const uint32_t h = pattern_of(ord);
+        const float v = half_exact(h);
+        if (ord < 0xfc00u) {
+            const uint32_t up = pattern_of(ord + 1u);
+            const float w = half_exact(up);
+            CHECK(v < w || (h == 0x8000u && up == 0u && v == 0.0f && w == 0.0f && std::signbit(v) && !std::signbit(w)), "exact is strictly increasing (-0 below +0)");
+            CHECK(step_f16(v, true) == up, "step up is the next pattern");
+            CHECK(step_f16(w, false) == h, "step down is the previous pattern");
+            if (ord >= 0x0400u && ord + 1u < 0xfc00u && v < w) {                  // two adjacent finite halves
+                const float mid = 0.5f * v + 0.5f * w;                            // exact: at most 12 significant bits
+                const float below = std::nextafterf(mid, -INFINITY), above = std::nextafterf(mid, INFINITY);
+                CHECK(v < below && below < mid && mid < above && above < w, "the midpoint and its neighbours lie between the halves");
+                CHECK(f16_bits_rtne(mid) == ((h & 1u) ? up : h), "a tie rounds to the even pattern");
+                CHECK(f16_bits_rtne(below) == h && f16_bits_rtne(above) == up, "below the midpoint rounds down, above it up");
+                uint32_t inner = (w <= 0.0f) ? up : h;                            // the pattern nearer zero
+                if ((inner & 0x7fffu) < 0x0400u) inner &= 0x8000u;                // which the truncating routine flushes when it is subnormal
+                CHECK(half_trunc(mid) == inner && half_trunc(below) == inner && half_trunc(above) == inner, "truncation gives the pattern nearer zero");
+            }
+        }
+    }
+    CHECK(bits_of(js_min_f(-0.0f, 0.0f)) == 0x80000000u && bits_of(js_min_f(0.0f, -0.0f)) == 0x80000000u, "js_min of the two zeros is -0");
+    CHECK(bits_of(js_max_f(-0.0f, 0.0f)) == 0u && bits_of(js_max_f(0.0f, -0.0f)) == 0u, "js_max of the two zeros is +0");
+    CHECK(wmin(nan, 1.0f) == 1.0f && wmin(1.0f, nan) == 1.0f && wmax(nan, 1.0f) == 1.0f && wmax(1.0f, nan) == 1.0f, "the v_min / v_max flavour returns the non-NaN operand");
+    CHECK(bits_of(wmin(0.0f, -0.0f)) == 0x80000000u && bits_of(wmax(-0.0f, 0.0f)) == 0u, "the v_min / v_max flavour orders -0 below +0");
+}
+
 int main() {
+    codec_facts();
     for (uint32_t n : {0u, 1u, 2u, 3u, 4u, 5u, 17u, 64u, 257u, 1000u, 20000u})
         for (int flavour = 0; flavour < 4; ++flavour) one_case(n, n * 7u + flavour, flavour);
     for (uint32_t kind = 0; kind < 2; ++kind)

@@ -12,6 +12,10 @@ Items: N per case from the recipes of the case modules under tests/, the first f
 origin or the direction, t_max <= 0, r_max <= 0, an inverted box).  The counters are sums and maxima over the twins' workers, so they do
 not depend on the thread count.
 
+Build twins (the arithmetic of pt_bounds.h): morton_sort, the collapse at build levels 0 and 1, build_bvh2_ploc, bvh2_to_bvh4_wide,
+refit_bvh4, refit_bvh2 and bvh4_cost over the tetrahedron, soup1k and a hostile soup (hostile_geometry: signed zeros, f16 subnormals,
+coordinates beyond +-65504, an infinite and a NaN vertex, exact area ties); the LBVH2 they start from is the oracle's.
+
     python tools/twin_pins.py [--out tests/golden/twin_pins.json]
 """
 import argparse
@@ -108,6 +112,51 @@ def cases(rt, orc):
         it = items_of(rt, name, tris)
         out += route_cases(rt, name + "/walk", tris, tree_of(rt, orc, name, tris), it)
         out += route_cases(rt, name + "/brute", tris, None, it)
+    return out + build_cases(rt, orc)
+
+
+BUILD_GEOMETRIES = ("tetra", "soup1k", "hostile")
+HOSTILE_N, HOSTILE_SEED = 300, 41
+
+
+def hostile_geometry(n=HOSTILE_N, seed=HOSTILE_SEED):
+    """A soup of n triangles with what the scenes are thin in, each in a known triangle: 0: +0 and -0 coordinates; 1: magnitudes of about
+    1e-6, f16 subnormals; 2: a coordinate above 65504; 3: one below -65504; 4: an infinite vertex; 5: a NaN vertex; 6..9 and 10..13: two
+    groups of four equal triangles at offsets that are powers of two, so that the union of 6 and 7 has exactly the area of the union of 8 and 9
+    (and 10, 11 that of 12, 13): ties in PLOC's key and in the area-guided collapse."""
+    t = cc.random_soup(n, seed).reshape(n, 3, 3)
+    t[0] = [[0.0, -0.0, 0.25], [-0.0, 0.0, 0.25], [0.0, 0.25, -0.0]]
+    t[1] = [[1e-6, -2e-6, 3e-6], [-1e-6, 2e-6, -3e-6], [5e-7, 6e-8, -6e-8]]
+    t[2, 0, 0] = 70000.0
+    t[3, 1, 1] = -70000.0
+    t[4, 2, 2] = np.inf
+    t[5, 0, 1] = np.nan
+    shape = np.array([[0.0, 0.0, 0.0], [0.125, 0.0, 0.0625], [0.0, 0.125, 0.03125]], np.float32)
+    for first, origin in ((6, (2.0, 2.0, 2.0)), (10, (-4.0, 2.0, -2.0))):
+        for k, off in enumerate(((0.0, 0.0, 0.0), (0.25, 0.0, 0.0), (0.0, 0.0, 1.0), (0.25, 0.0, 1.0))):
+            t[first + k] = shape + np.array(origin, np.float32) + np.array(off, np.float32)
+    return t.reshape(-1)
+
+
+def build_cases(rt, orc):
+    """The build and refit twins over BUILD_GEOMETRIES; the refits take each triangle's successor as its new vertices (no arithmetic, so
+    the hostile values stay what they are)."""
+    out = []
+    for name in BUILD_GEOMETRIES:
+        tris = hostile_geometry() if name == "hostile" else cc.geometry(rt, name)
+        n = tris.size // 9
+        moved = np.roll(tris.reshape(n, 9), -1, axis=0).reshape(-1)
+        b2 = orc.build_lbvh2(tris)
+        b4 = rt.collapse_bvh2_to_bvh4_accel(b2, n, 0)[0]
+        twins = [("morton_sort", lambda tris=tris: rt.morton_sort(tris)),
+                 ("collapse_accel0", lambda b2=b2, n=n: rt.collapse_bvh2_to_bvh4_accel(b2, n, 0)),
+                 ("collapse_accel1", lambda b2=b2, n=n: rt.collapse_bvh2_to_bvh4_accel(b2, n, 1)),
+                 ("build_bvh2_ploc", lambda tris=tris: (rt.build_bvh2_ploc(tris),)),
+                 ("bvh2_to_bvh4_wide", lambda b2=b2: (rt.bvh2_to_bvh4_wide(b2),)),
+                 ("refit_bvh4", lambda moved=moved, b4=b4: (rt.refit_bvh4(moved, b4),)),
+                 ("refit_bvh2", lambda moved=moved, b2=b2: (rt.refit_bvh2(moved, b2),)),
+                 ("bvh4_cost", lambda b4=b4: (np.float64(rt.bvh4_cost(b4)),))]
+        out += [("build/%s/%s" % (name, twin), lambda run=run: tuple(np.asarray(a) for a in run()) + (None,)) for twin, run in twins]
     return out
 
 
