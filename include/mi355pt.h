@@ -635,6 +635,58 @@ PT_API int pt_box_search_host(PtContext* ctx, const PtBox* boxes, uint64_t n, ui
 PT_API int pt_box_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtBox* boxes, uint64_t n,
                               uint32_t flags, uint64_t* offsets, PtOverlap* entries, uint64_t capacity, PtStats* stats);
 
+/* ---- triangle-overlap queries: which mesh triangles does a caller triangle cut -- all of them? (an extension beyond the reference;
+ * DESIGN.md section 23) ----------------------------------------------------------------------------------------------------------
+ * Records: PtTri in (48 B, read as 3 x 16 B; the pads are ignored), one PtCross per accepted mesh triangle out (16 B, written as one
+ *   record; both reserved words are written as 0); offsets is uint64_t[n + 1].  Every result is an integer.
+ *   edges: bits 0-2 say which of the caller triangle's edges q0->q1, q1->q2, q2->q0 cross the mesh triangle; bits 3-5 say which of the
+ *   mesh triangle's edges (v0, e1), (v1, e2 - e1), (v0, e2) -- with v1 = v0 + e1 per component, as in the box query -- cross the caller's
+ *   triangle.  In general position exactly two of the six bits are set: the two crossing edges give the end points of the intersection
+ *   segment.
+ * Walked triangles: a caller triangle is walked iff its nine coordinates are finite.  Any other triangle has count 0 and an empty list.  A
+ *   degenerate triangle (zero area) is walked; it is then a segment or a point, and only the mesh side's tests can accept it.
+ * The bounding box: lo[k] = min, hi[k] = max of the three vertices as given (exact).
+ * The segment test (csrc/pt_tritri.h, one text for the kernels and the host twin; plain f32, each operation rounded once) of a segment
+ *   (p, d) -- from p to p + d -- against a triangle (a, f1, f2), a division-free, scale-free Moeller-Trumbore with dot(a, b) =
+ *   (a.x b.x + a.y b.y) + a.z b.z and cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), every product rounded:
+ *     pv = cross(d, f2), det = dot(f1, pv), sv = p - a, U = dot(sv, pv), qv = cross(sv, f1), V = dot(d, qv), T = dot(f2, qv);
+ *     crosses iff det > 0 and U >= 0, V >= 0, U + V <= det, T >= 0, T <= det, or det < 0 and the same five comparisons mirrored.
+ *   det == 0 or a NaN crosses nothing.  There is no epsilon: touching counts wherever the rounded values say so.
+ * The triangle test on a record as stored (v0, e1 = v1 - v0, e2 = v2 - v0):
+ *   (a) the box-axis stage of pt_box_search's triangle test, of the record's three vertices against lo, hi;
+ *   (b) the six segment tests: the caller's edges (q0, q1 - q0), (q1, q2 - q1), (q2, q0 - q2) against (v0, e1, e2), and the mesh edges
+ *       (v0, e1), (v1, e2 - e1), (v0, e2) against (q0, q1 - q0, q2 - q0); every difference per component, with one rounding.
+ *   A triangle is ACCEPTED iff (a) passes and edges != 0.
+ * COPLANAR PAIRS ARE NOT LISTED: every det is 0 for them.  A caller who needs them runs a 2-D test on the candidates of pt_box_search.
+ * The node test and the walk: pt_box_search's, on the caller triangle's bounding box (the slack s = 2^-12, depth-first slot order, 64 stack
+ *   entries with a push at the cap dropped and counted, a degenerate root box: 0 for every triangle, a leaf with tri >= num_tris skipped).
+ * The list, the offsets, the capacity and its truncation, n = 0, the three launches without a host wait, PT_TRI_BRUTE_FORCE, PT_TRI_STATS
+ *   and PT_TRI_SIMPLE_KERNEL: as pt_box_search and its PT_BOX_* flags, word for word.
+ * Completeness: for vertex coordinates within [-4, 4] and caller coordinates within [-32, 32], wherever every triangle is reachable from
+ *   the root and the walk drops nothing at the cap (stack_drops = 0), the walk lists exactly the set PT_TRI_BRUTE_FORCE lists: an accepted
+ *   triangle passed (a), which is the premise of the box query's proof.  With drops the walk's list is a subset.
+ * Ordering, errors and alignment: as pt_box_search.  Triangles and entries 16-byte aligned, offsets 8-byte, counts 4-byte. */
+typedef struct PtTri   { float v0[3]; float pad0; float v1[3]; float pad1; float v2[3]; float pad2; } PtTri;   /* 48 B, 16-byte aligned arrays */
+typedef struct PtCross { uint32_t prim; uint32_t edges; uint32_t reserved[2]; } PtCross;                      /* 16 B */
+enum { PT_TRI_STATS = 1u, PT_TRI_SIMPLE_KERNEL = 2u, PT_TRI_BRUTE_FORCE = 4u };
+/* n caller triangles from device memory (PtTri[n], 16-byte aligned), n counts into device memory (uint32_t[n], 4-byte aligned).
+ * Asynchronous on the context's stream (pt_get_stream). */
+PT_API int pt_tri_count(PtContext* ctx, const void* tris_device, uint64_t n, uint32_t flags, void* counts_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the counts are written. */
+PT_API int pt_tri_count_host(PtContext* ctx, const PtTri* tris, uint64_t n, uint32_t flags, uint32_t* counts);
+/* n caller triangles from device memory -> offsets_device: uint64_t[n + 1] (8-byte aligned); entries_device: PtCross[capacity] (16-byte
+ * aligned).  Asynchronous on the context's stream, no host wait. */
+PT_API int pt_tri_search(PtContext* ctx, const void* tris_device, uint64_t n, uint32_t flags,
+                         void* offsets_device, void* entries_device, uint64_t capacity);
+/* The same from host arrays: staged; the host reads the total between the scan and the second walk; returns when everything is written. */
+PT_API int pt_tri_search_host(PtContext* ctx, const PtTri* tris, uint64_t n, uint32_t flags,
+                              uint64_t* offsets, PtCross* entries, uint64_t capacity);
+/* Host twin (no context, no GPU): the same offsets, entry words and order (and the same truncation at `capacity`) and, with PT_TRI_STATS
+ * and stats != NULL, the same counters as the device gives for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(mesh).
+ * bvh4 = NULL (words = 0) only with PT_TRI_BRUTE_FORCE; errors as pt_box_search_bvh4. */
+PT_API int pt_tri_search_bvh4(const float* mesh, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtTri* tris, uint64_t n,
+                              uint32_t flags, uint64_t* offsets, PtCross* entries, uint64_t capacity, PtStats* stats);
+
 /* ---- hit lists: which triangles does a ray cross, and where -- all of them, each with t and u, v? (an extension beyond the reference;
  * DESIGN.md section 20) -----------------------------------------------------------------------------------------------------------
  * Records: PtRay in, one PtHit (t, prim, u, v) per crossing out; offsets is uint64_t[n + 1].  Every result is an integer or a bit pattern.

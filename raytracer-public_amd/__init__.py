@@ -43,6 +43,8 @@ PT_RADIUS_STATS, PT_RADIUS_SIMPLE_KERNEL, PT_RADIUS_BRUTE_FORCE = 1, 2, 4
 PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL, PT_HITS_BRUTE_FORCE, PT_HITS_SORTED = 1, 2, 4, 8
 # box-overlap queries (include/mi355pt.h pt_box_search)
 PT_BOX_STATS, PT_BOX_SIMPLE_KERNEL, PT_BOX_BRUTE_FORCE = 1, 2, 4
+# triangle-overlap queries (include/mi355pt.h pt_tri_search)
+PT_TRI_STATS, PT_TRI_SIMPLE_KERNEL, PT_TRI_BRUTE_FORCE = 1, 2, 4
 # sphere-cast queries (include/mi355pt.h pt_sweep_spheres)
 PT_SWEEP_STATS, PT_SWEEP_SIMPLE_KERNEL, PT_SWEEP_BRUTE_FORCE = 1, 2, 4
 # k-nearest queries (include/mi355pt.h pt_nearest_k)
@@ -115,6 +117,18 @@ class PtOverlap(C.Structure):
     _fields_ = [("prim", C.c_uint32), ("verts_inside", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class PtTri(C.Structure):
+    """include/mi355pt.h PtTri (48 B); arrays of it must be 16-byte aligned.  As numpy / torch data: 12 float32 per caller triangle (v0 xyz,
+    pad, v1 xyz, pad, v2 xyz, pad)."""
+    _fields_ = [("v0", C.c_float * 3), ("pad0", C.c_float), ("v1", C.c_float * 3), ("pad1", C.c_float), ("v2", C.c_float * 3), ("pad2", C.c_float)]
+
+
+class PtCross(C.Structure):
+    """include/mi355pt.h PtCross (16 B): prim, edges (bits 0-2: the caller triangle's edges that cross mesh triangle prim; bits 3-5: the mesh
+    triangle's edges that cross the caller's triangle), two zero words."""
+    _fields_ = [("prim", C.c_uint32), ("edges", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class PtSurfel(C.Structure):
     """include/mi355pt.h PtSurfel (32 B, the shape of PtRay); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per surfel
     (p xyz, r_max, n xyz, 0)."""
@@ -161,6 +175,7 @@ EXPORTS = [
     "pt_signed_distance", "pt_signed_distance_host",
     "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
     "pt_box_count", "pt_box_count_host", "pt_box_search", "pt_box_search_host", "pt_box_search_bvh4",
+    "pt_tri_count", "pt_tri_count_host", "pt_tri_search", "pt_tri_search_host", "pt_tri_search_bvh4",
     "pt_list_hits", "pt_list_hits_host", "pt_list_hits_bvh4",
     "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
     "pt_sweep_spheres", "pt_sweep_spheres_host", "pt_sweep_spheres_bvh4",
@@ -366,6 +381,29 @@ def _box_records(lo, hi, what=None):
     return torch.cat([a, z, b, z], dim=1).contiguous()
 
 
+def pack_tris(verts):
+    """numpy: (n, 12) float32 PtTri records (v0 xyz, 0, v1 xyz, 0, v2 xyz, 0) in a 16-byte aligned buffer, from (n, 3, 3) or (n, 9) vertices."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3, 3)
+    out = _aligned_zeros((v.shape[0], 12), np.float32)
+    out.reshape(-1, 3, 4)[:, :, 0:3] = v
+    return out
+
+
+def _tri_records(tris, what=None):
+    """(n, 3, 3) or (n, 9) vertices, or (n, 12) PtTri records -> aligned (n, 12) float32 records; of a torch tensor the same as a tensor."""
+    if not _is_torch(tris):
+        a = np.asarray(tris, np.float32)
+        return _records(a) if a.ndim == 2 and a.shape[1] == 12 else pack_tris(a)
+    if tris.dim() == 2 and tris.shape[1] == 12:
+        return _torch_records(tris, what)
+    import torch
+    dev = _torch_device(tris, what)
+    if tuple(tris.shape[1:]) not in ((3, 3), (9,)):
+        raise ValueError("%s: expected (n, 12) PtTri records or vertices of shape (n, 3, 3) or (n, 9), got shape %s" % (what, tuple(tris.shape)))
+    v = tris.reshape(-1, 3, 3).to(torch.float32)
+    return torch.cat([v, torch.zeros((v.shape[0], 3, 1), dtype=torch.float32, device=dev)], dim=2).reshape(-1, 12).contiguous()
+
+
 def pack_surfels(points, normals, r_max=None):
     """numpy: (n, 8) float32 PtSurfel records (p xyz, r_max, n xyz, 0) in a 16-byte aligned buffer; r_max None = +inf, a scalar or (n,)."""
     return pack_rays(points, normals, r_max)
@@ -385,11 +423,11 @@ def _records8(a, what):
 # one flag word serves every query but trace_rays (whose bit 1 is PT_TRACE_ANY_HIT): the headers' constants share their values, as the C
 # front end asserts for box and radius
 _QUERY_STATS, _QUERY_SIMPLE_KERNEL, _QUERY_BRUTE_FORCE = 1, 2, 4
-assert {PT_CLOSEST_STATS, PT_OCCLUSION_STATS, PT_COUNT_STATS, PT_CONTAIN_STATS, PT_RADIUS_STATS, PT_HITS_STATS, PT_BOX_STATS,
+assert {PT_CLOSEST_STATS, PT_OCCLUSION_STATS, PT_COUNT_STATS, PT_CONTAIN_STATS, PT_RADIUS_STATS, PT_HITS_STATS, PT_BOX_STATS, PT_TRI_STATS,
         PT_SWEEP_STATS, PT_NEAREST_STATS} == {_QUERY_STATS}
 assert {PT_CLOSEST_SIMPLE_KERNEL, PT_OCCLUSION_SIMPLE_KERNEL, PT_COUNT_SIMPLE_KERNEL, PT_CONTAIN_SIMPLE_KERNEL, PT_RADIUS_SIMPLE_KERNEL,
-        PT_HITS_SIMPLE_KERNEL, PT_BOX_SIMPLE_KERNEL, PT_SWEEP_SIMPLE_KERNEL, PT_NEAREST_SIMPLE_KERNEL} == {_QUERY_SIMPLE_KERNEL}
-assert {PT_CLOSEST_BRUTE_FORCE, PT_COUNT_BRUTE_FORCE, PT_RADIUS_BRUTE_FORCE, PT_HITS_BRUTE_FORCE, PT_BOX_BRUTE_FORCE, PT_SWEEP_BRUTE_FORCE,
+        PT_HITS_SIMPLE_KERNEL, PT_BOX_SIMPLE_KERNEL, PT_TRI_SIMPLE_KERNEL, PT_SWEEP_SIMPLE_KERNEL, PT_NEAREST_SIMPLE_KERNEL} == {_QUERY_SIMPLE_KERNEL}
+assert {PT_CLOSEST_BRUTE_FORCE, PT_COUNT_BRUTE_FORCE, PT_RADIUS_BRUTE_FORCE, PT_HITS_BRUTE_FORCE, PT_BOX_BRUTE_FORCE, PT_TRI_BRUTE_FORCE, PT_SWEEP_BRUTE_FORCE,
         PT_NEAREST_BRUTE_FORCE} == {_QUERY_BRUTE_FORCE}
 
 
@@ -556,6 +594,8 @@ _RADIUS_COUNT = _query("radius_count", PtPoint, C.c_uint32, None, ())
 _BOX_COUNT = _query("box_count", PtBox, C.c_uint32, None, ())
 _RADIUS = _query("radius_search", PtPoint, PtClosest, "fuff", guess=16)
 _BOX = _query("box_search", PtBox, PtOverlap, "uu", guess=16)               # (two columns, not four: prim, verts_inside)
+_TRI_COUNT = _query("tri_count", PtTri, C.c_uint32, None, ())
+_TRI = _query("tri_search", PtTri, PtCross, "uu", guess=16)                 # (two columns: prim, edges)
 _HITS = _query("list_hits", PtRay, PtHit, "fuff", guess=4)
 
 
@@ -623,6 +663,15 @@ def box_search_bvh4(tris, bvh4, lo, hi=None, capacity=None, stats=False, simple=
     brute_force).  capacity None: every entry (the twin runs twice, once for the total); else the first min(offsets[-1], capacity) entries,
     offsets complete.  The counters as a dict in fourth place with stats=True."""
     return _twin(_BOX, tris, bvh4, _box_records(lo, hi), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
+
+
+def tri_search_bvh4(mesh, bvh4, tris, capacity=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.tri_search (no GPU): every triangle of `mesh` that each caller triangle cuts over the tree set_bvh4(bvh4)
+    installs, with the device's words and order.  bvh4 None needs brute_force=True.  tris: (n, 3, 3) or (n, 9) vertices, or (n, 12) PtTri
+    records.  Returns (offsets, prim, edges): offsets (n + 1,) uint64, the list of caller triangle i at offsets[i]:offsets[i + 1], in visit
+    order (index order with brute_force).  capacity None: every entry (the twin runs twice, once for the total); else the first
+    min(offsets[-1], capacity) entries, offsets complete.  The counters as a dict in fourth place with stats=True."""
+    return _twin(_TRI, mesh, bvh4, _tri_records(tris), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
 
 
 def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):
@@ -1308,6 +1357,63 @@ class Context:
         stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
         self._ck(lib.pt_box_search(self.h, C.c_void_p(boxes_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
                                    C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    # ---- triangle-overlap queries (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 23) ----
+    def tri_count(self, tris, stats=False, simple=False, brute_force=False):
+        """How many mesh triangles does each caller triangle cut?  Returns the (n,) uint32 counts (0 for a triangle with a NaN or an infinity).
+
+        tris: (n, 3, 3) or (n, 9) float32 vertices, or (n, 12) PtTri records (v0 xyz, pad, v1 xyz, pad, v2 xyz, pad).  numpy arrays take the
+        host route (staged, returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host
+        synchronisation; the result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0
+        means that triangles were lost at the 64-entry stack cap); brute_force: every triangle, no tree.  Coplanar pairs are not counted."""
+        return self._run(_TRI_COUNT, _tri_records(tris, "tri_count"), C.c_uint32(_flags(stats, simple, brute_force)))
+
+    def tri_count_device(self, tris_ptr, n, counts_ptr, flags=0):
+        """Raw device route: n PtTri records at tris_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
+        context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_tri_count(self.h, C.c_void_p(tris_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
+
+    def tri_search(self, tris, capacity=None, stats=False, simple=False, brute_force=False):
+        """Which mesh triangles does each caller triangle cut -- all of them?  Returns (offsets, prim, edges): the list of caller triangle i
+        is entries offsets[i]:offsets[i + 1], in the walk's visit order (index order with brute_force).  Bits 0-2 of edges say which of the
+        caller's edges q0->q1, q1->q2, q2->q0 cross mesh triangle prim, bits 3-5 which of the mesh triangle's edges v0->v1, v1->v2, v0->v2
+        cross the caller's triangle; in general position two bits are set, the end points of the intersection segment.  offsets has n + 1
+        elements and is always complete: offsets[-1] is the total, and offsets[-1] > capacity says that only the first `capacity` entries
+        were written.  Touching counts wherever the rounded f32 values say so.  COPLANAR PAIRS ARE NOT LISTED: run a 2-D test on the
+        candidates of box_search for those.
+
+        tris: as tri_count.  numpy arrays take the host route (staged, returns when done): offsets is uint64 and the entry arrays hold
+        min(offsets[-1], capacity) elements; capacity=None starts with room for 16 entries per triangle and runs the query again when
+        offsets[-1] says that this was too little.
+        torch tensors on the context's device stay there, on the context's stream: offsets is int64, prim and edges torch.uint32.  With
+        `capacity` given the torch route waits for nothing on the host and the entry tensors hold `capacity` elements, of which those from
+        offsets[-1] on are not written.  With capacity=None it reads offsets[-1] once to size the entries: that is the one host wait of this
+        call (the triangles are then counted a second time); pass a capacity to avoid it.
+        stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack cap;
+        brute_force lists every cut triangle regardless."""
+        return self._list(_TRI, _tri_records(tris, "tri_search"), _flags(stats, simple, brute_force), capacity)
+
+    def tri_search_device(self, tris_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
+        """Raw device route: n PtTri records at tris_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned) and up to
+        `capacity` PtCross records at entries_ptr (16-byte aligned; 0 with capacity 0: offsets only).  Three launches on the context's
+        stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_tri_search(self.h, C.c_void_p(tris_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
+                                   C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    def intersecting_pairs(self, tris, capacity=None):
+        """tri_search flattened: returns (pairs, edges), pairs the (m, 2) int64 array of (caller triangle index, prim) of every entry that
+        was written, in list order, and edges its edges column.  numpy in, numpy out; torch in, torch out (the torch route then reads the
+        offsets on the host once, to expand them)."""
+        offsets, prim, edges = self.tri_search(tris, capacity)
+        if isinstance(offsets, np.ndarray):
+            m = prim.shape[0]
+            counts = np.diff(np.minimum(offsets, np.uint64(m)).astype(np.int64))
+            return np.stack([np.repeat(np.arange(counts.size, dtype=np.int64), counts), prim.astype(np.int64)], axis=1), edges
+        import torch
+        m = min(int(offsets[-1].item()), prim.shape[0])
+        counts = torch.diff(torch.clamp(offsets, max=m))
+        caller = torch.repeat_interleave(torch.arange(counts.shape[0], dtype=torch.int64, device=offsets.device), counts)
+        return torch.stack([caller, prim[:m].to(torch.int64)], dim=1), edges[:m]
 
     # ---- hit lists (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 20) ----
     def list_hits(self, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):

@@ -1,5 +1,5 @@
 // pt_api_queries.cpp -- the batched queries over the context's tree (include/mi355pt.h): closest hit / any hit, closest point,
-// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, hit lists, k-nearest and sphere casts, with the host twins
+// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, triangle count / search, hit lists, k-nearest and sphere casts, with the host twins
 // (*_bvh4) next to them.
 #include "pt_context.h"
 
@@ -505,8 +505,8 @@ int radius_fill_on_stream(PtContext* ctx, const void* points, uint32_t n, uint32
     return region_walk_on_stream(ctx, ptk::launch_radius, PT_RD_WAVES_PER_SIMD, PT_RD_SHORT_STACK, points, n, flags, nullptr, offsets, entries, capacity);
 }
 
-// A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, box search over boxes, hit
-// lists over rays.  The counts, the scan's scratch and the staging buffers (d_rd_*) are shared: the queries use them between launches of one call on the
+// A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, box search over boxes,
+// triangle search over caller triangles, hit lists over rays.  The counts, the scan's scratch and the staging buffers (d_rd_*) are shared: the queries use them between launches of one call on the
 // context's stream, which orders them, and the host forms wait for the stream before they return.
 struct ListQuery {
     size_t in_bytes;             // one input record
@@ -667,6 +667,71 @@ int pt_box_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh
     uint64_t counters[5] = {0, 0, 0, 0, 0};
     if (!pt::box_search(tris, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(boxes), n, offsets,
                         reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_BOX_STATS) && stats ? counters : nullptr, err))
+        return fail(nullptr, PT_ERR_BAD_BVH, err);
+    if (stats) stats_from(stats, counters);
+    return PT_OK;
+}
+
+// ---- triangle-overlap queries (include/mi355pt.h; pt_tritri.hip) -----------------------------------------------------------------
+
+static_assert(sizeof(PtTri) == 48 && sizeof(PtCross) == sizeof(uint4), "PtTri / PtCross are read and written as 3 x 16 B and 16 B records");
+static_assert(PT_TRI_STATS == PT_RADIUS_STATS && PT_TRI_SIMPLE_KERNEL == PT_RADIUS_SIMPLE_KERNEL && PT_TRI_BRUTE_FORCE == PT_RADIUS_BRUTE_FORCE,
+              "the PT_TRI_* flags take the values of the PT_RADIUS_* flags");
+
+namespace {
+constexpr uint32_t kTriFlags = kRadiusFlags;
+// the count walk and the fill walk (region_walk_on_stream)
+int tri_count_on_stream(PtContext* ctx, const void* tris, uint32_t n, uint32_t flags, void* counts) {
+    return region_walk_on_stream(ctx, ptk::launch_tri, PT_TT_WAVES_PER_SIMD, PT_TT_SHORT_STACK, tris, n, flags, counts, nullptr, nullptr, 0);
+}
+int tri_fill_on_stream(PtContext* ctx, const void* tris, uint32_t n, uint32_t flags, const unsigned long long* offsets, void* entries, uint64_t capacity) {
+    return region_walk_on_stream(ctx, ptk::launch_tri, PT_TT_WAVES_PER_SIMD, PT_TT_SHORT_STACK, tris, n, flags, nullptr, offsets, entries, capacity);
+}
+constexpr ListQuery kTriList = {sizeof(PtTri), tri_count_on_stream, tri_fill_on_stream};
+} // namespace
+
+int pt_tri_count(PtContext* ctx, const void* tris_device, uint64_t n, uint32_t flags, void* counts_device) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_region(ctx, "pt_tri_count", tris_device, n, flags, "triangles")) return rc;
+    if (int rc = check_counts(ctx, "pt_tri_count", counts_device)) return rc;
+    if (int rc = check_scene(ctx, "pt_tri_count")) return rc;
+    return tri_count_on_stream(ctx, tris_device, uint32_t(n), flags, counts_device);
+}
+
+int pt_tri_count_host(PtContext* ctx, const PtTri* tris, uint64_t n, uint32_t flags, uint32_t* counts) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_region(ctx, "pt_tri_count_host", tris, n, flags, "triangles")) return rc;
+    if (int rc = check_counts(ctx, "pt_tri_count_host", counts)) return rc;
+    if (int rc = check_scene(ctx, "pt_tri_count_host")) return rc;
+    return staged(ctx, n, tris, sizeof(PtTri), ctx->d_rd_counts, counts, sizeof(uint32_t),
+                  [&](const void* d_in, void* d_out) { return tri_count_on_stream(ctx, d_in, uint32_t(n), flags, d_out); });
+}
+
+// three launches, no host wait (list_device)
+int pt_tri_search(PtContext* ctx, const void* tris_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_region(ctx, "pt_tri_search", tris_device, n, flags, "triangles")) return rc;
+    if (int rc = check_list(ctx, "pt_tri_search", offsets_device, entries_device, capacity, "entries")) return rc;
+    if (int rc = check_scene(ctx, "pt_tri_search")) return rc;
+    return list_device(ctx, kTriList, tris_device, n, flags, offsets_device, entries_device, capacity);
+}
+
+int pt_tri_search_host(PtContext* ctx, const PtTri* tris, uint64_t n, uint32_t flags, uint64_t* offsets, PtCross* entries, uint64_t capacity) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_region(ctx, "pt_tri_search_host", tris, n, flags, "triangles")) return rc;
+    if (int rc = check_list(ctx, "pt_tri_search_host", offsets, entries, capacity, "entries")) return rc;
+    if (int rc = check_scene(ctx, "pt_tri_search_host")) return rc;
+    return list_host(ctx, kTriList, tris, n, flags, offsets, entries, capacity);
+}
+
+int pt_tri_search_bvh4(const float* mesh, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtTri* tris, uint64_t n,
+                       uint32_t flags, uint64_t* offsets, PtCross* entries, uint64_t capacity, PtStats* stats) {
+    const bool brute = (flags & PT_TRI_BRUTE_FORCE) != 0;
+    if (int rc = check_list_bvh4("pt_tri_search_bvh4", flags, kTriFlags, brute, mesh, num_tris, bvh4, tris, n, "triangles", offsets, entries, capacity)) return rc;
+    std::string err;
+    uint64_t counters[5] = {0, 0, 0, 0, 0};
+    if (!pt::tri_search(mesh, num_tris, brute ? nullptr : bvh4, words, reinterpret_cast<const float*>(tris), n, offsets,
+                        reinterpret_cast<uint32_t*>(entries), capacity, (flags & PT_TRI_STATS) && stats ? counters : nullptr, err))
         return fail(nullptr, PT_ERR_BAD_BVH, err);
     if (stats) stats_from(stats, counters);
     return PT_OK;

@@ -7,6 +7,7 @@
 #include "pt_closest.h"
 #include "pt_raymath.h"
 #include "pt_overlap.h"
+#include "pt_tritri.h"
 #include "pt_sweep.h"
 
 #include <cmath>
@@ -718,6 +719,43 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
             uint32_t in;
             if (ptov::tri_overlaps(b, r.axis[0][0], r.axis[1][0], r.axis[2][0], r.axis[0][1], r.axis[1][1], r.axis[2][1],
                                    r.axis[0][2], r.axis[1][2], r.axis[2][2], in)) accept([&](uint32_t* o) { o[0] = t; o[1] = in; o[2] = 0u; o[3] = 0u; });
+        };
+        if (bvh4) {
+            const float bound = 1.0f;
+            walk_keys_h(S.W, [&](const uint32_t* w, uint32_t) {
+                const Box c = unpack_box(w);
+                const bool meets = ptov::node_overlaps(b, c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2]);
+                return meets ? 0.0f : std::numeric_limits<float>::infinity();
+            }, bound, cnt, leaf);
+            return;
+        }
+        for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+        cnt.tris += num_tris;
+    }, [](uint64_t, uint64_t) {});
+    S.reduce(counters, n);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Triangle-overlap queries (host twin of pt_tritri.hip): box_search's walk on the caller triangle's exact bounding box, every accepted
+// leaf counted and, in a second walk of the same steps, listed at offsets[i] + k.  The arithmetic is pt_tritri.h, the text the kernels
+// compile; both walks compute all six bits (the device's count walk may stop at the first: the same accepted set).
+// ------------------------------------------------------------------------------------
+bool tri_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* in, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    // one caller triangle: the walk (or every triangle in index order)
+    list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
+        const float* p = in + i * 12;
+        const pttt::Tri q = {p[0], p[1], p[2], p[4], p[5], p[6], p[8], p[9], p[10]};
+        if (!pttt::tri_walked(q)) return;
+        const ptov::Box b = pttt::tri_box(q);
+        auto leaf = [&](uint32_t t) {
+            const TriRecord& r = S.rec[t];
+            const uint32_t edges = pttt::tri_crosses<true>(b, q, r.axis[0][0], r.axis[1][0], r.axis[2][0], r.axis[0][1], r.axis[1][1], r.axis[2][1],
+                                                           r.axis[0][2], r.axis[1][2], r.axis[2][2]);
+            if (edges) accept([&](uint32_t* o) { o[0] = t; o[1] = edges; o[2] = 0u; o[3] = 0u; });
         };
         if (bvh4) {
             const float bound = 1.0f;

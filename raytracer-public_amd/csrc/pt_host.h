@@ -109,6 +109,14 @@ bool radius_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, u
 bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* boxes, uint64_t n,
                 uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
 
+// ---- triangle-overlap queries (pt_tri_count, pt_tri_search; host twin of pt_tritri.hip, word for word) -------------------------------
+// in: n x (q0.xyz, pad, q1.xyz, pad, q2.xyz, pad); offsets and entries as box_search, an entry being (prim, edges, 0, 0).  bvh4 = nullptr:
+// every triangle in index order; else box_search's walk on the caller triangle's exact bounding box, and the leaf test of pt_tritri.h.
+// counters (optional): caller triangles, nodes examined, triangles tested, stack drops, max stack of the count walk -- as the device's
+// PT_TRI_STATS counts them.
+bool tri_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* in, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
+
 // ---- sphere-cast queries (pt_sweep_spheres; host twin of pt_sweep.hip, bit for bit) ----------------------------------------------------
 // sweeps: n x (org.xyz, t_max, dir.xyz, radius); out: n x (t bits, prim, u bits, v bits).  bvh4 = nullptr: every triangle in index order;
 // else closest_points' walk with the key of a child = tmin of the slab test on its box grown by r + s (pt_sweep.h::node_pass) and `best`
