@@ -14,7 +14,7 @@ import crossing_cases as cc
 import crossref
 
 N_RAYS = 3000
-PT_ERR_INVALID_ARG, PT_ERR_BAD_BVH = 1, 5        # include/mi355pt.h PtStatus
+PT_ERR_BAD_BVH = 5                                # include/mi355pt.h PtStatus
 
 
 @pytest.fixture(scope="module")
@@ -174,13 +174,8 @@ def test_arguments(rt, orc):
     def count(tp=tp, bp=bp, w=w, rp=rp, n=1, flags=0, cp=cp):
         return lib.pt_count_hits_bvh4(tp, n4, bp, w, rp, C.c_uint64(n), C.c_uint32(flags), cp, None)
     assert count() == 0 and counts[0] == 2
-    assert count(flags=8) == PT_ERR_INVALID_ARG and b"unknown flags" in lib.pt_last_error(None)
-    assert count(rp=None) == PT_ERR_INVALID_ARG and count(cp=None) == PT_ERR_INVALID_ARG and count(tp=None) == PT_ERR_INVALID_ARG
-    assert count(bp=None, w=C.c_uint64(0)) == PT_ERR_INVALID_ARG                      # a NULL bvh4 only with brute force
+    # what the two twins refuse, in which order and words: test_twin_query_errors.py
     assert count(bp=None, w=C.c_uint64(0), flags=rt.PT_COUNT_BRUTE_FORCE) == 0 and counts[0] == 2
-    assert count(rp=None, cp=None, n=0) == 0
-    assert count(n=1 << 32) == PT_ERR_INVALID_ARG
-    assert count(w=C.c_uint64(b4.size - 3)) == PT_ERR_BAD_BVH                         # shorter than its node count
     twice = b4.copy(); inner = next(i for i in range(int(b4[0])) if not b4[1 + 8 * i + 7] & 0x80000000)
     kids = [s for s in range(4) if twice[1 + 8 * inner + 3 + s] != 0xFFFFFFFF]
     twice[1 + 8 * inner + 3 + kids[1]] = twice[1 + 8 * inner + 3 + kids[0]]
@@ -190,13 +185,7 @@ def test_arguments(rt, orc):
         p = rt.PtContainParams(samples, 0, 0, flags)
         return lib.pt_contains_bvh4(tp, n4, bp, w, pp, C.c_uint64(n), C.byref(p) if params else None, op, None)
     assert contains() == 0 and out[0].tolist() == [1, 3, 3, 0]
-    for bad in (0, 2, 4, 256, 257):
-        assert contains(samples=bad) == PT_ERR_INVALID_ARG, bad
     assert contains(samples=255) == 0 and out[0].tolist() == [1, 255, 255, 0]
-    assert contains(flags=4) == PT_ERR_INVALID_ARG and contains(params=False) == PT_ERR_INVALID_ARG
-    assert contains(pp=None) == PT_ERR_INVALID_ARG and contains(op=None) == PT_ERR_INVALID_ARG and contains(bp=None) == PT_ERR_INVALID_ARG
-    assert contains(samples=3, n=(1 << 32) // 3 + 1, pp=None, op=None) == PT_ERR_INVALID_ARG and b"n * samples" in lib.pt_last_error(None)
-    assert contains(n=0, pp=None, op=None) == 0
     nanp = rt.pack_points([[np.nan, 0, 0], [0, 0, 0]]); out2 = np.full((2, 4), 7, np.uint32)
     p = rt.PtContainParams(3, 0, 0, 0)
     assert lib.pt_contains_bvh4(tp, n4, bp, w, nanp.ctypes.data_as(C.POINTER(rt.PtPoint)), C.c_uint64(2), C.byref(p),

@@ -100,6 +100,22 @@ FAMILIES = {
                       ("k must be 1 .. PT_NEAREST_MAX_K", [{"k": 0}, {"k": 65}]),
                       ("more than 2^32 - 1 points", [{"n": BIG}]),
                       ("points and results must be non-null and 16-byte aligned", P16("rec", "out"))], NO_SCENE),
+    "pt_sweep_spheres": (("rec", "n", "flags", "out"),
+                         [("unknown flags", [{"flags": 8}]),
+                          ("more than 2^32 - 1 sweeps", [{"n": BIG}]),
+                          ("sweeps and hits must be non-null and 16-byte aligned", P16("rec", "out"))], NO_SCENE),
+    "pt_box_count": (("rec", "n", "flags", "out"),
+                     [("unknown flags", [{"flags": 8}]),
+                      ("more than 2^32 - 1 boxes", [{"n": BIG}]),
+                      ("boxes must be non-null and 16-byte aligned", P16("rec")),
+                      ("counts must be non-null and 4-byte aligned", [{"out": NULL}, {"out": BY2}])], NO_SCENE),
+    "pt_box_search": (("rec", "n", "flags", "off", "ent", "cap"), list_checks("boxes", "entries"), NO_SCENE),
+    "pt_tri_count": (("rec", "n", "flags", "out"),
+                     [("unknown flags", [{"flags": 8}]),
+                      ("more than 2^32 - 1 triangles", [{"n": BIG}]),
+                      ("triangles must be non-null and 16-byte aligned", P16("rec")),
+                      ("counts must be non-null and 4-byte aligned", [{"out": NULL}, {"out": BY2}])], NO_SCENE),
+    "pt_tri_search": (("rec", "n", "flags", "off", "ent", "cap"), list_checks("triangles", "entries"), NO_SCENE),
 }
 # the entry points without a host form of the same shape: device only, and needing no scene
 DEVICE_ONLY = {

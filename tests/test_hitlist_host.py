@@ -21,7 +21,6 @@ import hitlistref
 
 N_RAYS = 2000
 RAY_SEED = 11
-PT_ERR_INVALID_ARG, PT_ERR_BAD_BVH = 1, 5        # include/mi355pt.h PtStatus
 
 
 @pytest.fixture(scope="module")
@@ -236,15 +235,9 @@ def test_arguments_and_rays_that_are_not_walked(rt, orc):
     def search(tp=tp, bp=bp, w=w, rp=rp, n=1, flags=0, op=op, ep=ep, cap=16):
         return lib.pt_list_hits_bvh4(tp, n12, bp, w, rp, C.c_uint64(n), C.c_uint32(flags), op, ep, C.c_uint64(cap), None)
     assert search() == 0 and off.tolist() == [0, 2]
-    assert search(flags=16) == PT_ERR_INVALID_ARG and b"unknown flags" in lib.pt_last_error(None)
-    assert search(rp=None) == PT_ERR_INVALID_ARG and search(op=None) == PT_ERR_INVALID_ARG and search(tp=None) == PT_ERR_INVALID_ARG
-    assert search(ep=None) == PT_ERR_INVALID_ARG and search(ep=None, cap=0) == 0 and off.tolist() == [0, 2]
-    assert search(bp=None, w=C.c_uint64(0)) == PT_ERR_INVALID_ARG                     # a NULL bvh4 only with brute force
+    assert search(ep=None, cap=0) == 0 and off.tolist() == [0, 2]
     assert search(bp=None, w=C.c_uint64(0), flags=rt.PT_HITS_BRUTE_FORCE | rt.PT_HITS_SORTED) == 0 and off.tolist() == [0, 2]
     assert search(flags=rt.PT_HITS_SIMPLE_KERNEL | rt.PT_HITS_STATS | rt.PT_HITS_SORTED) == 0
-    odd = C.cast(C.c_void_p(raw.ctypes.data + 4), C.POINTER(C.c_uint64))
-    assert search(op=odd) == PT_ERR_INVALID_ARG and b"8-byte aligned" in lib.pt_last_error(None)
     assert search(rp=None, ep=None, n=0, cap=0) == 0 and off[0] == 0
-    assert search(n=1 << 32) == PT_ERR_INVALID_ARG
-    assert search(w=C.c_uint64(b4.size - 3)) == PT_ERR_BAD_BVH                        # shorter than its node count
+    # what the twin refuses, in which order and words: test_twin_query_errors.py
     assert C.sizeof(rt.PtHit) == 16 and C.sizeof(rt.PtRay) == 32
