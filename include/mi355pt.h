@@ -687,6 +687,61 @@ PT_API int pt_tri_search_host(PtContext* ctx, const PtTri* tris, uint64_t n, uin
 PT_API int pt_tri_search_bvh4(const float* mesh, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtTri* tris, uint64_t n,
                               uint32_t flags, uint64_t* offsets, PtCross* entries, uint64_t capacity, PtStats* stats);
 
+/* ---- plane-cut queries: which mesh triangles does a plane cut inside a window, and where? (an extension beyond the reference;
+ * DESIGN.md section 24) ----------------------------------------------------------------------------------------------------------
+ * Records: PtCutPlane in (48 B, read as 3 x 16 B; the pads are ignored), one PtCut per accepted mesh triangle out (16 B, written as one
+ *   record); offsets is uint64_t[n + 1].  The plane is n.x = d; n need not be normalised.  [lo, hi] is a window, an axis-aligned box: it
+ *   bounds a list and lets a caller tile one plane over many records.  THE WINDOW DOES NOT CLIP: it filters on the triangle's bounding
+ *   box (stage (a) below), so a triangle whose box overlaps two windows is listed by both, with the same code, t0 and t1.
+ * Walked records: a record is walked iff n and d are finite, n is not the zero vector, and the window's six coordinates are finite with
+ *   lo <= hi on every axis (a zero-extent window is valid).  Any other record has count 0 and an empty list.
+ * The plane function (csrc/pt_cut.h, one text for the kernels and the host twin; plain f32, each operation rounded once, no fused
+ *   multiply-add): side(x, y, z) = ((n.x*x + n.y*y) + n.z*z) - d, in that order.
+ * The triangle test on a record as stored (v0, e1 = v1 - v0, e2 = v2 - v0), with v1 = v0 + e1, v2 = v0 + e2 per component:
+ *   (a) the box-axis stage of pt_box_search's triangle test, of the record's three vertices against lo, hi;
+ *   (b) s_i = side(v_i): every s_i passes >= 0 or < 0 (a NaN fails), some s_i >= 0 and some s_i < 0.
+ *   A triangle is ACCEPTED iff (a) and (b) pass.  This is the half-open rule of slicers: a triangle lying in the plane is not listed, nor
+ *   one that touches the plane from the >= 0 side; one that touches it from below with one vertex is listed as a zero-length segment at
+ *   that vertex.  Every accepted triangle has one lone vertex and exactly two crossing edges, so on a closed mesh the segments of a
+ *   plane close into loops.
+ * code: bits 0-2 say which edges cross, v0-v1, v1-v2, v0-v2 (the numbering of PtCross bits 3-5): exactly two are set.  Bits 3-5 are the
+ *   classes s_0 >= 0, s_1 >= 0, s_2 >= 0.
+ * t0, t1: t0 belongs to the lowest set edge bit, t1 to the highest.  Each is s_a / (s_a - s_b), a being that edge's vertex with s < 0
+ *   and b the one with s >= 0: measured from a towards b, one subtraction and one division, within [0, 1].  The crossing point is
+ *   v_a + t (v_b - v_a).
+ * The node test: a child is entered iff pt_box_search's node test passes on the window AND, with the child's f16 box grown by the slack
+ *   s = 2^-12 to fl(mn - s), fl(mx + s), side(p-corner) >= 0 and side(n-corner) < 0, the p-corner taking the grown upper value on the
+ *   axes where n_k >= 0 and the lower one elsewhere, the n-corner the opposite.  The walk is pt_box_search's (depth-first slot order,
+ *   64 stack entries with a push at the cap dropped and counted, a degenerate root box: 0 for every plane, a leaf with tri >= num_tris
+ *   skipped).
+ * The list, the offsets, the capacity and its truncation, n = 0, the three launches without a host wait, PT_CUT_BRUTE_FORCE, PT_CUT_STATS
+ *   and PT_CUT_SIMPLE_KERNEL: as pt_box_search and its PT_BOX_* flags, word for word.
+ * Completeness: for vertex coordinates within [-4, 4], window coordinates within [-32, 32] and |n_k|, |d| <= 2^100, wherever every
+ *   triangle is reachable from the root and the walk drops nothing at the cap (stack_drops = 0), the walk lists exactly the set
+ *   PT_CUT_BRUTE_FORCE lists: every f32 operation is monotone in each operand, so side of any point between the grown corners lies between
+ *   side(n-corner) and side(p-corner) in the rounded values.  With drops the walk's list is a subset.
+ * Ordering, errors and alignment: as pt_box_search.  Planes and entries 16-byte aligned, offsets 8-byte, counts 4-byte. */
+typedef struct PtCutPlane { float n[3]; float d; float lo[3]; float pad0; float hi[3]; float pad1; } PtCutPlane;   /* 48 B, 16-byte aligned arrays */
+typedef struct PtCut { uint32_t prim; uint32_t code; float t0; float t1; } PtCut;                                /* 16 B */
+enum { PT_CUT_STATS = 1u, PT_CUT_SIMPLE_KERNEL = 2u, PT_CUT_BRUTE_FORCE = 4u };
+/* n records from device memory (PtCutPlane[n], 16-byte aligned), n counts into device memory (uint32_t[n], 4-byte aligned).
+ * Asynchronous on the context's stream (pt_get_stream). */
+PT_API int pt_cut_count(PtContext* ctx, const void* planes_device, uint64_t n, uint32_t flags, void* counts_device);
+/* The same from host arrays: staged through device buffers of the context; returns when the counts are written. */
+PT_API int pt_cut_count_host(PtContext* ctx, const PtCutPlane* planes, uint64_t n, uint32_t flags, uint32_t* counts);
+/* n records from device memory -> offsets_device: uint64_t[n + 1] (8-byte aligned); entries_device: PtCut[capacity] (16-byte aligned).
+ * Asynchronous on the context's stream, no host wait. */
+PT_API int pt_cut_search(PtContext* ctx, const void* planes_device, uint64_t n, uint32_t flags,
+                         void* offsets_device, void* entries_device, uint64_t capacity);
+/* The same from host arrays: staged; the host reads the total between the scan and the second walk; returns when everything is written. */
+PT_API int pt_cut_search_host(PtContext* ctx, const PtCutPlane* planes, uint64_t n, uint32_t flags,
+                              uint64_t* offsets, PtCut* entries, uint64_t capacity);
+/* Host twin (no context, no GPU): the same offsets, entry words and order (and the same truncation at `capacity`) and, with PT_CUT_STATS
+ * and stats != NULL, the same counters as the device gives for the tree pt_set_bvh4(bvh4) installs over pt_set_triangles(tris).
+ * bvh4 = NULL (words = 0) only with PT_CUT_BRUTE_FORCE; errors as pt_box_search_bvh4. */
+PT_API int pt_cut_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtCutPlane* planes, uint64_t n,
+                              uint32_t flags, uint64_t* offsets, PtCut* entries, uint64_t capacity, PtStats* stats);
+
 /* ---- hit lists: which triangles does a ray cross, and where -- all of them, each with t and u, v? (an extension beyond the reference;
  * DESIGN.md section 20) -----------------------------------------------------------------------------------------------------------
  * Records: PtRay in, one PtHit (t, prim, u, v) per crossing out; offsets is uint64_t[n + 1].  Every result is an integer or a bit pattern.

@@ -45,6 +45,8 @@ PT_HITS_STATS, PT_HITS_SIMPLE_KERNEL, PT_HITS_BRUTE_FORCE, PT_HITS_SORTED = 1, 2
 PT_BOX_STATS, PT_BOX_SIMPLE_KERNEL, PT_BOX_BRUTE_FORCE = 1, 2, 4
 # triangle-overlap queries (include/mi355pt.h pt_tri_search)
 PT_TRI_STATS, PT_TRI_SIMPLE_KERNEL, PT_TRI_BRUTE_FORCE = 1, 2, 4
+# plane-cut queries (include/mi355pt.h pt_cut_search)
+PT_CUT_STATS, PT_CUT_SIMPLE_KERNEL, PT_CUT_BRUTE_FORCE = 1, 2, 4
 # sphere-cast queries (include/mi355pt.h pt_sweep_spheres)
 PT_SWEEP_STATS, PT_SWEEP_SIMPLE_KERNEL, PT_SWEEP_BRUTE_FORCE = 1, 2, 4
 # k-nearest queries (include/mi355pt.h pt_nearest_k)
@@ -129,6 +131,19 @@ class PtCross(C.Structure):
     _fields_ = [("prim", C.c_uint32), ("edges", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class PtCutPlane(C.Structure):
+    """include/mi355pt.h PtCutPlane (48 B); arrays of it must be 16-byte aligned.  As numpy / torch data: 12 float32 per record (n xyz, d,
+    lo xyz, pad, hi xyz, pad): the plane n.x = d and the window [lo, hi]."""
+    _fields_ = [("n", C.c_float * 3), ("d", C.c_float), ("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
+
+
+class PtCut(C.Structure):
+    """include/mi355pt.h PtCut (16 B): prim, code (bits 0-2: the crossing edges v0-v1, v1-v2, v0-v2 of mesh triangle prim, exactly two;
+    bits 3-5: the classes s_i >= 0 of its vertices), t0 and t1 (where the plane crosses the lowest and the highest crossing edge,
+    measured from the edge's vertex below the plane)."""
+    _fields_ = [("prim", C.c_uint32), ("code", C.c_uint32), ("t0", C.c_float), ("t1", C.c_float)]
+
+
 class PtSurfel(C.Structure):
     """include/mi355pt.h PtSurfel (32 B, the shape of PtRay); arrays of it must be 16-byte aligned.  As numpy / torch data: 8 float32 per surfel
     (p xyz, r_max, n xyz, 0)."""
@@ -176,6 +191,7 @@ EXPORTS = [
     "pt_radius_count", "pt_radius_count_host", "pt_radius_search", "pt_radius_search_host", "pt_radius_search_bvh4",
     "pt_box_count", "pt_box_count_host", "pt_box_search", "pt_box_search_host", "pt_box_search_bvh4",
     "pt_tri_count", "pt_tri_count_host", "pt_tri_search", "pt_tri_search_host", "pt_tri_search_bvh4",
+    "pt_cut_count", "pt_cut_count_host", "pt_cut_search", "pt_cut_search_host", "pt_cut_search_bvh4",
     "pt_list_hits", "pt_list_hits_host", "pt_list_hits_bvh4",
     "pt_nearest_k", "pt_nearest_k_host", "pt_nearest_k_bvh4",
     "pt_sweep_spheres", "pt_sweep_spheres_host", "pt_sweep_spheres_bvh4",
@@ -404,6 +420,85 @@ def _tri_records(tris, what=None):
     return torch.cat([v, torch.zeros((v.shape[0], 3, 1), dtype=torch.float32, device=dev)], dim=2).reshape(-1, 12).contiguous()
 
 
+CUT_WINDOW = 32.0        # the default window of a plane-cut record: [-32, 32]^3, the largest the completeness claim covers
+
+
+def pack_cuts(normal, d, lo=None, hi=None):
+    """numpy: (n, 12) float32 PtCutPlane records (n xyz, d, lo xyz, 0, hi xyz, 0) in a 16-byte aligned buffer.  normal: one normal (3,) or
+    (n, 3); d: a scalar or (n,); lo, hi: the window, one corner (3,) or (n, 3) each, None = -32 and +32 on every axis."""
+    nv = np.asarray(normal, np.float32).reshape(-1, 3)
+    dv = np.asarray(d, np.float32).reshape(-1)
+    a = np.asarray(-CUT_WINDOW if lo is None else lo, np.float32)
+    b = np.asarray(CUT_WINDOW if hi is None else hi, np.float32)
+    n = max(nv.shape[0], dv.shape[0], a.size // 3, b.size // 3)
+    out = _aligned_zeros((n, 12), np.float32)
+    try:
+        out[:, 0:3] = nv
+        out[:, 3] = dv
+        out[:, 4:7] = a if a.ndim == 0 else a.reshape(-1, 3)
+        out[:, 8:11] = b if b.ndim == 0 else b.reshape(-1, 3)
+    except ValueError:
+        raise ValueError("normal, d, lo and hi differ in length: %s, %s, %s, %s" % (nv.shape, dv.shape, a.shape, b.shape)) from None
+    return out
+
+
+def _cut_records(normal, d, lo, hi, what=None):
+    """normal + d (+ lo, hi), or (n, 12) PtCutPlane records (d None) -> aligned (n, 12) float32 records; of torch tensors the same as a
+    tensor."""
+    if not _is_torch(normal):
+        if d is not None:
+            return pack_cuts(normal, d, lo, hi)
+        a = np.asarray(normal, np.float32)
+        if a.ndim != 2 or a.shape[1] != 12:
+            raise ValueError("%s: expected (n, 12) PtCutPlane records or a normal and d, got shape %s" % (what or "cut records", a.shape))
+        return _records(a)
+    import torch
+    dev = _torch_device(normal, what)
+    if d is None:
+        if normal.dim() != 2 or normal.shape[1] != 12:
+            raise ValueError("%s: expected (n, 12) PtCutPlane records or a normal and d, got shape %s" % (what, tuple(normal.shape)))
+        return _torch_records(normal, what)
+    nv = normal.reshape(-1, 3).to(torch.float32)
+    dv = torch.as_tensor(d, dtype=torch.float32, device=dev).reshape(-1, 1)
+    a = torch.as_tensor(-CUT_WINDOW if lo is None else lo, dtype=torch.float32, device=dev)
+    b = torch.as_tensor(CUT_WINDOW if hi is None else hi, dtype=torch.float32, device=dev)
+    a = a.reshape(1, 1) if a.dim() == 0 else a.reshape(-1, 3)
+    b = b.reshape(1, 1) if b.dim() == 0 else b.reshape(-1, 3)
+    n = max(nv.shape[0], dv.shape[0], a.shape[0], b.shape[0])
+    z = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+    try:
+        return torch.cat([nv.expand(n, 3), dv.expand(n, 1), a.expand(n, 3), z, b.expand(n, 3), z], dim=1).contiguous()
+    except RuntimeError:
+        raise ValueError("%s: normal, d, lo and hi differ in length: %s, %s, %s, %s" % (what, tuple(nv.shape), tuple(dv.shape), tuple(a.shape), tuple(b.shape))) from None
+
+
+_CUT_EDGES = np.array([[0, 1], [1, 2], [0, 2]], np.int64)     # the vertices of edge bit 0, 1, 2
+
+
+def cut_segments(tris, prim, code, t0, t1):
+    """The segments of cut_search's entries: (m, 2, 3) float32, from the caller's own vertices tris ((num_tris, 3, 3) or (num_tris, 9), the
+    mesh the context holds) and the entry columns (numpy).  Each end point is va + t (vb - va), evaluated in float64 and rounded once.
+    segments[:, 0] lies on the lowest crossing edge of the triangle (the lowest set bit of code & 7, in the order v0-v1, v1-v2, v0-v2)
+    at t0, segments[:, 1] on the highest at t1; va is that edge's vertex below the plane (its class bit in code is 0) and vb the one on or
+    above it, so t runs from below the plane upwards.  t0 and t1 come from the f32 records the tree stores (v0, v1 - v0, v2 - v0), not from
+    `tris`: two triangles that share an edge give the same point on it only as far as their record vertices agree and the edge has the
+    same direction in both, which is to within a few float32 roundings, not bit for bit."""
+    v = np.asarray(tris, np.float64).reshape(-1, 3, 3)[np.asarray(prim, np.int64)]
+    code = np.asarray(code, np.int64)
+    m = code.shape[0]
+    lowest = np.where(code & 1, 0, 1)
+    highest = np.where(code & 4, 2, 1)
+    out = np.empty((m, 2, 3), np.float32)
+    rows = np.arange(m)
+    for end, (edge, t) in enumerate(((lowest, t0), (highest, t1))):
+        i, j = _CUT_EDGES[edge, 0], _CUT_EDGES[edge, 1]
+        i_above = ((code >> (3 + i)) & 1).astype(bool)
+        a, b = np.where(i_above, j, i), np.where(i_above, i, j)
+        va, vb = v[rows, a], v[rows, b]
+        out[:, end] = va + np.asarray(t, np.float64)[:, None] * (vb - va)
+    return out
+
+
 def pack_surfels(points, normals, r_max=None):
     """numpy: (n, 8) float32 PtSurfel records (p xyz, r_max, n xyz, 0) in a 16-byte aligned buffer; r_max None = +inf, a scalar or (n,)."""
     return pack_rays(points, normals, r_max)
@@ -423,11 +518,11 @@ def _records8(a, what):
 # one flag word serves every query but trace_rays (whose bit 1 is PT_TRACE_ANY_HIT): the headers' constants share their values, as the C
 # front end asserts for box and radius
 _QUERY_STATS, _QUERY_SIMPLE_KERNEL, _QUERY_BRUTE_FORCE = 1, 2, 4
-assert {PT_CLOSEST_STATS, PT_OCCLUSION_STATS, PT_COUNT_STATS, PT_CONTAIN_STATS, PT_RADIUS_STATS, PT_HITS_STATS, PT_BOX_STATS, PT_TRI_STATS,
+assert {PT_CLOSEST_STATS, PT_OCCLUSION_STATS, PT_COUNT_STATS, PT_CONTAIN_STATS, PT_RADIUS_STATS, PT_HITS_STATS, PT_BOX_STATS, PT_TRI_STATS, PT_CUT_STATS,
         PT_SWEEP_STATS, PT_NEAREST_STATS} == {_QUERY_STATS}
 assert {PT_CLOSEST_SIMPLE_KERNEL, PT_OCCLUSION_SIMPLE_KERNEL, PT_COUNT_SIMPLE_KERNEL, PT_CONTAIN_SIMPLE_KERNEL, PT_RADIUS_SIMPLE_KERNEL,
-        PT_HITS_SIMPLE_KERNEL, PT_BOX_SIMPLE_KERNEL, PT_TRI_SIMPLE_KERNEL, PT_SWEEP_SIMPLE_KERNEL, PT_NEAREST_SIMPLE_KERNEL} == {_QUERY_SIMPLE_KERNEL}
-assert {PT_CLOSEST_BRUTE_FORCE, PT_COUNT_BRUTE_FORCE, PT_RADIUS_BRUTE_FORCE, PT_HITS_BRUTE_FORCE, PT_BOX_BRUTE_FORCE, PT_TRI_BRUTE_FORCE, PT_SWEEP_BRUTE_FORCE,
+        PT_HITS_SIMPLE_KERNEL, PT_BOX_SIMPLE_KERNEL, PT_TRI_SIMPLE_KERNEL, PT_CUT_SIMPLE_KERNEL, PT_SWEEP_SIMPLE_KERNEL, PT_NEAREST_SIMPLE_KERNEL} == {_QUERY_SIMPLE_KERNEL}
+assert {PT_CLOSEST_BRUTE_FORCE, PT_COUNT_BRUTE_FORCE, PT_RADIUS_BRUTE_FORCE, PT_HITS_BRUTE_FORCE, PT_BOX_BRUTE_FORCE, PT_TRI_BRUTE_FORCE, PT_CUT_BRUTE_FORCE, PT_SWEEP_BRUTE_FORCE,
         PT_NEAREST_BRUTE_FORCE} == {_QUERY_BRUTE_FORCE}
 
 
@@ -596,6 +691,8 @@ _RADIUS = _query("radius_search", PtPoint, PtClosest, "fuff", guess=16)
 _BOX = _query("box_search", PtBox, PtOverlap, "uu", guess=16)               # (two columns, not four: prim, verts_inside)
 _TRI_COUNT = _query("tri_count", PtTri, C.c_uint32, None, ())
 _TRI = _query("tri_search", PtTri, PtCross, "uu", guess=16)                 # (two columns: prim, edges)
+_CUT_COUNT = _query("cut_count", PtCutPlane, C.c_uint32, None, ())
+_CUT = _query("cut_search", PtCutPlane, PtCut, "uuff", guess=16)            # (prim, code, t0, t1)
 _HITS = _query("list_hits", PtRay, PtHit, "fuff", guess=4)
 
 
@@ -672,6 +769,15 @@ def tri_search_bvh4(mesh, bvh4, tris, capacity=None, stats=False, simple=False, 
     order (index order with brute_force).  capacity None: every entry (the twin runs twice, once for the total); else the first
     min(offsets[-1], capacity) entries, offsets complete.  The counters as a dict in fourth place with stats=True."""
     return _twin(_TRI, mesh, bvh4, _tri_records(tris), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
+
+
+def cut_search_bvh4(tris, bvh4, normal, d=None, lo=None, hi=None, capacity=None, stats=False, simple=False, brute_force=False):
+    """Host twin of Context.cut_search (no GPU): every triangle of `tris` that each plane cuts inside its window over the tree
+    set_bvh4(bvh4) installs, with the device's words and order.  bvh4 None needs brute_force=True.  normal, d, lo, hi: as pack_cuts, or
+    normal alone as (n, 12) PtCutPlane records.  Returns (offsets, prim, code, t0, t1): offsets (n + 1,) uint64, the list of plane i at
+    offsets[i]:offsets[i + 1], in visit order (index order with brute_force).  capacity None: every entry (the twin runs twice, once for the
+    total); else the first min(offsets[-1], capacity) entries, offsets complete.  The counters as a dict in sixth place with stats=True."""
+    return _twin(_CUT, tris, bvh4, _cut_records(normal, d, lo, hi), (C.c_uint32(_flags(stats, simple, brute_force)),), stats, capacity=capacity)
 
 
 def list_hits_bvh4(tris, bvh4, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):
@@ -1414,6 +1520,79 @@ class Context:
         counts = torch.diff(torch.clamp(offsets, max=m))
         caller = torch.repeat_interleave(torch.arange(counts.shape[0], dtype=torch.int64, device=offsets.device), counts)
         return torch.stack([caller, prim[:m].to(torch.int64)], dim=1), edges[:m]
+
+    # ---- plane-cut queries (an extension beyond the reference; include/mi355pt.h) ----
+    def cut_count(self, normal, d=None, lo=None, hi=None, stats=False, simple=False, brute_force=False):
+        """How many mesh triangles does each plane n.x = d cut inside its window [lo, hi]?  Returns the (n,) uint32 counts (0 for a record
+        with a NaN or an infinity, n = 0 or lo > hi).
+
+        normal, d, lo, hi: one normal (3,) or (n, 3), d a scalar or (n,), the window's corners (3,) or (n, 3) each (None: [-32, 32]^3) -- or
+        normal alone as (n, 12) PtCutPlane records (n xyz, d, lo xyz, pad, hi xyz, pad).  numpy arrays take the host route (staged,
+        returns when done).  torch tensors on the context's device stay there, on the context's stream, with no host synchronisation;
+        the result is a torch.uint32 tensor.  stats: the counting kernel, counters in stats() afterwards (stack_drops > 0 means that
+        triangles were lost at the 64-entry stack cap); brute_force: every triangle, no tree."""
+        return self._run(_CUT_COUNT, _cut_records(normal, d, lo, hi, "cut_count"), C.c_uint32(_flags(stats, simple, brute_force)))
+
+    def cut_count_device(self, planes_ptr, n, counts_ptr, flags=0):
+        """Raw device route: n PtCutPlane records at planes_ptr (16-byte aligned) -> n uint32 counts at counts_ptr.  Asynchronous on the
+        context's stream (get_stream); the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_cut_count(self.h, C.c_void_p(planes_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(counts_ptr)))
+
+    def cut_search(self, normal, d=None, lo=None, hi=None, capacity=None, stats=False, simple=False, brute_force=False):
+        """Which mesh triangles does each plane n.x = d cut inside its window, and where?  Returns (offsets, prim, code, t0, t1): the list
+        of plane i is entries offsets[i]:offsets[i + 1], in the walk's visit order (index order with brute_force).  Bits 0-2 of code say
+        which edges of mesh triangle prim cross the plane, v0-v1, v1-v2, v0-v2 (exactly two); bits 3-5 are the classes s_i >= 0 of its
+        vertices, s = n.v - d.  t0 belongs to the lowest crossing edge, t1 to the highest, each measured from the edge's vertex below the
+        plane: cut_segments turns them into points.  The rule is half-open: a triangle in the plane or touching it from the s >= 0 side is
+        not listed, one touching it from below with one vertex is, as a zero-length segment.  The window does not clip: it filters on the
+        triangle's bounding box, so a triangle whose box overlaps two windows is listed by both.  offsets has n + 1 elements and is always
+        complete: offsets[-1] is the total, and offsets[-1] > capacity says that only the first `capacity` entries were written.
+
+        normal, d, lo, hi: as cut_count.  numpy arrays take the host route (staged, returns when done): offsets is uint64 and the entry
+        arrays hold min(offsets[-1], capacity) elements; capacity=None starts with room for 16 entries per plane and runs the query
+        again when offsets[-1] says that this was too little.
+        torch tensors on the context's device stay there, on the context's stream: offsets is int64, prim and code torch.uint32, t0 and
+        t1 torch.float32.  With `capacity` given the torch route waits for nothing on the host and the entry tensors hold `capacity`
+        elements, of which those from offsets[-1] on are not written.  With capacity=None it reads offsets[-1] once to size the entries:
+        that is the one host wait of this call (the planes are then counted a second time); pass a capacity to avoid it.
+        stats: counters of the count walk in stats() afterwards -- stack_drops > 0 means that triangles were lost at the 64-entry stack
+        cap; brute_force lists every cut triangle regardless."""
+        return self._list(_CUT, _cut_records(normal, d, lo, hi, "cut_search"), _flags(stats, simple, brute_force), capacity)
+
+    def cut_search_device(self, planes_ptr, n, offsets_ptr, entries_ptr, capacity, flags=0):
+        """Raw device route: n PtCutPlane records at planes_ptr (16-byte aligned) -> n + 1 uint64 offsets at offsets_ptr (8-byte aligned)
+        and up to `capacity` PtCut records at entries_ptr (16-byte aligned; 0 with capacity 0: offsets only).  Three launches on the
+        context's stream (get_stream), no host wait; the buffers must stay allocated until a later synchronize()."""
+        self._ck(lib.pt_cut_search(self.h, C.c_void_p(planes_ptr), C.c_uint64(n), C.c_uint32(flags), C.c_void_p(offsets_ptr),
+                                   C.c_void_p(entries_ptr) if entries_ptr else None, C.c_uint64(capacity)))
+
+    def cross_section(self, tris, normal, d, grid=1):
+        """The section of the mesh by the plane normal.x = d: returns (prim, code, segments), one row per cut triangle, segments the
+        (m, 2, 3) float32 array of cut_segments.  tris: the mesh the context holds, as numpy vertices ((num_tris, 3, 3) or (num_tris, 9)).
+        The mesh's bounding box is tiled into grid x grid windows over the two axes other than argmax |normal_k|, each with the box's full
+        extent on that third axis, and all of them go through one cut_search call; a triangle that several windows list is kept once, at
+        its first listing.  The segments are not stitched into polylines."""
+        v = np.asarray(tris, np.float32).reshape(-1, 3)
+        nrm = np.asarray(normal, np.float32).reshape(3)
+        grid = int(grid)
+        if grid < 1:
+            raise ValueError("cross_section: grid must be at least 1, got %d" % grid)
+        lo, hi = v.min(axis=0), v.max(axis=0)
+        k = int(np.argmax(np.abs(nrm)))
+        a, b = [ax for ax in range(3) if ax != k]
+        steps = np.arange(grid + 1, dtype=np.float32) / np.float32(grid)
+        edges = {ax: (lo[ax] + (hi[ax] - lo[ax]) * steps).astype(np.float32) for ax in (a, b)}
+        for ax in (a, b):
+            edges[ax][0], edges[ax][-1] = lo[ax], hi[ax]
+            edges[ax] = np.maximum.accumulate(edges[ax])
+        wlo = np.empty((grid, grid, 3), np.float32); whi = np.empty((grid, grid, 3), np.float32)
+        wlo[..., k], whi[..., k] = lo[k], hi[k]
+        wlo[..., a], whi[..., a] = edges[a][:-1, None], edges[a][1:, None]
+        wlo[..., b], whi[..., b] = edges[b][None, :-1], edges[b][None, 1:]
+        _, prim, code, t0, t1 = self.cut_search(nrm, np.float32(d), wlo.reshape(-1, 3), whi.reshape(-1, 3))
+        _, first = np.unique(prim, return_index=True)
+        first.sort()
+        return prim[first], code[first], cut_segments(tris, prim[first], code[first], t0[first], t1[first])
 
     # ---- hit lists (an extension beyond the reference; include/mi355pt.h, DESIGN.md section 20) ----
     def list_hits(self, origins, directions=None, t_max=None, capacity=None, sort=False, stats=False, simple=False, brute_force=False):

@@ -1,8 +1,8 @@
 // pt_api_queries.cpp -- the batched queries over the context's tree (include/mi355pt.h): closest hit / any hit, closest point,
-// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, triangle count / search, hit lists,
+// occlusion, crossing counts, containment, signed distance, radius count / search, box count / search, triangle count / search, plane-cut count / search, hit lists,
 // k-nearest and sphere casts, with the host twins (*_bvh4) next to them.
 // Each query states its facts once -- the nouns of its error texts, its record sizes, its flags, its two launch knobs, its launcher and its
-// pt::* twin -- as a descriptor: a WalkQuery (closest points, sphere casts, crossing counts), a ListQuery (radius, box, triangle search,
+// pt::* twin -- as a descriptor: a WalkQuery (closest points, sphere casts, crossing counts), a ListQuery (radius, box, triangle, plane-cut search,
 // hit lists), or a small struct that also carries the call's extra arguments (Trace, Nearest, Occlusion, Contains, SignedDistance).  The
 // entry points are forwarding statements into the forms written once: item_device / item_host (n records in, n records out),
 // list_search / list_search_host (offsets and entries), and for the twins walk_bvh4 / list_bvh4 over check_item_bvh4 / check_list_bvh4
@@ -180,7 +180,7 @@ int walk_bvh4(const char* fn, const WalkQuery& q, const float* tris, uint32_t nu
 }
 
 // A list query is a count walk, the scan of its counts into offsets, and a fill walk: radius search over points, box search over boxes,
-// triangle search over caller triangles, hit lists over rays.  The counts, the scan's scratch and the staging buffers (d_rd_*) are shared:
+// triangle search over caller triangles, plane-cut search over planes, hit lists over rays.  The counts, the scan's scratch and the staging buffers (d_rd_*) are shared:
 // the queries use them between launches of one call on the context's stream, which orders them, and the host forms wait for the stream
 // before they return.
 struct ListQuery {
@@ -255,7 +255,7 @@ int list_bvh4(const char* fn, const ListQuery& q, const float* tris, uint32_t nu
         return q.twin(tris, num_tris, tree, words, static_cast<const float*>(in), n, offsets, static_cast<uint32_t*>(entries), capacity, flags, counters, err); });
 }
 
-// The region queries (radius: points, box: boxes, tri: caller triangles) are list queries with one launcher for both walks, and a count of
+// The region queries (radius: points, box: boxes, tri: caller triangles, cut: planes) are list queries with one launcher for both walks, and a count of
 // their own: the count walk alone, an item-to-record query.  The STATS flag counts over the count walk only; its fill walk is the
 // one-item-per-thread kernel.
 template <decltype(&ptk::launch_radius) launch>
@@ -654,6 +654,38 @@ int pt_tri_search_host(PtContext* ctx, const PtTri* tris, uint64_t n, uint32_t f
 int pt_tri_search_bvh4(const float* mesh, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtTri* tris, uint64_t n,
                        uint32_t flags, uint64_t* offsets, PtCross* entries, uint64_t capacity, PtStats* stats) {
     return list_bvh4("pt_tri_search_bvh4", kTri, mesh, num_tris, bvh4, words, tris, n, flags, offsets, entries, capacity, stats);
+}
+
+// ---- plane-cut queries (include/mi355pt.h; pt_cut.hip) ---------------------------------------------------------------------------
+
+static_assert(sizeof(PtCutPlane) == 48 && sizeof(PtCut) == sizeof(uint4), "PtCutPlane / PtCut are read and written as 3 x 16 B and 16 B records");
+static_assert(PT_CUT_STATS == PT_RADIUS_STATS && PT_CUT_SIMPLE_KERNEL == PT_RADIUS_SIMPLE_KERNEL && PT_CUT_BRUTE_FORCE == PT_RADIUS_BRUTE_FORCE,
+              "the PT_CUT_* flags take the values of the PT_RADIUS_* flags");
+
+namespace {
+constexpr ListQuery kCut = {"planes", "entries", sizeof(PtCutPlane), kRegionFlags, PT_CT_WAVES_PER_SIMD, PT_CT_SHORT_STACK,
+                            region_walk<ptk::launch_cut>, region_twin<pt::cut_search>};
+} // namespace
+
+int pt_cut_count(PtContext* ctx, const void* planes_device, uint64_t n, uint32_t flags, void* counts_device) {
+    return item_device(ctx, "pt_cut_count", RegionCount{kCut, flags}, planes_device, n, counts_device);
+}
+
+int pt_cut_count_host(PtContext* ctx, const PtCutPlane* planes, uint64_t n, uint32_t flags, uint32_t* counts) {
+    return item_host(ctx, "pt_cut_count_host", RegionCount{kCut, flags}, planes, n, counts, &PtContext::d_rd_counts);
+}
+
+int pt_cut_search(PtContext* ctx, const void* planes_device, uint64_t n, uint32_t flags, void* offsets_device, void* entries_device, uint64_t capacity) {
+    return list_search(ctx, "pt_cut_search", kCut, planes_device, n, flags, offsets_device, entries_device, capacity);
+}
+
+int pt_cut_search_host(PtContext* ctx, const PtCutPlane* planes, uint64_t n, uint32_t flags, uint64_t* offsets, PtCut* entries, uint64_t capacity) {
+    return list_search_host(ctx, "pt_cut_search_host", kCut, planes, n, flags, offsets, entries, capacity);
+}
+
+int pt_cut_search_bvh4(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const PtCutPlane* planes, uint64_t n,
+                       uint32_t flags, uint64_t* offsets, PtCut* entries, uint64_t capacity, PtStats* stats) {
+    return list_bvh4("pt_cut_search_bvh4", kCut, tris, num_tris, bvh4, words, planes, n, flags, offsets, entries, capacity, stats);
 }
 
 // ---- hit lists (include/mi355pt.h; pt_hitlist.hip) ------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include "pt_raymath.h"
 #include "pt_overlap.h"
 #include "pt_tritri.h"
+#include "pt_cut.h"
 #include "pt_sweep.h"
 
 #include <cmath>
@@ -762,6 +763,46 @@ bool tri_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
             walk_keys_h(S.W, [&](const uint32_t* w, uint32_t) {
                 const Box c = unpack_box(w);
                 const bool meets = ptov::node_overlaps(b, c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2]);
+                return meets ? 0.0f : std::numeric_limits<float>::infinity();
+            }, bound, cnt, leaf);
+            return;
+        }
+        for (uint32_t t = 0; t < num_tris; ++t) leaf(t);
+        cnt.tris += num_tris;
+    }, [](uint64_t, uint64_t) {});
+    S.reduce(counters, n);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Plane-cut queries (host twin of pt_cut.hip): box_search's walk on the window, a child entered iff the window's node test passes and
+// the plane separates two corners of the child's grown box; every accepted leaf counted and, in a second walk of the same steps, listed
+// at offsets[i] + k with where the plane crosses its two crossing edges.  The arithmetic is pt_cut.h, the text the kernels compile; both
+// walks compute t0 and t1 (the device's count walk classifies only: the same accepted set).
+// ------------------------------------------------------------------------------------
+bool cut_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* in, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err) {
+    TwinScene S;
+    if (!S.init(tris, num_tris, bvh4, words, n, err)) return false;
+    // one plane and its window: the walk (or every triangle in index order)
+    list_twin(S, offsets, entries, capacity, [&](uint64_t i, WalkCounters& cnt, auto accept) {
+        const float* q = in + i * 12;
+        const ptct::Plane p = {q[0], q[1], q[2], q[3]};
+        if (!ptct::plane_walked(p) || !ptov::box_walked(q[4], q[5], q[6], q[8], q[9], q[10])) return;
+        const ptov::Box b = ptov::make_box(q[4], q[5], q[6], q[8], q[9], q[10]);
+        auto leaf = [&](uint32_t t) {
+            const TriRecord& r = S.rec[t];
+            ptct::Cut c = {0u, 0.0f, 0.0f};
+            if (ptct::tri_cut<true>(b, p, r.axis[0][0], r.axis[1][0], r.axis[2][0], r.axis[0][1], r.axis[1][1], r.axis[2][1],
+                                    r.axis[0][2], r.axis[1][2], r.axis[2][2], c))
+                accept([&](uint32_t* o) { o[0] = t; o[1] = c.code; std::memcpy(o + 2, &c.t0, 4); std::memcpy(o + 3, &c.t1, 4); });
+        };
+        if (bvh4) {
+            const float bound = 1.0f;
+            walk_keys_h(S.W, [&](const uint32_t* w, uint32_t) {
+                const Box c = unpack_box(w);
+                const bool meets = ptov::node_overlaps(b, c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2]) &&
+                                   ptct::node_cut(p, c.mn[0], c.mn[1], c.mn[2], c.mx[0], c.mx[1], c.mx[2]);
                 return meets ? 0.0f : std::numeric_limits<float>::infinity();
             }, bound, cnt, leaf);
             return;

@@ -117,6 +117,14 @@ bool box_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint
 bool tri_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* in, uint64_t n,
                 uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
 
+// ---- plane-cut queries (pt_cut_count, pt_cut_search; host twin of pt_cut.hip, word for word) -------------------------------------------
+// in: n x (n.xyz, d, lo.xyz, pad, hi.xyz, pad); offsets and entries as box_search, an entry being (prim, code, t0 bits, t1 bits).
+// bvh4 = nullptr: every triangle in index order; else box_search's walk on the window with the plane test of pt_cut.h::node_cut added to
+// the node test, and the leaf test of pt_cut.h.  counters (optional): planes, nodes examined, triangles tested, stack drops, max stack of
+// the count walk -- as the device's PT_CUT_STATS counts them.
+bool cut_search(const float* tris, uint32_t num_tris, const uint32_t* bvh4, uint64_t words, const float* in, uint64_t n,
+                uint64_t* offsets, uint32_t* entries, uint64_t capacity, uint64_t* counters, std::string& err);
+
 // ---- sphere-cast queries (pt_sweep_spheres; host twin of pt_sweep.hip, bit for bit) ----------------------------------------------------
 // sweeps: n x (org.xyz, t_max, dir.xyz, radius); out: n x (t bits, prim, u bits, v bits).  bvh4 = nullptr: every triangle in index order;
 // else closest_points' walk with the key of a child = tmin of the slab test on its box grown by r + s (pt_sweep.h::node_pass) and `best`

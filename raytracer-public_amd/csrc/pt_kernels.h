@@ -109,6 +109,19 @@
 #ifndef PT_TT_FILL
 #define PT_TT_FILL 8                // idle lanes of a wavefront at which they take the next triangles of its chunk
 #endif
+// plane-cut queries (pt_cut.hip): the box queries' values taken over, UNMEASURED for these kernels -- no GPU run has compared them with
+// any other value, nor the form of cut_kernel<FILL> that derives the corner selectors from the sign of n_k at each node (kept: 61 / 62
+// VGPRs, 7 waves per SIMD by registers) with the one that holds the three selectors per lane (62 / 63 VGPRs, 7 waves; DESIGN.md section
+// 24).  The LDS stack is what holds the grid at 6 waves per SIMD: 7 x 4 x PT_CT_SHORT_STACK x 512 B is above a CU's 160 KiB
+#ifndef PT_CT_SHORT_STACK
+#define PT_CT_SHORT_STACK 12        // LDS stack entries per lane of cut_kernel<FILL>; deeper entries spill to the context's spill area
+#endif
+#ifndef PT_CT_WAVES_PER_SIMD
+#define PT_CT_WAVES_PER_SIMD 6      // wavefronts of cut_kernel<FILL> per SIMD in the launch grid (what its registers and LDS allow)
+#endif
+#ifndef PT_CT_FILL
+#define PT_CT_FILL 8                // idle lanes of a wavefront at which they take the next planes of its chunk
+#endif
 // sphere-cast queries (pt_sweep.hip): the ray queries' values taken over.  tools/sweep_bench.py ran with them (profiles/sweep_ab.json); no
 // other value has been tried, so as choices they are unmeasured
 #ifndef PT_SW_SHORT_STACK
@@ -372,6 +385,14 @@ hipError_t launch_box(const RenderArgs& A, const void* boxes, uint32_t n, void* 
 // entries[offsets[i] + k] where that index is below `capacity`.  brute, simple, stats, grid, queue and spill as launch_radius, with
 // PT_TT_WAVES_PER_SIMD and PT_TT_SHORT_STACK.  The scan between the two is launch_radius_scan.
 hipError_t launch_tri(const RenderArgs& A, const void* tris_in, uint32_t n, void* counts, const unsigned long long* offsets, void* entries,
+                      unsigned long long capacity, bool simple, bool stats, bool brute,
+                      unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
+// ---- plane-cut queries (pt_cut.hip): every mesh triangle that a plane cuts inside a window, and where ---------------------------------
+// planes: PtCutPlane[n] (three float4 each, 16-byte aligned).  One walk per launch, launch_radius' two forms: offsets = nullptr counts the
+// accepted leaves of plane i into counts[i]; offsets != nullptr stores entry k of plane i (a PtCut record, in visit order) at
+// entries[offsets[i] + k] where that index is below `capacity`.  brute, simple, stats, grid, queue and spill as launch_radius, with
+// PT_CT_WAVES_PER_SIMD and PT_CT_SHORT_STACK.  The scan between the two is launch_radius_scan.
+hipError_t launch_cut(const RenderArgs& A, const void* planes, uint32_t n, void* counts, const unsigned long long* offsets, void* entries,
                       unsigned long long capacity, bool simple, bool stats, bool brute,
                       unsigned long long* queue, unsigned long long* spill, uint32_t grid, hipStream_t stream);
 // ---- hit lists (pt_hitlist.hip): every crossing along a ray, with t, triangle and u, v -------------------------------------------
